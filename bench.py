@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- scanned GB/s of the MI355X scan path on BASELINE.json's headline workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up (the dense-row ranking learned on a held-out corpus included), warms up, times exactly K steps and
+prints the line.  `--full` adds the legs the headline value does not need: the table with its ranking frozen as created,
+the enqueue-only caller, the from-idle launches, the dense-row trap counts, the CPU baseline with its parity check on a
+sample and the working set of the wide tables.  `--dump-outputs DIR` writes what the last timed step computed (state
+index and final flag per string, the match counters) as DIR/<name>.npy, for comparing two builds output for output.
 
 `python bench.py --gpus N` with N > 1 and no torch.distributed environment launches the N ranks itself (it re-executes
 itself under torch.distributed.run on 127.0.0.1); under an external launcher it is one of the ranks.
@@ -109,7 +115,31 @@ def parse():
                          "all-reduce kernel waits for a CU of a GPU the persistent scan fills) instead of once per fence")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL; gloo only to "
                     "exercise the multi-rank control flow on a box with fewer GPUs than ranks)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline value does not need: the ranking-frozen and enqueue-only legs, the "
+                         "from-idle leg, the trap counts, the CPU baseline (with its parity check) and the working set")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB in all: a fixed seeded sample of the strings where the batch is larger)")
     return ap.parse_args()
+
+
+DUMP_BYTES = 60 << 20   # --dump-outputs: the budget of all ranks together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(dirname, per_string, whole, budget=DUMP_BYTES, suffix=""):
+    """Write DIR/<name><suffix>.npy for every array of `per_string` (one value per string, float32 / float64) and of
+    `whole`.  Where the per-string arrays do not fit the budget, a sample of the strings -- drawn with a fixed seed, in
+    ascending order -- is written instead, their numbers as `string_index`."""
+    os.makedirs(dirname, exist_ok=True)
+    n = len(next(iter(per_string.values())))
+    room = budget - sum(a.nbytes for a in whole.values())
+    per = sum(a.itemsize for a in per_string.values())
+    if n * per > room:
+        pick = np.sort(np.random.RandomState(SEED).choice(n, room // (per + 8), replace=False))
+        per_string = dict({k: a[pick] for k, a in per_string.items()}, string_index=pick.astype(np.float64))
+    for name, a in list(per_string.items()) + list(whole.items()):
+        np.save(os.path.join(dirname, name + suffix + ".npy"), a)
 
 
 def spawn_ranks(args) -> int:
@@ -276,7 +306,10 @@ def bench_slow(args):
                                          "frac": round(achieved / peak, 4) if peak else None, "model": model},
                         "kernel": symbol, "kernel_avg_ms": round(float(np.mean(ms)), 4)},
            "match_counts": {"final": int(cnt[0].item()), "strings": int(cnt[1].item())}}
-    if not args.no_cpu:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"final": fin.cpu().numpy().astype(np.float32)},
+                     {"match_counts": cnt.cpu().numpy().astype(np.float64)})
+    if args.full and not args.no_cpu:
         from oracle import binding as ob   # the cpu_baseline leg: the checker, never the thing measured
 
         sample = min(n, 1 << args.cpu_sample_log2)   # the whole batch when asked for (C5b at its stated size: 16 GiB, ~8 s on 256 cores)
@@ -343,17 +376,20 @@ def bench_c1(args):
            "cpu_baseline": {"value": runs[top]["GBps"], "unit": "GB/s", "cores": runs[top]["threads"],
                             "kind": "reference" if ref else "port", "sample": f"the whole batch, {n} x {length} B", "runs": runs},
            "match_counts": {"final": int(want[1].sum()), "strings": n, "distinct_end_states": int(len(np.unique(want[0])))}}
-    try:
-        import torch
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"state_index": want[0].astype(np.float64), "final": want[1].astype(np.float32)}, {})
+    if args.full:
+        try:
+            import torch
 
-        if torch.cuda.is_available():
-            import pire_amd
+            if torch.cuda.is_available():
+                import pire_amd
 
-            t = pire_amd.Table(blob)
-            gi, gf = t.run_strided_host(host)
-            res["gpu_parity"] = bool((gi == want[0]).all() and (gf == want[1]).all())
-    except ImportError:
-        pass
+                t = pire_amd.Table(blob)
+                gi, gf = t.run_strided_host(host)
+                res["gpu_parity"] = bool((gi == want[0]).all() and (gf == want[1]).all())
+        except ImportError:
+            pass
     print(json.dumps(res))
 
 
@@ -468,7 +504,7 @@ def main():
     # CU's LDS the persistent scan holds (`--reduce-every-step` restores it for comparison).
     settle = max(0, args.settle)
     cold_steps = max(1, min(args.steps, 10))
-    cold_launches = max(0, args.cold_launches)
+    cold_launches = max(0, args.cold_launches) if args.full else 0
     total_steps = 3 * (settle + args.warmup) + 2 * cold_steps + args.steps + cold_launches + 24
     counts_all = torch.zeros((total_steps + 16 if args.reduce_every_step else 16, table.RegexpsCount + 2), dtype=torch.int64,
                              device=dev)
@@ -581,16 +617,18 @@ def main():
     # launches at boost clocks, a dip to 0.8-0.9 ms per launch, recovery after 20-30 launches (~25 ms); profiles/
     # r03_warmup_curve.log.  Every timed leg is therefore preceded by `settle` untimed passes (default 60, 40 ms of
     # scanning) issued back to back with the W warm-up passes: the metric is the throughput of sustained scanning.
-    cold_table = pire_amd.Table(blob)
-    cold_table.upload()
-    cold_elapsed, cold_ms = timed(cold_table, cold_steps, settle + args.warmup)
-    del cold_table
+    cold_ms = None
+    if args.full:
+        cold_table = pire_amd.Table(blob)
+        cold_table.upload()
+        cold_elapsed, cold_ms = timed(cold_table, cold_steps, settle + args.warmup)
+        del cold_table
     # --- 2b. (round 6) the same for a caller that only ENQUEUES and never calls adapt(): a third handle under the library's default
     # policy (auto_adapt = 0: such calls start a re-ranking in the background and swap it in at a later launch boundary; the walk
     # follows the trap signal meanwhile) -- a handful of passes on the timed corpus with nothing but the caller's own stream
     # synchronisation between them, then a short timed leg.  Reported as value_enqueue_only_no_adapt.
     enq = None
-    if not args.no_adapt and not args.one_string:
+    if args.full and not args.no_adapt and not args.one_string:
         pb.set_config(auto_adapt=0)
         enq_table = pire_amd.Table(blob)
         enq_table.upload()
@@ -620,6 +658,12 @@ def main():
     total_counts = timed_stats["counts_row"].cpu().numpy().astype(np.uint64)   # the timed passes', reduced over the ranks
     assert (total_counts % timed_stats["passes_in_row"] == 0).all(), "the same batch every pass: the totals are multiples of the pass count"
     total_counts //= timed_stats["passes_in_row"]   # one pass's
+    gpu_idx = out_idx.cpu().numpy().astype(np.uint32)   # the last timed pass's (every pass writes the same)
+    gpu_fin = out_fin.cpu().numpy()
+    if args.dump_outputs:   # every rank its own shard; the counters are the reduced ones
+        dump_outputs(args.dump_outputs, {"state_index": gpu_idx.astype(np.float64), "final": gpu_fin.astype(np.float32)},
+                     {"match_counts": total_counts.astype(np.float64)}, budget=DUMP_BYTES // world,
+                     suffix=f"_rank{rank}" if world > 1 else "")
     # --- 4. from idle: what a caller gets who scans one batch on a GPU that was doing nothing.  Behind the
     # timed region and outside it: the device is drained, left idle for 0.3 s (its clocks drop), then `cold_launches`
     # passes are timed back to back with no warm-up at all (the first ones run in the power management's transient,
@@ -630,12 +674,10 @@ def main():
         time.sleep(args.cold_idle_ms / 1e3)
         cold_el, cold_start_ms = timed(table, cold_launches, 0)
         from_idle = (cold_el, cold_start_ms)
-    gpu_idx = out_idx.cpu().numpy().astype(np.uint32)
-    gpu_fin = out_fin.cpu().numpy()
 
     if rank == 0:
         scanned = float(n) * length * args.steps * world
-        frozen_value = round(float(n) * length * cold_steps * world / cold_elapsed / 1e9, 2)
+        frozen_value = round(float(n) * length * cold_steps * world / cold_elapsed / 1e9, 2) if args.full else None
         value = scanned / elapsed / 1e9
         algo_bytes = n * length + 5 * run_n                # input read once + u32 state idx + u8 final per string
         avg_ms = float(np.mean(kernel_ms))
@@ -694,12 +736,13 @@ def main():
             "data": data,
             # (round 6) "before adapt()" = what a caller gets who never calls pire_hip_table_adapt(): the library's default policy,
             # calls that only enqueue (leg 2b).  The table whose ranking is FROZEN as created (auto_adapt = 1, leg 2) beside it.
-            "value_before_adapt": enq["value"] if enq else frozen_value,
-            "value_before_adapt_is": ("value_enqueue_only_no_adapt: a fresh table, library defaults, no adapt() call, no device-wide "
-                                      "synchronisation" if enq else "value_ranking_frozen (this run made no enqueue-only leg)"),
-            "value_enqueue_only_no_adapt": enq["value"] if enq else None,
-            "value_ranking_frozen": frozen_value,
-            "enqueue_only_no_adapt": enq,
+            # Both legs run with --full only.
+            **({"value_before_adapt": enq["value"] if enq else frozen_value,
+                "value_before_adapt_is": ("value_enqueue_only_no_adapt: a fresh table, library defaults, no adapt() call, no device-wide "
+                                          "synchronisation" if enq else "value_ranking_frozen (this run made no enqueue-only leg)"),
+                "value_enqueue_only_no_adapt": enq["value"] if enq else None,
+                "value_ranking_frozen": frozen_value,
+                "enqueue_only_no_adapt": enq} if args.full else {}),
             "config": {
                 "workload": f"{WORKLOADS.get(args.set, args.set)} ({args.set}), {shape}, "
                             f"Begin().Run().End() per string, match counters accumulated on the device and reduced "
@@ -737,7 +780,7 @@ def main():
                 "lds_gather": lds,
                 "kernel": kernel_name, "kernel_avg_ms": round(avg_ms, 4),
                 "kernel_min_ms": round(float(np.min(kernel_ms)), 4),
-                "kernel_avg_ms_ranking_frozen": round(float(np.mean(cold_ms)), 4),
+                "kernel_avg_ms_ranking_frozen": round(float(np.mean(cold_ms)), 4) if cold_ms else None,
                 "algorithmic_bytes_per_launch": algo_bytes,
                 "frac_of_measured_copy_ceiling_6290": round(achieved / 6290.0, 4),
             },
@@ -746,15 +789,16 @@ def main():
         }
         # how often the timed corpus left the dense rows: the table's cold-state samples since the ranking was frozen (one
         # rotating lane of 64 per chunk that ended outside the dense rows), read by an adapt() AFTER every
-        # timed leg -- it re-ranks a table nobody uses any more
-        launches_since_ranking = settle + args.warmup + args.steps + (cold_launches if from_idle else 0)
-        table.adapt()
-        samples = int(table.refresh_info().last_trap_samples)
-        wide_chunks = int(table.info.last_wide_trap_chunks)
-        res["traps"] = {"cold_samples": samples, "launches": launches_since_ranking,
-                        "wide_walk_wave_chunk_share_walked_twice": round(wide_chunks / max(1.0, launches_since_ranking * float(n) * length / 1024.0), 6),
-                        "cold_lane_chunk_share": round(samples * 64.0 / max(1.0, launches_since_ranking * float(n) * length / 16.0), 8),
-                        "what": "share of (lane, 16-byte chunk) pairs of the timed corpus that ended in a state without a dense row"}
+        # timed leg -- it re-ranks a table nobody uses any more (--full only)
+        if args.full:
+            launches_since_ranking = settle + args.warmup + args.steps + (cold_launches if from_idle else 0)
+            table.adapt()
+            samples = int(table.refresh_info().last_trap_samples)
+            wide_chunks = int(table.info.last_wide_trap_chunks)
+            res["traps"] = {"cold_samples": samples, "launches": launches_since_ranking,
+                            "wide_walk_wave_chunk_share_walked_twice": round(wide_chunks / max(1.0, launches_since_ranking * float(n) * length / 1024.0), 6),
+                            "cold_lane_chunk_share": round(samples * 64.0 / max(1.0, launches_since_ranking * float(n) * length / 16.0), 8),
+                            "what": "share of (lane, 16-byte chunk) pairs of the timed corpus that ended in a state without a dense row"}
         if from_idle:
             cel, cms = from_idle
             cold_achieved = algo_bytes / (float(np.mean(cms)) * 1e-3) / 1e9
@@ -767,7 +811,7 @@ def main():
                 "kernel_max_ms": round(float(np.max(cms)), 4),
                 "frac": round(cold_achieved / HBM_PEAK_GBS, 4)}
         assert int(total_counts[1]) == run_n * world, "match-count reduce lost strings"
-        if not args.no_cpu and world == 1 and not args.one_string:   # the reported CPU baseline belongs to the N=1 line
+        if args.full and not args.no_cpu and world == 1 and not args.one_string:   # the reported CPU baseline belongs to the N=1 line
             sample = min(n, 1 << args.cpu_sample_log2)
             if wide_entry:
                 sample = min(sample, wide_base.shape[0])

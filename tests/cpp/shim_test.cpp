@@ -3,7 +3,7 @@
 //     Pire::Runner(sc).Begin().Run(str).End().State()            (run.h:365-392; call shape of tests/common.h:158-169)
 // returns, so sc.Final(st) and sc.AcceptedRegexps(st) agree as well.  Patterns/strings are those of the reference's
 // tests (tests/pire_ut.cpp: String, Boundaries, Primitives, Repetition, TestShortcuts, Glue, Aligned, EmptyScanner).
-// Built only where /root/reference exists (tests/cpp/Makefile); the binary ships to the GPU box.
+// Built where the reference tree exists (`make -C oracle shim`, into oracle/_ref/bin with the library it links).
 #include <cstdio>
 #include <cstring>
 #include <string>

@@ -7,7 +7,7 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "examples", "bin")
+BIN = os.path.join(ROOT, "oracle", "_ref", "bin")
 REF_PRESENT = os.path.exists("/root/reference/samples/pigrep/pigrep.cpp")
 
 CASES = [
@@ -33,7 +33,7 @@ def test_examples_build_against_reference_headers():
     from oracle import binding as ob
 
     ob.build()
-    r = subprocess.run(["make", "-C", os.path.join(ROOT, "examples")], stdout=subprocess.PIPE,
+    r = subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "examples"], stdout=subprocess.PIPE,
                        stderr=subprocess.STDOUT, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:]
     assert os.path.exists(os.path.join(BIN, "pigrep_hip")) and os.path.exists(os.path.join(BIN, "pigrep_ref"))
@@ -43,7 +43,7 @@ def test_examples_build_against_reference_headers():
 @pytest.mark.parametrize("args,files", CASES)
 def test_pigrep_hip_prints_what_pigrep_prints(args, files):
     if not os.path.exists(os.path.join(BIN, "pigrep_hip")):
-        pytest.skip("examples/bin was not built (needs /root/reference at build time)")
+        pytest.skip("oracle/_ref/bin was not built (needs the reference tree at build time)")
     want = run("pigrep_ref", args, files)
     got = run("pigrep_hip", args, files)
     assert got[0] == 0, got[2][-2000:]
@@ -55,7 +55,7 @@ def test_pigrep_hip_prints_what_pigrep_prints(args, files):
 @pytest.mark.gpu
 def test_pigrep_hip_stdin_and_unterminated_last_line():
     if not os.path.exists(os.path.join(BIN, "pigrep_hip")):
-        pytest.skip("examples/bin was not built (needs /root/reference at build time)")
+        pytest.skip("oracle/_ref/bin was not built (needs the reference tree at build time)")
     text = b"alpha\n\nbeta gamma\n" + b"x" * 5000 + b" gamma\nlast gamma without newline"
     for args in (["gamma"], ["^$"], ["-i", "ALPHA|x{4000}"]):
         want = run("pigrep_ref", args, [], stdin=text)
@@ -79,7 +79,7 @@ def test_pigrep_hip_fails_loudly_without_gpu():
 def test_pigrep_hip_on_a_file_with_very_long_lines(tmp_path):
     """Lines of a megabyte and more next to short ones: the batch goes through the segmented scan; same output."""
     if not os.path.exists(os.path.join(BIN, "pigrep_hip")):
-        pytest.skip("examples/bin was not built (needs /root/reference at build time)")
+        pytest.skip("oracle/_ref/bin was not built (needs the reference tree at build time)")
     import random
 
     rnd = random.Random(7)
