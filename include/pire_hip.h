@@ -338,7 +338,8 @@ uint32_t pire_hip_abi_version(void);
 int pire_hip_table_final(const pire_hip_table* t, uint32_t state_idx);
 /* Scanner::Dead(state)   multi.h:147 */
 int pire_hip_table_dead(const pire_hip_table* t, uint32_t state_idx);
-/* Scanner::AcceptedRegexps(state) multi.h:149-158: (begin, count) describe an array owned by the table. */
+/* Scanner::AcceptedRegexps(state) multi.h:149-158: (begin, count) describe an array owned by the table, valid until
+ * pire_hip_table_destroy(t) whatever re-rankings (pire_hip_table_adapt, the automatic ones) happen in between. */
 int pire_hip_table_accepted_regexps(const pire_hip_table* t, uint32_t state_idx,
                                     const uint64_t** begin, size_t* count);
 /* The letter class of ch (Translate(ch) - HEADER_SIZE, multi.h:163-166); ch < 264. */

@@ -547,6 +547,8 @@ int Dispatch(const ScanParams& p, hipStream_t stream, unsigned long long* workCo
 	const int kind = wide ? kKindWide : tiled ? kKindTiled : streamWide ? kKindStreamWide : raggedWide ? kKindRaggedWide : streamed ? kKindStream
 	                 : ragged ? kKindRagged : kKindGeneric;
 	static const char* const kNames[] = {"generic", "tiled", "wide", "ragged", "ragged_wide", "stream", "stream_wide"};
+	static_assert(kSelfTestedOnWideImage == ((1u << kKindWide) | (1u << kKindRaggedWide) | (1u << kKindStreamWide) | (0xFu << 8)),
+	              "internal.h kSelfTestedOnWideImage: the kinds on the wide image and the entry bits");
 	if (p.owner && !(p.owner->selfTested[p.workDevice].load(std::memory_order_relaxed) & (1u << kind))) {
 		const uint32_t mode = GetConfig().selftest;
 		hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
@@ -1227,6 +1229,9 @@ try {
 		SetError("null table");
 		return PIRE_HIP_EINVAL;
 	}
+	std::shared_lock<std::shared_mutex> stable(t->adaptMutex);   // (an adaptation replaces t->host and the images)
+	TableConfigScope scope;   // the image is built under the table's configuration, as an entry point would build it
+	scope.Push(t);
 	DeviceTable image;
 	if (int rc = UploadTable(t, &image))
 		return rc;
@@ -1337,8 +1342,8 @@ try {
 		SetError("null argument");
 		return PIRE_HIP_EINVAL;
 	}
-	EnsureRanked(const_cast<pire_hip_table*>(t));   // hot_states / lds_table_bytes describe the ranked device layout
 	std::shared_lock<std::shared_mutex> stable(const_cast<pire_hip_table*>(t)->adaptMutex);
+	EnsureRanked(const_cast<pire_hip_table*>(t));   // hot_states / lds_table_bytes describe the ranked device layout
 	const HostTable& h = t->host;
 	memset(out, 0, sizeof(*out));
 	out->abi_version = PIRE_HIP_ABI_VERSION;
@@ -1379,6 +1384,13 @@ try {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
 
+// The accessors read t->host under adaptMutex SHARED: a swap in of a table ranked in the background replaces it (table.cpp
+// BackgroundAdaptStep).  (Never from inside an entry point, which holds the lock already.)
+static std::shared_lock<std::shared_mutex> HostLock(const pire_hip_table* t)
+{
+	return t ? std::shared_lock<std::shared_mutex>(const_cast<pire_hip_table*>(t)->adaptMutex) : std::shared_lock<std::shared_mutex>();
+}
+
 static int CheckIdx(const pire_hip_table* t, uint32_t idx)
 {
 	if (!t) {
@@ -1394,6 +1406,7 @@ static int CheckIdx(const pire_hip_table* t, uint32_t idx)
 
 int pire_hip_table_final(const pire_hip_table* t, uint32_t idx)
 try {
+	const auto stable = HostLock(t);
 	if (int rc = CheckIdx(t, idx))
 		return rc;
 	return (t->host.flags[idx] & kFinal) ? 1 : 0;
@@ -1403,6 +1416,7 @@ try {
 
 int pire_hip_table_dead(const pire_hip_table* t, uint32_t idx)
 try {
+	const auto stable = HostLock(t);
 	if (int rc = CheckIdx(t, idx))
 		return rc;
 	return (t->host.flags[idx] & kDead) ? 1 : 0;
@@ -1412,6 +1426,7 @@ try {
 
 int pire_hip_table_accepted_regexps(const pire_hip_table* t, uint32_t idx, const uint64_t** begin, size_t* count)
 try {
+	const auto stable = HostLock(t);
 	if (int rc = CheckIdx(t, idx))
 		return rc;
 	if (!begin || !count) {
@@ -1432,13 +1447,15 @@ try {
 		SetError("bad argument");
 		return PIRE_HIP_EINVAL;
 	}
+	const auto stable = HostLock(t);
 	return t->host.cls[ch];
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
 
 int64_t pire_hip_table_next(const pire_hip_table* t, uint32_t idx, uint32_t ch)
-{
+try {
+	const auto stable = HostLock(t);
 	if (int rc = CheckIdx(t, idx))
 		return rc;
 	if (ch >= kMaxCharUnaligned || ch == kEpsilon) {
@@ -1447,6 +1464,8 @@ int64_t pire_hip_table_next(const pire_hip_table* t, uint32_t idx, uint32_t ch)
 	}
 	const HostTable& h = t->host;
 	return h.next[size_t(idx) * h.letters + h.cls[ch]];
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
 
 int pire_hip_table_layout(const pire_hip_table* t, uint32_t* orig_of_perm, uint8_t* hot_rows)
@@ -1455,6 +1474,7 @@ try {
 		SetError("null table");
 		return PIRE_HIP_EINVAL;
 	}
+	std::shared_lock<std::shared_mutex> stable(const_cast<pire_hip_table*>(t)->adaptMutex);
 	EnsureRanked(const_cast<pire_hip_table*>(t));
 	const HostTable& h = t->host;
 	if (orig_of_perm)
@@ -1473,8 +1493,8 @@ try {
 		SetError("null table");
 		return PIRE_HIP_EINVAL;
 	}
-	EnsureRanked(const_cast<pire_hip_table*>(t));
 	std::shared_lock<std::shared_mutex> stable(const_cast<pire_hip_table*>(t)->adaptMutex);
+	EnsureRanked(const_cast<pire_hip_table*>(t));
 	const HostTable& h = t->host;
 	const uint32_t wide = h.zipFull ? 0 : h.wide;   // a zipped image: pire_hip_table_zip_layout
 	const WideLayout wl = MakeWideLayout(wide, h.letters, 0);
@@ -1504,8 +1524,8 @@ try {
 		SetError("null table / geometry");
 		return PIRE_HIP_EINVAL;
 	}
-	EnsureRanked(const_cast<pire_hip_table*>(t));
 	std::shared_lock<std::shared_mutex> stable(const_cast<pire_hip_table*>(t)->adaptMutex);
+	EnsureRanked(const_cast<pire_hip_table*>(t));
 	const HostTable& h = t->host;
 	memset(geometry, 0, 8 * sizeof(uint32_t));
 	if (!h.zipFull)
@@ -1667,20 +1687,38 @@ KnownBatch TableBatch(const HostWalk& w, uint32_t n, uint32_t maxLen, uint32_t s
 	                      [&](uint32_t st, uint32_t ch) { return w.Next(st, ch); }, [&](uint32_t st) { return w.Dead(st); });
 }
 
+// Marks an entry point tested on this device -- unless a re-ranking has meanwhile zipped the wide image or given the plain rows
+// back (it cleared the bit: ForgetLayoutSelfTests), so that the next call tests the other instantiations.
+void MarkEntryTested(pire_hip_table* t, int dev, uint32_t bit, bool zipped)
+{
+	std::shared_lock<std::shared_mutex> stable(t->adaptMutex);
+	if ((t->host.zipFull != 0) == zipped)
+		t->selfTested[dev].fetch_or(1u << bit);
+}
+
 int SelfTestPrefix(pire_hip_table* t, bool suffix, int a, int b, hipStream_t stream)
 {
 	uint32_t mode = 0;
 	int dev = -1;
 	const uint32_t bit = suffix ? kEntrySuffix : kEntryPrefix;
-	if (t->host.empty || EntryTested(t, bit, &dev) || !EntrySelfTestDue(stream, &mode))
+	if (EntryTested(t, bit, &dev))
 		return PIRE_HIP_OK;
+	// The known batch, its answers and the variants come from the host table under adaptMutex SHARED (a background swap replaces
+	// t->host) and the table's configuration; the lock is released before the variants call the entry point, which takes it again.
+	TableConfigScope scope;
+	std::shared_lock<std::shared_mutex> stable(t->adaptMutex);
+	scope.Push(t);
+	if (t->host.empty || !EntrySelfTestDue(stream, &mode))
+		return PIRE_HIP_OK;
+	const bool zipped = t->host.zipFull != 0;
 	const HostWalk w{t->host};
 	// (prefix: a = throughBegin, b = throughEnd; suffix: a = throughEnd, b = throughBegin -- the mark the walk starts with first)
 	const uint32_t start = a ? w.Next(t->host.initial, suffix ? kEndMark : kBeginMark) : t->host.initial;
 	const KnownBatch kb = TableBatch(w, 320, 200, start, suffix ? 2 : 1);
-	OwnStream own;
+	std::vector<int64_t> wants[2];
 	for (int longest = 0; longest < 2; ++longest) {
-		std::vector<int64_t> want(kb.n), got(kb.n);
+		std::vector<int64_t>& want = wants[longest];
+		want.resize(kb.n);
 		for (uint32_t i = 0; i < kb.n; ++i) {
 			const uint8_t* s0 = kb.text.data() + kb.offsets[i];
 			const uint8_t* s1 = kb.text.data() + kb.offsets[i + 1];
@@ -1688,12 +1726,18 @@ int SelfTestPrefix(pire_hip_table* t, bool suffix, int a, int b, hipStream_t str
 		}
 		if (mode == 2)
 			want[kb.n / 2] += 1;
-		std::vector<std::function<void(pire_hip_config&)>> variants;
-		variants.push_back([](pire_hip_config& c) { c.ragged_act_always = 1; c.no_ragged_act = 0; });   // the ragged kernel with actions
-		if (!suffix)
-			variants.push_back([](pire_hip_config& c) { c.no_ragged_act = 1; c.ragged_act_always = 0; });   // one string per lane
-		if (!suffix && t->host.wide && t->host.states <= 65536)   // ... and the ragged kernel with actions on the class-indexed walk
-			variants.push_back([](pire_hip_config& c) { c.ragged_act_always = 1; c.no_ragged_act = 0; c.walk_variant = 2; c.tiled_variant = 0; c.checked = 0; });
+	}
+	std::vector<std::function<void(pire_hip_config&)>> variants;
+	variants.push_back([](pire_hip_config& c) { c.ragged_act_always = 1; c.no_ragged_act = 0; });   // the ragged kernel with actions
+	if (!suffix)
+		variants.push_back([](pire_hip_config& c) { c.no_ragged_act = 1; c.ragged_act_always = 0; });   // one string per lane
+	if (!suffix && t->host.wide && t->host.states <= 65536)   // ... and the ragged kernel with actions on the class-indexed walk
+		variants.push_back([](pire_hip_config& c) { c.ragged_act_always = 1; c.no_ragged_act = 0; c.walk_variant = 2; c.tiled_variant = 0; c.checked = 0; });
+	stable.unlock();
+	OwnStream own;
+	for (int longest = 0; longest < 2; ++longest) {
+		const std::vector<int64_t>& want = wants[longest];
+		std::vector<int64_t> got(kb.n);
 		const int rc = RunSelfTestVariants(variants, [&]() -> int {
 			std::fill(got.begin(), got.end(), int64_t(-77));
 			const int r = suffix ? pire_hip_suffix(t, kb.text.data(), kb.offsets.data(), kb.n, longest, a, b, 0, got.data(), own.s)
@@ -1709,7 +1753,7 @@ int SelfTestPrefix(pire_hip_table* t, bool suffix, int a, int b, hipStream_t str
 		if (rc != PIRE_HIP_OK)
 			return rc;
 	}
-	t->selfTested[dev].fetch_or(1u << bit);
+	MarkEntryTested(t, dev, bit, zipped);
 	return PIRE_HIP_OK;
 }
 
@@ -1718,8 +1762,14 @@ int SelfTestHalfFinal(pire_hip_table* t, uint32_t flags, hipStream_t stream)
 {
 	uint32_t mode = 0;
 	int dev = -1;
-	if (t->host.empty || EntryTested(t, kEntryHalfFinal, &dev) || !EntrySelfTestDue(stream, &mode))
+	if (EntryTested(t, kEntryHalfFinal, &dev))
 		return PIRE_HIP_OK;
+	TableConfigScope scope;   // (as SelfTestPrefix: the host table under the lock, released before the entry point is called)
+	std::shared_lock<std::shared_mutex> stable(t->adaptMutex);
+	scope.Push(t);
+	if (t->host.empty || !EntrySelfTestDue(stream, &mode))
+		return PIRE_HIP_OK;
+	const bool zipped = t->host.zipFull != 0;
 	const HostTable& h = t->host;
 	const HostWalk w{h};
 	const uint32_t R = h.regexps;
@@ -1754,6 +1804,7 @@ int SelfTestHalfFinal(pire_hip_table* t, uint32_t flags, hipStream_t stream)
 	variants.push_back([](pire_hip_config& c) { c.counting_variant = 1; c.no_ragged_act = 1; });   // one string per lane
 	if (h.wide && h.states <= 65536)   // the ragged kernel with actions on the class-indexed walk
 		variants.push_back([](pire_hip_config& c) { c.counting_variant = 1; c.no_ragged_act = 0; c.walk_variant = 2; c.tiled_variant = 0; c.checked = 0; });
+	stable.unlock();
 	OwnStream own;
 	const int rc = RunSelfTestVariants(variants, [&]() -> int {
 		std::fill(gotIdx.begin(), gotIdx.end(), ~0u);
@@ -1773,7 +1824,7 @@ int SelfTestHalfFinal(pire_hip_table* t, uint32_t flags, hipStream_t stream)
 	});
 	if (rc != PIRE_HIP_OK)
 		return rc;
-	t->selfTested[dev].fetch_or(1u << kEntryHalfFinal);
+	MarkEntryTested(t, dev, kEntryHalfFinal, zipped);
 	return PIRE_HIP_OK;
 }
 

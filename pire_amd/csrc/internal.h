@@ -405,8 +405,21 @@ struct pire_hip_table {
 	bool hasConfig = false;
 	pire_hip_config config = {};
 	std::atomic<uint32_t> selfTested[pirehip::kMaxDevices] = {};   // per device, bit k: Dispatch's kernel kind k passed its known-answer
-	                                                               // batch on this table there (api.cpp SelfTest)
+	                                                               // batch on this table there (api.cpp SelfTest); bits 8-11: the
+	                                                               // entry points with actions (api.cpp SelfTestPrefix, ...)
 };
+namespace pirehip {
+// The bits of pire_hip_table::selfTested whose kernels take a different instantiation on a zipped wide image (wide, ragged_wide,
+// stream_wide and the entry points with actions, whose variants include the wide walk): a ranking that zips the image or gives the
+// plain rows back clears them on every device (ForgetLayoutSelfTests), and the next call of each kind is tested again.  A ranking
+// that keeps the layout keeps them: a background swap may land inside a timed loop.
+constexpr uint32_t kSelfTestedOnWideImage = (1u << 2) | (1u << 4) | (1u << 6) | (0xFu << 8);
+inline void ForgetLayoutSelfTests(pire_hip_table* t)
+{
+	for (auto& bits : t->selfTested)
+		bits.fetch_and(~kSelfTestedOnWideImage);
+}
+}  // namespace pirehip
 namespace pirehip { constexpr uint32_t kMaxAutoAdapts = 6; }
 
 namespace pirehip {
@@ -829,32 +842,48 @@ int LaunchRaggedCapture(const ScanParams& p, unsigned long long* workCounter, co
 // image its ScanParams point at, and an adaptation may run concurrently with scans on other host threads (ADVICE r3:
 // round 3 dropped the lock when FillParams returned).  Two tables (pire_hip_run_pair): acquire in address order.
 extern thread_local const pire_hip_config* g_cfgOverride;   // api.cpp: what GetConfig() returns on this thread when set
-struct TableUse {
-	std::shared_lock<std::shared_mutex> lock;
+// The table's own configuration (pire_hip_table_config_set), if it has one, as what GetConfig() returns on this thread while the
+// scope lives: for an entry point, an adaptation (explicit, automatic or in the background worker), the ranking of a glued table
+// and the entry self-tests, so that every GetConfig() on the paths that rank a table and build its images (ChooseZip,
+// PermuteByScore, BuildDeviceImage, ScoreFromCounters) is the table's.  An override already in force stays: a first-use self-test
+// in progress keeps its own (it already started from the table's).  Push(): the caller holds t->adaptMutex, shared or exclusive;
+// the configuration is COPIED there, so the scope may outlive the lock.
+struct TableConfigScope {
+	pire_hip_config copy = {};
 	const pire_hip_config* outer = nullptr;
 	bool pushed = false;
-	TableUse() {}
-	TableUse(pire_hip_table* t, bool enqueueOnly) { Acquire(t, enqueueOnly); }
-	TableUse(const TableUse&) = delete;
-	TableUse& operator=(const TableUse&) = delete;
-	~TableUse()
+	TableConfigScope() {}
+	TableConfigScope(const TableConfigScope&) = delete;
+	TableConfigScope& operator=(const TableConfigScope&) = delete;
+	~TableConfigScope()
 	{
 		if (pushed)
 			g_cfgOverride = outer;
 	}
+	void Push(const pire_hip_table* t)
+	{
+		if (pushed || !t->hasConfig || g_cfgOverride)
+			return;
+		copy = t->config;
+		outer = g_cfgOverride;
+		g_cfgOverride = &copy;
+		pushed = true;
+	}
+};
+struct TableUse {
+	std::shared_lock<std::shared_mutex> lock;
+	TableConfigScope cfg;
+	TableUse() {}
+	TableUse(pire_hip_table* t, bool enqueueOnly) { Acquire(t, enqueueOnly); }
+	TableUse(const TableUse&) = delete;
+	TableUse& operator=(const TableUse&) = delete;
 	void Acquire(pire_hip_table* t, bool enqueueOnly)
 	{
 		if (lock.owns_lock())
 			return;   // a second look at the same table inside one entry point (an adaptation would wait for this very lock)
 		MaybeAutoAdapt(t, enqueueOnly);
 		lock = std::shared_lock<std::shared_mutex>(t->adaptMutex);
-		// the table's own configuration, if it has one, for everything this entry point does on this thread (a first-use
-		// self-test in progress keeps its own: it already started from the table's)
-		if (t->hasConfig && !g_cfgOverride) {
-			outer = g_cfgOverride;
-			g_cfgOverride = &t->config;
-			pushed = true;
-		}
+		cfg.Push(t);   // for everything this entry point does on this thread
 	}
 };
 // for the other translation units: TableUse::Acquire(t) + FillParams

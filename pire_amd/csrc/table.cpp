@@ -1318,10 +1318,13 @@ int EnsureActDist(pire_hip_table* t, const uint8_t** distFinalPerm, const uint8_
 	return PIRE_HIP_OK;
 }
 
+// (the caller holds adaptMutex, shared or exclusive: the ranking of a glued table is made under the table's configuration)
 void EnsureRanked(pire_hip_table* t)
 {
 	std::lock_guard<std::mutex> lock(t->uploadMutex);
 	if (!t->host.ranked) {
+		TableConfigScope scope;
+		scope.Push(t);
 		ChooseHotAndPermute(t->host);
 		t->host.ranked = true;
 	}
@@ -1500,9 +1503,11 @@ void BackgroundWorker(pire_hip_table* t, int dev)
 	std::unique_ptr<HostTable> h;
 	DeviceTable cur;
 	uint64_t launched = 0;
+	TableConfigScope scope;   // the ranking and the image below follow the table's configuration (this thread has no other)
 	{
 		// the table as it is now (an adaptation of another kind would have waited for this thread before it took the lock)
 		std::shared_lock<std::shared_mutex> stable(t->adaptMutex);
+		scope.Push(t);
 		std::lock_guard<std::mutex> lock(t->uploadMutex);
 		cur = t->devs[dev];
 		if (cur.device == dev)
@@ -1613,7 +1618,18 @@ void BackgroundAdaptStep(pire_hip_table* t, uint64_t threshold)
 				t->retired.push_back(t->devs[k]);
 				t->devs[k] = DeviceTable();
 			}
-		t->host = std::move(*bg.host);
+		// The arrays in the reference's numbering are the same in both tables (a ranking renumbers the device side only): the
+		// table keeps its own allocations, so that what the accessors handed out (pire_hip_table_accepted_regexps) stays valid
+		// until pire_hip_table_destroy.
+		HostTable& fresh = *bg.host;
+		fresh.cls.swap(t->host.cls);
+		fresh.next.swap(t->host.next);
+		fresh.flags.swap(t->host.flags);
+		fresh.acceptOff.swap(t->host.acceptOff);
+		fresh.acceptIds.swap(t->host.acceptIds);
+		if ((fresh.zipFull != 0) != (t->host.zipFull != 0))
+			ForgetLayoutSelfTests(t);   // the zipped / plain instantiations have not run their known-answer batches on this table
+		t->host = std::move(fresh);
 		bg.host.reset();
 		t->devs[bg.device] = bg.image;
 		bg.image = DeviceTable();
@@ -1702,6 +1718,8 @@ int AdaptTable(pire_hip_table* t, uint32_t* changedRows, bool automatic)
 		*changedRows = 0;
 	JoinBackgroundAdapt(t);   // (before the lock: the worker takes it shared)
 	std::unique_lock<std::shared_mutex> exclusive(t->adaptMutex);
+	TableConfigScope scope;   // the ranking, the zip decision and the new images follow the table's configuration
+	scope.Push(t);
 	if (automatic) {
 		// re-check under the lock: another thread may just have done it
 		uint64_t traps = 0;
@@ -1769,9 +1787,12 @@ int AdaptTable(pire_hip_table* t, uint32_t* changedRows, bool automatic)
 		(void)hipSetDevice(cur);
 		return PIRE_HIP_OK;   // nothing trapped: the current rows already cover the traffic
 	}
+	const bool zipped = h.zipFull != 0;
 	PermuteByScore(h, sc.score);
 	if (sc.wideSeen)
 		h.outsideWide = sc.wideSeenOutside;
+	if ((h.zipFull != 0) != zipped)
+		ForgetLayoutSelfTests(t);   // the zipped / plain instantiations have not run their known-answer batches on this table
 	std::vector<uint32_t> after(h.origOfPerm.begin(), h.origOfPerm.begin() + h.hot);
 	std::sort(after.begin(), after.end());
 	std::vector<uint32_t> diff;
