@@ -460,9 +460,11 @@ int pire_hip_prefix(pire_hip_table* t, const void* text, const uint64_t* offsets
  *   out_state_idx1[i], out_state_idx2[i] = StateIndex of the two end states (pair.h:79-82),
  *   out_final[i] = Final(state1) || Final(state2)                            (pair.h:69-72).
  * Device pointers only (flags must carry PIRE_HIP_RUN_ON_DEVICE; BEGIN / END apply to both scanners).  Fixed-length
- * records (pire_hip_run_pair_strided; len a multiple of 256, stride of 16, text 16-byte aligned) take ONE pass with
- * both tables' dense rows in LDS: the text is read once and the two lookups of a byte overlap; anything else, and the
- * last n mod 64 records, takes two ordinary passes behind the same call.  Any output pointer may be NULL.
+ * records (pire_hip_run_pair_strided; len >= 256 with an EVEN number of whole 128-byte tiles, i.e. (len / 128) % 2 == 0
+ * -- 256..383, 512..639, ... --, stride a multiple of 16, text 16-byte aligned, at least 64 records) take ONE pass with
+ * both tables' dense rows in LDS: the text is read once and the two lookups of a byte overlap; what is left of a record
+ * behind its whole tiles (len % 128 bytes) is walked byte by byte in the same pass.  Anything else, and the last
+ * n mod 64 records, takes two ordinary passes behind the same call.  Any output pointer may be NULL.
  */
 int pire_hip_run_pair(pire_hip_table* t1, pire_hip_table* t2, const void* text, const uint64_t* offsets, uint64_t n,
                       uint32_t flags, uint32_t* out_state_idx1, uint32_t* out_state_idx2, uint8_t* out_final, void* stream);

@@ -296,6 +296,8 @@ __global__ __launch_bounds__(1024, 4) void ScanPairTiledKernel(PairParams q)
 	PairWaitTile<0>(b);
 }
 
+// Whole pairs of 128-byte tiles (the ring of two), at least one; len need NOT be a multiple of 256 or of 128: the kernel walks
+// the len % 128 bytes behind the last whole tile straight from memory (tests/test_pair_seg_tails.py pins both).
 bool PairTiledEligible(const ScanParams& a, const ScanParams& b)
 {
 	const uint32_t need = kPairBaseB + (b.hot + 1) * 256 + 512 + 2 * 528 + 64;
