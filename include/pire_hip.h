@@ -423,6 +423,55 @@ int pire_hip_run_strided(pire_hip_table* t, const void* text, uint64_t n, uint64
  */
 int pire_hip_step(pire_hip_table* t, uint32_t* state_idx, uint64_t n, uint32_t ch, void* stream);
 
+/* ---- which strings matched which regexps, on the device --------------------------------------------------- */
+
+/* W = max(1, ceil(RegexpsCount() / 64)): the number of 64-bit words of a regexp mask of this table (0: null table). */
+uint32_t pire_hip_table_mask_words(const pire_hip_table* t);
+
+/*
+ * From end states to matches.  state_idx[i] is a StateIndex as pire_hip_run writes it (reference numbering).
+ *   mask(i)[w] bit b  <=>  regexp 64*w + b is in AcceptedRegexps(state_idx[i])   (multi.h:149-158)
+ *   selected(i)       <=>  want == NULL ? Final(state_idx[i]) : (mask(i) & want) != 0     (want: W words; bits at or
+ *                          above RegexpsCount() are ignored; a scanner with 0 regexps selects nothing)
+ * out_masks     (nullable) [n][W]   mask(i) of every string
+ * out_hits      (nullable) [hit_cap] the indices i of the selected strings, ASCENDING
+ * out_hit_masks (nullable) [hit_cap][W] mask of out_hits[k]
+ * out_hit_count (required) *count = number of selected strings, also when it exceeds hit_cap; only the first
+ *               min(count, hit_cap) entries of out_hits / out_hit_masks are written, nothing behind them
+ * n == 0 writes a count of 0.  n < 2^32.
+ * flags: PIRE_HIP_RUN_ON_DEVICE -> every pointer (want included) is a device pointer and the call only enqueues on
+ *        `stream`: three small kernels whose per-call scratch (n / 8 + n / 256 bytes) comes from the stream-ordered
+ *        allocator (hipMallocAsync / hipFreeAsync on `stream`), as the row kernels' does (see pire_hip_run_half_final):
+ *        enqueue-only, and legal inside a stream capture under the same condition as those calls -- not something every
+ *        capture mode accepts.  The first call on a device uploads the table's mask image (W words and the Final flag
+ *        per state, by reference state index -- no re-ranking touches it) synchronously; pire_hip_table_upload()
+ *        beforehand does that too.  A state_idx[i] >= Size() is undefined in this mode.
+ *        Otherwise host pointers: staged, synchronises; a state_idx[i] >= Size() is PIRE_HIP_EINVAL.
+ * PIRE_HIP_EINVAL before any device is touched: null table, n with a null state_idx, null out_hit_count, hit_cap > 0
+ * with null out_hits, out_hit_masks without out_hits.
+ * pire_hip_last_kernel() is not changed by the select pass: it keeps naming the scan kernel.
+ */
+int pire_hip_select(pire_hip_table* t, const uint32_t* state_idx, uint64_t n, const uint64_t* want, uint32_t flags,
+                    uint64_t* out_masks, uint64_t* out_hits, uint64_t* out_hit_masks, uint64_t hit_cap,
+                    uint64_t* out_hit_count, void* stream);
+
+/*
+ * pire_hip_run / pire_hip_run_strided followed by pire_hip_select behind one call, on the same stream.  The first
+ * arguments, the flags (BEGIN / END / ON_DEVICE / GENERIC / HOST_OFFSETS / NO_PEEK) and out_state_idx / out_final /
+ * out_counts (each nullable) are the run calls'; the rest pire_hip_select's.  With out_state_idx == NULL the state indices
+ * live in scratch of the library's own (stream-ordered in ON_DEVICE mode).  In host-pointer mode the hit indices are
+ * relative to the whole batch, whatever chunks the staging cut it into.  With PIRE_HIP_RUN_HOST_OFFSETS only `offsets`
+ * is a host pointer; what makes the run call wait makes this one wait.
+ */
+int pire_hip_run_select(pire_hip_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
+                        const uint32_t* init_state_idx, uint32_t* out_state_idx, uint8_t* out_final, uint64_t* out_counts,
+                        const uint64_t* want, uint64_t* out_masks, uint64_t* out_hits, uint64_t* out_hit_masks,
+                        uint64_t hit_cap, uint64_t* out_hit_count, void* stream);
+int pire_hip_run_select_strided(pire_hip_table* t, const void* text, uint64_t n, uint64_t len, uint64_t stride, uint32_t flags,
+                                const uint32_t* init_state_idx, uint32_t* out_state_idx, uint8_t* out_final,
+                                uint64_t* out_counts, const uint64_t* want, uint64_t* out_masks, uint64_t* out_hits,
+                                uint64_t* out_hit_masks, uint64_t hit_cap, uint64_t* out_hit_count, void* stream);
+
 /*
  * Batched Runner over the table walked as a Pire::HalfFinalScanner (scanners/half_final.h:32-227).  A
  * HalfFinalScanner IS a Scanner (same Save() bytes, ingest it with pire_hip_table_create), but its Initialize and

@@ -258,12 +258,42 @@ public:
 	const uint32_t* DeviceStateIndices() { Execute(); return static_cast<const uint32_t*>(m_devIdx.Get()); }
 	const uint8_t* DeviceFinals() { Execute(); return static_cast<const uint8_t*>(m_devFin.Get()); }
 
+	/*
+	 * Which strings matched which regexps, answered on the device (pire_hip_select) -- after a Run*().End():
+	 *     run.Begin().Run(text, offsets, n).End().Select();      // the strings that end in a Final state
+	 *     run.Select({2, 5});                                    // ... that match regexp 2 or regexp 5
+	 *     run.Hits()       ascending indices of the selected strings          run.HitCount()  how many
+	 *     run.HitMasks()   MaskWords() words per hit: bit r of the mask <=> r is in AcceptedRegexps(State())
+	 * The host loop over States() with one Final / AcceptedRegexps lookup per string gives the same answer in time
+	 * proportional to the batch; this one moves 8 * (1 + MaskWords()) bytes per HIT.  After RunDevice*: DeviceHits() /
+	 * DeviceHitMasks() / DeviceHitCount() leave them where a consumer on the GPU wants them (ordered on RunDevice's stream).
+	 */
+	BatchRunner& Select(const std::vector<size_t>& want = std::vector<size_t>())
+	{
+		m_want.assign(MaskWords(), 0);
+		m_haveWant = !want.empty();
+		for (size_t i = 0; i < want.size(); ++i)
+			if (want[i] < m_want.size() * 64)
+				m_want[want[i] / 64] |= uint64_t(1) << (want[i] % 64);
+		m_selected = m_hitsFetched = false;
+		return *this;
+	}
+	size_t MaskWords() const { return pire_hip_table_mask_words(m_table->Handle()); }
+	uint64_t HitCount() { FetchHits(); return m_hitCount; }
+	const std::vector<uint64_t>& Hits() { FetchHits(); return m_hits; }
+	const std::vector<uint64_t>& HitMasks() { FetchHits(); return m_hitMasks; }
+	const uint64_t* DeviceHits() { ExecuteSelect(); return static_cast<const uint64_t*>(m_devHits.Get()); }
+	const uint64_t* DeviceHitMasks() { ExecuteSelect(); return static_cast<const uint64_t*>(m_devHitMasks.Get()); }
+	const uint64_t* DeviceHitCount() { ExecuteSelect(); return static_cast<const uint64_t*>(m_devHitCount.Get()); }
+
 	const Table<Scanner>& GetTable() const { return *m_table; }
 	uint32_t Flags() const { return m_flags; }
 
 private:
 	void Reset()
 	{
+		m_selected = m_hitsFetched = m_haveWant = false;
+		m_hitCount = 0;
 		m_flags = 0;
 		m_text = nullptr;
 		m_offsets = nullptr;
@@ -312,6 +342,59 @@ private:
 		m_ran = true;
 	}
 
+	void ExecuteSelect()
+	{
+		const bool ranBefore = m_ran;
+		Execute();
+		if (m_selected && ranBefore)
+			return;
+		if (m_want.empty())
+			Select();
+		const size_t w = m_want.size();
+		if (m_onDevice) {
+			uint64_t* hits = static_cast<uint64_t*>(m_devHits.Reserve((m_n + 1) * 8));
+			uint64_t* masks = static_cast<uint64_t*>(m_devHitMasks.Reserve((m_n + 1) * w * 8));
+			uint64_t* count = static_cast<uint64_t*>(m_devHitCount.Reserve(8));
+			const uint64_t* want = nullptr;
+			if (m_haveWant) {
+				want = static_cast<const uint64_t*>(m_devWant.Reserve(w * 8));
+				Check(pire_hip_copy_to_device(m_devWant.Get(), m_want.data(), w * 8, m_stream));
+			}
+			Check(pire_hip_select(m_table->Handle(), static_cast<const uint32_t*>(m_devIdx.Get()), m_n, want,
+			                      PIRE_HIP_RUN_ON_DEVICE, nullptr, hits, masks, m_n, count, m_stream));
+			if (m_haveWant)
+				Check(pire_hip_stream_synchronize(m_stream));   // m_want was the source of an asynchronous copy
+			m_hitsFetched = false;
+		} else {
+			m_hits.resize(m_n);
+			m_hitMasks.resize(m_n * w);
+			Check(pire_hip_select(m_table->Handle(), m_idx.data(), m_n, m_haveWant ? m_want.data() : nullptr, 0, nullptr,
+			                      m_hits.data(), m_hitMasks.data(), m_n, &m_hitCount, nullptr));
+			m_hits.resize(m_hitCount);
+			m_hitMasks.resize(m_hitCount * w);
+			m_hitsFetched = true;
+		}
+		m_selected = true;
+	}
+
+	void FetchHits()
+	{
+		ExecuteSelect();
+		if (m_hitsFetched)
+			return;
+		const size_t w = m_want.size();
+		Check(pire_hip_copy_to_host(&m_hitCount, m_devHitCount.Get(), 8, m_stream));
+		Check(pire_hip_stream_synchronize(m_stream));
+		m_hits.resize(m_hitCount);
+		m_hitMasks.resize(m_hitCount * w);
+		if (m_hitCount) {
+			Check(pire_hip_copy_to_host(m_hits.data(), m_devHits.Get(), m_hitCount * 8, m_stream));
+			Check(pire_hip_copy_to_host(m_hitMasks.data(), m_devHitMasks.Get(), m_hitCount * w * 8, m_stream));
+			Check(pire_hip_stream_synchronize(m_stream));
+		}
+		m_hitsFetched = true;
+	}
+
 	/* Per-string results on the host, as Scanner::State values. */
 	void Fetch()
 	{
@@ -351,6 +434,10 @@ private:
 	std::vector<char> m_final;
 	std::vector<uint64_t> m_counts;
 	DeviceBuffer m_devIdx, m_devFin, m_devCounts, m_devInit;
+	bool m_selected, m_hitsFetched, m_haveWant;
+	uint64_t m_hitCount;
+	std::vector<uint64_t> m_want, m_hits, m_hitMasks;
+	DeviceBuffer m_devHits, m_devHitMasks, m_devHitCount, m_devWant;
 	ystring m_ownText;
 	std::vector<uint64_t> m_ownOffsets;
 };

@@ -167,6 +167,15 @@ ABI = [
     ("pire_hip_run_strided", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_step", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
+    ("pire_hip_table_mask_words", C.c_uint32, [C.c_void_p]),
+    ("pire_hip_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_run_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                      C.c_void_p, C.c_void_p]),
+    ("pire_hip_run_select_strided", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_run_half_final", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_prefix", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_uint32,
@@ -506,6 +515,93 @@ class Table:
         _check(lib().pire_hip_run(self._h, text_ptr or None, offsets_ptr or None, n, flags | FLAG_ON_DEVICE,
                                   init_ptr or None, out_idx_ptr or None, out_final_ptr or None,
                                   out_counts_ptr or None, stream or None))
+
+    # --- which strings matched which regexps (pire_hip_select): masks are uint64[n, mask_words], hits ascending indices
+    @property
+    def mask_words(self) -> int:
+        """W = max(1, ceil(RegexpsCount / 64)): 64-bit words of a regexp mask."""
+        return int(lib().pire_hip_table_mask_words(self._h))
+
+    def want_mask(self, want):
+        """None, or uint64[mask_words] from an iterable of regexp numbers / an array that already is one."""
+        if want is None:
+            return None
+        if isinstance(want, np.ndarray) and want.dtype == np.uint64:
+            if want.size != self.mask_words:
+                raise ValueError("want: %d words, the table's masks have %d" % (want.size, self.mask_words))
+            return np.ascontiguousarray(want)
+        m = np.zeros(self.mask_words, dtype=np.uint64)
+        for r in want:
+            if int(r) < 64 * self.mask_words:
+                m[int(r) // 64] |= np.uint64(1 << (int(r) % 64))
+        return m
+
+    def _select_outputs(self, n, hit_cap, masks, hit_masks):
+        cap = n if hit_cap is None else int(hit_cap)
+        w = self.mask_words
+        return (cap, np.zeros((n, w), dtype=np.uint64) if masks else None, np.zeros(cap, dtype=np.uint64),
+                np.zeros((cap, w), dtype=np.uint64) if hit_masks else None, C.c_uint64(0))
+
+    @staticmethod
+    def _select_result(cap, om, oh, ohm, cnt):
+        k = min(int(cnt.value), cap)
+        return {"masks": om, "hits": oh[:k], "hit_masks": None if ohm is None else ohm[:k], "count": int(cnt.value)}
+
+    def select(self, state_idx, want=None, hit_cap=None, masks=True, hit_masks=True):
+        """pire_hip_select on host arrays: {"masks", "hits", "hit_masks", "count"}; hit_cap None = room for every string."""
+        idx = np.ascontiguousarray(state_idx, dtype=np.uint32)
+        wm = self.want_mask(want)
+        cap, om, oh, ohm, cnt = self._select_outputs(len(idx), hit_cap, masks, hit_masks)
+        _check(lib().pire_hip_select(self._h, idx.ctypes.data if idx.size else None, len(idx), _np_ptr(wm), 0, _np_ptr(om),
+                                     oh.ctypes.data if cap else None, _np_ptr(ohm) if cap else None, cap, C.byref(cnt), None))
+        return self._select_result(cap, om, oh, ohm, cnt)
+
+    def run_select(self, text, offsets, flags=FLAG_BEGIN | FLAG_END, want=None, hit_cap=None, init_idx=None, masks=True,
+                   hit_masks=True, states=True):
+        """pire_hip_run_select on host arrays: select()'s dict plus "idx" / "final" of the scan (states=False: the library
+        keeps the state indices to itself)."""
+        text = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray))
+                                    else text, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        idx = np.empty(n, dtype=np.uint32) if states else None
+        fin = np.empty(n, dtype=np.uint8) if states else None
+        init = None if init_idx is None else np.ascontiguousarray(init_idx, dtype=np.uint32)
+        wm = self.want_mask(want)
+        cap, om, oh, ohm, cnt = self._select_outputs(n, hit_cap, masks, hit_masks)
+        _check(lib().pire_hip_run_select(self._h, text.ctypes.data if text.size else None, offsets.ctypes.data, n,
+                                         flags & ~FLAG_ON_DEVICE, _np_ptr(init), _np_ptr(idx), _np_ptr(fin), None, _np_ptr(wm),
+                                         _np_ptr(om), oh.ctypes.data if cap else None, _np_ptr(ohm) if cap else None, cap,
+                                         C.byref(cnt), None))
+        out = self._select_result(cap, om, oh, ohm, cnt)
+        out["idx"], out["final"] = idx, fin
+        return out
+
+    def select_device(self, state_idx_ptr: int, n: int, out_hit_count_ptr: int, want_ptr=0, out_masks_ptr=0, out_hits_ptr=0,
+                      out_hit_masks_ptr=0, hit_cap=0, stream: int = 0):
+        """pire_hip_select with PIRE_HIP_RUN_ON_DEVICE: raw device addresses, only enqueues on `stream`."""
+        _check(lib().pire_hip_select(self._h, state_idx_ptr or None, n, want_ptr or None, FLAG_ON_DEVICE, out_masks_ptr or None,
+                                     out_hits_ptr or None, out_hit_masks_ptr or None, hit_cap, out_hit_count_ptr or None,
+                                     stream or None))
+
+    def run_select_device(self, text_ptr: int, offsets_ptr: int, n: int, flags, out_hit_count_ptr: int, want_ptr=0,
+                          out_masks_ptr=0, out_hits_ptr=0, out_hit_masks_ptr=0, hit_cap=0, out_idx_ptr=0, out_final_ptr=0,
+                          out_counts_ptr=0, init_ptr=0, stream: int = 0):
+        """pire_hip_run_select on device pointers (FLAG_HOST_OFFSETS in `flags`: offsets_ptr is a host address)."""
+        _check(lib().pire_hip_run_select(self._h, text_ptr or None, offsets_ptr or None, n, flags | FLAG_ON_DEVICE,
+                                         init_ptr or None, out_idx_ptr or None, out_final_ptr or None, out_counts_ptr or None,
+                                         want_ptr or None, out_masks_ptr or None, out_hits_ptr or None,
+                                         out_hit_masks_ptr or None, hit_cap, out_hit_count_ptr or None, stream or None))
+
+    def run_select_strided_device(self, text_ptr: int, n: int, length: int, stride: int, flags, out_hit_count_ptr: int,
+                                  want_ptr=0, out_masks_ptr=0, out_hits_ptr=0, out_hit_masks_ptr=0, hit_cap=0, out_idx_ptr=0,
+                                  out_final_ptr=0, out_counts_ptr=0, init_ptr=0, stream: int = 0):
+        """pire_hip_run_select_strided on device pointers: fixed-length records, only enqueues on `stream`."""
+        _check(lib().pire_hip_run_select_strided(self._h, text_ptr or None, n, length, stride, flags | FLAG_ON_DEVICE,
+                                                 init_ptr or None, out_idx_ptr or None, out_final_ptr or None,
+                                                 out_counts_ptr or None, want_ptr or None, out_masks_ptr or None,
+                                                 out_hits_ptr or None, out_hit_masks_ptr or None, hit_cap,
+                                                 out_hit_count_ptr or None, stream or None))
 
     def run_half_final(self, text, offsets, flags=FLAG_BEGIN | FLAG_END):
         """The table walked as a Pire::HalfFinalScanner: (StateIndex, Final, Result[n, regexps]) for host strings."""

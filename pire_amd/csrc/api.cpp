@@ -1238,8 +1238,10 @@ try {
 	// ... and what the counting walk of the same table (pire_hip_run_half_final) keeps on the device, when the table
 	// qualifies for its row kernel: an ON_DEVICE call after this uploads nothing
 	if (!t->host.empty && t->host.regexps && t->host.regexps <= 8)
-		return UploadHalfRows(t);
-	return PIRE_HIP_OK;
+		if (int rc = UploadHalfRows(t))
+			return rc;
+	// ... and the mask image of pire_hip_select (reference numbering: uploaded once per device, select.hip)
+	return UploadSelect(t, nullptr);
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
@@ -1314,6 +1316,7 @@ void pire_hip_table_destroy(pire_hip_table* t)
 	JoinBackgroundAdapt(t);
 	FreeAllDeviceTables(t);
 	FreeHalfRows(t);
+	FreeSelect(t);
 	if (t->segProduct)
 		FreeAllDeviceTables(t->segProduct.get());   // the product automaton of the segmented scan's two modes
 	delete t;
@@ -1580,6 +1583,189 @@ try {
 	}
 	return RunImpl(t, text, nullptr, n, len, stride, flags, init_state_idx, out_state_idx, out_final, out_counts,
 	               stream);
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+// ---- from end states to matches (select.hip) ---------------------------------------------------------------------------
+namespace {
+
+// What pire_hip_select refuses before any device is touched
+int SelectArgsInvalid(const pire_hip_table* t, const uint32_t* stateIdx, bool needIdx, uint64_t n, const uint64_t* outHits,
+                      const uint64_t* outHitMasks, uint64_t hitCap, const uint64_t* outHitCount)
+{
+	const char* what = !t                           ? "null table"
+	                   : needIdx && n && !stateIdx  ? "null state_idx"
+	                   : !outHitCount               ? "null out_hit_count"
+	                   : hitCap && !outHits         ? "hit_cap > 0 with null out_hits"
+	                   : outHitMasks && !outHits    ? "out_hit_masks without out_hits"
+	                                                : nullptr;
+	if (!what)
+		return PIRE_HIP_OK;
+	SetError(std::string("pire_hip_select: ") + what);
+	return PIRE_HIP_EINVAL;
+}
+
+int SelectImpl(pire_hip_table* t, const uint32_t* stateIdx, uint64_t n, const uint64_t* want, uint32_t flags,
+               uint64_t* outMasks, uint64_t* outHits, uint64_t* outHitMasks, uint64_t hitCap, uint64_t* outHitCount,
+               hipStream_t stream)
+{
+	uint32_t states, words;
+	{
+		const std::shared_lock<std::shared_mutex> stable(t->adaptMutex);
+		states = t->host.states;
+		words = SelectMaskWords(t->host.regexps);
+	}
+	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
+	if (!onDevice) {
+		for (uint64_t i = 0; i < n; ++i)
+			if (stateIdx[i] >= states) {
+				SetError("pire_hip_select: state_idx out of range");
+				return PIRE_HIP_EINVAL;
+			}
+		if (n == 0) {
+			*outHitCount = 0;
+			return PIRE_HIP_OK;
+		}
+	}
+	SelectDevice image;
+	{
+		// (the image is in reference numbering: built once, whatever re-rankings come; the lock is for reading t->host)
+		const std::shared_lock<std::shared_mutex> stable(t->adaptMutex);
+		if (int rc = UploadSelect(t, &image))
+			return rc;
+	}
+	if (onDevice)
+		return LaunchSelect(image, states, words, stateIdx, n, want, outMasks, outHits, outHitMasks, hitCap, outHitCount, stream);
+
+	// host pointers: staged in, the three kernels, staged out -- the hits only as far as they were written
+	Staging st(stream);
+	const uint32_t* dIdx = nullptr;
+	const uint64_t* dWant = nullptr;
+	if (int rc = st.In(stateIdx, size_t(n), &dIdx, stream))
+		return rc;
+	if (want)
+		if (int rc = st.In(want, size_t(words), &dWant, stream))
+			return rc;
+	const uint64_t cap = std::min<uint64_t>(hitCap, n);
+	void *dMasks = nullptr, *dHits = nullptr, *dHitMasks = nullptr, *dCount = nullptr;
+	if (int rc = st.Alloc(&dCount, 8))
+		return rc;
+	if (outMasks)
+		if (int rc = st.Alloc(&dMasks, size_t(n) * words * 8))
+			return rc;
+	if (outHits && cap)
+		if (int rc = st.Alloc(&dHits, size_t(cap) * 8))
+			return rc;
+	if (outHitMasks && cap)
+		if (int rc = st.Alloc(&dHitMasks, size_t(cap) * words * 8))
+			return rc;
+	if (int rc = st.Flush())
+		return rc;
+	if (int rc = LaunchSelect(image, states, words, dIdx, n, dWant, static_cast<uint64_t*>(dMasks), static_cast<uint64_t*>(dHits),
+	                          static_cast<uint64_t*>(dHitMasks), dHits ? cap : 0, static_cast<uint64_t*>(dCount), stream))
+		return rc;
+	uint64_t count = 0;
+	if (int rc = st.Out(&count, dCount, 8))
+		return rc;
+	if (int rc = st.Out(outMasks, dMasks, size_t(n) * words * 8))
+		return rc;
+	if (int rc = st.Finish())
+		return rc;
+	*outHitCount = count;
+	const uint64_t written = std::min<uint64_t>(count, dHits ? cap : 0);
+	if (written) {
+		hipError_t e = hipMemcpy(outHits, dHits, size_t(written) * 8, hipMemcpyDeviceToHost);
+		if (e == hipSuccess && dHitMasks)
+			e = hipMemcpy(outHitMasks, dHitMasks, size_t(written) * words * 8, hipMemcpyDeviceToHost);
+		if (e != hipSuccess)
+			return HipFail(e, "hipMemcpy(hits)");
+	}
+	return PIRE_HIP_OK;
+}
+
+// pire_hip_run[_strided] followed by pire_hip_select on the same stream; `run` makes the scan call with the state-index
+// array it is given
+int RunSelectImpl(pire_hip_table* t, uint64_t n, const uint64_t* want, uint32_t flags, uint32_t* outIdx, uint64_t* outMasks,
+                  uint64_t* outHits, uint64_t* outHitMasks, uint64_t hitCap, uint64_t* outHitCount, void* streamPtr,
+                  const std::function<int(uint32_t*)>& run)
+{
+	if (int rc = SelectArgsInvalid(t, nullptr, false, n, outHits, outHitMasks, hitCap, outHitCount))
+		return rc;
+	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+	if (!(flags & PIRE_HIP_RUN_ON_DEVICE)) {
+		// (whatever staging path the scan takes -- chunked, one piece, segmented --, its state indices arrive in ONE host
+		// array before the select pass sees them: hit indices are relative to the whole batch)
+		std::vector<uint32_t> own;
+		if (!outIdx) {
+			own.resize(size_t(n));
+			outIdx = own.data();
+		}
+		if (int rc = run(outIdx))
+			return rc;
+		return SelectImpl(t, outIdx, n, want, 0, outMasks, outHits, outHitMasks, hitCap, outHitCount, stream);
+	}
+	void* scratch = nullptr;
+	if (!outIdx && n) {
+		const hipError_t e = hipMallocAsync(&scratch, size_t(n) * 4, stream);
+		if (e != hipSuccess)
+			return HipFail(e, "hipMallocAsync(state indices)");
+		outIdx = static_cast<uint32_t*>(scratch);
+	}
+	int rc = run(outIdx);
+	if (!rc)
+		rc = SelectImpl(t, outIdx, n, want, PIRE_HIP_RUN_ON_DEVICE, outMasks, outHits, outHitMasks, hitCap, outHitCount, stream);
+	if (scratch)
+		(void)hipFreeAsync(scratch, stream);
+	return rc;
+}
+
+}  // namespace
+
+uint32_t pire_hip_table_mask_words(const pire_hip_table* t)
+try {
+	const auto stable = HostLock(t);
+	return t ? SelectMaskWords(t->host.regexps) : 0;
+} catch (...) {
+	pirehip::HandleException();
+	return 0;
+}
+
+int pire_hip_select(pire_hip_table* t, const uint32_t* state_idx, uint64_t n, const uint64_t* want, uint32_t flags,
+                    uint64_t* out_masks, uint64_t* out_hits, uint64_t* out_hit_masks, uint64_t hit_cap,
+                    uint64_t* out_hit_count, void* stream)
+try {
+	if (int rc = SelectArgsInvalid(t, state_idx, true, n, out_hits, out_hit_masks, hit_cap, out_hit_count))
+		return rc;
+	return SelectImpl(t, state_idx, n, want, flags, out_masks, out_hits, out_hit_masks, hit_cap, out_hit_count,
+	                  static_cast<hipStream_t>(stream));
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_run_select(pire_hip_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
+                        const uint32_t* init_state_idx, uint32_t* out_state_idx, uint8_t* out_final, uint64_t* out_counts,
+                        const uint64_t* want, uint64_t* out_masks, uint64_t* out_hits, uint64_t* out_hit_masks,
+                        uint64_t hit_cap, uint64_t* out_hit_count, void* stream)
+try {
+	return RunSelectImpl(t, n, want, flags, out_state_idx, out_masks, out_hits, out_hit_masks, hit_cap, out_hit_count, stream,
+	                     [&](uint32_t* idx) {
+		                     return pire_hip_run(t, text, offsets, n, flags, init_state_idx, idx, out_final, out_counts, stream);
+	                     });
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_run_select_strided(pire_hip_table* t, const void* text, uint64_t n, uint64_t len, uint64_t stride, uint32_t flags,
+                                const uint32_t* init_state_idx, uint32_t* out_state_idx, uint8_t* out_final,
+                                uint64_t* out_counts, const uint64_t* want, uint64_t* out_masks, uint64_t* out_hits,
+                                uint64_t* out_hit_masks, uint64_t hit_cap, uint64_t* out_hit_count, void* stream)
+try {
+	return RunSelectImpl(t, n, want, flags, out_state_idx, out_masks, out_hits, out_hit_masks, hit_cap, out_hit_count, stream,
+	                     [&](uint32_t* idx) {
+		                     return pire_hip_run_strided(t, text, n, len, stride, flags, init_state_idx, idx, out_final, out_counts,
+		                                                 stream);
+	                     });
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }

@@ -347,6 +347,22 @@ struct HalfRowsDevice {
 	uint8_t* letterOf = nullptr;
 	uint8_t* finalTag = nullptr;
 };
+// pire_hip_select (select.hip): per state, by REFERENCE state index, the W = max(1, ceil(regexps / 64)) words of its
+// AcceptedRegexps() mask and its Final flag.  A re-ranking (pire_hip_table_adapt, the automatic ones, a swap in the
+// background) renumbers the DEVICE ids and nothing else, so this image is built once per table, uploaded once per device
+// and never touched again: the adaptation paths do not know it exists.  (FinRec::acceptMask behind permOfOrig holds the
+// same bits for <= 64 regexps -- in the numbering that does change under a swap.)
+struct SelectHost {
+	bool built = false;
+	uint32_t words = 1;
+	std::vector<uint64_t> masks;   // [states * words]
+	std::vector<uint8_t> fin;      // [states]
+};
+struct SelectDevice {
+	int device = -1;
+	uint64_t* masks = nullptr;
+	uint8_t* fin = nullptr;
+};
 }  // namespace pirehip
 
 struct pire_hip_table {
@@ -354,6 +370,9 @@ struct pire_hip_table {
 	pirehip::HalfRowsHost halfRows;
 	pirehip::HalfRowsDevice halfRowsDev[pirehip::kMaxDevices];
 	std::mutex halfRowsMutex;
+	pirehip::SelectHost select;
+	pirehip::SelectDevice selectDev[pirehip::kMaxDevices];
+	std::mutex selectMutex;
 	// One image per HIP device (devs[d].device == d once uploaded), so that one handle serves every GPU of the node,
 	// from one host thread or from several.  Guarded by uploadMutex; the run entry points COPY the image's pointers
 	// while holding it (UploadTable) and never look at devs[] afterwards.
@@ -826,6 +845,15 @@ bool LengthOrderWanted(uint64_t n);
 size_t LengthOrderScratchBytes(uint64_t n);
 // *serpentine: whether the kernels should walk the order with OrderedIndex's serpentine (the global order) or plainly
 int BuildLengthOrder(const uint64_t* offsets, uint64_t n, void* scratch, hipStream_t stream, const uint32_t** perm, bool* serpentine);
+// select.hip: from end states to matches (pire_hip_select).  UploadSelect: the mask image of the CURRENT device, built on
+// first use (the caller holds t->adaptMutex, shared: the host image is built from t->host), copied out to *image (nullable).
+// LaunchSelect: device pointers only, enqueues three small kernels on `stream`, scratch from the stream-ordered allocator.
+uint32_t SelectMaskWords(uint32_t regexps);
+int UploadSelect(pire_hip_table* t, SelectDevice* image);
+void FreeSelect(pire_hip_table* t);
+int LaunchSelect(const SelectDevice& image, uint32_t states, uint32_t words, const uint32_t* stateIdx, uint64_t n,
+                 const uint64_t* want, uint64_t* outMasks, uint64_t* outHits, uint64_t* outHitMasks, uint64_t hitCap,
+                 uint64_t* outHitCount, hipStream_t stream);
 void NoteKernel(const char* name, const char* symbol = nullptr);   // what pire_hip_last_kernel[_symbol]() report (thread local)
 bool RaggedActEligible(const ScanParams& p);
 int LaunchRaggedHalfFinal(const ScanParams& p, unsigned long long* workCounter, uint32_t* outResults, hipStream_t stream);

@@ -1,0 +1,327 @@
+// From end states to matches on the device (pire_hip_select): which strings matched which regexps.
+//
+// Every scan entry point answers with one StateIndex per string.  What a caller of a multi-regexp scanner wants is the
+// set of regexps that state accepts (AcceptedRegexps, multi.h:149-158) and, usually, only the strings that matched at
+// all -- a compacted, ascending list of their indices.  This unit turns the one into the other without leaving the
+// device, behind ANY of the scan kernels (it reads state indices, nothing else of a scan):
+//
+//   image     per state, by REFERENCE state index: W = max(1, ceil(regexps / 64)) mask words and the Final flag
+//             (internal.h SelectHost).  Reference numbering, so no re-ranking ever touches it.
+//   classify  one lane per string: state index -> mask record -> selected?  The masks go out if asked for; the selected
+//             bits of a wave are one ballot word, kept in scratch; one count per tile of 1 024 strings.
+//   scan      exclusive scan of the tile counts, one block; the total is the hit count.
+//   scatter   rank of a selected string = tile offset + the popcounts of the waves in front + mbcnt of its own wave's
+//             ballot word: the hits come out in ascending order, deterministically, with no atomics.
+//
+// Three launches on the caller's stream, the shape of order.hip.  No block ever waits for another block (no look-back,
+// no flags between blocks): the order of the three kernels on the stream is the only synchronisation.
+//
+// The gather is 8 * W bytes per string from a table of a few hundred KiB at most (L2 resident).  For W == 1 and up to
+// 8 192 states a block that has enough tiles to pay for it copies the table to LDS first: one ds_read_b64 per lane.
+// Plain HIP with compiler-placed waits: nothing here keeps data on its way in registers.
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "internal.h"
+
+namespace pirehip {
+
+namespace {
+
+constexpr uint32_t kSelThreads = 1024;             // one tile = 1 024 strings = 16 ballot words
+constexpr uint32_t kSelWaves = kSelThreads / 64;
+constexpr uint32_t kSelLdsStates = 8192;           // x 8 bytes = 64 KiB: two blocks a CU
+constexpr uint32_t kSelLdsBlocks = 512;            // the LDS form's grid: 2 blocks on each of 256 CUs, tiles in a grid-stride loop
+constexpr uint32_t kSelMaxBlocks = 8192;
+
+struct SelectParams {
+	const uint64_t* masks;   // [states * words], reference numbering
+	const uint8_t* fin;      // [states]
+	uint32_t states, words;
+	const uint32_t* stateIdx;
+	uint64_t n;
+	const uint64_t* want;    // nullable: [words]
+	uint64_t* outMasks;      // nullable
+	uint32_t store16;        // outMasks is 16-byte aligned and words is even: pairs of words in one store
+	uint64_t* outHits;
+	uint64_t* outHitMasks;   // nullable
+	uint64_t hitCap;
+	uint64_t* ballots;       // [tiles * 16] selected bits, one word per wave
+	uint32_t* tileCounts;    // [tiles] selected strings per tile; after the scan: selected strings in front of the tile
+	uint32_t tiles;
+};
+
+// A state index beyond the table (undefined behaviour of the ON_DEVICE form; the host-pointer form refuses it) reads
+// nothing: an empty mask, not selected.
+template <bool kLds>
+__global__ __launch_bounds__(kSelThreads) void SelectClassifyKernel(SelectParams p)
+{
+	extern __shared__ uint64_t ldsMasks[];
+	__shared__ uint32_t waveCount[kSelWaves];
+	if (kLds) {
+		for (uint32_t s = threadIdx.x; s < p.states; s += kSelThreads)
+			ldsMasks[s] = p.masks[s];
+		__syncthreads();
+	}
+	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const bool needMask = p.want || p.outMasks;
+	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
+		const uint64_t i = uint64_t(tile) * kSelThreads + threadIdx.x;
+		bool sel = false;
+		if (i < p.n) {
+			const uint32_t s = p.stateIdx[i];
+			const bool known = s < p.states;
+			if (!p.want)
+				sel = known && p.fin[s] != 0;
+			if (needMask) {
+				if (kLds || p.words == 1) {
+					const uint64_t m = !known ? 0 : kLds ? ldsMasks[s] : p.masks[s];
+					if (p.want)
+						sel = (m & p.want[0]) != 0;
+					if (p.outMasks)
+						p.outMasks[i] = m;
+				} else if (p.store16) {
+					const ulonglong2* rec = reinterpret_cast<const ulonglong2*>(p.masks + size_t(s) * p.words);
+					ulonglong2* out = reinterpret_cast<ulonglong2*>(p.outMasks + i * p.words);
+					uint64_t any = 0;
+					for (uint32_t w = 0; w < p.words; w += 2) {
+						ulonglong2 m = known ? rec[w / 2] : make_ulonglong2(0, 0);
+						if (p.want)
+							any |= (m.x & p.want[w]) | (m.y & p.want[w + 1]);
+						out[w / 2] = m;
+					}
+					if (p.want)
+						sel = any != 0;
+				} else {
+					uint64_t any = 0;
+					for (uint32_t w = 0; w < p.words; ++w) {
+						const uint64_t m = known ? p.masks[size_t(s) * p.words + w] : 0;
+						if (p.want)
+							any |= m & p.want[w];
+						if (p.outMasks)
+							p.outMasks[i * p.words + w] = m;
+					}
+					if (p.want)
+						sel = any != 0;
+				}
+			}
+		}
+		const uint64_t ballot = __ballot(sel);
+		if (lane == 0) {
+			p.ballots[size_t(tile) * kSelWaves + wave] = ballot;
+			waveCount[wave] = uint32_t(__popcll(ballot));
+		}
+		__syncthreads();
+		if (threadIdx.x == 0) {
+			uint32_t sum = 0;
+			for (uint32_t w = 0; w < kSelWaves; ++w)
+				sum += waveCount[w];
+			p.tileCounts[tile] = sum;
+		}
+		__syncthreads();
+	}
+}
+
+// Exclusive scan of counts[entries] in place, one block: 1 024 entries (2^20 strings) a step, a carry between the steps.
+// A batch of 2^20 strings is one step; 2^24 strings, sixteen.  *outCount = the total.
+__global__ __launch_bounds__(kSelThreads) void SelectScanKernel(uint32_t* counts, uint32_t entries, uint64_t* outCount)
+{
+	__shared__ uint32_t waveSum[kSelWaves];
+	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	uint32_t carry = 0;
+	for (uint32_t base = 0; base < entries; base += kSelThreads) {
+		const uint32_t i = base + threadIdx.x;
+		const uint32_t v = i < entries ? counts[i] : 0;
+		uint32_t incl = v;
+		for (uint32_t d = 1; d < 64; d <<= 1) {
+			const uint32_t up = uint32_t(__shfl_up(int(incl), int(d), 64));
+			if (lane >= d)
+				incl += up;
+		}
+		if (lane == 63)
+			waveSum[wave] = incl;
+		__syncthreads();
+		uint32_t before = 0, total = 0;
+		for (uint32_t w = 0; w < kSelWaves; ++w) {
+			const uint32_t ws = waveSum[w];
+			before += w < wave ? ws : 0;
+			total += ws;
+		}
+		if (i < entries)
+			counts[i] = carry + before + incl - v;
+		carry += total;
+		__syncthreads();
+	}
+	if (threadIdx.x == 0)
+		*outCount = carry;
+}
+
+__global__ __launch_bounds__(kSelThreads) void SelectScatterKernel(SelectParams p)
+{
+	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
+		const uint64_t* words = p.ballots + size_t(tile) * kSelWaves;
+		// lanes 0..15 hold the tile's ballot words: the selected strings of the waves in front of this one ...
+		const uint64_t word = lane < kSelWaves ? words[lane] : 0;
+		uint32_t front = lane < wave ? uint32_t(__popcll(word)) : 0;
+		for (uint32_t d = 1; d < 64; d <<= 1)
+			front += uint32_t(__shfl_xor(int(front), int(d), 64));   // (over all 64 lanes: every lane ends with the sum)
+		// ... and this wave's own word
+		const uint32_t lo = uint32_t(__shfl(int(uint32_t(word)), int(wave), 64));
+		const uint32_t hi = uint32_t(__shfl(int(uint32_t(word >> 32)), int(wave), 64));
+		const uint64_t mine = (uint64_t(hi) << 32) | lo;
+		const uint64_t rank = uint64_t(p.tileCounts[tile]) + front + __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0));
+		if (((mine >> lane) & 1) && rank < p.hitCap) {
+			const uint64_t i = uint64_t(tile) * kSelThreads + threadIdx.x;
+			p.outHits[rank] = i;
+			if (p.outHitMasks) {
+				const uint32_t s = p.stateIdx[i];
+				for (uint32_t w = 0; w < p.words; ++w)
+					p.outHitMasks[rank * p.words + w] = s < p.states ? p.masks[size_t(s) * p.words + w] : 0;
+			}
+		}
+	}
+}
+
+void FreeSelectDevice(SelectDevice* d)
+{
+	if (d->masks) (void)hipFree(d->masks);
+	if (d->fin) (void)hipFree(d->fin);
+	*d = SelectDevice();
+}
+
+void BuildSelectHost(const HostTable& h, SelectHost& s)
+{
+	s.words = SelectMaskWords(h.regexps);
+	s.masks.assign(size_t(h.states) * s.words, 0);
+	s.fin.assign(h.states, 0);
+	for (uint32_t st = 0; st < h.states; ++st) {
+		for (uint64_t k = h.acceptOff[st]; k < h.acceptOff[st + 1]; ++k) {
+			const uint64_t r = h.acceptIds[k];
+			if (r < h.regexps)
+				s.masks[size_t(st) * s.words + r / 64] |= uint64_t(1) << (r % 64);
+		}
+		// (a scanner without regexps selects nothing, whatever its flags say)
+		s.fin[st] = h.regexps && (h.flags[st] & kFinal) ? 1 : 0;
+	}
+	s.built = true;
+}
+
+}  // namespace
+
+uint32_t SelectMaskWords(uint32_t regexps)
+{
+	return std::max<uint32_t>(1, (regexps + 63) / 64);
+}
+
+void FreeSelect(pire_hip_table* t)
+{
+	int cur = -1;
+	(void)hipGetDevice(&cur);
+	for (int k = 0; k < kMaxDevices; ++k)
+		if (t->selectDev[k].device >= 0) {
+			(void)hipSetDevice(k);
+			FreeSelectDevice(&t->selectDev[k]);
+		}
+	if (cur >= 0)
+		(void)hipSetDevice(cur);
+}
+
+int UploadSelect(pire_hip_table* t, SelectDevice* image)
+{
+	int dev = 0;
+	hipError_t e = hipGetDevice(&dev);
+	if (e != hipSuccess)
+		return HipFail(e, "hipGetDevice");
+	if (dev < 0 || dev >= kMaxDevices) {
+		SetError("device number out of range");
+		return PIRE_HIP_EUNSUPPORTED;
+	}
+	std::lock_guard<std::mutex> lock(t->selectMutex);
+	if (!t->select.built)
+		BuildSelectHost(t->host, t->select);
+	const SelectHost& h = t->select;
+	SelectDevice& d = t->selectDev[dev];
+	if (d.device != dev) {
+		// (16 bytes of slack: an empty table still gets two valid pointers)
+		e = hipMalloc(reinterpret_cast<void**>(&d.masks), h.masks.size() * 8 + 16);
+		if (e == hipSuccess && !h.masks.empty())
+			e = hipMemcpy(d.masks, h.masks.data(), h.masks.size() * 8, hipMemcpyHostToDevice);
+		if (e == hipSuccess)
+			e = hipMalloc(reinterpret_cast<void**>(&d.fin), h.fin.size() + 16);
+		if (e == hipSuccess && !h.fin.empty())
+			e = hipMemcpy(d.fin, h.fin.data(), h.fin.size(), hipMemcpyHostToDevice);
+		if (e != hipSuccess) {
+			FreeSelectDevice(&d);
+			return HipFail(e, "uploading the select image");
+		}
+		d.device = dev;
+	}
+	if (image)
+		*image = d;
+	return PIRE_HIP_OK;
+}
+
+int LaunchSelect(const SelectDevice& image, uint32_t states, uint32_t words, const uint32_t* stateIdx, uint64_t n,
+                 const uint64_t* want, uint64_t* outMasks, uint64_t* outHits, uint64_t* outHitMasks, uint64_t hitCap,
+                 uint64_t* outHitCount, hipStream_t stream)
+{
+	if (n == 0) {
+		const hipError_t e = hipMemsetAsync(outHitCount, 0, 8, stream);
+		return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemsetAsync(hit count)");
+	}
+	if (n >= (1ull << 32)) {
+		SetError("pire_hip_select: 2^32 strings or more in one call");   // tile offsets are 32 bits (as order.hip's indices)
+		return PIRE_HIP_EUNSUPPORTED;
+	}
+	SelectParams p;
+	p.masks = image.masks;
+	p.fin = image.fin;
+	p.states = states;
+	p.words = words;
+	p.stateIdx = stateIdx;
+	p.n = n;
+	p.want = want;
+	p.outMasks = outMasks;
+	p.store16 = outMasks && words % 2 == 0 && reinterpret_cast<uintptr_t>(outMasks) % 16 == 0;
+	p.outHits = outHits;
+	p.outHitMasks = outHitMasks;
+	p.hitCap = outHits ? hitCap : 0;
+	p.tiles = uint32_t((n + kSelThreads - 1) / kSelThreads);
+	// scratch: n / 8 bytes of ballot words + n / 256 bytes of tile counts, stream-ordered (the call only enqueues)
+	const size_t ballotBytes = size_t(p.tiles) * kSelWaves * 8;
+	void* scratch = nullptr;
+	hipError_t e = hipMallocAsync(&scratch, ballotBytes + size_t(p.tiles) * 4, stream);
+	if (e != hipSuccess)
+		return HipFail(e, "hipMallocAsync(select scratch)");
+	p.ballots = static_cast<uint64_t*>(scratch);
+	p.tileCounts = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(scratch) + ballotBytes);
+	// The LDS form reads states * 8 bytes per BLOCK to save 8 bytes per STRING: only where a block of the small grid
+	// walks at least twice as many strings as the table has states
+	const uint32_t ldsGrid = std::min(p.tiles, kSelLdsBlocks);
+	const uint64_t ldsStrings = uint64_t((p.tiles + ldsGrid - 1) / ldsGrid) * kSelThreads;
+	const bool lds = words == 1 && (want || outMasks) && states <= kSelLdsStates && ldsStrings >= 2ull * states;
+	int rc = PIRE_HIP_OK;
+	if (lds) {
+		e = SetDynamicLds(reinterpret_cast<const void*>(SelectClassifyKernel<true>), kSelLdsStates * 8);
+		if (e != hipSuccess) {
+			(void)hipFreeAsync(scratch, stream);
+			return HipFail(e, "hipFuncSetAttribute(LDS)");
+		}
+		hipLaunchKernelGGL(SelectClassifyKernel<true>, dim3(ldsGrid), dim3(kSelThreads), size_t(states) * 8, stream, p);
+	} else {
+		hipLaunchKernelGGL(SelectClassifyKernel<false>, dim3(std::min(p.tiles, kSelMaxBlocks)), dim3(kSelThreads), 0, stream, p);
+	}
+	hipLaunchKernelGGL(SelectScanKernel, dim3(1), dim3(kSelThreads), 0, stream, p.tileCounts, p.tiles, outHitCount);
+	if (p.hitCap)
+		hipLaunchKernelGGL(SelectScatterKernel, dim3(std::min(p.tiles, kSelMaxBlocks)), dim3(kSelThreads), 0, stream, p);
+	e = hipGetLastError();
+	if (e != hipSuccess)
+		rc = HipFail(e, "select launch");
+	(void)hipFreeAsync(scratch, stream);
+	return rc;
+}
+
+}  // namespace pirehip
