@@ -1020,8 +1020,13 @@ __global__ __launch_bounds__(1024) void CaptureRowKernel(CountingParams p)
 		};
 		// `at` of a step = the string's byte index it consumes (BeginMark: -1, EndMark: len); its own position in steps
 		// is at + beginStep, the position of the step whose action it applies one less
-		if (ok && beginStep)
+		// The BeginMark step's own action is applied here, at the string's first position: the steps that follow may be
+		// the bytes of the line in front of the string (lead > 0: `at` "negative"), or idle ones of an empty string.
+		if (ok && beginStep) {
 			mark(0, npos);
+			take(0u);
+			pendB = pendE = 0;
+		}
 		u32x4 tile[8];
 		AccTile acc;
 		asm volatile("" : "={a[0:3]}"(acc.r[0]), "={a[4:7]}"(acc.r[1]), "={a[8:11]}"(acc.r[2]), "={a[12:15]}"(acc.r[3]),

@@ -126,6 +126,94 @@ SET_B_WITNESS = [(b"hello  world", True), (b"ABCDEFGHIJKLMNOPQRSTUVWXYZ", True),
 CORPUS_SEED = 0x5EED5EED
 
 
+ANY = object()   # capture_shapes(): "this string must capture; the substring is whatever the reference says"
+
+
+def capture_shapes():
+    """(name, source, pattern, capture index, options, shape label, shape predicate(states, letters, states*letters*8),
+    [(string, expected capture | None | ANY)], witnesses to plant in batches, noise alphabet) -- one scanner per row of
+    the kernel table of pire_hip_capture_run (pire_amd/csrc/counting.hip): kCaptureRowStates = 34, the dense form up to
+    255 states in blocks of 256 threads while states * 512 <= 40 KiB (80 states) and of 1024 above, the letter +
+    transition kernel with the transitions in LDS up to 60 KiB and in device memory above, and no expanded table (no
+    ragged_capture) above 127 letter classes."""
+    K = 1024
+    out = []
+    out.append(("capture_kv", "shape: capture_rows at its limit of 34 states",
+                "(user|session|token|request)_(id|key|name)\\s*[:=]\\s*\"([^\"]+)\"", 3, "i", "rows",
+                lambda s, l, b: s == 34 and l <= 127,
+                [(b'user_id: "alice"', b"alice"), (b'SESSION_KEY = "Zx9"', b"Zx9"), (b'token_name:"t" request_id="r2"', b"t"),
+                 (b"user_id = alice", None), (b'x request_key =  "a b" tail', b"a b"), (b'user_id=""', None)],
+                [b'user_id: "alice"', b'Session_Key = "Zx9"', b'token_name:"t"', b'request_id=\t"r 2"'],
+                b'user_idsession_keytoken_namerequest :="q1'))
+    out.append(("capture_gap", "shape: the first table beyond capture_rows (35..80 states: capture_dense, 256 threads)",
+                "k=.{0,7}([a-d]{2,5})[^a-d]", 1, "", "dense256", lambda s, l, b: 34 < s <= 80 and l <= 127,
+                [(b"k=ab;", ANY), (b"k=xxabcd!", ANY), (b"k=a;", None), (b"k=1234567dcba k=ab;", ANY), (b"k=12345678ab;", None),
+                 (b"zk=abcdabcd-", ANY)],
+                [b"k=ab;", b"k=xxabcd!", b"k=1234567dcba ", b"k=abcdabcd-"], b"k=abcd xy;k="))
+    alt40 = ["w%02dxyz" % i + "abcdefgh"[i % 8] * 3 for i in range(40)]
+    out.append(("capture_alt40", "shape: capture_dense in blocks of 256 threads (35..80 states)",
+                "(" + "|".join(alt40) + ")=([0-9a-f]+);", 2, "", "dense256", lambda s, l, b: 34 < s <= 80 and l <= 127,
+                [(b"w00xyzaaa=1f;", b"1f"), (b"w39xyzhhh=deadbeef; x", b"deadbeef"), (b"w01xyzbbb=;", None),
+                 (b"w07xyzhhh=00;w08xyzaaa=11;", b"00"), (b"w40xyzaaa=1;", None), (b"w01xyzbbb=1g;w02xyzccc=2;", b"2")],
+                [("%s=%x;" % (w, 7 * i + 1)).encode() for i, w in enumerate(alt40)], b"w0123xyzabch=1f;"))
+    out.append(("capture_rep", "shape: capture_dense in blocks of 1024 threads (81..255 states)",
+                "id=.{0,6}([a-c]{3,9})[^a-c].{0,4};", 1, "", "dense1024", lambda s, l, b: 80 < s <= 255 and l <= 127,
+                [(b"id=abc;;", ANY), (b"id=xxabcabc-12;", ANY), (b"id=ab;;", None), (b"id=abcabcabcabc;;", ANY), (b"xid=q abca.;", ANY),
+                 (b"id=abc;", ANY)],
+                [b"id=abc;;", b"id=xxabcabc-12;", b"id=q abca.;", b"id=cccccc.;"], b"id=abc x;-id="))
+    symbols = [chr(0x410 + k) for k in range(64)] + list("0123456789ABCDEFGHIJKLMNOPQRSTUVWXYcdefghijklmnopqrstuvwxy_,:!@#%<>/' ")
+    assert len(symbols) == 134 and len(set(symbols)) == 134
+
+    def code(i):
+        return "".join("ab"[(i >> k) & 1] for k in range(8))
+
+    def sword(i):
+        return (symbols[i] + code(i)).encode("utf-8")
+
+    out.append(("capture_sym134", "shape: capture_dense, 1024 threads; under PIRE_HIP_RUN_GENERIC the transitions stay in device "
+                "memory (the construction of test_many_letter_classes_disable_the_compact_tier)",
+                ("(" + "|".join(symbols[i] + code(i) for i in range(134)) + ")z").encode("utf-8"), 1, "u", "dense1024",
+                lambda s, l, b: 80 < s <= 255 and l <= 127 and b > 60 * K,
+                [(sword(64) + b"z", sword(64)), (sword(100) + b"z", sword(100)), (sword(64) + b"y", None),
+                 (b"xx" + sword(70) + b"ztail", sword(70)), (sword(133) + b"z" + sword(65) + b"z", sword(133)), (sword(66)[1:] + b"z", None)],
+                [sword(i) + b"z" for i in range(64, 134)], b"ab0Ycyz_ ,ab" + "Ая".encode("utf-8")))
+    out.append(("capture_dotgap", "shape: no dense form (more than 255 states), transitions in LDS: capture",
+                "a.{7}(b+)c", 1, "", "lds", lambda s, l, b: s > 255 and b <= 60 * K and l <= 127,
+                [(b"a1234567bc", b"b"), (b"a1234567bbbc", ANY), (b"a123456bc", None), (b"aaaaaaaabbc", ANY), (b"a1234567bxc", None),
+                 (b"cca7654321bbcbc", ANY)],
+                [b"a1234567bc", b"abcabcabbbc", b"aaaaaaaabbc"], b"abc"))
+    rng0 = np.random.RandomState(7)
+    abc = "abcdefghijklmnopqrstuvwxyz"
+    words = sorted({"".join(abc[i] for i in rng0.randint(0, 26, size=int(rng0.randint(5, 10)))) for _ in range(150)})
+    assert len(words) == 150
+    out.append(("capture_words150", "shape: no dense form, transitions in device memory (more than 60 KiB): capture; the expanded "
+                "table of ragged_capture has far more states than dense rows",
+                "(" + "|".join(words) + ")=([0-9a-f]+);", 2, "", "global", lambda s, l, b: s > 255 and b > 60 * K and l <= 127,
+                [(words[0].encode() + b"=1f;", b"1f"), (b"x" + words[149].encode() + b"=00ff; y", b"00ff"), (words[3].encode() + b"=;", None),
+                 (words[5].encode() + b"=g;" + words[6].encode() + b"=7;", b"7"), (words[7].encode()[:-1] + b"=1;", None),
+                 (words[8].encode() + b"=1" + words[9].encode() + b"=2;", b"2")],
+                [("%s=%x;" % (w, 11 * i + 3)).encode() for i, w in enumerate(words)],
+                (" ".join(words[:20]) + "=1f; ").encode()))
+    # more than 127 letter classes: every ASCII byte 1..127 except the code letters is a symbol of its own (bytes from
+    # 0x80 on cannot be told apart by this scanner: the lexer takes the pattern byte by byte and refuses them), and ^ / $
+    # give BeginMark and EndMark classes of their own
+    asc = [b for b in range(1, 0x80) if chr(b) not in "abz"]
+
+    def esc(b):
+        return (b"\\" if bytes([b]) in b"|().*+?^$\\[]{}" else b"") + bytes([b])
+
+    def aword(i):
+        return bytes([asc[i]]) + code(i).encode()
+
+    out.append(("capture_ascii124", "shape: more than 127 letter classes -- no expanded table, ragged_capture declines",
+                b"(^|q)(" + b"|".join(esc(s) + code(i).encode() for i, s in enumerate(asc)) + b")z($|q)", 2, "", "letters128",
+                lambda s, l, b: l > 127 and 80 < s <= 255 and b > 60 * K,
+                [(aword(50) + b"z", aword(50)), (b"xq" + aword(0) + b"zq..", aword(0)), (b"x" + aword(7) + b"zq", None),
+                 (b"q" + aword(123) + b"z", aword(123)), (b"q" + aword(60) + b"zx", ANY), (b"q" + aword(61)[:-1] + b"zq", None)],
+                [b"q" + aword(i) + b"zq" for i in range(len(asc))], b"qabz" + bytes(asc[::5])))
+    return out
+
+
 def write_blob(name, blob):
     if len(blob) > 65536:
         path = name + ".blob.gz"
@@ -428,6 +516,57 @@ def main():
                           "idx": [int(x) for x in idx], "final": [int(x) for x in fin], "captured": [int(x) for x in cap],
                           "begin": [int(x) for x in b], "end": [int(x) for x in e]})
 
+    # CapturingScanners of fixed, known SHAPE: one per device form behind pire_hip_capture_run (counting.hip chooses the
+    # kernel from states / letters / states * letters * 8).  Same record layout as above plus what
+    # tests/test_capture_shapes.py builds its batches from (alphabet, witnesses).  Every entry asserts the shape it is
+    # there for, so a change of pattern or words cannot silently move a fixture to another kernel.
+    rng = np.random.RandomState(81)
+    for name, source, pat, index, opt, shape, want_shape, items, witnesses, alphabet in capture_shapes():
+        sc = RefCapturingScanner.compile(pat, index, opt)
+        blob = sc.save()
+        from oracle.binding import OracleCountingScanner
+        orc = OracleCountingScanner(blob, 0)
+        states, letters = int(sc.size), int(orc.letters)
+        assert states == orc.size and want_shape(states, letters, states * letters * 8), (name, states, letters, states * letters * 8)
+        strings = [s_ for s_, _ in items]
+        a = np.frombuffer(alphabet, dtype=np.uint8)
+        strings += [bytes(rng.choice(a, size=int(k))) for k in rng.randint(0, 100, size=30)]
+        strings += [s_ + b" tail" for s_, _ in items] + [b"xx " + s_ for s_, _ in items]
+        idx, fin, cap, b, e = sc.run_strings(strings)
+        expect = []
+        for (s_, want), c_, b_, e_ in zip(items, cap, b, e):
+            got = s_[b_ - 1:e_ - 1] if c_ else None           # capture_ut.cpp:85-91
+            if want is ANY:                                   # must capture; which substring is the reference's word
+                assert got is not None, (name, s_)
+            else:
+                assert got == want, (name, s_, got, want)
+            expect.append(got)
+        # the test's batches: every witness must be captured by the reference, and plain noise must not always be
+        wcap = sc.run_strings(witnesses)[2]
+        assert wcap.all(), (name, [w for w, c_ in zip(witnesses, wcap) if not c_][:3])
+        capturing.append({"name": name, "source": source, "pattern": pat.decode("latin-1") if isinstance(pat, bytes) else pat,
+                          "index": index, "options": opt, "states": states, "letters": letters, "shape": shape,
+                          "blob": write_blob(name, blob), "strings_hex": [x.hex() for x in strings],
+                          "expect_hex": [None if w is None else w.hex() for w in expect],
+                          "idx": [int(x) for x in idx], "final": [int(x) for x in fin], "captured": [int(x) for x in cap],
+                          "begin": [int(x) for x in b], "end": [int(x) for x in e],
+                          "alphabet_hex": alphabet.hex(), "witnesses_hex": [w.hex() for w in witnesses]})
+
+    # BeginCapture as the action of the BeginMark step itself (begin = 0) that no later step re-arms: a group under `*` at
+    # the start of an unanchored pattern whose match ends the re-arming.  (Such a group is never reported as captured --
+    # no EndCapture -- so this scanner is not one of `capturing`, whose tests ask for captured strings.)
+    pat = "([ab].{5})*\\dc{2}"
+    sc = RefCapturingScanner.compile(pat, 1, "")
+    strings = [b"1cc", b"1ccx", b"", b"x1cc", b"abbbbb1cc", b"7cc" + b"ab" * 100, b"cc1", b"0cc1cc"]
+    strings += [bytes(rng.choice(np.frombuffer(b"ab1cc x", dtype=np.uint8), size=int(k))) for k in rng.randint(0, 60, size=30)]
+    idx, fin, cap, b, e = sc.run_strings(strings)
+    assert b[0] == 0 and b[1] == 0 and b[5] == 0 and (b[:8] > 0).any() and sc.size <= 34
+    blob = sc.save()
+    capturing_edge = [{"name": "capture_begin_mark", "source": "regression: CaptureRowKernel, action pending from the BeginMark step",
+                       "pattern": pat, "index": 1, "options": "", "states": int(sc.size), "blob": write_blob("capture_begin_mark", blob),
+                       "strings_hex": [x.hex() for x in strings], "idx": [int(x) for x in idx], "final": [int(x) for x in fin],
+                       "captured": [int(x) for x in cap], "begin": [int(x) for x in b], "end": [int(x) for x in e]}]
+
     # Scanner::Glue parts: every pattern of set_a / set_d compiled on its own (bench.cpp:114-129 glues such scanners
     # left to right); gluing these blobs must reproduce the big sets' tables, state for state.
     glue_parts = []
@@ -442,7 +581,7 @@ def main():
 
     with open(os.path.join(OUT, "cases.json"), "w") as f:
         json.dump({"generator": "tests/golden/make_golden.py", "reference": "yandex/pire @ /root/reference (v0.0.6)",
-                   "cases": cases, "big": big, "slow": slow, "simple": simple, "half_final": half, "counting": counting, "capturing": capturing, "glue_parts": glue_parts, "corpus": corpus}, f, indent=1)
+                   "cases": cases, "big": big, "slow": slow, "simple": simple, "half_final": half, "counting": counting, "capturing": capturing, "capturing_edge": capturing_edge, "glue_parts": glue_parts, "corpus": corpus}, f, indent=1)
     print("wrote", len(cases), "cases,", len(big), "big sets,", len(slow), "slow scanners,", len(simple), "simple scanners")
 
 

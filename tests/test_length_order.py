@@ -40,7 +40,7 @@ def test_counting_kernels_do_not_depend_on_the_order(name, cfg):
     assert orr.sum() > 0
 
 
-@pytest.mark.parametrize("name", ["capture_digits", "capture_path"])
+@pytest.mark.parametrize("name", ["capture_digits", "capture_path", "capture_rep", "capture_dotgap"])
 def test_capture_kernels_do_not_depend_on_the_order(name, cfg):
     import pire_amd
     from pire_amd import binding as pb
@@ -52,6 +52,10 @@ def test_capture_kernels_do_not_depend_on_the_order(name, cfg):
     t, o = pire_amd.CountingTable(blob, 0), ob.OracleCountingScanner(blob, 0)
     many = batch(np.random.RandomState(8), b"google_id ='\";x1/=0123456789to-match-with")
     many = [s[:len(s) // 3] + b" /to-match-with=42;" + s[len(s) // 3:] if i % 50 == 0 else s for i, s in enumerate(many)]
+    if "witnesses_hex" in case[0]:                # the fixtures of known shape (110 and 321 states) bring their own text
+        wit = [bytes.fromhex(h) for h in case[0]["witnesses_hex"]]
+        many = batch(np.random.RandomState(8), bytes.fromhex(case[0]["alphabet_hex"]))
+        many = [s[:len(s) // 3] + wit[i % len(wit)] + s[len(s) // 3:] if i % 20 == 0 else s for i, s in enumerate(many)]
     want = o.capture(*ob.pack_strings(many))
     cfg.set(no_ragged_act=1)                      # the one-string-per-lane kernels (dense rows, or letter + transition)
     for off in (0, 1):
@@ -60,7 +64,7 @@ def test_capture_kernels_do_not_depend_on_the_order(name, cfg):
             got = t.capture(*H.pack(many), flags=flags)
             assert pb.last_kernel() in ("capture_dense", "capture")
             assert all((x == y).all() for x, y in zip(want, got)), (name, off, flags)
-    assert want[2].sum() > 0
+    assert 0 < want[2].sum() < len(many)
 
 
 @pytest.mark.parametrize("name", ["slow_x40_utf8", "slow_alt"])

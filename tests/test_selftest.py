@@ -131,6 +131,8 @@ def _entry_calls(pa):
     text, offs = H.pack(strings)
     counting = [c for c in H.golden()["counting"] if c["kind"] == 1 and c["regexps"] >= 2][0]
     capturing = H.golden()["capturing"][0]
+    # ... and capturing scanners beyond the row kernel: more than 80 states (dense rows in blocks of 1024), more than 255 (no dense form)
+    cap_big = {n: H.load_blob([c for c in H.golden()["capturing"] if c["name"] == n][0]["blob"]) for n in ("capture_rep", "capture_dotgap")}
     return [
         ("Prefix (kernel", lambda: pa.Table(set_a).prefix(text, offs, True), {"ragged_prefix", "prefix", "ragged_prefix_wide"}),
         ("Suffix (kernel", lambda: pa.Table(set_a).suffix(text, offs, True), {"suffix"}),
@@ -139,6 +141,8 @@ def _entry_calls(pa):
          {"counting", "counting_packed", "counting_rows"}),
         ("the capturing scanner", lambda: pa.CountingTable(H.load_blob(capturing["blob"]), 0).capture(text, offs),
          {"capture", "capture_dense", "capture_rows"}),
+        ("the capturing scanner", lambda: pa.CountingTable(cap_big["capture_rep"], 0).capture(text, offs), {"capture", "capture_dense", "ragged_capture"}),
+        ("the capturing scanner", lambda: pa.CountingTable(cap_big["capture_dotgap"], 0).capture(text, offs), {"capture", "ragged_capture"}),
     ]
 
 
@@ -160,6 +164,48 @@ def test_entry_points_with_actions_test_every_kernel_they_can_take_on_first_use(
         assert kernels <= tested, (label, kernels - tested, tested)
         cfg.set(selftest=1)
         call()   # switched off: nothing tested, nothing refused
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["capture_rep", "capture_dotgap", "capture_words150"])
+def test_capture_self_test_on_large_tables_refuses_and_writes_nothing(pa, torch_cuda, cfg, name):
+    """The capture kernels' first-use self-test on tables of 110, 321 and 819 states (dense rows in blocks of 1024; no dense
+    form with the transitions in LDS / in device memory): with the expectation altered the call returns PIRE_HIP_ESELFTEST
+    and leaves the caller's arrays alone; with the real one it passes and the answers are the oracle's."""
+    import ctypes as C
+    from pire_amd import binding as pb
+    from tests import helpers as H
+
+    case = [c for c in H.golden()["capturing"] if c["name"] == name][0]
+    blob = H.load_blob(case["blob"])
+    strings = [bytes.fromhex(h) for h in case["witnesses_hex"]] * 3 + _strings(6)
+    text, offs = H.pack(strings)
+    n = len(strings)
+    assert n >= 256 and case["states"] > 80
+    t, o = pa.CountingTable(blob, 0), ob.OracleCountingScanner(blob, 0)
+    idx = np.full(n, 0xABCDEF, dtype=np.uint32)
+    fin = np.full(n, 99, dtype=np.uint8)
+    b = np.full(n, -1234, dtype=np.int64)
+    e = np.full(n, -4321, dtype=np.int64)
+
+    def call():
+        return pb.lib().pire_hip_capture_run(t._h, text.ctypes.data, offs.ctypes.data, n, 3, idx.ctypes.data, fin.ctypes.data,
+                                             b.ctypes.data, e.ctypes.data, None)
+
+    cfg.set(selftest=2)
+    for _ in range(2):
+        assert call() == ESELFTEST
+        assert "self-test of the capturing scanner" in pb.lib().pire_hip_last_error().decode()
+        assert (idx == 0xABCDEF).all() and (fin == 99).all() and (b == -1234).all() and (e == -4321).all()
+    cfg.set(selftest=0)
+    assert call() == 0
+    want = o.capture(text, offs)
+    assert (idx == want[0]).all() and (fin == want[1]).all() and (b == want[3]).all() and (e == want[4]).all()
+    assert 0 < want[2].sum() < n
+    assert {"capture", "ragged_capture"} <= set(pb.selftested_kernels())
+    cfg.set(selftest=2)           # tested once: trusted from now on
+    b[:] = -1234
+    assert call() == 0 and (b == want[3]).all()
 
 
 def test_every_kernel_name_the_library_can_emit_has_a_self_test():
