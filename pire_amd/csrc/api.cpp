@@ -897,33 +897,14 @@ int RunImpl(pire_hip_table* t, const void* text, const uint64_t* offsets, uint64
 		p.outFinal = outFinal;
 		p.outCounts = reinterpret_cast<unsigned long long*>(outCounts);
 		if ((flags & PIRE_HIP_RUN_HOST_OFFSETS) && offsets && n) {
-			// resident text, offsets known to the host: copy them into stream-ordered scratch
-			for (uint64_t i = 0; i < n; ++i)
-				if (offsets[i] > offsets[i + 1]) {
-					SetError("offsets must be non-decreasing");
-					return PIRE_HIP_EINVAL;
-				}
-			void* d = nullptr;
-			hipError_t e = hipMallocAsync(&d, (n + 1) * 8, stream);
-			if (e != hipSuccess)
-				return HipFail(e, "hipMallocAsync(offsets)");
-			e = hipMemcpyAsync(d, offsets, (n + 1) * 8, hipMemcpyHostToDevice, stream);
-			int rc = e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(offsets)");
-			p.offsets = static_cast<const uint64_t*>(d);
-			const uint64_t textBytes = offsets[n];
-			if (!rc) {
+			// resident text, offsets known to the host
+			return WithOffsetsOnDevice(offsets, n, stream, [&](const uint64_t* dOffsets) {
+				p.offsets = dOffsets;
+				const uint64_t textBytes = offsets[n];
 				if (!(flags & PIRE_HIP_RUN_GENERIC) && SegmentedEligible(n, textBytes - offsets[0]))
-					rc = RunSegmented(t, p, offsets, stream);
-				else
-					rc = Dispatch(p, stream, NextWorkSlot(t, p), textBytes);
-			}
-			(void)hipFreeAsync(d, stream);
-			if (!rc) {
-				e = hipStreamSynchronize(stream);   // the caller's offsets array was the source of an async copy
-				if (e != hipSuccess)
-					rc = HipFail(e, "hipStreamSynchronize");
-			}
-			return rc;
+					return RunSegmented(t, p, offsets, stream);
+				return Dispatch(p, stream, NextWorkSlot(t, p), textBytes);
+			});
 		}
 		// device offsets: the total text size is not known on the host; n >= 256 strings of unknown length still
 		// need 128 readable bytes at `text` for the ragged kernel, which the caller guarantees by passing a batch
@@ -955,11 +936,8 @@ int RunImpl(pire_hip_table* t, const void* text, const uint64_t* offsets, uint64
 					e = hipStreamSynchronize(stream);
 				if (e != hipSuccess)
 					return HipFail(e, "reading the offsets back");
-				for (uint64_t i = 0; i < n; ++i)
-					if (hostOffsets[i] > hostOffsets[i + 1]) {
-						SetError("offsets must be non-decreasing");
-						return PIRE_HIP_EINVAL;
-					}
+				if (int rc = CheckOffsets(hostOffsets.data(), n))
+					return rc;
 				return RunSegmented(t, p, hostOffsets.data(), stream);
 			}
 			return Dispatch(p, stream, NextWorkSlot(t, p), total);
@@ -974,21 +952,8 @@ int RunImpl(pire_hip_table* t, const void* text, const uint64_t* offsets, uint64
 		return PIRE_HIP_OK;
 	Staging st(stream);
 	uint64_t textBytes;
-	if (offsets) {
-		for (uint64_t i = 0; i < n; ++i)
-			if (offsets[i] > offsets[i + 1]) {
-				SetError("offsets must be non-decreasing");
-				return PIRE_HIP_EINVAL;
-			}
-		textBytes = offsets[n];
-	} else {
-		textBytes = (n - 1) * stride + len;
-	}
-	if (!text && textBytes) {
-		// a null text pointer is fine only when every string is empty (tests/pire_ut.cpp:832-837)
-		SetError("null text pointer with non-empty strings");
-		return PIRE_HIP_EINVAL;
-	}
+	if (int rc = CheckHostBatch(text, offsets, n, len, stride, &textBytes))
+		return rc;
 	if (init)
 		for (uint64_t i = 0; i < n; ++i)
 			if (init[i] >= t->host.states) {
@@ -1635,43 +1600,37 @@ int SelectImpl(pire_hip_table* t, const uint32_t* stateIdx, uint64_t n, const ui
 		if (int rc = UploadSelect(t, &image))
 			return rc;
 	}
-	if (onDevice)
-		return LaunchSelect(image, states, words, stateIdx, n, want, outMasks, outHits, outHitMasks, hitCap, outHitCount, stream);
-
 	// host pointers: staged in, the three kernels, staged out -- the hits only as far as they were written
-	Staging st(stream);
+	BatchIO io(stream, onDevice);
 	const uint32_t* dIdx = nullptr;
 	const uint64_t* dWant = nullptr;
-	if (int rc = st.In(stateIdx, size_t(n), &dIdx, stream))
+	if (int rc = io.In(stateIdx, size_t(n), &dIdx))
 		return rc;
 	if (want)
-		if (int rc = st.In(want, size_t(words), &dWant, stream))
+		if (int rc = io.In(want, size_t(words), &dWant))
 			return rc;
-	const uint64_t cap = std::min<uint64_t>(hitCap, n);
-	void *dMasks = nullptr, *dHits = nullptr, *dHitMasks = nullptr, *dCount = nullptr;
-	if (int rc = st.Alloc(&dCount, 8))
+	const uint64_t cap = std::min<uint64_t>(hitCap, n);   // n strings have at most n hits: a host call stages no more
+	uint64_t count = 0;   // host pointers: the count comes back here first
+	uint64_t *dCount = nullptr, *dMasks = nullptr, *dHits = nullptr, *dHitMasks = nullptr;
+	if (int rc = io.Result(onDevice ? outHitCount : &count, 1, 1, &dCount))
 		return rc;
 	if (outMasks)
-		if (int rc = st.Alloc(&dMasks, size_t(n) * words * 8))
+		if (int rc = io.Result(outMasks, size_t(n) * words, size_t(n) * words, &dMasks))
 			return rc;
 	if (outHits && cap)
-		if (int rc = st.Alloc(&dHits, size_t(cap) * 8))
+		if (int rc = io.Result(outHits, size_t(cap), 0, &dHits))
 			return rc;
 	if (outHitMasks && cap)
-		if (int rc = st.Alloc(&dHitMasks, size_t(cap) * words * 8))
+		if (int rc = io.Result(outHitMasks, size_t(cap) * words, 0, &dHitMasks))
 			return rc;
-	if (int rc = st.Flush())
+	if (int rc = io.Ready())
 		return rc;
-	if (int rc = LaunchSelect(image, states, words, dIdx, n, dWant, static_cast<uint64_t*>(dMasks), static_cast<uint64_t*>(dHits),
-	                          static_cast<uint64_t*>(dHitMasks), dHits ? cap : 0, static_cast<uint64_t*>(dCount), stream))
+	if (int rc = LaunchSelect(image, states, words, dIdx, n, dWant, dMasks, dHits, dHitMasks, dHits ? cap : 0, dCount, stream))
 		return rc;
-	uint64_t count = 0;
-	if (int rc = st.Out(&count, dCount, 8))
+	if (int rc = io.Finish())
 		return rc;
-	if (int rc = st.Out(outMasks, dMasks, size_t(n) * words * 8))
-		return rc;
-	if (int rc = st.Finish())
-		return rc;
+	if (onDevice)
+		return PIRE_HIP_OK;
 	*outHitCount = count;
 	const uint64_t written = std::min<uint64_t>(count, dHits ? cap : 0);
 	if (written) {
@@ -1705,19 +1664,15 @@ int RunSelectImpl(pire_hip_table* t, uint64_t n, const uint64_t* want, uint32_t 
 			return rc;
 		return SelectImpl(t, outIdx, n, want, 0, outMasks, outHits, outHitMasks, hitCap, outHitCount, stream);
 	}
-	void* scratch = nullptr;
+	StreamScratch scratch(stream);
 	if (!outIdx && n) {
-		const hipError_t e = hipMallocAsync(&scratch, size_t(n) * 4, stream);
-		if (e != hipSuccess)
-			return HipFail(e, "hipMallocAsync(state indices)");
-		outIdx = static_cast<uint32_t*>(scratch);
+		if (int rc = scratch.Alloc(size_t(n) * 4, "hipMallocAsync(state indices)"))
+			return rc;
+		outIdx = scratch.as<uint32_t>();
 	}
-	int rc = run(outIdx);
-	if (!rc)
-		rc = SelectImpl(t, outIdx, n, want, PIRE_HIP_RUN_ON_DEVICE, outMasks, outHits, outHitMasks, hitCap, outHitCount, stream);
-	if (scratch)
-		(void)hipFreeAsync(scratch, stream);
-	return rc;
+	if (int rc = run(outIdx))
+		return rc;
+	return SelectImpl(t, outIdx, n, want, PIRE_HIP_RUN_ON_DEVICE, outMasks, outHits, outHitMasks, hitCap, outHitCount, stream);
 }
 
 }  // namespace
@@ -2084,88 +2039,40 @@ try {
 		// of the steps a third of the ragged kernel's chunks are walked again)
 		if (!exactOnly && (!RaggedActEligible(p) || p.finalShare > 0.002f)) {
 			bool done = false;
-			uint32_t* list = nullptr;
+			StreamScratch list(stream);   // the strings the row kernel left: alive until the kernel that counts them is enqueued
 			if (int rc = LaunchHalfFinalRows(t, p.text, p.offsets, n, flags, p.outIdx, p.outFinal, dResults, stream, &done, &list))
 				return rc;
-			if (done) {
-				const int rc = LaunchHalfFinal(p, dResults, stream, nullptr, list);
-				(void)hipFreeAsync(list, stream);
-				return rc;
-			}
+			if (done)
+				return LaunchHalfFinal(p, dResults, stream, nullptr, list.as<uint32_t>());
 		}
 		return LaunchHalfFinal(p, dResults, stream, exactOnly ? nullptr : NextWorkSlot(t, p));
 	};
-	if (flags & PIRE_HIP_RUN_ON_DEVICE) {
-		p.text = static_cast<const uint8_t*>(text);
-		p.offsets = offsets;
-		p.outIdx = out_state_idx;
-		p.outFinal = out_final;
-		if (!(flags & PIRE_HIP_RUN_HOST_OFFSETS))
-			return launchCounting(out_results);
-		// resident text, offsets known to the host (see pire_hip_run)
-		for (uint64_t i = 0; i < n; ++i)
-			if (offsets[i] > offsets[i + 1]) {
-				SetError("offsets must be non-decreasing");
-				return PIRE_HIP_EINVAL;
-			}
-		void* d = nullptr;
-		hipError_t e = hipMallocAsync(&d, (n + 1) * 8, stream);
-		if (e != hipSuccess)
-			return HipFail(e, "hipMallocAsync(offsets)");
-		e = hipMemcpyAsync(d, offsets, (n + 1) * 8, hipMemcpyHostToDevice, stream);
-		int rc = e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(offsets)");
-		p.offsets = static_cast<const uint64_t*>(d);
+	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
+	BatchIO io(stream, onDevice);
+	uint32_t* dRes = nullptr;
+	int rc;
+	if ((rc = io.Text(text, offsets, n, 0, 0, &p.text, &p.offsets)) || (rc = io.Result(out_state_idx, size_t(n), size_t(n), &p.outIdx)) ||
+	    (rc = io.Result(out_final, size_t(n), size_t(n), &p.outFinal)) ||
+	    (rc = io.Result(out_results, size_t(n) * std::max<uint32_t>(R, 1), size_t(n) * R, &dRes)) || (rc = io.Ready()))
+		return rc;
+	// the lengths on the host (its own arrays, or PIRE_HIP_RUN_HOST_OFFSETS: resident text, see pire_hip_run): the
+	// segmented scan first
+	const bool hostOffsets = !enqueueOnly;
+	auto count = [&]() -> int {
 		bool counted = false;
-		if (!rc)
-			rc = segmented(offsets, out_results, &counted);
-		if (!rc && !counted)
-			rc = launchCounting(out_results);
-		(void)hipFreeAsync(d, stream);
-		if (!rc) {
-			e = hipStreamSynchronize(stream);   // the caller's offsets array was the source of an async copy
-			if (e != hipSuccess)
-				rc = HipFail(e, "hipStreamSynchronize");
-		}
-		return rc;
-	}
-	Staging st(stream);
-	for (uint64_t i = 0; i < n; ++i)
-		if (offsets[i] > offsets[i + 1]) {
-			SetError("offsets must be non-decreasing");
-			return PIRE_HIP_EINVAL;
-		}
-	const uint64_t textBytes = offsets[n];
-	if (!text && textBytes) {
-		SetError("null text pointer with non-empty strings");
-		return PIRE_HIP_EINVAL;
-	}
-	const uint8_t* dText = nullptr;
-	if (int rc = st.In(static_cast<const uint8_t*>(text), size_t(textBytes), &dText, stream))
-		return rc;
-	p.text = dText;
-	if (int rc = st.In(offsets, size_t(n + 1), &p.offsets, stream))
-		return rc;
-	void *dIdx = nullptr, *dFin = nullptr, *dRes = nullptr;
-	if (int rc = st.Alloc(&dIdx, size_t(n) * 4))
-		return rc;
-	if (int rc = st.Alloc(&dFin, size_t(n)))
-		return rc;
-	if (int rc = st.Alloc(&dRes, size_t(n) * std::max<uint32_t>(R, 1) * 4))
-		return rc;
-	p.outIdx = static_cast<uint32_t*>(dIdx);
-	p.outFinal = static_cast<uint8_t*>(dFin);
-	bool counted = false;
-	if (int rc = segmented(offsets, static_cast<uint32_t*>(dRes), &counted))
-		return rc;
-	if (!counted)
-		if (int rc = launchCounting(static_cast<uint32_t*>(dRes)))
-			return rc;
-	int rc = st.Out(out_state_idx, dIdx, size_t(n) * 4);
-	if (!rc)
-		rc = st.Out(out_final, dFin, size_t(n));
-	if (!rc && R)
-		rc = st.Out(out_results, dRes, size_t(n) * R * 4);
-	return rc ? rc : st.Finish();
+		if (hostOffsets)
+			if (int src = segmented(offsets, dRes, &counted))
+				return src;
+		return counted ? PIRE_HIP_OK : launchCounting(dRes);
+	};
+	if (onDevice && hostOffsets)
+		rc = WithOffsetsOnDevice(offsets, n, stream, [&](const uint64_t* dOffsets) {
+			p.offsets = dOffsets;
+			return count();
+		});
+	else
+		rc = count();
+	return rc ? rc : io.Finish();
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
@@ -2189,38 +2096,17 @@ try {
 	if (n == 0)
 		return PIRE_HIP_OK;
 	p.actDist = p.distFlaggedPerm;
-	if (flags & PIRE_HIP_RUN_ON_DEVICE) {
-		p.text = static_cast<const uint8_t*>(text);
-		p.offsets = offsets;
-		return LaunchPrefix(p, longest != 0, through_end != 0, reinterpret_cast<long long*>(out_len), stream,
-		                    (flags & PIRE_HIP_RUN_GENERIC) ? nullptr : NextWorkSlot(t, p));
-	}
-	Staging st(stream);
-	for (uint64_t i = 0; i < n; ++i)
-		if (offsets[i] > offsets[i + 1]) {
-			SetError("offsets must be non-decreasing");
-			return PIRE_HIP_EINVAL;
-		}
-	const uint64_t textBytes = offsets[n];
-	if (!text && textBytes) {
-		SetError("null text pointer with non-empty strings");
-		return PIRE_HIP_EINVAL;
-	}
-	const uint8_t* dText = nullptr;
-	if (int rc = st.In(static_cast<const uint8_t*>(text), size_t(textBytes), &dText, stream))
+	BatchIO io(stream, (flags & PIRE_HIP_RUN_ON_DEVICE) != 0);
+	long long* dOut = nullptr;
+	if (int rc = io.Text(text, offsets, n, 0, 0, &p.text, &p.offsets))
 		return rc;
-	p.text = dText;
-	if (int rc = st.In(offsets, size_t(n + 1), &p.offsets, stream))
+	if (int rc = io.Result(reinterpret_cast<long long*>(out_len), size_t(n), size_t(n), &dOut))
 		return rc;
-	void* dOut = nullptr;
-	if (int rc = st.Alloc(&dOut, size_t(n) * 8))
+	if (int rc = io.Ready())
 		return rc;
-	if (int rc = LaunchPrefix(p, longest != 0, through_end != 0, static_cast<long long*>(dOut), stream,
-	                          (flags & PIRE_HIP_RUN_GENERIC) ? nullptr : NextWorkSlot(t, p)))
+	if (int rc = LaunchPrefix(p, longest != 0, through_end != 0, dOut, stream, (flags & PIRE_HIP_RUN_GENERIC) ? nullptr : NextWorkSlot(t, p)))
 		return rc;
-	if (int rc = st.Out(out_len, dOut, size_t(n) * 8))
-		return rc;
-	return st.Finish();
+	return io.Finish();
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
@@ -2268,12 +2154,10 @@ static int RunPairImpl(pire_hip_table* t1, pire_hip_table* t2, const void* text,
 	}
 	// what is left (everything, when the batch is not made of fixed-length records): two ordinary passes, Final = either
 	const uint64_t rest = n - fused;
-	void* fin2 = nullptr;
-	if (outFinal) {
-		hipError_t e = hipMallocAsync(&fin2, size_t(rest), stream);
-		if (e != hipSuccess)
-			return HipFail(e, "hipMallocAsync(pair finals)");
-	}
+	StreamScratch fin2(stream);
+	if (outFinal)
+		if (int rc = fin2.Alloc(size_t(rest), "hipMallocAsync(pair finals)"))
+			return rc;
 	auto shift = [&](ScanParams& p, uint32_t* idx, uint8_t* fin) {
 		p.n = rest;
 		if (!offsets)
@@ -2284,15 +2168,12 @@ static int RunPairImpl(pire_hip_table* t1, pire_hip_table* t2, const void* text,
 		p.outFinal = fin;
 	};
 	shift(a, outIdx1, outFinal ? outFinal + fused : nullptr);
-	shift(b, outIdx2, static_cast<uint8_t*>(fin2));
-	int rc = Dispatch(a, stream, NextWorkSlot(t1, a), offsets ? ~0ull : 0);
-	if (!rc)
-		rc = Dispatch(b, stream, NextWorkSlot(t2, b), offsets ? ~0ull : 0);
-	if (!rc && outFinal)
-		rc = LaunchOrFinal(outFinal + fused, static_cast<const uint8_t*>(fin2), rest, stream);
-	if (fin2)
-		(void)hipFreeAsync(fin2, stream);
-	return rc;
+	shift(b, outIdx2, fin2.as<uint8_t>());
+	if (int rc = Dispatch(a, stream, NextWorkSlot(t1, a), offsets ? ~0ull : 0))
+		return rc;
+	if (int rc = Dispatch(b, stream, NextWorkSlot(t2, b), offsets ? ~0ull : 0))
+		return rc;
+	return outFinal ? LaunchOrFinal(outFinal + fused, fin2.as<const uint8_t>(), rest, stream) : PIRE_HIP_OK;
 }
 
 int pire_hip_run_pair(pire_hip_table* t1, pire_hip_table* t2, const void* text, const uint64_t* offsets, uint64_t n,
@@ -2342,36 +2223,17 @@ try {
 	p.n = n;
 	if (n == 0)
 		return PIRE_HIP_OK;
-	if (flags & PIRE_HIP_RUN_ON_DEVICE) {
-		p.text = static_cast<const uint8_t*>(text);
-		p.offsets = offsets;
-		return LaunchSuffix(p, longest != 0, through_begin != 0, reinterpret_cast<long long*>(out_len), stream);
-	}
-	Staging st(stream);
-	for (uint64_t i = 0; i < n; ++i)
-		if (offsets[i] > offsets[i + 1]) {
-			SetError("offsets must be non-decreasing");
-			return PIRE_HIP_EINVAL;
-		}
-	const uint64_t textBytes = offsets[n];
-	if (!text && textBytes) {
-		SetError("null text pointer with non-empty strings");
-		return PIRE_HIP_EINVAL;
-	}
-	const uint8_t* dText = nullptr;
-	if (int rc = st.In(static_cast<const uint8_t*>(text), size_t(textBytes), &dText, stream))
+	BatchIO io(stream, (flags & PIRE_HIP_RUN_ON_DEVICE) != 0);
+	long long* dOut = nullptr;
+	if (int rc = io.Text(text, offsets, n, 0, 0, &p.text, &p.offsets))
 		return rc;
-	p.text = dText;
-	if (int rc = st.In(offsets, size_t(n + 1), &p.offsets, stream))
+	if (int rc = io.Result(reinterpret_cast<long long*>(out_len), size_t(n), size_t(n), &dOut))
 		return rc;
-	void* dOut = nullptr;
-	if (int rc = st.Alloc(&dOut, size_t(n) * 8))
+	if (int rc = io.Ready())
 		return rc;
-	if (int rc = LaunchSuffix(p, longest != 0, through_begin != 0, static_cast<long long*>(dOut), stream))
+	if (int rc = LaunchSuffix(p, longest != 0, through_begin != 0, dOut, stream))
 		return rc;
-	if (int rc = st.Out(out_len, dOut, size_t(n) * 8))
-		return rc;
-	return st.Finish();
+	return io.Finish();
 } catch (...) {
 	return pirehip::HandleException();
 }

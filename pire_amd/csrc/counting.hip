@@ -1469,38 +1469,19 @@ int LaunchCounting(CountingParams p, int kind, hipStream_t stream, uint32_t nreg
 	if (e != hipSuccess)
 		return HipFail(e, "device query");
 	// the strings by length class (order.hip), so that a wave's 64 lanes finish together
-	void* orderScratch = nullptr;
-	struct OrderGuard {
-		void*& q;
-		hipStream_t s;
-		~OrderGuard()
-		{
-			if (q)
-				(void)hipFreeAsync(q, s);
-		}
-	} orderGuard{orderScratch, stream};
+	StreamScratch orderScratch(stream);
 	p.order = nullptr;
 	if (p.offsets && LengthOrderWanted(p.n)) {
-		e = hipMallocAsync(&orderScratch, LengthOrderScratchBytes(p.n), stream);
-		if (e != hipSuccess)
-			return HipFail(e, "hipMallocAsync(length order)");
+		if (int rc = orderScratch.Alloc(LengthOrderScratchBytes(p.n), "hipMallocAsync(length order)"))
+			return rc;
 		bool serp = false;
-		if (int rc = BuildLengthOrder(p.offsets, p.n, orderScratch, stream, &p.order, &serp))
+		if (int rc = BuildLengthOrder(p.offsets, p.n, orderScratch.get(), stream, &p.order, &serp))
 			return rc;
 		p.serpentine = serp ? 1u : 0u;
 	}
 	// Dense rows + packed 16-bit counters first (CountingPackedKernel); the strings it leaves on the overflow list
 	// (longer than 65 000 bytes) go through the 32-bit kernel below on the same stream.
-	void* list = nullptr;
-	struct ListGuard {
-		void*& q;
-		hipStream_t s;
-		~ListGuard()
-		{
-			if (q)
-				(void)hipFreeAsync(q, s);
-		}
-	} listGuard{list, stream};
+	StreamScratch list(stream);
 	// letter-indexed rows (CountingRowKernel<.., LETTERS>): any table whose (states + 1) x (letters + 1) entries fit
 	const uint32_t lnreg = p.lnreg;
 	const int variant = GetConfig().counting_variant;
@@ -1508,12 +1489,12 @@ int LaunchCounting(CountingParams p, int kind, hipStream_t stream, uint32_t nreg
 	const bool byteRows = nreg && p.dense && nreg <= 4 && p.states <= kCountingRowStates && variant != 1 && fills;
 	const bool letterRows = !byteRows && lnreg && p.lrows && variant != 1 && fills;
 	if (((nreg && p.dense) || letterRows) && kind != PIRE_HIP_COUNTING_NOGLUELIMIT && p.n < (1ull << 32) - 1) {
-		e = hipMallocAsync(&list, (size_t(p.n) + 1) * 4, stream);
-		if (e == hipSuccess)
-			e = hipMemsetAsync(list, 0, 4, stream);
+		if (int rc = list.Alloc((size_t(p.n) + 1) * 4, "hipMallocAsync(counting overflow list)"))
+			return rc;
+		e = hipMemsetAsync(list.get(), 0, 4, stream);
 		if (e != hipSuccess)
 			return HipFail(e, "hipMallocAsync(counting overflow list)");
-		p.overflow = static_cast<uint32_t*>(list);
+		p.overflow = list.as<uint32_t>();
 		const bool adv = kind == PIRE_HIP_COUNTING_ADVANCED;
 		// entries that are LDS addresses (CountingRowKernel) where the table leaves room for them and the batch fills the
 		// GPU; pire_hip_config.counting_variant: 1 = never, 2 = whenever the table fits
@@ -1722,10 +1703,9 @@ int UploadHalfRows(pire_hip_table* t)
 
 int LaunchHalfFinalRows(pire_hip_table* t, const uint8_t* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
                         uint32_t* outIdx, uint8_t* outFinal, uint32_t* outResults, hipStream_t stream, bool* done,
-                        uint32_t** overflow)
+                        StreamScratch* overflow)
 {
 	*done = false;
-	*overflow = nullptr;
 	const int variant = GetConfig().counting_variant;
 	if (variant == 1 || n == 0 || n >= (1ull << 32) - 1 || !offsets)
 		return PIRE_HIP_OK;
@@ -1775,24 +1755,20 @@ int LaunchHalfFinalRows(pire_hip_table* t, const uint8_t* text, const uint64_t* 
 	p.outFinal = outFinal;
 	p.outResults = outResults;
 	// strings by length class, as the counting scanners (order.hip)
-	void* orderScratch = nullptr;
+	StreamScratch orderScratch(stream);
 	if (LengthOrderWanted(n)) {
-		e = hipMallocAsync(&orderScratch, LengthOrderScratchBytes(n), stream);
-		if (e != hipSuccess)
-			return HipFail(e, "hipMallocAsync(length order)");
-		bool serp = false;
-		if (int rc = BuildLengthOrder(offsets, n, orderScratch, stream, &p.order, &serp)) {
-			(void)hipFreeAsync(orderScratch, stream);
+		if (int rc = orderScratch.Alloc(LengthOrderScratchBytes(n), "hipMallocAsync(length order)"))
 			return rc;
-		}
+		bool serp = false;
+		if (int rc = BuildLengthOrder(offsets, n, orderScratch.get(), stream, &p.order, &serp))
+			return rc;
 		p.serpentine = serp ? 1u : 0u;
 	}
-	void* list = nullptr;
-	e = hipMallocAsync(&list, (size_t(n) + 1) * 4, stream);
-	if (e == hipSuccess)
-		e = hipMemsetAsync(list, 0, 4, stream);
+	if (int rc = overflow->Alloc((size_t(n) + 1) * 4, "half-final row kernel"))
+		return rc;
+	e = hipMemsetAsync(overflow->get(), 0, 4, stream);
 	if (e == hipSuccess) {
-		p.overflow = static_cast<uint32_t*>(list);
+		p.overflow = overflow->as<uint32_t>();
 		const uint32_t rowLds = uint32_t(((size_t(p.states + 1) * (p.letters + 1) * 8 + 15) & ~size_t(15)) + size_t(lactCount) * 2 * nreg * 4 + 512);
 		p.spreadWaves = n <= uint64_t(cus) * 1024 ? 1u : 0u;
 		const unsigned rblocks = unsigned(std::max<uint64_t>(1, std::min<uint64_t>(p.spreadWaves ? (n + 63) / 64 : (n + 1023) / 1024, uint64_t(cus))));
@@ -1802,15 +1778,9 @@ int LaunchHalfFinalRows(pire_hip_table* t, const uint8_t* text, const uint64_t* 
 		default: LaunchRow<4, true>(p, 2, rblocks, rowLds, stream, &e); break;
 		}
 	}
-	if (orderScratch)
-		(void)hipFreeAsync(orderScratch, stream);
-	if (e != hipSuccess) {
-		if (list)
-			(void)hipFreeAsync(list, stream);
+	if (e != hipSuccess)
 		return HipFail(e, "half-final row kernel");
-	}
 	NoteKernel("half_final_rows");
-	*overflow = static_cast<uint32_t*>(list);
 	*done = true;
 	return PIRE_HIP_OK;
 }
@@ -2161,22 +2131,12 @@ try {
 	memset(&p, 0, sizeof(p));
 	p.actions = image.actions;
 	// more than 16 regexps: per-string `current` rows in a temporary device array (freed after the stream is drained)
-	void* scratch = nullptr;
 	// stream-ordered: allocated and freed on the call's stream (the free is ordered after the kernel that uses it)
-	struct ScratchGuard {
-		void*& q;
-		hipStream_t s;
-		~ScratchGuard()
-		{
-			if (q)
-				(void)hipFreeAsync(q, s);
-		}
-	} scratchGuard{scratch, stream};
+	StreamScratch scratch(stream);
 	if (kind == PIRE_HIP_COUNTING_NOGLUELIMIT && t->host.regexps > kMaxReCount) {
-		hipError_t se = hipMallocAsync(&scratch, size_t(n) * t->host.regexps * 4, stream);
-		if (se != hipSuccess)
-			return HipFail(se, "hipMallocAsync(counting scratch)");
-		p.scratch = static_cast<uint32_t*>(scratch);
+		if (int rc = scratch.Alloc(size_t(n) * t->host.regexps * 4, "hipMallocAsync(counting scratch)"))
+			return rc;
+		p.scratch = scratch.as<uint32_t>();
 	}
 	p.letterOf = image.letterOf;
 	p.trans = image.trans;
@@ -2196,42 +2156,14 @@ try {
 	// PIRE_HIP_RUN_GENERIC keeps the 32-bit kernel alone (the tests compare the two)
 	const uint32_t nreg = (flags & PIRE_HIP_RUN_GENERIC) ? 0 : t->host.nreg;
 	const uint32_t R = std::max<uint32_t>(t->host.regexps, 1);
-	if (flags & PIRE_HIP_RUN_ON_DEVICE) {
-		p.text = static_cast<const uint8_t*>(text);
-		p.offsets = offsets;
-		p.outIdx = out_state_idx;
-		p.outResults = out_results;
-		return LaunchCounting(p, kind, stream, nreg);
-	}
-	for (uint64_t i = 0; i < n; ++i)
-		if (offsets[i] > offsets[i + 1]) {
-			SetError("offsets must be non-decreasing");
-			return PIRE_HIP_EINVAL;
-		}
-	const uint64_t textBytes = offsets[n];
-	if (!text && textBytes) {
-		SetError("null text pointer with non-empty strings");
-		return PIRE_HIP_EINVAL;
-	}
-	Staging stage(stream);
-	const uint8_t* dText = nullptr;
-	const uint64_t* dOffs = nullptr;
-	void *dIdx = nullptr, *dRes = nullptr;
+	BatchIO io(stream, (flags & PIRE_HIP_RUN_ON_DEVICE) != 0);
 	int rc;
-	if ((rc = stage.In(static_cast<const uint8_t*>(text), size_t(textBytes), &dText, stream)) ||
-	    (rc = stage.In(offsets, size_t(n + 1), &dOffs, stream)) || (rc = stage.Alloc(&dIdx, n * 4)) ||
-	    (rc = stage.Alloc(&dRes, n * R * 4)))
+	if ((rc = io.Text(text, offsets, n, 0, 0, &p.text, &p.offsets)) || (rc = io.Result(out_state_idx, n, n, &p.outIdx)) ||
+	    (rc = io.Result(out_results, n * R, n * t->host.regexps, &p.outResults)) || (rc = io.Ready()))
 		return rc;
-	p.text = dText;
-	p.offsets = dOffs;
-	p.outIdx = static_cast<uint32_t*>(dIdx);
-	p.outResults = static_cast<uint32_t*>(dRes);
 	if ((rc = LaunchCounting(p, kind, stream, nreg)))
 		return rc;
-	rc = stage.Out(out_state_idx, dIdx, n * 4);
-	if (!rc && t->host.regexps)
-		rc = stage.Out(out_results, dRes, n * t->host.regexps * 4);
-	return rc ? rc : stage.Finish();
+	return io.Finish();
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
@@ -2379,16 +2311,7 @@ try {
 	// one string per lane: the dense-row kernel when the table has the dense form (<= 255 states), else letter + transition
 	p.dense = image.dense;
 	p.denseMarks = image.denseMarks;
-	void* orderScratch = nullptr;   // freed on the stream, behind the kernel that reads it
-	struct OrderGuard {
-		void*& q;
-		hipStream_t s;
-		~OrderGuard()
-		{
-			if (q)
-				(void)hipFreeAsync(q, s);
-		}
-	} orderGuard{orderScratch, stream};
+	StreamScratch orderScratch(stream);   // freed on the stream, behind the kernel that reads it
 	auto launchPerLane = [&]() -> int {
 		hipError_t le;
 		// (order.hip, measured on the capture walks: 1 025-1 045 GB/s in the caller's order, 941-977 by length -- the walk
@@ -2400,11 +2323,10 @@ try {
 		const bool rows = p.dense && !(flags & PIRE_HIP_RUN_GENERIC) && p.states <= kCaptureRowStates && variant != 1 &&
 		                  (variant == 2 || p.n >= uint64_t(cus) * 256);
 		if (p.offsets && LengthOrderWanted(p.n) && (GetConfig().capture_by_length || (rows && !GetConfig().no_length_order))) {
-			le = hipMallocAsync(&orderScratch, LengthOrderScratchBytes(p.n), stream);
-			if (le != hipSuccess)
-				return HipFail(le, "hipMallocAsync(length order)");
+			if (int rc = orderScratch.Alloc(LengthOrderScratchBytes(p.n), "hipMallocAsync(length order)"))
+				return rc;
 			bool serp = false;
-			if (int rc = BuildLengthOrder(p.offsets, p.n, orderScratch, stream, &p.order, &serp))
+			if (int rc = BuildLengthOrder(p.offsets, p.n, orderScratch.get(), stream, &p.order, &serp))
 				return rc;
 			p.serpentine = serp ? 1u : 0u;
 		}
@@ -2468,58 +2390,18 @@ try {
 		*done = true;
 		return LaunchRaggedCapture(sp, TakeWorkSlot(ct, sp), infoDev, dB, dE, stream);
 	};
-	if (flags & PIRE_HIP_RUN_ON_DEVICE) {
-		p.text = static_cast<const uint8_t*>(text);
-		p.offsets = offsets;
-		p.outIdx = out_state_idx;
-		p.outFinal = out_final;
-		p.outBegin = reinterpret_cast<long long*>(out_begin);
-		p.outEnd = reinterpret_cast<long long*>(out_end);
-		bool done = false;
-		if (int rc = ragged(p.text, p.offsets, p.outIdx, p.outFinal, p.outBegin, p.outEnd, &done))
-			return rc;
-		if (done)
-			return PIRE_HIP_OK;
-		return launchPerLane();
-	}
-	for (uint64_t i = 0; i < n; ++i)
-		if (offsets[i] > offsets[i + 1]) {
-			SetError("offsets must be non-decreasing");
-			return PIRE_HIP_EINVAL;
-		}
-	const uint64_t textBytes = offsets[n];
-	if (!text && textBytes) {
-		SetError("null text pointer with non-empty strings");
-		return PIRE_HIP_EINVAL;
-	}
-	Staging stage(stream);
-	const uint8_t* dText = nullptr;
-	const uint64_t* dOffs = nullptr;
-	void *dIdx = nullptr, *dFin = nullptr, *dB = nullptr, *dE = nullptr;
+	BatchIO io(stream, (flags & PIRE_HIP_RUN_ON_DEVICE) != 0);
 	int rc;
-	if ((rc = stage.In(static_cast<const uint8_t*>(text), size_t(textBytes), &dText, stream)) ||
-	    (rc = stage.In(offsets, size_t(n + 1), &dOffs, stream)) || (rc = stage.Alloc(&dIdx, n * 4)) ||
-	    (rc = stage.Alloc(&dFin, n)) || (rc = stage.Alloc(&dB, n * 8)) || (rc = stage.Alloc(&dE, n * 8)))
+	if ((rc = io.Text(text, offsets, n, 0, 0, &p.text, &p.offsets)) || (rc = io.Result(out_state_idx, n, n, &p.outIdx)) ||
+	    (rc = io.Result(out_final, n, n, &p.outFinal)) || (rc = io.Result(reinterpret_cast<long long*>(out_begin), n, n, &p.outBegin)) ||
+	    (rc = io.Result(reinterpret_cast<long long*>(out_end), n, n, &p.outEnd)) || (rc = io.Ready()))
 		return rc;
-	p.text = dText;
-	p.offsets = dOffs;
-	p.outIdx = static_cast<uint32_t*>(dIdx);
-	p.outFinal = static_cast<uint8_t*>(dFin);
-	p.outBegin = static_cast<long long*>(dB);
-	p.outEnd = static_cast<long long*>(dE);
 	bool done = false;
 	if ((rc = ragged(p.text, p.offsets, p.outIdx, p.outFinal, p.outBegin, p.outEnd, &done)))
 		return rc;
 	if (!done && (rc = launchPerLane()))
 		return rc;
-	rc = stage.Out(out_state_idx, dIdx, n * 4);
-	if (!rc)
-		rc = stage.Out(out_final, dFin, n);
-	if (!rc)
-		rc = stage.Out(out_begin, dB, n * 8);
-	if (!rc)
-		rc = stage.Out(out_end, dE, n * 8);
-	return rc ? rc : stage.Finish();
+	return io.Finish();
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }

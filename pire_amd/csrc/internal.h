@@ -10,6 +10,7 @@
 #include <atomic>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <shared_mutex>
 #include <string>
 #include <thread>
@@ -532,11 +533,66 @@ void SetError(const std::string& msg);
 int HandleException() noexcept;
 int HipFail(hipError_t e, const char* what);   // sets the error, returns PIRE_HIP_ENODEVICE / ENOMEM
 
+// One block of stream-ordered scratch (hipMallocAsync), freed on the same stream when the owner leaves its scope: declare
+// it in the scope that encloses every launch using the block, and the free is ordered behind those launches on every
+// path out.  Where a block outlives the function that allocates it, the caller passes the owner in.
+class StreamScratch {
+	void* p = nullptr;
+	hipStream_t stream;
+
+public:
+	explicit StreamScratch(hipStream_t s) : stream(s) {}
+	StreamScratch(const StreamScratch&) = delete;
+	StreamScratch& operator=(const StreamScratch&) = delete;
+	~StreamScratch()
+	{
+		if (p)
+			(void)hipFreeAsync(p, stream);
+	}
+	int Alloc(size_t bytes, const char* what)   // once per owner
+	{
+		const hipError_t e = hipMallocAsync(&p, bytes, stream);
+		if (e == hipSuccess)
+			return PIRE_HIP_OK;
+		p = nullptr;
+		return HipFail(e, what);
+	}
+	void* get() const { return p; }
+	template <class T>
+	T* as() const { return static_cast<T*>(p); }
+};
+
+// What every entry point asks of a batch whose arrays the HOST can read: offsets that do not decrease, and text behind
+// them unless every string is empty (a null text pointer is fine then, tests/pire_ut.cpp:832-837).
+inline int CheckOffsets(const uint64_t* offsets, uint64_t n)
+{
+	for (uint64_t i = 0; i < n; ++i)
+		if (offsets[i] > offsets[i + 1]) {
+			SetError("offsets must be non-decreasing");
+			return PIRE_HIP_EINVAL;
+		}
+	return PIRE_HIP_OK;
+}
+// offsets == nullptr: n records of `len` bytes, `stride` apart.  *textBytes: what is read at `text`.
+inline int CheckHostBatch(const void* text, const uint64_t* offsets, uint64_t n, uint64_t len, uint64_t stride, uint64_t* textBytes)
+{
+	if (offsets)
+		if (int rc = CheckOffsets(offsets, n))
+			return rc;
+	*textBytes = offsets ? offsets[n] : n ? (n - 1) * stride + len : 0;
+	if (!text && *textBytes) {
+		SetError("null text pointer with non-empty strings");
+		return PIRE_HIP_EINVAL;
+	}
+	return PIRE_HIP_OK;
+}
+
 // Owns the temporary device buffers of a host-pointer call (PCIe-inclusive convenience mode).  Default: blocks from the
 // per-device cache of api.cpp (StagingAcquire / StagingRelease: no allocation in steady state); they go back when the
 // call returns -- after its stream has been drained, which the destructor sees to itself: an error path may leave
 // copies or kernels in flight.  pire_hip_config.host_staging: 1 = hipMalloc + hipFree per call (round 2), 2 = the
-// stream-ordered pool.
+// stream-ordered pool.  The entry points reach it through BatchIO (below), which is also where a call's pointers pass
+// through untouched when they are the device's already.
 int StagingAcquire(size_t bytes, void** out, size_t* blockBytes);
 void StagingRelease(void* p, size_t blockBytes);
 // the same for PINNED host blocks: small inputs and results cross PCIe from / into pinned memory (a copy between
@@ -737,6 +793,102 @@ struct Staging {
 	}
 };
 
+// The pointers of ONE call of a batch entry point, whichever side they live on: with PIRE_HIP_RUN_ON_DEVICE they pass
+// through, otherwise they are checked (CheckHostBatch) and staged (Staging).  The entry point fills its parameters from
+// what this hands back, launches once and returns Finish().  Order of a call: Text(), further In()s, Result()s, Ready(),
+// the launches, Finish() -- which is Staging's order (inputs, result arrays, Flush, launches, Outs, Finish), so a small
+// call crosses PCIe in one copy each way.
+struct BatchIO {
+	const hipStream_t stream;
+	std::optional<Staging> st;   // of a host-pointer call; a device-pointer call has none
+	struct Back {
+		void* host;
+		const void* dev;
+		size_t bytes;
+	};
+	std::vector<Back> backs;   // results to copy back, in the order they were asked for
+	BatchIO(hipStream_t s, bool onDevice) : stream(s)
+	{
+		if (!onDevice)
+			st.emplace(s);
+	}
+	// offsets == nullptr: fixed-length records (len, stride)
+	int Text(const void* text, const uint64_t* offsets, uint64_t n, uint64_t len, uint64_t stride, const uint8_t** dText,
+	         const uint64_t** dOffsets)
+	{
+		*dText = static_cast<const uint8_t*>(text);
+		*dOffsets = offsets;
+		if (!st)
+			return PIRE_HIP_OK;
+		uint64_t textBytes = 0;
+		if (int rc = CheckHostBatch(text, offsets, n, len, stride, &textBytes))
+			return rc;
+		if (int rc = st->In(static_cast<const uint8_t*>(text), size_t(textBytes), dText, stream))
+			return rc;
+		return offsets ? st->In(offsets, size_t(n) + 1, dOffsets, stream) : PIRE_HIP_OK;
+	}
+	template <class T>
+	int In(const T* host, size_t count, const T** dev)
+	{
+		*dev = host;
+		return st ? st->In(host, count, dev, stream) : PIRE_HIP_OK;
+	}
+	// `bytes` at `dev` into the caller's `host` array when the call finishes (host-pointer calls; nothing when host is null)
+	void CopyBack(void* host, const void* dev, size_t bytes)
+	{
+		if (st)
+			backs.push_back(Back{host, dev, bytes});
+	}
+	// A result array of allocCount elements on the device -- the caller's own when that is where it lives -- of which
+	// the first copyCount come back (the two differ where a kernel wants room that nobody reads: a table of no regexps)
+	template <class T>
+	int Result(T* caller, size_t allocCount, size_t copyCount, T** dev)
+	{
+		*dev = caller;
+		if (!st)
+			return PIRE_HIP_OK;
+		void* d = nullptr;
+		if (int rc = st->Alloc(&d, allocCount * sizeof(T)))
+			return rc;
+		*dev = static_cast<T*>(d);
+		CopyBack(caller, d, copyCount * sizeof(T));
+		return PIRE_HIP_OK;
+	}
+	// In front of the first launch: the inputs that still wait in the staging arena go to the device now.  (A Result()
+	// sends them too, but a call may have none: pire_hip_slow_run with out_counts alone.)
+	int Ready() { return st ? st->Flush() : PIRE_HIP_OK; }
+	int Finish()
+	{
+		if (!st)
+			return PIRE_HIP_OK;
+		for (const Back& b : backs)
+			if (int rc = st->Out(b.host, b.dev, b.bytes))
+				return rc;
+		return st->Finish();
+	}
+};
+
+// PIRE_HIP_RUN_HOST_OFFSETS: the text is resident, the offsets are the host's.  They are checked, copied into
+// stream-ordered scratch and handed to `body` (which launches); the stream is drained on success, because the caller's
+// array was the source of an asynchronous copy.
+template <class Body>
+int WithOffsetsOnDevice(const uint64_t* offsets, uint64_t n, hipStream_t stream, Body&& body)
+{
+	if (int rc = CheckOffsets(offsets, n))
+		return rc;
+	{
+		StreamScratch d(stream);
+		if (int rc = d.Alloc((n + 1) * 8, "hipMallocAsync(offsets)"))
+			return rc;
+		const hipError_t e = hipMemcpyAsync(d.get(), offsets, (n + 1) * 8, hipMemcpyHostToDevice, stream);
+		if (e != hipSuccess)
+			return HipFail(e, "hipMemcpy(offsets)");
+		if (int rc = body(d.as<const uint64_t>()))
+			return rc;
+	}
+	const hipError_t e = hipStreamSynchronize(stream);
+	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipStreamSynchronize");
+}
 
 // table.cpp
 int BuildHostTable(const void* blob, size_t len, HostTable* out);
@@ -924,11 +1076,11 @@ int LaunchStep(const ScanParams& p, uint32_t* stateIdx, uint64_t n, uint32_t cls
 int LaunchHalfFinal(const ScanParams& p, uint32_t* outResults, hipStream_t stream, unsigned long long* workCounter,
                     const uint32_t* list = nullptr);
 // counting.hip: dense HalfFinal counting on the row kernel.  *done = false: not this table / batch.  Strings the 16-bit
-// counters cannot hold are left on `*overflow` (device: [0] = count, then string indices; stream-ordered memory the
-// caller frees) for LaunchHalfFinal(.., list).
+// counters cannot hold are left on `*overflow` (device: [0] = count, then string indices; the caller's owner, allocated
+// here) for LaunchHalfFinal(.., list).
 int LaunchHalfFinalRows(pire_hip_table* t, const uint8_t* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
                         uint32_t* outIdx, uint8_t* outFinal, uint32_t* outResults, hipStream_t stream, bool* done,
-                        uint32_t** overflow);
+                        StreamScratch* overflow);
 void FreeHalfRows(pire_hip_table* t);
 int UploadHalfRows(pire_hip_table* t);   // counting.hip: the dense HalfFinal row image of the current device (first need / table_upload)
 int LaunchPrefix(const ScanParams& p, bool longest, bool throughEnd, long long* outLen, hipStream_t stream,

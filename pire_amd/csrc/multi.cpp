@@ -567,11 +567,9 @@ try {
 		SetError("null argument");
 		return PIRE_HIP_EINVAL;
 	}
-	for (uint64_t i = 0; i < n; ++i)
-		if (offsets[i + 1] < offsets[i]) {
-			SetError("offsets must be non-decreasing");
-			return PIRE_HIP_EINVAL;
-		}
+	if (int rc = CheckOffsets(offsets, n))
+		return rc;
+	// (the shards read [offsets[0], offsets[n]) only: text in front of the first string need not exist)
 	if (n && offsets[n] > offsets[0] && !text) {
 		SetError("null text pointer with non-empty strings");
 		return PIRE_HIP_EINVAL;

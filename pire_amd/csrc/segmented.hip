@@ -527,16 +527,11 @@ struct HostWord {
 	}
 };
 
-struct StreamScratch {
-	hipStream_t stream;
+struct ScratchArena {
+	StreamScratch block;
 	uint8_t* base = nullptr;
 	size_t size = 0, used = 0;
-	explicit StreamScratch(hipStream_t s) : stream(s) {}
-	~StreamScratch()
-	{
-		if (base)
-			(void)hipFreeAsync(base, stream);
-	}
+	explicit ScratchArena(hipStream_t s) : block(s) {}
 	int Reserve(size_t bytes)
 	{
 		// keep freed scratch in the device's pool: by default it goes back to the driver at the next synchronize
@@ -546,11 +541,9 @@ struct StreamScratch {
 			uint64_t keep = 1ull << 30;
 			(void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
 		}
-		void* d = nullptr;
-		hipError_t e = hipMallocAsync(&d, bytes, stream);
-		if (e != hipSuccess)
-			return HipFail(e, "hipMallocAsync(segments)");
-		base = static_cast<uint8_t*>(d);
+		if (int rc = block.Alloc(bytes, "hipMallocAsync(segments)"))
+			return rc;
+		base = block.as<uint8_t>();
 		size = bytes;
 		return PIRE_HIP_OK;
 	}
@@ -893,7 +886,7 @@ int RunSegmented(pire_hip_table* t, const ScanParams& p, const uint64_t* hostOff
 		g.nSeg = acc;
 	}
 	const uint64_t S = g.nSeg;
-	StreamScratch scratch(stream);
+	ScratchArena scratch(stream);
 	const uint64_t chainBlocks = (S + kChainBlock - 1) / kChainBlock;
 	{
 		const size_t perSeg = 3 * 8 + 3 * 4            // the cut
@@ -1113,16 +1106,7 @@ int RunSegmented(pire_hip_table* t, const ScanParams& p, const uint64_t* hostOff
 	};
 	// Modes 0 and B as one walk of their product automaton (EnsureModeProduct) over the grid's whole tasks; the rest as
 	// in addModePair.
-	void* productScratch = nullptr;   // the product walk's own arrays: freed on the stream behind the kernels that use them
-	struct ProductGuard {
-		void*& q;
-		hipStream_t s;
-		~ProductGuard()
-		{
-			if (q)
-				(void)hipFreeAsync(q, s);
-		}
-	} productGuard{productScratch, stream};
+	StreamScratch productScratch(stream);   // the product walk's own arrays: freed on the stream behind the kernels that use them
 	void* pinnedComp = nullptr;
 	size_t pinnedCompBytes = 0;
 	struct PinnedCompGuard {
@@ -1147,8 +1131,8 @@ int RunSegmented(pire_hip_table* t, const ScanParams& p, const uint64_t* hostOff
 		const HostTable& ph = mp.table->host;
 		const uint32_t PN = ph.states;
 		const size_t bytes = ((fusedSegs * 4 + 255) & ~size_t(255)) * 2 + ((size_t(PN) * 4 + 255) & ~size_t(255)) * 2;
-		PIRE_TRY(HipOk(hipMallocAsync(&productScratch, bytes, stream), "hipMallocAsync(product walk)"));
-		uint8_t* base = static_cast<uint8_t*>(productScratch);
+		PIRE_TRY(productScratch.Alloc(bytes, "hipMallocAsync(product walk)"));
+		uint8_t* base = productScratch.as<uint8_t>();
 		uint32_t* guessP = reinterpret_cast<uint32_t*>(base);
 		uint32_t* endP = reinterpret_cast<uint32_t*>(base + ((fusedSegs * 4 + 255) & ~size_t(255)));
 		uint32_t* dCompA = reinterpret_cast<uint32_t*>(base + ((fusedSegs * 4 + 255) & ~size_t(255)) * 2);

@@ -292,24 +292,20 @@ int LaunchSelect(const SelectDevice& image, uint32_t states, uint32_t words, con
 	p.tiles = uint32_t((n + kSelThreads - 1) / kSelThreads);
 	// scratch: n / 8 bytes of ballot words + n / 256 bytes of tile counts, stream-ordered (the call only enqueues)
 	const size_t ballotBytes = size_t(p.tiles) * kSelWaves * 8;
-	void* scratch = nullptr;
-	hipError_t e = hipMallocAsync(&scratch, ballotBytes + size_t(p.tiles) * 4, stream);
-	if (e != hipSuccess)
-		return HipFail(e, "hipMallocAsync(select scratch)");
-	p.ballots = static_cast<uint64_t*>(scratch);
-	p.tileCounts = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(scratch) + ballotBytes);
+	StreamScratch scratch(stream);
+	if (int rc = scratch.Alloc(ballotBytes + size_t(p.tiles) * 4, "hipMallocAsync(select scratch)"))
+		return rc;
+	p.ballots = scratch.as<uint64_t>();
+	p.tileCounts = reinterpret_cast<uint32_t*>(scratch.as<uint8_t>() + ballotBytes);
 	// The LDS form reads states * 8 bytes per BLOCK to save 8 bytes per STRING: only where a block of the small grid
 	// walks at least twice as many strings as the table has states
 	const uint32_t ldsGrid = std::min(p.tiles, kSelLdsBlocks);
 	const uint64_t ldsStrings = uint64_t((p.tiles + ldsGrid - 1) / ldsGrid) * kSelThreads;
 	const bool lds = words == 1 && (want || outMasks) && states <= kSelLdsStates && ldsStrings >= 2ull * states;
-	int rc = PIRE_HIP_OK;
 	if (lds) {
-		e = SetDynamicLds(reinterpret_cast<const void*>(SelectClassifyKernel<true>), kSelLdsStates * 8);
-		if (e != hipSuccess) {
-			(void)hipFreeAsync(scratch, stream);
+		const hipError_t e = SetDynamicLds(reinterpret_cast<const void*>(SelectClassifyKernel<true>), kSelLdsStates * 8);
+		if (e != hipSuccess)
 			return HipFail(e, "hipFuncSetAttribute(LDS)");
-		}
 		hipLaunchKernelGGL(SelectClassifyKernel<true>, dim3(ldsGrid), dim3(kSelThreads), size_t(states) * 8, stream, p);
 	} else {
 		hipLaunchKernelGGL(SelectClassifyKernel<false>, dim3(std::min(p.tiles, kSelMaxBlocks)), dim3(kSelThreads), 0, stream, p);
@@ -317,11 +313,8 @@ int LaunchSelect(const SelectDevice& image, uint32_t states, uint32_t words, con
 	hipLaunchKernelGGL(SelectScanKernel, dim3(1), dim3(kSelThreads), 0, stream, p.tileCounts, p.tiles, outHitCount);
 	if (p.hitCap)
 		hipLaunchKernelGGL(SelectScatterKernel, dim3(std::min(p.tiles, kSelMaxBlocks)), dim3(kSelThreads), 0, stream, p);
-	e = hipGetLastError();
-	if (e != hipSuccess)
-		rc = HipFail(e, "select launch");
-	(void)hipFreeAsync(scratch, stream);
-	return rc;
+	const hipError_t e = hipGetLastError();
+	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "select launch");
 }
 
 }  // namespace pirehip

@@ -1016,12 +1016,11 @@ int LaunchSlowWide(const SlowParams& p0, uint32_t njumps, hipStream_t stream)
 		room -= posBytes;
 	const uint32_t jumpsInLds = posInLds && jumpBytes <= room ? 1 : 0;
 	const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((p.n + waves - 1) / waves, uint64_t(cus)));
-	void* scratch = nullptr;
+	StreamScratch scratch(stream);
 	if (!inLds) {
-		e = hipMallocAsync(&scratch, blocks * waves * setBytes, stream);
-		if (e != hipSuccess)
-			return HipFail(e, "hipMallocAsync(slow scanner sets)");
-		p.scratch = static_cast<uint32_t*>(scratch);
+		if (int rc = scratch.Alloc(blocks * waves * setBytes, "hipMallocAsync(slow scanner sets)"))
+			return rc;
+		p.scratch = scratch.as<uint32_t>();
 	}
 	const uint32_t ldsBytes = uint32_t(272 + (inLds ? waves * setBytes : 0) + (posInLds ? posBytes : 0) + (jumpsInLds ? jumpBytes : 0));
 	const void* fn = inLds ? reinterpret_cast<const void*>(SlowWideKernel<true>) : reinterpret_cast<const void*>(SlowWideKernel<false>);
@@ -1035,8 +1034,6 @@ int LaunchSlowWide(const SlowParams& p0, uint32_t njumps, hipStream_t stream)
 		hipLaunchKernelGGL(SlowWideKernel<false>, dim3(unsigned(blocks)), dim3(waves * 64), ldsBytes, stream, p, waves, posInLds,
 		                   jumpsInLds, njumps);
 	e = hipGetLastError();
-	if (scratch)
-		(void)hipFreeAsync(scratch, stream);
 	if (e != hipSuccess)
 		return HipFail(e, "slow kernel launch");
 	return PIRE_HIP_OK;
@@ -1054,41 +1051,30 @@ int LaunchSlowListThen(const SlowParams& p0, hipStream_t stream, Fallback fallba
 	if ((e = hipGetDevice(&dev)) != hipSuccess ||
 	    (e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess)
 		return HipFail(e, "device query");
-	void* list = nullptr;
-	e = hipMallocAsync(&list, (size_t(p.n) + 1) * 4, stream);
-	if (e == hipSuccess)
-		e = hipMemsetAsync(list, 0, 4, stream);
-	if (e != hipSuccess) {
-		if (list)
-			(void)hipFreeAsync(list, stream);
+	StreamScratch list(stream);
+	if (int rc = list.Alloc((size_t(p.n) + 1) * 4, "hipMallocAsync(slow scanner overflow list)"))
+		return rc;
+	e = hipMemsetAsync(list.get(), 0, 4, stream);
+	if (e != hipSuccess)
 		return HipFail(e, "hipMallocAsync(slow scanner overflow list)");
-	}
-	p.overflow = static_cast<uint32_t*>(list);
+	p.overflow = list.as<uint32_t>();
 	// ragged batches: the strings by length class (order.hip) -- this kernel is all VALU, a wave waiting for its longest
 	// string is its one avoidable cost
-	void* orderScratch = nullptr;
+	StreamScratch orderScratch(stream);
 	p.order = nullptr;
 	if (p.offsets && LengthOrderWanted(p.n)) {
-		e = hipMallocAsync(&orderScratch, LengthOrderScratchBytes(p.n), stream);
-		if (e != hipSuccess) {
-			(void)hipFreeAsync(list, stream);
-			return HipFail(e, "hipMallocAsync(length order)");
-		}
+		if (int rc = orderScratch.Alloc(LengthOrderScratchBytes(p.n), "hipMallocAsync(length order)"))
+			return rc;
 		bool serp = false;
-		const int orc = BuildLengthOrder(p.offsets, p.n, orderScratch, stream, &p.order, &serp);
+		if (int rc = BuildLengthOrder(p.offsets, p.n, orderScratch.get(), stream, &p.order, &serp))
+			return rc;
 		p.serpentine = serp ? 1u : 0u;
-		if (orc) {
-			(void)hipFreeAsync(orderScratch, stream);
-			(void)hipFreeAsync(list, stream);
-			return orc;
-		}
 	}
 	const uint32_t ldsBytes = uint32_t(1056 + 16 + size_t(p.states + 1) * p.letters * 4);
 	e = SetDynamicLds(reinterpret_cast<const void*>(SlowListKernel), uint32_t(ldsBytes));
-	int rc = PIRE_HIP_OK;
-	if (e != hipSuccess) {
-		rc = HipFail(e, "hipFuncSetAttribute(LDS)");
-	} else {
+	if (e != hipSuccess)
+		return HipFail(e, "hipFuncSetAttribute(LDS)");
+	{
 		// one string per lane and ~100 VALU instructions per byte: spread the waves over every SIMD of the chip before
 		// stacking them (65 536 strings are 1 024 waves = one per SIMD: 256-thread blocks, one per CU)
 		const unsigned threads = p.n >= uint64_t(cus) * 2048 ? 1024 : p.n >= uint64_t(cus) * 512 ? 512 : 256;
@@ -1098,20 +1084,15 @@ int LaunchSlowListThen(const SlowParams& p0, hipStream_t stream, Fallback fallba
 		hipLaunchKernelGGL(SlowListKernel, dim3(blocks), dim3(threads), ldsBytes, stream, p);
 		e = hipGetLastError();
 		if (e != hipSuccess)
-			rc = HipFail(e, "slow kernel launch");
+			return HipFail(e, "slow kernel launch");
 	}
-	if (rc == PIRE_HIP_OK && GetConfig().slow_stats) {   // measurements: how many strings the 16-slot list could not hold
+	if (GetConfig().slow_stats) {   // measurements: how many strings the 16-slot list could not hold
 		uint32_t over = 0;
-		if (hipStreamSynchronize(stream) == hipSuccess && hipMemcpy(&over, list, 4, hipMemcpyDeviceToHost) == hipSuccess)
+		if (hipStreamSynchronize(stream) == hipSuccess && hipMemcpy(&over, list.get(), 4, hipMemcpyDeviceToHost) == hipSuccess)
 			fprintf(stderr, "pire_hip slow: %u of %llu strings left the list kernel for the %s one\n", over,
 			        static_cast<unsigned long long>(p.n), p.words > 8 ? "wave-per-string" : "bitset");
 	}
-	if (rc == PIRE_HIP_OK)
-		rc = fallback(p);   // p.overflow set: only the strings on the list
-	if (orderScratch)
-		(void)hipFreeAsync(orderScratch, stream);
-	(void)hipFreeAsync(list, stream);
-	return rc;
+	return fallback(p);   // p.overflow set: only the strings on the list
 }
 
 int RunSlow(pire_hip_slow_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint64_t len, uint64_t stride,
@@ -1169,57 +1150,21 @@ int RunSlow(pire_hip_slow_table* t, const void* text, const uint64_t* offsets, u
 			                    K == 4 ? "pirehip::SlowScanKernel<4>" : "pirehip::SlowScanKernel<8>");
 		return plain(q);
 	};
-	if (flags & PIRE_HIP_RUN_ON_DEVICE) {
-		p.text = static_cast<const uint8_t*>(text);
-		p.offsets = offsets;
-		p.outFinal = outFinal;
-		p.outBits = outBits;
-		p.outCounts = reinterpret_cast<unsigned long long*>(outCounts);
-		return launch(p);
-	}
-	// host-pointer mode: stage through HBM
-	Staging stage(stream);
-	auto alloc = [&](void** d, size_t bytes) { return stage.Alloc(d, bytes); };
-	auto cleanup = [] {};   // the staging frees itself when the call returns
-	uint64_t textBytes = offsets ? offsets[n] : (n - 1) * stride + len;
-	if (!text && textBytes) {
-		SetError("null text pointer with non-empty strings");
-		return PIRE_HIP_EINVAL;
-	}
-	void *dText = nullptr, *dOff = nullptr, *dFin = nullptr, *dBits = nullptr, *dCnt = nullptr;
-	int rc = alloc(&dText, textBytes);
-	if (!rc && textBytes)
-		if (hipMemcpyAsync(dText, text, textBytes, hipMemcpyHostToDevice, stream) != hipSuccess)
-			rc = HipFail(hipGetLastError(), "hipMemcpy(H2D)");
-	if (!rc && offsets) {
-		rc = alloc(&dOff, (n + 1) * 8);
-		if (!rc && hipMemcpyAsync(dOff, offsets, (n + 1) * 8, hipMemcpyHostToDevice, stream) != hipSuccess)
-			rc = HipFail(hipGetLastError(), "hipMemcpy(H2D)");
-	}
-	if (!rc && outFinal) rc = alloc(&dFin, n);
-	if (!rc && outBits) rc = alloc(&dBits, n * h.words * 4);
+	BatchIO io(stream, (flags & PIRE_HIP_RUN_ON_DEVICE) != 0);
+	const unsigned long long* dCnt = nullptr;   // accumulated into: an input as well as a result
+	int rc = io.Text(text, offsets, n, len, stride, &p.text, &p.offsets);
 	if (!rc && outCounts) {
-		rc = alloc(&dCnt, 16);
-		if (!rc && hipMemcpyAsync(dCnt, outCounts, 16, hipMemcpyHostToDevice, stream) != hipSuccess)
-			rc = HipFail(hipGetLastError(), "hipMemcpy(H2D)");
+		rc = io.In(reinterpret_cast<const unsigned long long*>(outCounts), 2, &dCnt);
+		p.outCounts = const_cast<unsigned long long*>(dCnt);
 	}
-	if (!rc) {
-		p.text = static_cast<const uint8_t*>(dText);
-		p.offsets = static_cast<const uint64_t*>(dOff);
-		p.outFinal = static_cast<uint8_t*>(dFin);
-		p.outBits = static_cast<uint32_t*>(dBits);
-		p.outCounts = static_cast<unsigned long long*>(dCnt);
-		rc = launch(p);
-	}
-	hipError_t e = hipSuccess;
-	if (!rc && outFinal) e = hipMemcpyAsync(outFinal, dFin, n, hipMemcpyDeviceToHost, stream);
-	if (!rc && e == hipSuccess && outBits) e = hipMemcpyAsync(outBits, dBits, n * h.words * 4, hipMemcpyDeviceToHost, stream);
-	if (!rc && e == hipSuccess && outCounts) e = hipMemcpyAsync(outCounts, dCnt, 16, hipMemcpyDeviceToHost, stream);
-	if (!rc && e == hipSuccess) e = hipStreamSynchronize(stream);
-	if (!rc && e != hipSuccess)
-		rc = HipFail(e, "copy back / synchronize");
-	cleanup();
-	return rc;
+	if (!rc && outFinal)
+		rc = io.Result(outFinal, n, n, &p.outFinal);
+	if (!rc && outBits)
+		rc = io.Result(outBits, n * h.words, n * h.words, &p.outBits);
+	io.CopyBack(outCounts, dCnt, 16);
+	if (rc || (rc = io.Ready()) || (rc = launch(p)))
+		return rc;
+	return io.Finish();
 }
 
 }  // namespace

@@ -55,3 +55,28 @@ for mode in (0, 1, 2):
         print("%-10s %d strings x ~%d B: median %.0f us, min %.0f us per call (host_staging=%d)" % (
             name, n, ln, 1e6 * np.median(ts), 1e6 * min(ts), mode))
 pb.set_config(host_staging=0)
+
+# the scanners with actions in host mode (counting, capturing, slow): 10 and 1 000 strings of the same text, tables from
+# tests/golden; what `profiles/host_call_latency_one_path.txt` records
+def golden(section, name):
+    return [c for c in H.golden()[section] if c["name"] == name][0]
+
+
+cc = golden("counting", "count2_basic")
+counting = pire_amd.CountingTable(H.load_blob(cc["blob"]), cc["kind"])
+capturing = pire_amd.CountingTable(H.load_blob(golden("capturing", "capture_digits")["blob"]), 0)
+slow = pire_amd.SlowTable(H.load_blob(golden("slow", "slow_alt")["blob"]))
+for n in (10, 1000):
+    lens = rng.randint(ln // 2, ln + 1, size=n)
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum(lens)
+    text = text_of(int(offs[-1]))
+    for name, fn in (("counting_run", lambda: counting.run(text, offs)), ("capture_run", lambda: capturing.capture(text, offs)),
+                     ("slow_run", lambda: slow.run(text, offs))):
+        fn()
+        ts = []
+        for _ in range(200):
+            t0 = time.perf_counter()
+            fn()
+            ts.append(time.perf_counter() - t0)
+        print("%-12s %4d strings x ~%d B: median %.1f us, min %.1f us per call" % (name, n, ln, 1e6 * np.median(ts), 1e6 * min(ts)))
