@@ -324,8 +324,10 @@ pire_hip_config GetConfig()
 	return ConfigStorage();
 }
 
-int RunSelfTestVariants(const std::vector<std::function<void(pire_hip_config&)>>& edits, const std::function<int()>& body)
+int RunKnownAnswer(const std::vector<ConfigEdit>& edits, const std::function<void()>& poison,
+                   const std::function<int(hipStream_t)>& call, const std::function<int()>& compare)
 {
+	OwnStream own;
 	const pire_hip_config base = GetConfig();
 	const pire_hip_config* const outer = g_cfgOverride;
 	const bool was = g_inEntrySelfTest;
@@ -339,7 +341,10 @@ int RunSelfTestVariants(const std::vector<std::function<void(pire_hip_config&)>>
 		g_cfgOverride = &c;
 		g_inEntrySelfTest = true;
 		try {
-			rc = body();
+			poison();
+			rc = call(own.s);
+			if (rc == PIRE_HIP_OK)
+				rc = compare();
 		} catch (...) {
 			g_cfgOverride = outer;
 			g_inEntrySelfTest = was;
@@ -1730,18 +1735,6 @@ namespace {
 
 enum : uint32_t { kEntryPrefix = 8, kEntrySuffix = 9, kEntryHalfFinal = 10, kEntryPair = 11 };   // bits of pire_hip_table::selfTested
 
-struct OwnStream {
-	hipStream_t s = nullptr;
-	OwnStream() { (void)hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
-	~OwnStream()
-	{
-		if (s) {
-			(void)hipStreamSynchronize(s);
-			(void)hipStreamDestroy(s);
-		}
-	}
-};
-
 // the table's transitions, flags and final lists in the reference's numbering: they never change (an adaptation renumbers
 // the DEVICE side only)
 struct HostWalk {
@@ -1749,15 +1742,8 @@ struct HostWalk {
 	uint32_t Next(uint32_t st, uint32_t ch) const { return h.next[size_t(st) * h.letters + h.cls[ch]]; }
 	bool Final(uint32_t st) const { return (h.flags[st] & kFinal) != 0; }
 	bool Dead(uint32_t st) const { return (h.flags[st] & kDead) != 0; }
+	uint64_t Salt() const { return (uint64_t(h.states) << 20) ^ h.letters; }   // (KnownBatchFor)
 };
-
-bool EntryTested(pire_hip_table* t, uint32_t bit, int* dev)
-{
-	*dev = -1;
-	if (hipGetDevice(dev) != hipSuccess || *dev < 0 || *dev >= kMaxDevices)
-		return true;   // (no device: the entry point says so itself)
-	return (t->selfTested[*dev].load(std::memory_order_relaxed) & (1u << bit)) != 0;
-}
 
 // LongestPrefix / ShortestPrefix as the reference walks them (run.h:69-100, 277-311), on the host table
 int64_t HostPrefix(const HostWalk& w, const uint8_t* b, const uint8_t* e, bool longest, bool throughBegin, bool throughEnd)
@@ -1822,19 +1808,13 @@ int64_t HostSuffix(const HostWalk& w, const uint8_t* first, const uint8_t* last1
 	return w.Final(st) ? int64_t(last1 - r) : -1;
 }
 
-KnownBatch TableBatch(const HostWalk& w, uint32_t n, uint32_t maxLen, uint32_t start, uint64_t seed)
-{
-	return MakeKnownBatch(n, maxLen, start, seed ^ (uint64_t(w.h.states) << 20) ^ w.h.letters,
-	                      [&](uint32_t st, uint32_t ch) { return w.Next(st, ch); }, [&](uint32_t st) { return w.Dead(st); });
-}
-
 // Marks an entry point tested on this device -- unless a re-ranking has meanwhile zipped the wide image or given the plain rows
 // back (it cleared the bit: ForgetLayoutSelfTests), so that the next call tests the other instantiations.
 void MarkEntryTested(pire_hip_table* t, int dev, uint32_t bit, bool zipped)
 {
 	std::shared_lock<std::shared_mutex> stable(t->adaptMutex);
 	if ((t->host.zipFull != 0) == zipped)
-		t->selfTested[dev].fetch_or(1u << bit);
+		MarkTested(t, dev, bit);
 }
 
 int SelfTestPrefix(pire_hip_table* t, bool suffix, int a, int b, hipStream_t stream)
@@ -1855,7 +1835,7 @@ int SelfTestPrefix(pire_hip_table* t, bool suffix, int a, int b, hipStream_t str
 	const HostWalk w{t->host};
 	// (prefix: a = throughBegin, b = throughEnd; suffix: a = throughEnd, b = throughBegin -- the mark the walk starts with first)
 	const uint32_t start = a ? w.Next(t->host.initial, suffix ? kEndMark : kBeginMark) : t->host.initial;
-	const KnownBatch kb = TableBatch(w, 320, 200, start, suffix ? 2 : 1);
+	const KnownBatch kb = KnownBatchFor(w, start, suffix ? 2 : 1);
 	std::vector<int64_t> wants[2];
 	for (int longest = 0; longest < 2; ++longest) {
 		std::vector<int64_t>& want = wants[longest];
@@ -1868,23 +1848,20 @@ int SelfTestPrefix(pire_hip_table* t, bool suffix, int a, int b, hipStream_t str
 		if (mode == 2)
 			want[kb.n / 2] += 1;
 	}
-	std::vector<std::function<void(pire_hip_config&)>> variants;
+	std::vector<ConfigEdit> variants;
 	variants.push_back([](pire_hip_config& c) { c.ragged_act_always = 1; c.no_ragged_act = 0; });   // the ragged kernel with actions
 	if (!suffix)
 		variants.push_back([](pire_hip_config& c) { c.no_ragged_act = 1; c.ragged_act_always = 0; });   // one string per lane
 	if (!suffix && t->host.wide && t->host.states <= 65536)   // ... and the ragged kernel with actions on the class-indexed walk
 		variants.push_back([](pire_hip_config& c) { c.ragged_act_always = 1; c.no_ragged_act = 0; c.walk_variant = 2; c.tiled_variant = 0; c.checked = 0; });
 	stable.unlock();
-	OwnStream own;
 	for (int longest = 0; longest < 2; ++longest) {
 		const std::vector<int64_t>& want = wants[longest];
 		std::vector<int64_t> got(kb.n);
-		const int rc = RunSelfTestVariants(variants, [&]() -> int {
-			std::fill(got.begin(), got.end(), int64_t(-77));
-			const int r = suffix ? pire_hip_suffix(t, kb.text.data(), kb.offsets.data(), kb.n, longest, a, b, 0, got.data(), own.s)
-			                     : pire_hip_prefix(t, kb.text.data(), kb.offsets.data(), kb.n, longest, a, b, 0, got.data(), own.s);
-			if (r != PIRE_HIP_OK)
-				return r;
+		const int rc = RunKnownAnswer(variants, [&] { std::fill(got.begin(), got.end(), int64_t(-77)); }, [&](hipStream_t own) {
+			return suffix ? pire_hip_suffix(t, kb.text.data(), kb.offsets.data(), kb.n, longest, a, b, 0, got.data(), own)
+			              : pire_hip_prefix(t, kb.text.data(), kb.offsets.data(), kb.n, longest, a, b, 0, got.data(), own);
+		}, [&]() -> int {
 			for (uint32_t i = 0; i < kb.n; ++i)
 				if (got[i] != want[i])
 					return SelfTestMismatch(suffix ? (longest ? "LongestSuffix" : "ShortestSuffix") : (longest ? "LongestPrefix" : "ShortestPrefix"),
@@ -1916,7 +1893,7 @@ int SelfTestHalfFinal(pire_hip_table* t, uint32_t flags, hipStream_t stream)
 	const uint32_t R = h.regexps;
 	flags &= PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END;
 	const uint32_t start = (flags & PIRE_HIP_RUN_BEGIN) ? w.Next(h.initial, kBeginMark) : h.initial;
-	const KnownBatch kb = TableBatch(w, 320, 200, start, 3);
+	const KnownBatch kb = KnownBatchFor(w, start, 3);
 	std::vector<uint32_t> wantIdx(kb.n), wantRes(size_t(kb.n) * R, 0), gotIdx(kb.n), gotRes(size_t(kb.n) * R);
 	std::vector<uint8_t> wantFin(kb.n), gotFin(kb.n);
 	for (uint32_t i = 0; i < kb.n; ++i) {
@@ -1939,20 +1916,19 @@ int SelfTestHalfFinal(pire_hip_table* t, uint32_t flags, hipStream_t stream)
 	}
 	if (mode == 2)
 		wantIdx[kb.n / 2] ^= 1;
-	std::vector<std::function<void(pire_hip_config&)>> variants;
+	std::vector<ConfigEdit> variants;
 	variants.push_back([](pire_hip_config& c) { c.counting_variant = 2; });                        // the row kernel where the table has that image
 	variants.push_back([](pire_hip_config& c) { c.counting_variant = 1; c.no_ragged_act = 0; });   // the ragged kernel with actions
 	variants.push_back([](pire_hip_config& c) { c.counting_variant = 1; c.no_ragged_act = 1; });   // one string per lane
 	if (h.wide && h.states <= 65536)   // the ragged kernel with actions on the class-indexed walk
 		variants.push_back([](pire_hip_config& c) { c.counting_variant = 1; c.no_ragged_act = 0; c.walk_variant = 2; c.tiled_variant = 0; c.checked = 0; });
 	stable.unlock();
-	OwnStream own;
-	const int rc = RunSelfTestVariants(variants, [&]() -> int {
+	const int rc = RunKnownAnswer(variants, [&] {
 		std::fill(gotIdx.begin(), gotIdx.end(), ~0u);
 		std::fill(gotRes.begin(), gotRes.end(), ~0u);
-		const int r = pire_hip_run_half_final(t, kb.text.data(), kb.offsets.data(), kb.n, flags, gotIdx.data(), gotFin.data(), gotRes.data(), own.s);
-		if (r != PIRE_HIP_OK)
-			return r;
+	}, [&](hipStream_t own) {
+		return pire_hip_run_half_final(t, kb.text.data(), kb.offsets.data(), kb.n, flags, gotIdx.data(), gotFin.data(), gotRes.data(), own);
+	}, [&]() -> int {
 		for (uint32_t i = 0; i < kb.n; ++i) {
 			if (gotIdx[i] != wantIdx[i] || gotFin[i] != wantFin[i])
 				return SelfTestMismatch("HalfFinalScanner", i, "state " + std::to_string(gotIdx[i]), "state " + std::to_string(wantIdx[i]));

@@ -645,7 +645,7 @@ __global__ __launch_bounds__(1024) void CountingRowKernel(CountingParams p)
 
 // KIND: PIRE_HIP_COUNTING_BASIC / _ADVANCED / _NOGLUELIMIT (the latter with at most RMAX regexps: counters in registers)
 // (blocks of up to 16 waves -- 8 for the sixteen-counter instantiations, whose counters need more than 128 registers --
-// so that a table of up to 150 KB can sit in LDS: LaunchOne)
+// so that a table of up to 150 KB can sit in LDS: DenseGrid)
 template <int RMAX, int KIND>
 __global__ __launch_bounds__(RMAX > 8 ? 512 : 1024) void CountingKernel(CountingParams p)
 {
@@ -1096,9 +1096,41 @@ __global__ __launch_bounds__(1024) void CaptureRowKernel(CountingParams p)
 	}
 }
 
-// The dense, packed form of CountingPackedKernel for LoadedScanner tables (CountingScanner / AdvancedCountingScanner:
-// the action word is increment bits 0..15 | reset bits 16..31, loaded.h:223-224).  Left empty -- the 32-bit kernel
-// stays -- for more than 255 states or distinct actions, or a table that would not leave room for several blocks per CU.
+// The action words of a row image as the packed kernels take them: per id (slot 0 = no action) 2 * nreg words, the
+// 16-bit halves of the counters -- what a step adds to each in the first nreg words, the reset masks in the next.
+// step(word, r) = {what the word adds to regexp r's counter, whether it resets it}.
+struct CounterStep {
+	uint32_t add;
+	bool reset;
+};
+template <class StepFn>
+std::vector<uint32_t> PackActionWords(const std::vector<uint64_t>& ids, size_t slots, uint32_t nreg, uint32_t regexps, StepFn step)
+{
+	std::vector<uint32_t> words(slots * 2 * nreg, 0);
+	for (size_t i = 0; i < ids.size(); ++i) {
+		uint32_t* w = &words[(i + 1) * 2 * nreg];
+		for (uint32_t r = 0; r < regexps; ++r) {
+			const CounterStep s = step(ids[i], r);
+			w[r >> 1] |= s.add << (16 * (r & 1));                         // added to the counter's 16-bit half
+			if (s.reset)
+				w[nreg + (r >> 1)] |= 0xFFFFu << (16 * (r & 1));      // the counter's reset mask
+		}
+	}
+	return words;
+}
+// (a LoadedScanner action word: increment bits 0..15 | reset bits 16..31, loaded.h:223-224)
+CounterStep CountingStep(uint64_t action, uint32_t r)
+{
+	return {uint32_t(action >> r) & 1u, ((action >> (kMaxReCount + r)) & 1u) != 0};
+}
+
+// The dense, packed form of CountingPackedKernel for LoadedScanner tables (CountingScanner / AdvancedCountingScanner).
+// Left empty -- the 32-bit kernel stays -- for more than 255 states or distinct actions, or a table that would not leave
+// room for several blocks per CU.
+uint32_t PackedLds(uint32_t states, uint32_t nreg)
+{
+	return uint32_t(size_t(states) * 512 + 256 * 2 * nreg * 4);
+}
 void BuildDenseCounting(CountingHost& t)
 {
 	t.dense.clear();
@@ -1106,9 +1138,9 @@ void BuildDenseCounting(CountingHost& t)
 	if (t.type != 4 || t.states == 0 || t.states > 255 || t.regexps == 0 || t.regexps > kMaxReCount)
 		return;
 	const uint32_t nreg = t.regexps <= 2 ? 1 : t.regexps <= 4 ? 2 : t.regexps <= 8 ? 4 : 8;
-	if (size_t(t.states) * 512 + 256 * 2 * nreg * 4 > 150 * 1024)   // (more than 40 KB: one block of 16 waves per CU, LaunchPacked)
+	if (PackedLds(t.states, nreg) > 150 * 1024)   // (more than 40 KB: one block of 16 waves per CU, DenseGrid)
 		return;
-	std::vector<uint32_t> ids;   // distinct non-zero action words, id = index + 1
+	std::vector<uint64_t> ids;   // distinct non-zero action words, id = index + 1
 	// tables whose action words all fit a byte (CapturingScanner: 1 = BeginCapture, 2 = EndCapture) keep them as ids:
 	// CaptureDenseKernel reads the action itself out of the entry
 	uint32_t maxAction = 0;
@@ -1141,69 +1173,82 @@ void BuildDenseCounting(CountingHost& t)
 				marks[size_t(st) * 2 + (ch - 256)] = e;
 		}
 	}
-	t.actWords.assign(size_t(256) * 2 * nreg, 0);
-	for (size_t i = 0; i < ids.size(); ++i) {
-		uint32_t* w = &t.actWords[(i + 1) * 2 * nreg];
-		for (uint32_t r = 0; r < t.regexps; ++r) {
-			if ((ids[i] >> r) & 1u)
-				w[r >> 1] |= 1u << (16 * (r & 1));                    // +1 in the counter's 16-bit half
-			if ((ids[i] >> (kMaxReCount + r)) & 1u)
-				w[nreg + (r >> 1)] |= 0xFFFFu << (16 * (r & 1));      // the counter's reset mask
-		}
-	}
+	t.actWords = PackActionWords(ids, 256, nreg, t.regexps, CountingStep);
 	t.dense.swap(dense);
 	t.denseMarks.swap(marks);
 	t.nreg = nreg;
 }
 
-// The letter-indexed rows of CountingRowKernel: what BuildDenseCounting does for tables of up to 255 states, without the
-// expansion to 256 columns -- (states + 1) x (letters + 1) entries of 8 bytes in LDS, so hundreds of states fit.
+// The letter-indexed rows of CountingRowKernel<.., LETTERS>: what BuildDenseCounting does for tables of up to 255 states,
+// without the expansion to 256 columns -- (states + 1) x (letters + 1) entries of 8 bytes in LDS, so hundreds of states
+// fit -- with the action words of its entries behind them.
 constexpr size_t kCountingRowLds = 150 * 1024;
+uint32_t LetterRowLds(uint32_t states, uint32_t letters, uint32_t lactCount, uint32_t nreg)
+{
+	return uint32_t(((size_t(states + 1) * (letters + 1) * 8 + 15) & ~size_t(15)) + size_t(lactCount) * 2 * nreg * 4 + 512);
+}
+// The image as it is built on the host: entry (state, letter) = next state | id << 16 of what the step does, ids numbered
+// from 1 as the distinct non-zero action words first appear.  BuildLetterRows gives it the actions of a counting table's
+// transitions, BuildHalfRows the increments of the state a step arrives in.
+struct LetterRowImage {
+	uint32_t nreg = 0;
+	size_t maxIds = 0;
+	std::vector<uint32_t> rows;
+	std::vector<uint64_t> ids;
+	std::unordered_map<uint64_t, uint32_t> idOf;
+	// false: not a table for the row kernel (counters that do not pack, rows that do not fit the LDS)
+	bool Start(uint32_t states, uint32_t letters, uint32_t regexps)
+	{
+		if (states == 0 || states > 65535 || regexps == 0 || regexps > 8 || letters == 0 || letters > 255)
+			return false;
+		nreg = regexps <= 2 ? 1 : regexps <= 4 ? 2 : 4;
+		const size_t rowBytes = (size_t(states) + 1) * (letters + 1) * 8 + 16 + 512;
+		if (rowBytes + 2 * 8 * nreg > kCountingRowLds)
+			return false;
+		// as many distinct actions as fit behind the rows (8 * nreg bytes each), at most what 16 bits number
+		maxIds = std::min<size_t>(65535, (kCountingRowLds - rowBytes) / (8 * nreg) - 1);
+		return true;
+	}
+	bool Id(uint64_t action, uint32_t* id)   // false: one action too many
+	{
+		*id = 0;
+		if (!action)
+			return true;
+		auto it = idOf.find(action);
+		if (it == idOf.end()) {
+			if (ids.size() == maxIds)
+				return false;
+			ids.push_back(action);
+			it = idOf.emplace(action, uint32_t(ids.size())).first;
+		}
+		*id = it->second;
+		return true;
+	}
+	template <class NextFn, class ActionFn>
+	bool Rows(uint32_t states, uint32_t letters, NextFn next, ActionFn action)
+	{
+		rows.resize(size_t(states) * letters);
+		for (size_t i = 0; i < rows.size(); ++i) {
+			uint32_t id;
+			if (!Id(action(i), &id) || next(i) >= states)
+				return false;
+			rows[i] = next(i) | (id << 16);
+		}
+		return true;
+	}
+};
+
 void BuildLetterRows(CountingHost& t)
 {
 	t.lrows.clear();
 	t.lnreg = 0;
-	if (t.type != 4 || t.states == 0 || t.states > 65535 || t.regexps == 0 || t.regexps > 8 || t.letters == 0 || t.letters > 255)
+	LetterRowImage im;
+	if (t.type != 4 || !im.Start(t.states, t.letters, t.regexps) ||
+	    !im.Rows(t.states, t.letters, [&](size_t i) { return uint32_t(t.trans[i]); }, [&](size_t i) { return t.trans[i] >> 32; }))
 		return;
-	const uint32_t nreg = t.regexps <= 2 ? 1 : t.regexps <= 4 ? 2 : 4;
-	const size_t rowBytes = (size_t(t.states) + 1) * (t.letters + 1) * 8 + 16 + 512;
-	if (rowBytes + 2 * 8 * nreg > kCountingRowLds)
-		return;
-	// as many distinct actions as fit behind the rows (8 * nreg bytes each), at most what 16 bits number
-	const size_t maxIds = std::min<size_t>(65535, (kCountingRowLds - rowBytes) / (8 * nreg) - 1);
-	std::vector<uint32_t> ids;   // distinct non-zero action words, id = index + 1
-	std::unordered_map<uint32_t, uint32_t> idOf;
-	std::vector<uint32_t> rows(size_t(t.states) * t.letters);
-	for (size_t i = 0; i < rows.size(); ++i) {
-		const uint64_t x = t.trans[i];
-		const uint32_t a = uint32_t(x >> 32);
-		uint32_t id = 0;
-		if (a) {
-			auto it = idOf.find(a);
-			if (it == idOf.end()) {
-				if (ids.size() == maxIds)
-					return;
-				ids.push_back(a);
-				it = idOf.emplace(a, uint32_t(ids.size())).first;
-			}
-			id = it->second;
-		}
-		if (uint32_t(x) >= t.states)
-			return;
-		rows[i] = uint32_t(x) | (id << 16);
-	}
-	t.lactWords.assign((ids.size() + 1) * 2 * nreg, 0);
-	for (size_t i = 0; i < ids.size(); ++i) {
-		uint32_t* w = &t.lactWords[(i + 1) * 2 * nreg];
-		for (uint32_t r = 0; r < t.regexps; ++r) {
-			if ((ids[i] >> r) & 1u)
-				w[r >> 1] |= 1u << (16 * (r & 1));                    // +1 in the counter's 16-bit half
-			if ((ids[i] >> (kMaxReCount + r)) & 1u)
-				w[nreg + (r >> 1)] |= 0xFFFFu << (16 * (r & 1));      // the counter's reset mask
-		}
-	}
-	t.lrows.swap(rows);
-	t.lnreg = nreg;
+	t.lactWords = PackActionWords(im.ids, im.ids.size() + 1, im.nreg, t.regexps, CountingStep);
+	t.lrows.swap(im.rows);
+	t.lnreg = im.nreg;
 }
 
 int BuildCountingHost(const void* blob, size_t len, CountingHost* out)
@@ -1333,6 +1378,16 @@ void FreeCountingDevice(CountingDevice* d)
 	*d = CountingDevice();
 }
 
+// One array of a table image on the current device, `pad` bytes behind it that the kernels may read.
+template <class T>
+hipError_t PutOnDevice(T** dst, const std::vector<T>& v, size_t pad = 0)
+{
+	hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), v.size() * sizeof(T) + pad);
+	if (e == hipSuccess)
+		e = hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+	return e;
+}
+
 // Image of the current device (built on first use), copied out under the table's lock.
 int UploadCounting(pire_hip_counting_table* t, CountingDevice* image)
 {
@@ -1350,46 +1405,25 @@ int UploadCounting(pire_hip_counting_table* t, CountingDevice* image)
 		return PIRE_HIP_OK;
 	}
 	CountingDevice d;
-	e = hipMalloc(reinterpret_cast<void**>(&d.letterOf), 272);
+	const CountingHost& h = t->host;
+	e = PutOnDevice(&d.letterOf, h.letterOf, 8);
 	if (e == hipSuccess)
-		e = hipMalloc(reinterpret_cast<void**>(&d.trans), t->host.trans.size() * 8);
+		e = PutOnDevice(&d.trans, h.trans);
+	if (e == hipSuccess && !h.actions.empty())
+		e = PutOnDevice(&d.actions, h.actions);
 	if (e == hipSuccess)
-		e = hipMemcpy(d.letterOf, t->host.letterOf.data(), 264, hipMemcpyHostToDevice);
-	if (e == hipSuccess)
-		e = hipMemcpy(d.trans, t->host.trans.data(), t->host.trans.size() * 8, hipMemcpyHostToDevice);
-	if (e == hipSuccess && !t->host.actions.empty()) {
-		e = hipMalloc(reinterpret_cast<void**>(&d.actions), t->host.actions.size() * 4);
+		e = PutOnDevice(&d.tags, h.tags, 16);
+	if (e == hipSuccess && !h.dense.empty()) {
+		e = PutOnDevice(&d.dense, h.dense);
 		if (e == hipSuccess)
-			e = hipMemcpy(d.actions, t->host.actions.data(), t->host.actions.size() * 4, hipMemcpyHostToDevice);
+			e = PutOnDevice(&d.denseMarks, h.denseMarks);
+		if (e == hipSuccess)
+			e = PutOnDevice(&d.actWords, h.actWords);
 	}
-	if (e == hipSuccess) {
-		e = hipMalloc(reinterpret_cast<void**>(&d.tags), t->host.tags.size() + 16);
+	if (e == hipSuccess && !h.lrows.empty()) {
+		e = PutOnDevice(&d.lrows, h.lrows);
 		if (e == hipSuccess)
-			e = hipMemcpy(d.tags, t->host.tags.data(), t->host.tags.size(), hipMemcpyHostToDevice);
-	}
-	if (e == hipSuccess && !t->host.dense.empty()) {
-		const CountingHost& h = t->host;
-		e = hipMalloc(reinterpret_cast<void**>(&d.dense), h.dense.size() * 2);
-		if (e == hipSuccess)
-			e = hipMalloc(reinterpret_cast<void**>(&d.denseMarks), h.denseMarks.size() * 2);
-		if (e == hipSuccess)
-			e = hipMalloc(reinterpret_cast<void**>(&d.actWords), h.actWords.size() * 4);
-		if (e == hipSuccess)
-			e = hipMemcpy(d.dense, h.dense.data(), h.dense.size() * 2, hipMemcpyHostToDevice);
-		if (e == hipSuccess)
-			e = hipMemcpy(d.denseMarks, h.denseMarks.data(), h.denseMarks.size() * 2, hipMemcpyHostToDevice);
-		if (e == hipSuccess)
-			e = hipMemcpy(d.actWords, h.actWords.data(), h.actWords.size() * 4, hipMemcpyHostToDevice);
-	}
-	if (e == hipSuccess && !t->host.lrows.empty()) {
-		const CountingHost& h = t->host;
-		e = hipMalloc(reinterpret_cast<void**>(&d.lrows), h.lrows.size() * 4);
-		if (e == hipSuccess)
-			e = hipMalloc(reinterpret_cast<void**>(&d.lactWords), h.lactWords.size() * 4);
-		if (e == hipSuccess)
-			e = hipMemcpy(d.lrows, h.lrows.data(), h.lrows.size() * 4, hipMemcpyHostToDevice);
-		if (e == hipSuccess)
-			e = hipMemcpy(d.lactWords, h.lactWords.data(), h.lactWords.size() * 4, hipMemcpyHostToDevice);
+			e = PutOnDevice(&d.lactWords, h.lactWords);
 	}
 	d.device = dev;
 	if (e != hipSuccess) {
@@ -1401,174 +1435,164 @@ int UploadCounting(pire_hip_counting_table* t, CountingDevice* image)
 	return PIRE_HIP_OK;
 }
 
-template <int RMAX, int KIND>
-void LaunchOne(const CountingParams& p, unsigned cus, uint32_t ldsBytes, hipStream_t stream, hipError_t* err)
+// ---- the launches: what the entry points below have in common ----------------------------------------------------------
+
+// The part of the parameters that does not depend on the form of the table.
+CountingParams BatchParams(uint32_t states, uint32_t letters, uint32_t regexps, uint32_t initial, uint32_t flags, uint64_t n)
 {
-	*err = SetDynamicLds(reinterpret_cast<const void*>(CountingKernel<RMAX, KIND>), uint32_t(ldsBytes));
-	if (*err != hipSuccess)
-		return;
-	// (a table of more than 40 KB: blocks of 16 waves, as LaunchPacked)
-	const unsigned threads = ldsBytes > 40 * 1024 ? (RMAX > 8 ? 512 : 1024) : 256;
-	const uint64_t perCu = std::max<uint64_t>(1, std::min<uint64_t>(2048 / threads, (160 * 1024) / ldsBytes));
-	const uint64_t todo = p.n;   // (with an overflow list: at most this many)
-	const unsigned blocks = unsigned(std::max<uint64_t>(1, std::min<uint64_t>((todo + threads - 1) / threads, uint64_t(cus) * perCu)));
-	hipLaunchKernelGGL((CountingKernel<RMAX, KIND>), dim3(blocks), dim3(threads), ldsBytes, stream, p);
-	*err = hipGetLastError();
+	CountingParams p;
+	memset(&p, 0, sizeof(p));
+	p.states = states;
+	p.letters = letters;
+	p.regexps = regexps;
+	p.initial = initial;
+	p.flags = flags & (PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END);
+	p.n = n;
+	return p;
 }
 
-template <int NREG, bool LETTERS>
-void LaunchRow(const CountingParams& p, int mode, unsigned blocks, uint32_t ldsBytes, hipStream_t stream, hipError_t* err)
+// f(std::integral_constant<int, NREG>()) for the words of packed counters a table has: 1, 2, 4 or, where the kernel has
+// that instantiation (MAX = 8: the packed kernel), 8
+template <int MAX, class F>
+int WithNreg(uint32_t nreg, F f)
 {
-	auto go = [&](auto m) {
-		constexpr int MODE = decltype(m)::value;
-		*err = SetDynamicLds(reinterpret_cast<const void*>(CountingRowKernel<NREG, MODE, LETTERS>), uint32_t(ldsBytes));
-		if (*err != hipSuccess)
-			return;
-		hipLaunchKernelGGL((CountingRowKernel<NREG, MODE, LETTERS>), dim3(blocks), dim3(1024), ldsBytes, stream, p);
-		*err = hipGetLastError();
-	};
-	if (mode == 2) {
+	if (nreg == 1)
+		return f(std::integral_constant<int, 1>());
+	if (nreg == 2)
+		return f(std::integral_constant<int, 2>());
+	if (MAX == 4 || nreg <= 4)
+		return f(std::integral_constant<int, 4>());
+	return f(std::integral_constant<int, MAX>());
+}
+
+// The row kernels (whole text lines per lane, blocks of 1024): one block per CU at most; a batch with fewer strings than
+// the chip has lanes goes over the CUs wave by wave (one pass: the lengths of the order spread over the CUs as well).
+unsigned RowGrid(uint64_t n, int cus, uint32_t* spreadWaves)
+{
+	*spreadWaves = n <= uint64_t(cus) * 1024 ? 1u : 0u;
+	return unsigned(std::max<uint64_t>(1, std::min<uint64_t>(*spreadWaves ? (n + 63) / 64 : (n + 1023) / 1024, uint64_t(cus))));
+}
+
+// The kernels with the table in LDS, 16 bytes at a time: small tables take several 256-thread blocks per CU; a table of
+// more than 40 KB (up to 255 states: 128 KB of rows) leaves room for one to three blocks, so these are blocks of
+// `bigThreads` -- 16 waves where the registers allow (round 4: such tables went to the 32-bit kernel, a 143-state
+// scanner of 7 regexps at 0.45 TB/s)
+unsigned DenseGrid(uint64_t n, int cus, uint32_t ldsBytes, unsigned bigThreads, unsigned* threads)
+{
+	*threads = ldsBytes > 40 * 1024 ? bigThreads : 256;
+	return GridBlocks(n, cus, *threads, ldsBytes);
+}
+
+// The letter + transition kernels (32-bit counting, wide counting, generic capture), blocks of 256: the transitions in
+// LDS while they fit `limitKb`, up to eight blocks per CU
+uint32_t TransitionLds(CountingParams* p, uint32_t limitKb)
+{
+	const uint64_t tableBytes = uint64_t(p->states) * p->letters * 8;
+	p->transInLds = tableBytes <= limitKb * 1024 ? 1 : 0;
+	return 272 + (p->transInLds ? uint32_t(tableBytes) : 0);
+}
+unsigned LaneGrid(uint64_t n, int cus)
+{
+	return unsigned(std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, uint64_t(cus) * 8)));
+}
+
+uint32_t ByteRowLds(uint32_t states, uint32_t nreg)
+{
+	return uint32_t(((size_t(states + 1) * kCountingRowPitch + 15) & ~size_t(15)) + 256 * 2 * nreg * 4);
+}
+
+// CountingRowKernel<NREG, MODE, LETTERS>, rows by byte or by letter; mode: 0 basic, 1 advanced, 2 half-final (by letter only)
+template <bool LETTERS>
+int LaunchRow(const CountingParams& p, uint32_t nreg, int mode, unsigned blocks, uint32_t lds, hipStream_t stream, const char* what)
+{
+	return WithNreg<4>(nreg, [&](auto r) {
+		constexpr int NREG = decltype(r)::value;
 		if constexpr (LETTERS)
-			go(std::integral_constant<int, 2>());
-	} else if (mode == 1) {
-		go(std::integral_constant<int, 1>());
-	} else {
-		go(std::integral_constant<int, 0>());
-	}
-}
-
-template <int NREG>
-void LaunchPacked(const CountingParams& p, bool advanced, unsigned cus, uint32_t ldsBytes, hipStream_t stream, hipError_t* err)
-{
-	const void* fn = advanced ? reinterpret_cast<const void*>(CountingPackedKernel<NREG, true>)
-	                          : reinterpret_cast<const void*>(CountingPackedKernel<NREG, false>);
-	*err = SetDynamicLds(fn, uint32_t(ldsBytes));
-	if (*err != hipSuccess)
-		return;
-	// small tables: several 256-thread blocks per CU; a table of more than 40 KB (up to 255 states: 128 KB of rows) leaves
-	// room for one to three blocks, so these are blocks of 16 waves (round 4: such tables went to the 32-bit kernel, a
-	// 143-state scanner of 7 regexps at 0.45 TB/s)
-	const unsigned threads = ldsBytes > 40 * 1024 ? 1024 : 256;
-	const uint64_t perCu = std::max<uint64_t>(1, std::min<uint64_t>(2048 / threads, (160 * 1024) / ldsBytes));
-	const unsigned blocks = unsigned(std::max<uint64_t>(1, std::min<uint64_t>((p.n + threads - 1) / threads, uint64_t(cus) * perCu)));
-	if (advanced)
-		hipLaunchKernelGGL((CountingPackedKernel<NREG, true>), dim3(blocks), dim3(threads), ldsBytes, stream, p);
-	else
-		hipLaunchKernelGGL((CountingPackedKernel<NREG, false>), dim3(blocks), dim3(threads), ldsBytes, stream, p);
-	*err = hipGetLastError();
+			if (mode == 2)
+				return Launch(CountingRowKernel<NREG, 2, LETTERS>, blocks, 1024, lds, stream, what, p);
+		return mode == 1 ? Launch(CountingRowKernel<NREG, 1, LETTERS>, blocks, 1024, lds, stream, what, p)
+		                 : Launch(CountingRowKernel<NREG, 0, LETTERS>, blocks, 1024, lds, stream, what, p);
+	});
 }
 
 int LaunchCounting(CountingParams p, int kind, hipStream_t stream, uint32_t nreg = 0)
 {
 	if (p.n == 0)
 		return PIRE_HIP_OK;
-	int dev = 0, cus = 0;
-	hipError_t e = hipGetDevice(&dev);
-	if (e == hipSuccess)
-		e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-	if (e != hipSuccess)
-		return HipFail(e, "device query");
+	int cus = 0;
+	if (int rc = DeviceCUs(&cus))
+		return rc;
+	const char* const what = "counting kernel launch";
 	// the strings by length class (order.hip), so that a wave's 64 lanes finish together
 	StreamScratch orderScratch(stream);
 	p.order = nullptr;
-	if (p.offsets && LengthOrderWanted(p.n)) {
-		if (int rc = orderScratch.Alloc(LengthOrderScratchBytes(p.n), "hipMallocAsync(length order)"))
+	if (p.offsets)
+		if (int rc = OrderByLength(p.offsets, p.n, stream, orderScratch, &p.order, &p.serpentine))
 			return rc;
-		bool serp = false;
-		if (int rc = BuildLengthOrder(p.offsets, p.n, orderScratch.get(), stream, &p.order, &serp))
-			return rc;
-		p.serpentine = serp ? 1u : 0u;
-	}
 	// Dense rows + packed 16-bit counters first (CountingPackedKernel); the strings it leaves on the overflow list
 	// (longer than 65 000 bytes) go through the 32-bit kernel below on the same stream.
 	StreamScratch list(stream);
-	// letter-indexed rows (CountingRowKernel<.., LETTERS>): any table whose (states + 1) x (letters + 1) entries fit
-	const uint32_t lnreg = p.lnreg;
+	// entries that are LDS addresses (CountingRowKernel) where the table leaves room for them and the batch fills the
+	// GPU; pire_hip_config.counting_variant: 1 = never, 2 = whenever the table fits.  Rows by letter
+	// (CountingRowKernel<.., LETTERS>): any table whose (states + 1) x (letters + 1) entries fit
 	const int variant = GetConfig().counting_variant;
 	const bool fills = variant == 2 || p.n >= uint64_t(cus) * 256;   // the one block of 16 waves a CU then holds
 	const bool byteRows = nreg && p.dense && nreg <= 4 && p.states <= kCountingRowStates && variant != 1 && fills;
-	const bool letterRows = !byteRows && lnreg && p.lrows && variant != 1 && fills;
+	const bool letterRows = !byteRows && p.lnreg && p.lrows && variant != 1 && fills;
 	if (((nreg && p.dense) || letterRows) && kind != PIRE_HIP_COUNTING_NOGLUELIMIT && p.n < (1ull << 32) - 1) {
-		if (int rc = list.Alloc((size_t(p.n) + 1) * 4, "hipMallocAsync(counting overflow list)"))
+		if (int rc = OverflowList(list, p.n, stream, "hipMallocAsync(counting overflow list)", &p.overflow))
 			return rc;
-		e = hipMemsetAsync(list.get(), 0, 4, stream);
-		if (e != hipSuccess)
-			return HipFail(e, "hipMallocAsync(counting overflow list)");
-		p.overflow = list.as<uint32_t>();
 		const bool adv = kind == PIRE_HIP_COUNTING_ADVANCED;
-		// entries that are LDS addresses (CountingRowKernel) where the table leaves room for them and the batch fills the
-		// GPU; pire_hip_config.counting_variant: 1 = never, 2 = whenever the table fits
-		p.spreadWaves = p.n <= uint64_t(cus) * 1024 ? 1u : 0u;   // (one pass: the lengths of the order spread over the CUs as well)
-		const unsigned rblocks = unsigned(std::max<uint64_t>(1, std::min<uint64_t>(p.spreadWaves ? (p.n + 63) / 64 : (p.n + 1023) / 1024, uint64_t(cus))));
+		const unsigned rblocks = RowGrid(p.n, cus, &p.spreadWaves);
+		int rc;
 		if (byteRows) {
-			const uint32_t rowLds = uint32_t(((size_t(p.states + 1) * kCountingRowPitch + 15) & ~size_t(15)) + 256 * 2 * nreg * 4);
-			switch (nreg) {
-			case 1: LaunchRow<1, false>(p, adv ? 1 : 0, rblocks, rowLds, stream, &e); break;
-			case 2: LaunchRow<2, false>(p, adv ? 1 : 0, rblocks, rowLds, stream, &e); break;
-			default: LaunchRow<4, false>(p, adv ? 1 : 0, rblocks, rowLds, stream, &e); break;
-			}
+			rc = LaunchRow<false>(p, nreg, adv, rblocks, ByteRowLds(p.states, nreg), stream, what);
 		} else if (letterRows) {
-			const uint32_t rowLds = uint32_t(((size_t(p.states + 1) * (p.letters + 1) * 8 + 15) & ~size_t(15)) + size_t(p.lactCount) * 2 * lnreg * 4 + 512);
-			switch (lnreg) {
-			case 1: LaunchRow<1, true>(p, adv ? 1 : 0, rblocks, rowLds, stream, &e); break;
-			case 2: LaunchRow<2, true>(p, adv ? 1 : 0, rblocks, rowLds, stream, &e); break;
-			default: LaunchRow<4, true>(p, adv ? 1 : 0, rblocks, rowLds, stream, &e); break;
-			}
+			rc = LaunchRow<true>(p, p.lnreg, adv, rblocks, LetterRowLds(p.states, p.letters, p.lactCount, p.lnreg), stream, what);
 		} else {
-			const uint32_t packedLds = uint32_t(size_t(p.states) * 512 + 256 * 2 * nreg * 4);
-			switch (nreg) {
-			case 1: LaunchPacked<1>(p, adv, unsigned(cus), packedLds, stream, &e); break;
-			case 2: LaunchPacked<2>(p, adv, unsigned(cus), packedLds, stream, &e); break;
-			case 4: LaunchPacked<4>(p, adv, unsigned(cus), packedLds, stream, &e); break;
-			default: LaunchPacked<8>(p, adv, unsigned(cus), packedLds, stream, &e); break;
-			}
+			const uint32_t lds = PackedLds(p.states, nreg);
+			unsigned threads;
+			const unsigned blocks = DenseGrid(p.n, cus, lds, 1024, &threads);
+			rc = WithNreg<8>(nreg, [&](auto r) {
+				constexpr int NREG = decltype(r)::value;
+				return adv ? Launch(CountingPackedKernel<NREG, true>, blocks, threads, lds, stream, what, p)
+				           : Launch(CountingPackedKernel<NREG, false>, blocks, threads, lds, stream, what, p);
+			});
 		}
-		if (e != hipSuccess)
-			return HipFail(e, "counting kernel launch");
-		const bool rows = byteRows || letterRows;
+		if (rc)
+			return rc;
 		NoteKernel(byteRows ? "counting_rows" : letterRows ? "counting_letter_rows" : "counting_packed");
-		(void)rows;
 	} else {
 		NoteKernel("counting");
 	}
-	const uint64_t tableBytes = uint64_t(p.states) * p.letters * 8;
 	// the transitions in LDS while they fit a CU's 160 KB (round 4: up to 60 KB only -- a 573-state scanner of 7 regexps
-	// read every transition from memory); above 40 KB the blocks are of 16 waves (LaunchOne)
-	const bool wideKernel = kind == PIRE_HIP_COUNTING_NOGLUELIMIT && p.regexps > kMaxReCount;
-	p.transInLds = tableBytes <= (wideKernel ? 60 : 150) * 1024 ? 1 : 0;
-	const uint32_t ldsBytes = 272 + (p.transInLds ? uint32_t(tableBytes) : 0);
-	const unsigned blocks = unsigned(std::max<uint64_t>(1, std::min<uint64_t>((p.n + 255) / 256, uint64_t(cus) * 8)));
+	// read every transition from memory); above 40 KB the blocks are of 16 waves (DenseGrid)
 	if (kind == PIRE_HIP_COUNTING_NOGLUELIMIT && p.regexps > kMaxReCount) {
-		e = SetDynamicLds(reinterpret_cast<const void*>(CountingWideKernel), uint32_t(ldsBytes));
-		if (e == hipSuccess) {
-			hipLaunchKernelGGL(CountingWideKernel, dim3(blocks), dim3(256), ldsBytes, stream, p);
-			e = hipGetLastError();
-		}
-	} else {
-		// counters in registers, as many as the scanner has regexps (rounded up to 1, 2, 4, 8, 16): TakeAction touches
-		// every counter slot, so a single-regexp scanner should not pay for eight
-		auto launch = [&](auto rmax) {
-			constexpr int R = decltype(rmax)::value;
-			switch (kind) {
-			case PIRE_HIP_COUNTING_BASIC: LaunchOne<R, PIRE_HIP_COUNTING_BASIC>(p, unsigned(cus), ldsBytes, stream, &e); break;
-			case PIRE_HIP_COUNTING_ADVANCED: LaunchOne<R, PIRE_HIP_COUNTING_ADVANCED>(p, unsigned(cus), ldsBytes, stream, &e); break;
-			default: LaunchOne<R, PIRE_HIP_COUNTING_NOGLUELIMIT>(p, unsigned(cus), ldsBytes, stream, &e); break;
-			}
-		};
-		if (p.regexps <= 1)
-			launch(std::integral_constant<int, 1>());
-		else if (p.regexps <= 2)
-			launch(std::integral_constant<int, 2>());
-		else if (p.regexps <= 4)
-			launch(std::integral_constant<int, 4>());
-		else if (p.regexps <= 8)
-			launch(std::integral_constant<int, 8>());
-		else
-			launch(std::integral_constant<int, 16>());
+		const uint32_t lds = TransitionLds(&p, 60);
+		return Launch(CountingWideKernel, LaneGrid(p.n, cus), 256, lds, stream, what, p);
 	}
-	if (e != hipSuccess)
-		return HipFail(e, "counting kernel launch");
-	return PIRE_HIP_OK;
+	const uint32_t lds = TransitionLds(&p, 150);
+	// counters in registers, as many as the scanner has regexps (rounded up to 1, 2, 4, 8, 16): TakeAction touches
+	// every counter slot, so a single-regexp scanner should not pay for eight
+	auto launch = [&](auto rmax) {
+		constexpr int R = decltype(rmax)::value;
+		unsigned threads;
+		const unsigned blocks = DenseGrid(p.n, cus, lds, R > 8 ? 512 : 1024, &threads);   // (with an overflow list: at most p.n strings)
+		switch (kind) {
+		case PIRE_HIP_COUNTING_BASIC: return Launch(CountingKernel<R, PIRE_HIP_COUNTING_BASIC>, blocks, threads, lds, stream, what, p);
+		case PIRE_HIP_COUNTING_ADVANCED: return Launch(CountingKernel<R, PIRE_HIP_COUNTING_ADVANCED>, blocks, threads, lds, stream, what, p);
+		default: return Launch(CountingKernel<R, PIRE_HIP_COUNTING_NOGLUELIMIT>, blocks, threads, lds, stream, what, p);
+		}
+	};
+	if (p.regexps <= 1)
+		return launch(std::integral_constant<int, 1>());
+	if (p.regexps <= 2)
+		return launch(std::integral_constant<int, 2>());
+	if (p.regexps <= 4)
+		return launch(std::integral_constant<int, 4>());
+	if (p.regexps <= 8)
+		return launch(std::integral_constant<int, 8>());
+	return launch(std::integral_constant<int, 16>());
 }
 
 }  // namespace
@@ -1584,55 +1608,30 @@ void BuildHalfRows(const HostTable& h, HalfRowsHost& r)
 {
 	r.tried = true;
 	r.nreg = 0;
-	if (!h.incPacked || h.states == 0 || h.states > 65535 || h.letters == 0 || h.letters > 255 || h.regexps == 0 || h.regexps > 8)
+	auto incOf = [&](uint32_t st) -> uint64_t { return (h.flags[st] & kFinal) ? h.inc64[st] : 0; };
+	LetterRowImage im;
+	uint32_t initialAct = 0;
+	if (!h.incPacked || !im.Start(h.states, h.letters, h.regexps) ||
+	    !im.Rows(h.states, h.letters, [&](size_t i) { return h.next[i]; }, [&](size_t i) { return incOf(h.next[i]); }) ||
+	    !im.Id(incOf(h.initial), &initialAct))
 		return;
 	uint32_t maxMult = 1;   // how often a regexp is in one state's final list (a step bumps its counter by that much)
 	for (uint64_t inc : h.inc64)
 		for (int b = 0; b < 8; ++b)
 			maxMult = std::max(maxMult, uint32_t(inc >> (8 * b)) & 0xFFu);
-	const uint32_t nreg = h.regexps <= 2 ? 1 : h.regexps <= 4 ? 2 : 4;
-	const size_t rowBytes = (size_t(h.states) + 1) * (h.letters + 1) * 8 + 16 + 512;
-	if (rowBytes + 2 * 8 * nreg > kCountingRowLds)
-		return;
-	const size_t maxIds = std::min<size_t>(65535, (kCountingRowLds - rowBytes) / (8 * nreg) - 1);
-	std::vector<uint64_t> ids;   // distinct non-zero increment words, id = index + 1
-	std::unordered_map<uint64_t, uint32_t> idOf;
-	auto idFor = [&](uint32_t st, bool* ok) -> uint32_t {
-		const uint64_t inc = (h.flags[st] & kFinal) ? h.inc64[st] : 0;
-		if (!inc)
-			return 0;
-		auto it = idOf.find(inc);
-		if (it == idOf.end()) {
-			if (ids.size() == maxIds) {
-				*ok = false;
-				return 0;
-			}
-			ids.push_back(inc);
-			it = idOf.emplace(inc, uint32_t(ids.size())).first;
-		}
-		return it->second;
-	};
-	bool ok = true;
-	std::vector<uint32_t> rows(size_t(h.states) * h.letters);
-	for (size_t i = 0; i < rows.size() && ok; ++i)
-		rows[i] = h.next[i] | (idFor(h.next[i], &ok) << 16);
-	const uint32_t initialAct = idFor(h.initial, &ok);
-	if (!ok)
-		return;
-	r.lactWords.assign((ids.size() + 1) * 2 * nreg, 0);
-	for (size_t i = 0; i < ids.size(); ++i)
-		for (uint32_t q = 0; q < h.regexps; ++q)
-			r.lactWords[(i + 1) * 2 * nreg + (q >> 1)] |= (uint32_t(ids[i] >> (8 * q)) & 0xFFu) << (16 * (q & 1));   // the counter's 16-bit half
+	// (a byte of multiplicity per regexp in the increment word; no resets)
+	r.lactWords = PackActionWords(im.ids, im.ids.size() + 1, im.nreg, h.regexps,
+	                              [](uint64_t inc, uint32_t q) { return CounterStep{uint32_t(inc >> (8 * q)) & 0xFFu, false}; });
 	r.letterOf.resize(264);
 	for (size_t c = 0; c < 264; ++c)
 		r.letterOf[c] = uint8_t(h.cls[c]);
 	r.finalTag.resize(h.states);
 	for (uint32_t st = 0; st < h.states; ++st)
 		r.finalTag[st] = (h.flags[st] & kFinal) ? 1 : 0;
-	r.lrows.swap(rows);
+	r.lrows.swap(im.rows);
 	r.initialAct = initialAct;
 	r.maxLen = 65000u / maxMult;   // (+ the two marks and Initialize: 65 002 x 1, 32 502 x 2, ... all below 65 536)
-	r.nreg = nreg;
+	r.nreg = im.nreg;
 }
 
 void FreeHalfRowsDevice(HalfRowsDevice* d)
@@ -1644,14 +1643,6 @@ void FreeHalfRowsDevice(HalfRowsDevice* d)
 	*d = HalfRowsDevice();
 }
 
-template <class T>
-hipError_t PutHalf(T** dst, const std::vector<T>& v, size_t pad = 0)
-{
-	hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), v.size() * sizeof(T) + pad);
-	if (e == hipSuccess)
-		e = hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-	return e;
-}
 }  // namespace
 
 void FreeHalfRows(pire_hip_table* t)
@@ -1686,13 +1677,13 @@ int UploadHalfRows(pire_hip_table* t)
 	HalfRowsDevice& d = t->halfRowsDev[dev];
 	if (!h.nreg || d.device == dev)
 		return PIRE_HIP_OK;
-	e = PutHalf(&d.lrows, h.lrows, 128);
+	e = PutOnDevice(&d.lrows, h.lrows, 128);
 	if (e == hipSuccess)
-		e = PutHalf(&d.lactWords, h.lactWords);
+		e = PutOnDevice(&d.lactWords, h.lactWords);
 	if (e == hipSuccess)
-		e = PutHalf(&d.letterOf, h.letterOf, 8);
+		e = PutOnDevice(&d.letterOf, h.letterOf, 8);
 	if (e == hipSuccess)
-		e = PutHalf(&d.finalTag, h.finalTag, 16);
+		e = PutOnDevice(&d.finalTag, h.finalTag, 16);
 	if (e != hipSuccess) {
 		FreeHalfRowsDevice(&d);
 		return HipFail(e, "uploading the half-final rows");
@@ -1710,11 +1701,8 @@ int LaunchHalfFinalRows(pire_hip_table* t, const uint8_t* text, const uint64_t* 
 	if (variant == 1 || n == 0 || n >= (1ull << 32) - 1 || !offsets)
 		return PIRE_HIP_OK;
 	int dev = 0, cus = 0;
-	hipError_t e = hipGetDevice(&dev);
-	if (e == hipSuccess)
-		e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-	if (e != hipSuccess)
-		return HipFail(e, "device query");
+	if (int rc = DeviceCUs(&cus, &dev))
+		return rc;
 	if (dev < 0 || dev >= kMaxDevices || (variant != 2 && n < uint64_t(cus) * 256))
 		return PIRE_HIP_OK;
 	HalfRowsDevice image;
@@ -1733,8 +1721,7 @@ int LaunchHalfFinalRows(pire_hip_table* t, const uint8_t* text, const uint64_t* 
 		maxLen = h.maxLen;
 		lactCount = uint32_t(h.lactWords.size() / (2 * h.nreg));
 	}
-	CountingParams p;
-	memset(&p, 0, sizeof(p));
+	CountingParams p = BatchParams(t->host.states, t->host.letters, t->host.regexps, t->host.initial, flags, n);
 	p.letterOf = image.letterOf;
 	p.lrows = image.lrows;
 	p.lactWords = image.lactWords;
@@ -1743,43 +1730,20 @@ int LaunchHalfFinalRows(pire_hip_table* t, const uint8_t* text, const uint64_t* 
 	p.initialAct = initialAct;
 	p.maxLen = maxLen;
 	p.tags = image.finalTag;
-	p.states = t->host.states;
-	p.letters = t->host.letters;
-	p.regexps = t->host.regexps;
-	p.initial = t->host.initial;
-	p.flags = flags & (PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END);
 	p.text = text;
 	p.offsets = offsets;
-	p.n = n;
 	p.outIdx = outIdx;
 	p.outFinal = outFinal;
 	p.outResults = outResults;
 	// strings by length class, as the counting scanners (order.hip)
 	StreamScratch orderScratch(stream);
-	if (LengthOrderWanted(n)) {
-		if (int rc = orderScratch.Alloc(LengthOrderScratchBytes(n), "hipMallocAsync(length order)"))
-			return rc;
-		bool serp = false;
-		if (int rc = BuildLengthOrder(offsets, n, orderScratch.get(), stream, &p.order, &serp))
-			return rc;
-		p.serpentine = serp ? 1u : 0u;
-	}
-	if (int rc = overflow->Alloc((size_t(n) + 1) * 4, "half-final row kernel"))
+	if (int rc = OrderByLength(offsets, n, stream, orderScratch, &p.order, &p.serpentine))
 		return rc;
-	e = hipMemsetAsync(overflow->get(), 0, 4, stream);
-	if (e == hipSuccess) {
-		p.overflow = overflow->as<uint32_t>();
-		const uint32_t rowLds = uint32_t(((size_t(p.states + 1) * (p.letters + 1) * 8 + 15) & ~size_t(15)) + size_t(lactCount) * 2 * nreg * 4 + 512);
-		p.spreadWaves = n <= uint64_t(cus) * 1024 ? 1u : 0u;
-		const unsigned rblocks = unsigned(std::max<uint64_t>(1, std::min<uint64_t>(p.spreadWaves ? (n + 63) / 64 : (n + 1023) / 1024, uint64_t(cus))));
-		switch (nreg) {
-		case 1: LaunchRow<1, true>(p, 2, rblocks, rowLds, stream, &e); break;
-		case 2: LaunchRow<2, true>(p, 2, rblocks, rowLds, stream, &e); break;
-		default: LaunchRow<4, true>(p, 2, rblocks, rowLds, stream, &e); break;
-		}
-	}
-	if (e != hipSuccess)
-		return HipFail(e, "half-final row kernel");
+	if (int rc = OverflowList(*overflow, n, stream, "half-final row kernel", &p.overflow))
+		return rc;
+	const unsigned rblocks = RowGrid(n, cus, &p.spreadWaves);
+	if (int rc = LaunchRow<true>(p, nreg, 2, rblocks, LetterRowLds(p.states, p.letters, lactCount, nreg), stream, "half-final row kernel"))
+		return rc;
 	NoteKernel("half_final_rows");
 	*done = true;
 	return PIRE_HIP_OK;
@@ -1859,13 +1823,13 @@ try {
 	const CountingHost& h = t->host;
 	memset(out, 0, 8 * sizeof(uint32_t));
 	out[0] = h.dense.empty() ? 0 : h.nreg;
-	out[1] = out[0] ? uint32_t(size_t(h.states) * 512 + 256 * 2 * h.nreg * 4) : 0;
+	out[1] = out[0] ? PackedLds(h.states, h.nreg) : 0;
 	out[2] = (out[0] && h.nreg <= 4 && h.states <= kCountingRowStates) ? 1 : 0;
-	out[3] = out[2] ? uint32_t(((size_t(h.states + 1) * kCountingRowPitch + 15) & ~size_t(15)) + 256 * 2 * h.nreg * 4) : 0;
+	out[3] = out[2] ? ByteRowLds(h.states, h.nreg) : 0;
 	out[4] = h.lrows.empty() ? 0 : h.lnreg;
 	if (out[4]) {
 		const uint32_t count = uint32_t(h.lactWords.size() / (2 * h.lnreg));
-		out[5] = uint32_t(((size_t(h.states + 1) * (h.letters + 1) * 8 + 15) & ~size_t(15)) + size_t(count) * 2 * h.lnreg * 4 + 512);
+		out[5] = LetterRowLds(h.states, h.letters, count, h.lnreg);
 		out[6] = count - 1;
 	}
 	return PIRE_HIP_OK;
@@ -1876,37 +1840,15 @@ try {
 // ---- first-use self-tests (selftest.h): the counting scanners' and the capturing scanner's kernels -------------------------
 namespace {
 
-struct CountOwnStream {
-	hipStream_t s = nullptr;
-	CountOwnStream() { (void)hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
-	~CountOwnStream()
-	{
-		if (s) {
-			(void)hipStreamSynchronize(s);
-			(void)hipStreamDestroy(s);
-		}
-	}
-};
-
-bool CountingTested(pire_hip_counting_table* t, uint32_t bit, int* dev)
-{
-	*dev = -1;
-	if (hipGetDevice(dev) != hipSuccess || *dev < 0 || *dev >= pirehip::kMaxDevices)
-		return true;
-	return (t->selfTested[*dev].load(std::memory_order_relaxed) & (1u << bit)) != 0;
-}
-
 // the host's copy of the scanner: state | action << 32 per (state, letter) -- count.h / loaded.h as ingested
 struct CountWalk {
 	const pirehip::CountingHost& h;
 	uint64_t Trans(uint32_t st, uint32_t ch) const { return h.trans[size_t(st) * h.letters + h.letterOf[ch]]; }
+	// (KnownBatchFor)
+	uint32_t Next(uint32_t st, uint32_t ch) const { return uint32_t(Trans(st, ch)); }
+	bool Dead(uint32_t) const { return false; }
+	uint64_t Salt() const { return (uint64_t(h.states) << 24) ^ (uint64_t(h.letters) << 8); }
 };
-
-pirehip::KnownBatch CountingBatch(const CountWalk& w, uint32_t n, uint32_t maxLen, uint32_t start, uint64_t seed)
-{
-	return pirehip::MakeKnownBatch(n, maxLen, start, seed ^ (uint64_t(w.h.states) << 24) ^ (uint64_t(w.h.letters) << 8),
-	                               [&](uint32_t st, uint32_t ch) { return uint32_t(w.Trans(st, ch)); }, [](uint32_t) { return false; });
-}
 
 // CountingScanner / AdvancedCountingScanner / NoGlueLimitCountingScanner on the host: count.h:175-192 (PerformIncrement,
 // PerformReset), 251-257 / 287-295 (the order of the two), 306-325 + 404-437 (NoGlueLimit), Result = max(current, total) 206
@@ -1986,32 +1928,30 @@ int SelfTestCounting(pire_hip_counting_table* t, int kind, uint32_t flags, hipSt
 	using namespace pirehip;
 	uint32_t mode = 0;
 	int dev = -1;
-	if (CountingTested(t, 0, &dev) || !EntrySelfTestDue(stream, &mode) || !t->host.states)
+	if (EntryTested(t, 0, &dev) || !EntrySelfTestDue(stream, &mode) || !t->host.states)
 		return PIRE_HIP_OK;
 	const CountWalk w{t->host};
 	const uint32_t R = std::max<uint32_t>(t->host.regexps, 1);
 	flags &= PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END;
 	const uint32_t start = (flags & PIRE_HIP_RUN_BEGIN) ? uint32_t(w.Trans(t->host.initial, kBeginMark)) : t->host.initial;
-	const KnownBatch kb = CountingBatch(w, 320, 200, start, 11);
+	const KnownBatch kb = KnownBatchFor(w, start, 11);
 	std::vector<uint32_t> wantIdx(kb.n), gotIdx(kb.n), wantRes(size_t(kb.n) * R, 0), gotRes(size_t(kb.n) * R);
 	for (uint32_t i = 0; i < kb.n; ++i)
 		HostCount(w, kind, flags, kb.text.data() + kb.offsets[i], kb.text.data() + kb.offsets[i + 1], &wantIdx[i], &wantRes[size_t(i) * R]);
 	if (mode == 2)
 		wantIdx[kb.n / 2] ^= 1;
-	std::vector<std::function<void(pire_hip_config&)>> variants;
+	std::vector<ConfigEdit> variants;
 	variants.push_back([](pire_hip_config& c) { c.counting_variant = 2; });   // whole lines per lane: rows by byte / by letter where the table has them
 	variants.push_back([](pire_hip_config& c) { c.counting_variant = 1; });   // 16 bytes at a time: packed 16-bit counters / the 32-bit kernel
-	CountOwnStream own;
-	uint32_t extra = 0;   // the third pass: PIRE_HIP_RUN_GENERIC = the 32-bit kernel alone
-	variants.push_back([](pire_hip_config& c) { c.counting_variant = 1; });
+	variants.push_back([](pire_hip_config& c) { c.counting_variant = 1; });   // the third pass: PIRE_HIP_RUN_GENERIC = the 32-bit kernel alone
 	size_t pass = 0;
-	const int rc = RunSelfTestVariants(variants, [&]() -> int {
-		extra = pass++ == 2 ? PIRE_HIP_RUN_GENERIC : 0u;
+	const int rc = RunKnownAnswer(variants, [&] {
 		std::fill(gotIdx.begin(), gotIdx.end(), ~0u);
 		std::fill(gotRes.begin(), gotRes.end(), ~0u);
-		const int r = pire_hip_counting_run(t, kind, kb.text.data(), kb.offsets.data(), kb.n, flags | extra, gotIdx.data(), gotRes.data(), own.s);
-		if (r != PIRE_HIP_OK)
-			return r;
+	}, [&](hipStream_t own) {
+		const uint32_t extra = pass++ == 2 ? PIRE_HIP_RUN_GENERIC : 0u;
+		return pire_hip_counting_run(t, kind, kb.text.data(), kb.offsets.data(), kb.n, flags | extra, gotIdx.data(), gotRes.data(), own);
+	}, [&]() -> int {
 		for (uint32_t i = 0; i < kb.n; ++i) {
 			if (gotIdx[i] != wantIdx[i])
 				return SelfTestMismatch("the counting scanner", i, "state " + std::to_string(gotIdx[i]), "state " + std::to_string(wantIdx[i]));
@@ -2024,7 +1964,7 @@ int SelfTestCounting(pire_hip_counting_table* t, int kind, uint32_t flags, hipSt
 	});
 	if (rc != PIRE_HIP_OK)
 		return rc;
-	t->selfTested[dev].fetch_or(1u);
+	MarkTested(t, dev, 0);
 	return PIRE_HIP_OK;
 }
 
@@ -2035,12 +1975,12 @@ int SelfTestCapture(pire_hip_counting_table* t, uint32_t flags, hipStream_t stre
 	using namespace pirehip;
 	uint32_t mode = 0;
 	int dev = -1;
-	if (CountingTested(t, 1, &dev) || !EntrySelfTestDue(stream, &mode) || !t->host.states || t->host.type != 4)
+	if (EntryTested(t, 1, &dev) || !EntrySelfTestDue(stream, &mode) || !t->host.states || t->host.type != 4)
 		return PIRE_HIP_OK;
 	const CountWalk w{t->host};
 	flags &= PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END;
 	const uint32_t start = (flags & PIRE_HIP_RUN_BEGIN) ? uint32_t(w.Trans(t->host.initial, kBeginMark)) : t->host.initial;
-	const KnownBatch kb = CountingBatch(w, 320, 200, start, 12);
+	const KnownBatch kb = KnownBatchFor(w, start, 12);
 	std::vector<uint32_t> wantIdx(kb.n), gotIdx(kb.n);
 	std::vector<uint8_t> wantFin(kb.n), gotFin(kb.n);
 	std::vector<int64_t> wantB(kb.n), wantE(kb.n), gotB(kb.n), gotE(kb.n);
@@ -2071,21 +2011,20 @@ int SelfTestCapture(pire_hip_counting_table* t, uint32_t flags, hipStream_t stre
 	}
 	if (mode == 2)
 		wantIdx[kb.n / 2] ^= 1;
-	std::vector<std::function<void(pire_hip_config&)>> variants;
+	std::vector<ConfigEdit> variants;
 	variants.push_back([](pire_hip_config& c) { c.counting_variant = 2; c.ragged_act_always = 1; c.no_ragged_act = 0; });   // the ragged kernel with actions (>= 256 strings) ...
 	variants.push_back([](pire_hip_config& c) { c.counting_variant = 2; c.no_ragged_act = 1; });   // ... whole lines per lane (CaptureRowKernel) ...
 	variants.push_back([](pire_hip_config& c) { c.counting_variant = 1; c.no_ragged_act = 1; });   // ... dense rows, 16 bytes at a time ...
 	variants.push_back([](pire_hip_config& c) { c.counting_variant = 1; c.no_ragged_act = 1; });   // ... and (PIRE_HIP_RUN_GENERIC) letter + transition
-	CountOwnStream own;
 	size_t pass = 0;
-	const int rc = RunSelfTestVariants(variants, [&]() -> int {
-		const uint32_t extra = pass++ == 3 ? PIRE_HIP_RUN_GENERIC : 0u;
+	const int rc = RunKnownAnswer(variants, [&] {
 		std::fill(gotIdx.begin(), gotIdx.end(), ~0u);
 		std::fill(gotB.begin(), gotB.end(), int64_t(-77));
-		const int r = pire_hip_capture_run(t, kb.text.data(), kb.offsets.data(), kb.n, flags | extra, gotIdx.data(), gotFin.data(), gotB.data(),
-		                                   gotE.data(), own.s);
-		if (r != PIRE_HIP_OK)
-			return r;
+	}, [&](hipStream_t own) {
+		const uint32_t extra = pass++ == 3 ? PIRE_HIP_RUN_GENERIC : 0u;
+		return pire_hip_capture_run(t, kb.text.data(), kb.offsets.data(), kb.n, flags | extra, gotIdx.data(), gotFin.data(), gotB.data(),
+		                            gotE.data(), own);
+	}, [&]() -> int {
 		for (uint32_t i = 0; i < kb.n; ++i)
 			if (gotIdx[i] != wantIdx[i] || gotFin[i] != wantFin[i] || gotB[i] != wantB[i] || gotE[i] != wantE[i])
 				return SelfTestMismatch("the capturing scanner", i,
@@ -2095,7 +2034,7 @@ int SelfTestCapture(pire_hip_counting_table* t, uint32_t flags, hipStream_t stre
 	});
 	if (rc != PIRE_HIP_OK)
 		return rc;
-	t->selfTested[dev].fetch_or(2u);
+	MarkTested(t, dev, 1);
 	return PIRE_HIP_OK;
 }
 
@@ -2127,8 +2066,7 @@ try {
 	CountingDevice image;
 	if (int rc = UploadCounting(t, &image))
 		return rc;
-	CountingParams p;
-	memset(&p, 0, sizeof(p));
+	CountingParams p = BatchParams(t->host.states, t->host.letters, t->host.regexps, t->host.initial, flags, n);
 	p.actions = image.actions;
 	// more than 16 regexps: per-string `current` rows in a temporary device array (freed after the stream is drained)
 	// stream-ordered: allocated and freed on the call's stream (the free is ordered after the kernel that uses it)
@@ -2147,12 +2085,6 @@ try {
 	p.lactWords = image.lactWords;
 	p.lnreg = (flags & PIRE_HIP_RUN_GENERIC) ? 0 : t->host.lnreg;
 	p.lactCount = t->host.lnreg ? uint32_t(t->host.lactWords.size() / (2 * t->host.lnreg)) : 0;
-	p.states = t->host.states;
-	p.letters = t->host.letters;
-	p.regexps = t->host.regexps;
-	p.initial = t->host.initial;
-	p.flags = flags & (PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END);
-	p.n = n;
 	// PIRE_HIP_RUN_GENERIC keeps the 32-bit kernel alone (the tests compare the two)
 	const uint32_t nreg = (flags & PIRE_HIP_RUN_GENERIC) ? 0 : t->host.nreg;
 	const uint32_t R = std::max<uint32_t>(t->host.regexps, 1);
@@ -2284,78 +2216,44 @@ try {
 	CountingDevice image;
 	if (int rc = UploadCounting(t, &image))
 		return rc;
-	CountingParams p;
-	memset(&p, 0, sizeof(p));
+	CountingParams p = BatchParams(t->host.states, t->host.letters, t->host.regexps, t->host.initial, flags, n);
 	p.letterOf = image.letterOf;
 	p.trans = image.trans;
 	p.tags = image.tags;
-	p.states = t->host.states;
-	p.letters = t->host.letters;
-	p.regexps = t->host.regexps;
-	p.initial = t->host.initial;
-	p.flags = flags & (PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END);
-	p.n = n;
-	int dev = 0, cus = 0;
-	hipError_t e = hipGetDevice(&dev);
-	if (e == hipSuccess)
-		e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-	if (e != hipSuccess)
-		return HipFail(e, "device query");
-	const uint64_t tableBytes = uint64_t(p.states) * p.letters * 8;
-	p.transInLds = tableBytes <= 60 * 1024 ? 1 : 0;
-	const uint32_t ldsBytes = 272 + (p.transInLds ? uint32_t(tableBytes) : 0);
-	const unsigned blocks = unsigned(std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, uint64_t(cus) * 8)));
-	e = SetDynamicLds(reinterpret_cast<const void*>(CaptureKernel), uint32_t(ldsBytes));
-	if (e != hipSuccess)
-		return HipFail(e, "hipFuncSetAttribute(LDS)");
-	// one string per lane: the dense-row kernel when the table has the dense form (<= 255 states), else letter + transition
 	p.dense = image.dense;
 	p.denseMarks = image.denseMarks;
+	int cus = 0;
+	if (int rc = DeviceCUs(&cus))
+		return rc;
+	const uint32_t genericLds = TransitionLds(&p, 60);
 	StreamScratch orderScratch(stream);   // freed on the stream, behind the kernel that reads it
+	// one string per lane: whole text lines (CaptureRowKernel) where the table leaves room for 2 KB rows and the batch fills
+	// the one block of 16 waves a CU then holds, pire_hip_config.counting_variant as for the counting scanners; else the
+	// dense-row kernel when the table has the dense form (<= 255 states), else letter + transition
 	auto launchPerLane = [&]() -> int {
-		hipError_t le;
-		// (order.hip, measured on the capture walks: 1 025-1 045 GB/s in the caller's order, 941-977 by length -- the walk
-		// has little to win, its text reads lose their neighbours; `capture_by_length` keeps the A/B)
-		// whole text lines per lane (CaptureRowKernel) where the table leaves room for 2 KB rows and the batch fills the one
-		// block of 16 waves a CU then holds; pire_hip_config.counting_variant as for the counting scanners.  That kernel
-		// does take its strings by length: a line is a line wherever the neighbouring lanes read.
+		const char* const what = "capture kernel launch";
 		const int variant = GetConfig().counting_variant;
-		const bool rows = p.dense && !(flags & PIRE_HIP_RUN_GENERIC) && p.states <= kCaptureRowStates && variant != 1 &&
-		                  (variant == 2 || p.n >= uint64_t(cus) * 256);
-		if (p.offsets && LengthOrderWanted(p.n) && (GetConfig().capture_by_length || (rows && !GetConfig().no_length_order))) {
-			if (int rc = orderScratch.Alloc(LengthOrderScratchBytes(p.n), "hipMallocAsync(length order)"))
+		const bool dense = p.dense && !(flags & PIRE_HIP_RUN_GENERIC);
+		const bool rows = dense && p.states <= kCaptureRowStates && variant != 1 && (variant == 2 || p.n >= uint64_t(cus) * 256);
+		// (order.hip, measured on the capture walks: 1 025-1 045 GB/s in the caller's order, 941-977 by length -- the walk
+		// has little to win, its text reads lose their neighbours; `capture_by_length` keeps the A/B.  The row kernel
+		// does take its strings by length: a line is a line wherever the neighbouring lanes read.)
+		if (p.offsets && (GetConfig().capture_by_length || (rows && !GetConfig().no_length_order)))
+			if (int rc = OrderByLength(p.offsets, p.n, stream, orderScratch, &p.order, &p.serpentine))
 				return rc;
-			bool serp = false;
-			if (int rc = BuildLengthOrder(p.offsets, p.n, orderScratch.get(), stream, &p.order, &serp))
-				return rc;
-			p.serpentine = serp ? 1u : 0u;
-		}
 		if (rows) {
-			const uint32_t rowLds = uint32_t(size_t(p.states + 1) * kCaptureRowPitch);
-			le = SetDynamicLds(reinterpret_cast<const void*>(CaptureRowKernel), rowLds);
-			if (le != hipSuccess)
-				return HipFail(le, "hipFuncSetAttribute(LDS)");
 			NoteKernel("capture_rows");
-			p.spreadWaves = n <= uint64_t(cus) * 1024 ? 1u : 0u;
-			const unsigned rblocks = unsigned(std::max<uint64_t>(1, std::min<uint64_t>(p.spreadWaves ? (n + 63) / 64 : (n + 1023) / 1024, uint64_t(cus))));
-			hipLaunchKernelGGL(CaptureRowKernel, dim3(rblocks), dim3(1024), rowLds, stream, p);
-		} else if (p.dense && !(flags & PIRE_HIP_RUN_GENERIC)) {
-			const uint32_t denseLds = p.states * 512;
-			le = SetDynamicLds(reinterpret_cast<const void*>(CaptureDenseKernel), uint32_t(denseLds));
-			if (le != hipSuccess)
-				return HipFail(le, "hipFuncSetAttribute(LDS)");
-			NoteKernel("capture_dense");
-			// (a table of more than 40 KB: blocks of 16 waves, as LaunchPacked)
-			const unsigned dthreads = denseLds > 40 * 1024 ? 1024 : 256;
-			const uint64_t perCu = std::max<uint64_t>(1, std::min<uint64_t>(2048 / dthreads, (160 * 1024) / std::max<uint32_t>(denseLds, 1)));
-			const unsigned dblocks = unsigned(std::max<uint64_t>(1, std::min<uint64_t>((n + dthreads - 1) / dthreads, uint64_t(cus) * perCu)));
-			hipLaunchKernelGGL(CaptureDenseKernel, dim3(dblocks), dim3(dthreads), denseLds, stream, p);
-		} else {
-			NoteKernel("capture");
-			hipLaunchKernelGGL(CaptureKernel, dim3(blocks), dim3(256), ldsBytes, stream, p);
+			const unsigned blocks = RowGrid(n, cus, &p.spreadWaves);
+			return Launch(CaptureRowKernel, blocks, 1024, uint32_t(size_t(p.states + 1) * kCaptureRowPitch), stream, what, p);
 		}
-		le = hipGetLastError();
-		return le == hipSuccess ? PIRE_HIP_OK : HipFail(le, "capture kernel launch");
+		if (dense) {
+			NoteKernel("capture_dense");
+			unsigned threads;
+			const unsigned blocks = DenseGrid(n, cus, p.states * 512, 1024, &threads);
+			return Launch(CaptureDenseKernel, blocks, threads, p.states * 512, stream, what, p);
+		}
+		NoteKernel("capture");
+		return Launch(CaptureKernel, LaneGrid(n, cus), 256, genericLds, stream, what, p);
 	};
 	// Batches of >= 256 strings ride the ragged kernel with actions (the expanded table of BuildCaptureTable):
 	// 2-3 x the one-string-per-lane kernel below, which keeps the small batches and PIRE_HIP_RUN_GENERIC.

@@ -807,27 +807,6 @@ __device__ __forceinline__ void StepChunkShadow(const ScanParams& p, const uint8
 
 // ---- launch helpers --------------------------------------------------------------------------------------------------
 
-inline int DeviceCUs(int* cus)
-{
-	// asked on every launch: cache per device (hipGetDeviceProperties is far too slow for that)
-	static std::atomic<int> cached[64];
-	int dev = 0;
-	hipError_t e = hipGetDevice(&dev);
-	if (e != hipSuccess)
-		return HipFail(e, "hipGetDevice");
-	const bool slot = dev >= 0 && dev < 64;
-	int v = slot ? cached[dev].load(std::memory_order_relaxed) : 0;
-	if (v == 0) {
-		e = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
-		if (e != hipSuccess)
-			return HipFail(e, "hipDeviceGetAttribute(multiprocessor count)");
-		if (slot)
-			cached[dev].store(v, std::memory_order_relaxed);
-	}
-	*cus = v;
-	return PIRE_HIP_OK;
-}
-
 template <class K>
 hipError_t CachedOccupancy(int* perCu, K kernel, int threads, uint32_t ldsBytes)
 {

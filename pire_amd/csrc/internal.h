@@ -984,19 +984,77 @@ inline hipError_t SetDynamicLds(const void* fn, uint32_t ldsBytes)
 	return hipSuccess;
 }
 
+// The launch of a kernel with dynamic LDS: the attribute (remembered above), the launch, its error as a return code.
+template <class... A, class... P>
+int Launch(void (*kernel)(A...), unsigned blocks, unsigned threads, uint32_t ldsBytes, hipStream_t stream, const char* what,
+           const P&... args)
+{
+	hipError_t e = SetDynamicLds(reinterpret_cast<const void*>(kernel), ldsBytes);
+	if (e != hipSuccess)
+		return HipFail(e, "hipFuncSetAttribute(LDS)");
+	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), ldsBytes, stream, args...);
+	e = hipGetLastError();
+	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, what);
+}
+
+// The CUs of the current device (*dev, where asked for).
+inline int DeviceCUs(int* cus, int* dev = nullptr)
+{
+	// asked on every launch: cache per device (hipGetDeviceProperties is far too slow for that)
+	static std::atomic<int> cached[64];
+	int d = 0;
+	hipError_t e = hipGetDevice(&d);
+	if (e != hipSuccess)
+		return HipFail(e, "hipGetDevice");
+	const bool slot = d >= 0 && d < 64;
+	int v = slot ? cached[d].load(std::memory_order_relaxed) : 0;
+	if (v == 0) {
+		e = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, d);
+		if (e != hipSuccess)
+			return HipFail(e, "hipDeviceGetAttribute(multiprocessor count)");
+		if (slot)
+			cached[d].store(v, std::memory_order_relaxed);
+	}
+	*cus = v;
+	if (dev)
+		*dev = d;
+	return PIRE_HIP_OK;
+}
+
+// Blocks of `threads` for n items, one per lane, of a kernel with `ldsBytes` of LDS: as many per CU as its 2048 threads
+// and 160 KB allow, no more than the items fill.
+inline unsigned GridBlocks(uint64_t n, int cus, unsigned threads, uint32_t ldsBytes)
+{
+	const uint64_t perCu = std::max<uint64_t>(1, std::min<uint64_t>(2048 / threads, (160 * 1024) / std::max<uint32_t>(ldsBytes, 1)));
+	return unsigned(std::max<uint64_t>(1, std::min<uint64_t>((n + threads - 1) / threads, uint64_t(cus) * perCu)));
+}
+
+// The list a kernel with 16-bit state leaves the strings on that outgrow it: [0] = count (zeroed here, on the stream),
+// then up to n string indices.
+inline int OverflowList(StreamScratch& list, uint64_t n, hipStream_t stream, const char* what, uint32_t** out)
+{
+	if (int rc = list.Alloc((size_t(n) + 1) * 4, what))
+		return rc;
+	const hipError_t e = hipMemsetAsync(list.get(), 0, 4, stream);
+	if (e != hipSuccess)
+		return HipFail(e, what);
+	*out = list.as<uint32_t>();
+	return PIRE_HIP_OK;
+}
+
 // order.hip: the strings of an offset batch ordered by length class (longest first), built on the device, for the
-// one-string-per-lane kernels with per-byte actions.  `scratch`: LengthOrderScratchBytes(n) of device memory that stays
-// valid until the kernels that read *perm have run.
+// one-string-per-lane kernels with per-byte actions.
 // The k of pass `pass` (k = pass * lanes + t, or the same range backwards in odd passes when `serpentine`), for the
 // grid-stride loops of those kernels; >= n: nothing for this lane in this pass.
 __host__ __device__ inline uint64_t OrderedIndex(uint64_t pass, uint64_t t, uint64_t lanes, bool serpentine)
 {
 	return pass * lanes + ((serpentine && (pass & 1)) ? lanes - 1 - t : t);
 }
-bool LengthOrderWanted(uint64_t n);
-size_t LengthOrderScratchBytes(uint64_t n);
-// *serpentine: whether the kernels should walk the order with OrderedIndex's serpentine (the global order) or plainly
-int BuildLengthOrder(const uint64_t* offsets, uint64_t n, void* scratch, hipStream_t stream, const uint32_t** perm, bool* serpentine);
+// Where the batch is large enough for it (and pire_hip_config.no_length_order is not set): builds the order in `scratch`
+// -- the caller's owner, which has to live until the kernels that read *order are enqueued -- and says in *serpentine
+// whether the kernels should walk it with OrderedIndex's serpentine (the global order) or plainly.  Else leaves both alone.
+int OrderByLength(const uint64_t* offsets, uint64_t n, hipStream_t stream, StreamScratch& scratch, const uint32_t** order,
+                  uint32_t* serpentine);
 // select.hip: from end states to matches (pire_hip_select).  UploadSelect: the mask image of the CURRENT device, built on
 // first use (the caller holds t->adaptMutex, shared: the host image is built from t->host), copied out to *image (nullable).
 // LaunchSelect: device pointers only, enqueues three small kernels on `stream`, scratch from the stream-ordered allocator.

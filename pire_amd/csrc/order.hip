@@ -126,23 +126,18 @@ uint32_t OrderBlocks(uint64_t n)
 
 }  // namespace
 
-bool LengthOrderWanted(uint64_t n)
+int OrderByLength(const uint64_t* offsets, uint64_t n, hipStream_t stream, StreamScratch& scratch, const uint32_t** order,
+                  uint32_t* serpentine)
 {
 	// below a few lane-fills of the chip the launches cost more than the idle lanes; indices are 32 bits
-	return n >= 32768 && n < (1ull << 32) && !GetConfig().no_length_order;
-}
-
-size_t LengthOrderScratchBytes(uint64_t n)
-{
-	return ((size_t(n) * 4 + 255) & ~size_t(255)) + size_t(OrderBlocks(n)) * kOrderClasses * 4;
-}
-
-int BuildLengthOrder(const uint64_t* offsets, uint64_t n, void* scratch, hipStream_t stream, const uint32_t** perm, bool* serpentine)
-{
-	uint32_t* p = static_cast<uint32_t*>(scratch);
-	*serpentine = true;
-	uint32_t* hist = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(scratch) + ((size_t(n) * 4 + 255) & ~size_t(255)));
+	if (n < 32768 || n >= (1ull << 32) || GetConfig().no_length_order)
+		return PIRE_HIP_OK;
+	const size_t permBytes = (size_t(n) * 4 + 255) & ~size_t(255);
 	const uint32_t blocks = OrderBlocks(n);
+	if (int rc = scratch.Alloc(permBytes + size_t(blocks) * kOrderClasses * 4, "hipMallocAsync(length order)"))
+		return rc;
+	uint32_t* p = scratch.as<uint32_t>();
+	uint32_t* hist = reinterpret_cast<uint32_t*>(scratch.as<uint8_t>() + permBytes);
 	const uint64_t perBlock = (n + blocks - 1) / blocks;
 	hipLaunchKernelGGL(OrderHistKernel, dim3(blocks), dim3(kOrderThreads), 0, stream, offsets, n, perBlock, hist);
 	const hipError_t le = SetDynamicLds(reinterpret_cast<const void*>(OrderScanKernel), kOrderMaxBlocks * kOrderClasses * 4 * 17 / 16 + 64);
@@ -153,7 +148,8 @@ int BuildLengthOrder(const uint64_t* offsets, uint64_t n, void* scratch, hipStre
 	const hipError_t e = hipGetLastError();
 	if (e != hipSuccess)
 		return HipFail(e, "length order launch");
-	*perm = p;
+	*order = p;
+	*serpentine = 1u;
 	return PIRE_HIP_OK;
 }
 

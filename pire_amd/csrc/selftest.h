@@ -26,11 +26,14 @@ struct KnownBatch {
 	uint32_t n = 0;
 };
 
-// `n` strings of 0 .. maxLen bytes: each a walk from `start` through next(state, byte) that stays out of states dead(state) says
-// lead nowhere where it can (three attempts per byte), two thirds printable text; a few strings empty, a few one byte long.
-template <class NextFn, class DeadFn>
-KnownBatch MakeKnownBatch(uint32_t n, uint32_t maxLen, uint32_t start, uint64_t seed, NextFn next, DeadFn dead)
+// The batch of a table's self-tests: 320 strings of 0 .. 200 bytes, each a walk from `start` through w.Next(state, byte) that stays
+// out of states w.Dead(state) says lead nowhere where it can (three attempts per byte), two thirds printable text; a few strings
+// empty, a few one byte long.  `seed`: the entry point's, mixed with w.Salt() (the table's size).
+template <class Walk>
+KnownBatch KnownBatchFor(const Walk& w, uint32_t start, uint64_t seed)
 {
+	constexpr uint32_t n = 320, maxLen = 200;
+	seed ^= w.Salt();
 	KnownBatch b;
 	b.n = n;
 	b.offsets.resize(n + 1);
@@ -48,8 +51,8 @@ KnownBatch MakeKnownBatch(uint32_t n, uint32_t maxLen, uint32_t start, uint64_t 
 			for (int attempt = 0; attempt < 3; ++attempt) {
 				const uint32_t r = draw();
 				ch = r % 3 ? 32 + (r >> 8) % 95 : (r >> 8) & 255;
-				to = next(st, ch);
-				if (!dead(to))
+				to = w.Next(st, ch);
+				if (!w.Dead(to))
 					break;
 			}
 			b.text.push_back(uint8_t(ch));
@@ -62,9 +65,44 @@ KnownBatch MakeKnownBatch(uint32_t n, uint32_t maxLen, uint32_t start, uint64_t 
 	return b;
 }
 
-// Runs `body` once per variant of the routing knobs (each a full pire_hip_config copied from the caller's, edited by `edit[k]`)
-// with the override installed and recursion into the self-tests switched off; the first failure is returned.
-int RunSelfTestVariants(const std::vector<std::function<void(pire_hip_config&)>>& edits, const std::function<int()>& body);
+// a stream of the self-test's own: drained and destroyed when the test leaves
+struct OwnStream {
+	hipStream_t s = nullptr;
+	OwnStream() { (void)hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+	OwnStream(const OwnStream&) = delete;
+	OwnStream& operator=(const OwnStream&) = delete;
+	~OwnStream()
+	{
+		if (s) {
+			(void)hipStreamSynchronize(s);
+			(void)hipStreamDestroy(s);
+		}
+	}
+};
+
+// Whether entry point `bit` of a table (pire_hip_table, pire_hip_counting_table: selfTested[device]) has passed on the current
+// device, which goes to *dev; true without a device (the entry point says so itself).  MarkTested: it has.
+template <class Table>
+bool EntryTested(Table* t, uint32_t bit, int* dev)
+{
+	*dev = -1;
+	if (hipGetDevice(dev) != hipSuccess || *dev < 0 || *dev >= kMaxDevices)
+		return true;
+	return (t->selfTested[*dev].load(std::memory_order_relaxed) & (1u << bit)) != 0;
+}
+template <class Table>
+void MarkTested(Table* t, int dev, uint32_t bit)
+{
+	t->selfTested[dev].fetch_or(1u << bit);
+}
+
+// What is left of a self-test once the batch and its answers are there.  Once per variant of the routing knobs (each a full
+// pire_hip_config copied from the caller's, edited by `variants[k]`), with the override installed and recursion into the
+// self-tests switched off: poison() fills the outputs, call(stream) runs the entry point on a stream of the test's own,
+// compare() returns PIRE_HIP_OK or SelfTestMismatch(..).  The first failure is returned.
+using ConfigEdit = std::function<void(pire_hip_config&)>;
+int RunKnownAnswer(const std::vector<ConfigEdit>& variants, const std::function<void()>& poison,
+                   const std::function<int(hipStream_t)>& call, const std::function<int()>& compare);
 
 // "self-test of <what> failed: ..." into the thread's error string; returns PIRE_HIP_ESELFTEST
 int SelfTestMismatch(const char* what, uint32_t string, const std::string& got, const std::string& want);

@@ -973,24 +973,13 @@ int LaunchSlowK(const SlowParams& p0, hipStream_t stream)
 	p.singleInLds = singleBytes <= 64 * 1024 ? 1 : 0;
 	p.masksInLds = maskBytes + (p.singleInLds ? singleBytes : 0) <= 150 * 1024 ? 1 : 0;
 	const uint32_t ldsBytes = uint32_t(272 + (p.singleInLds ? singleBytes : 0) + (p.masksInLds ? maskBytes : 0));
-	hipError_t e = SetDynamicLds(reinterpret_cast<const void*>(SlowScanKernel<K>), uint32_t(ldsBytes));
-	if (e != hipSuccess)
-		return HipFail(e, "hipFuncSetAttribute(LDS)");
-	int dev = 0, cus = 0;
-	if ((e = hipGetDevice(&dev)) != hipSuccess ||
-	    (e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess)
-		return HipFail(e, "device query");
+	int cus = 0;
+	if (int rc = DeviceCUs(&cus))
+		return rc;
 	// big batches: 1024-thread blocks, as many per CU as the LDS copy of the masks allows (32 waves per CU at most);
 	// small ones: 256-thread blocks so that more CUs take part
 	const unsigned threads = p.n >= 128 * 1024 ? 1024 : 256;
-	const uint64_t perCu = std::max<uint64_t>(1, std::min<uint64_t>(2048 / threads, (160 * 1024) / std::max<uint32_t>(ldsBytes, 1)));
-	const uint64_t want = (p.n + threads - 1) / threads;
-	const unsigned blocks = unsigned(std::max<uint64_t>(1, std::min<uint64_t>(want, uint64_t(cus) * perCu)));
-	hipLaunchKernelGGL(SlowScanKernel<K>, dim3(blocks), dim3(threads), ldsBytes, stream, p);
-	e = hipGetLastError();
-	if (e != hipSuccess)
-		return HipFail(e, "slow kernel launch");
-	return PIRE_HIP_OK;
+	return Launch(SlowScanKernel<K>, GridBlocks(p.n, cus, threads, ldsBytes), threads, ldsBytes, stream, "slow kernel launch", p);
 }
 
 // One wave per string.  LDS budget, in this order: the two sets of every wave (16 waves per block, fewer when the sets
@@ -998,11 +987,9 @@ int LaunchSlowK(const SlowParams& p0, hipStream_t stream)
 int LaunchSlowWide(const SlowParams& p0, uint32_t njumps, hipStream_t stream)
 {
 	SlowParams p = p0;
-	int dev = 0, cus = 0;
-	hipError_t e;
-	if ((e = hipGetDevice(&dev)) != hipSuccess ||
-	    (e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess)
-		return HipFail(e, "device query");
+	int cus = 0;
+	if (int rc = DeviceCUs(&cus))
+		return rc;
 	const size_t setBytes = size_t(p.words) * 8;   // cur + next of one wave
 	const size_t ldsRoom = 158 * 1024 - 272;
 	uint32_t waves = uint32_t(std::min<size_t>(16, ldsRoom / setBytes));
@@ -1023,20 +1010,8 @@ int LaunchSlowWide(const SlowParams& p0, uint32_t njumps, hipStream_t stream)
 		p.scratch = scratch.as<uint32_t>();
 	}
 	const uint32_t ldsBytes = uint32_t(272 + (inLds ? waves * setBytes : 0) + (posInLds ? posBytes : 0) + (jumpsInLds ? jumpBytes : 0));
-	const void* fn = inLds ? reinterpret_cast<const void*>(SlowWideKernel<true>) : reinterpret_cast<const void*>(SlowWideKernel<false>);
-	e = SetDynamicLds(fn, uint32_t(ldsBytes));
-	if (e != hipSuccess)
-		return HipFail(e, "hipFuncSetAttribute(LDS)");
-	if (inLds)
-		hipLaunchKernelGGL(SlowWideKernel<true>, dim3(unsigned(blocks)), dim3(waves * 64), ldsBytes, stream, p, waves, posInLds,
-		                   jumpsInLds, njumps);
-	else
-		hipLaunchKernelGGL(SlowWideKernel<false>, dim3(unsigned(blocks)), dim3(waves * 64), ldsBytes, stream, p, waves, posInLds,
-		                   jumpsInLds, njumps);
-	e = hipGetLastError();
-	if (e != hipSuccess)
-		return HipFail(e, "slow kernel launch");
-	return PIRE_HIP_OK;
+	return Launch(inLds ? SlowWideKernel<true> : SlowWideKernel<false>, unsigned(blocks), waves * 64, ldsBytes, stream,
+	              "slow kernel launch", p, waves, posInLds, jumpsInLds, njumps);
 }
 
 // List form first: SlowListKernel over the whole batch, then `fallback` -- the bitset kernel (<= 256 states) or the
@@ -1046,46 +1021,25 @@ template <class Fallback>
 int LaunchSlowListThen(const SlowParams& p0, hipStream_t stream, Fallback fallback)
 {
 	SlowParams p = p0;
-	int dev = 0, cus = 0;
-	hipError_t e;
-	if ((e = hipGetDevice(&dev)) != hipSuccess ||
-	    (e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess)
-		return HipFail(e, "device query");
-	StreamScratch list(stream);
-	if (int rc = list.Alloc((size_t(p.n) + 1) * 4, "hipMallocAsync(slow scanner overflow list)"))
+	int cus = 0;
+	if (int rc = DeviceCUs(&cus))
 		return rc;
-	e = hipMemsetAsync(list.get(), 0, 4, stream);
-	if (e != hipSuccess)
-		return HipFail(e, "hipMallocAsync(slow scanner overflow list)");
-	p.overflow = list.as<uint32_t>();
+	StreamScratch list(stream);
+	if (int rc = OverflowList(list, p.n, stream, "hipMallocAsync(slow scanner overflow list)", &p.overflow))
+		return rc;
 	// ragged batches: the strings by length class (order.hip) -- this kernel is all VALU, a wave waiting for its longest
 	// string is its one avoidable cost
 	StreamScratch orderScratch(stream);
 	p.order = nullptr;
-	if (p.offsets && LengthOrderWanted(p.n)) {
-		if (int rc = orderScratch.Alloc(LengthOrderScratchBytes(p.n), "hipMallocAsync(length order)"))
+	if (p.offsets)
+		if (int rc = OrderByLength(p.offsets, p.n, stream, orderScratch, &p.order, &p.serpentine))
 			return rc;
-		bool serp = false;
-		if (int rc = BuildLengthOrder(p.offsets, p.n, orderScratch.get(), stream, &p.order, &serp))
-			return rc;
-		p.serpentine = serp ? 1u : 0u;
-	}
 	const uint32_t ldsBytes = uint32_t(1056 + 16 + size_t(p.states + 1) * p.letters * 4);
-	e = SetDynamicLds(reinterpret_cast<const void*>(SlowListKernel), uint32_t(ldsBytes));
-	if (e != hipSuccess)
-		return HipFail(e, "hipFuncSetAttribute(LDS)");
-	{
-		// one string per lane and ~100 VALU instructions per byte: spread the waves over every SIMD of the chip before
-		// stacking them (65 536 strings are 1 024 waves = one per SIMD: 256-thread blocks, one per CU)
-		const unsigned threads = p.n >= uint64_t(cus) * 2048 ? 1024 : p.n >= uint64_t(cus) * 512 ? 512 : 256;
-		const uint64_t perCu = std::max<uint64_t>(1, std::min<uint64_t>(2048 / threads, (160 * 1024) / ldsBytes));
-		const uint64_t want = (p.n + threads - 1) / threads;
-		const unsigned blocks = unsigned(std::max<uint64_t>(1, std::min<uint64_t>(want, uint64_t(cus) * perCu)));
-		hipLaunchKernelGGL(SlowListKernel, dim3(blocks), dim3(threads), ldsBytes, stream, p);
-		e = hipGetLastError();
-		if (e != hipSuccess)
-			return HipFail(e, "slow kernel launch");
-	}
+	// one string per lane and ~100 VALU instructions per byte: spread the waves over every SIMD of the chip before
+	// stacking them (65 536 strings are 1 024 waves = one per SIMD: 256-thread blocks, one per CU)
+	const unsigned threads = p.n >= uint64_t(cus) * 2048 ? 1024 : p.n >= uint64_t(cus) * 512 ? 512 : 256;
+	if (int rc = Launch(SlowListKernel, GridBlocks(p.n, cus, threads, ldsBytes), threads, ldsBytes, stream, "slow kernel launch", p))
+		return rc;
 	if (GetConfig().slow_stats) {   // measurements: how many strings the 16-slot list could not hold
 		uint32_t over = 0;
 		if (hipStreamSynchronize(stream) == hipSuccess && hipMemcpy(&over, list.get(), 4, hipMemcpyDeviceToHost) == hipSuccess)
