@@ -1,6 +1,7 @@
 // pigrep on the MI355X: the reference's sample grep (samples/pigrep/pigrep.cpp) with its one-line-at-a-time
 //     if (Pire::Runner(sc).Begin().Run(line).End()) print(line)
-// loop (pigrep.cpp:38-45) replaced by ONE batched call on the GPU.  Same command line, same output.
+// loop (pigrep.cpp:38-45) replaced by ONE batched call on the GPU, raw bytes in, matching lines out.  Same command
+// line, same output.
 //
 //   pigrep_hip [-i] [-u] [-x] [-e pattern | pattern] [file [file2...]]
 //
@@ -20,37 +21,18 @@
 
 namespace {
 
-// All lines of the stream in one buffer + their offsets (getline semantics: the newline is not part of the line, a
-// trailing fragment without newline is a line, an empty stream has no lines).
-void ReadLines(std::istream& in, std::string* text, std::vector<uint64_t>* offsets)
-{
-	const std::string raw((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
-	text->clear();
-	offsets->assign(1, 0);
-	size_t pos = 0;
-	while (pos < raw.size()) {
-		size_t nl = raw.find('\n', pos);
-		if (nl == std::string::npos)
-			nl = raw.size();
-		text->append(raw, pos, nl - pos);
-		offsets->push_back(text->size());
-		pos = nl + 1;
-	}
-}
-
+// The stream as it is, in one buffer: cutting it into lines (getline semantics: the newline is not part of the line, a
+// trailing fragment without newline is a line, an empty stream has no lines), scanning them and picking the lines that
+// matched all happen on the GPU; what comes back is the byte range of every hit.
 void GrepStream(std::istream& in, const Pire::Hip::Table<Pire::Scanner>& table, const std::string& prefix)
 {
-	std::string text;
-	std::vector<uint64_t> offsets;
-	ReadLines(in, &text, &offsets);
-	const size_t n = offsets.size() - 1;
-	if (!n)
+	const std::string raw((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+	if (raw.empty())
 		return;
 	Pire::Hip::BatchRunner<Pire::Scanner> run(table);
-	const std::vector<char>& hit = run.Begin().Run(text.data(), offsets.data(), n).End().Finals();
-	for (size_t i = 0; i < n; ++i)
-		if (hit[i])
-			std::cout << prefix << text.substr(offsets[i], offsets[i + 1] - offsets[i]) << std::endl;
+	const std::vector<uint64_t>& spans = run.Begin().RunLines(raw.data(), raw.size()).End().HitSpans();
+	for (size_t k = 0; k + 1 < spans.size(); k += 2)
+		std::cout << prefix << raw.substr(spans[k], spans[k + 1] - spans[k]) << std::endl;
 }
 
 void Usage()

@@ -472,6 +472,55 @@ int pire_hip_run_select_strided(pire_hip_table* t, const void* text, uint64_t n,
                                 uint64_t* out_counts, const uint64_t* want, uint64_t* out_masks, uint64_t* out_hits,
                                 uint64_t* out_hit_masks, uint64_t hit_cap, uint64_t* out_hit_count, void* stream);
 
+/* ---- raw text into strings, on the device ------------------------------------------------------------------- */
+
+/* The split pass cuts raw into tiles of this many bytes, on the 16-byte grid of raw's address (tests aim at its edges). */
+#define PIRE_HIP_SPLIT_TILE_BYTES 16384u
+
+/*
+ * Where the strings of a delimited buffer are: the step in front of every scan call, which wants text + offsets[n + 1]
+ * with nothing between the strings.  getline's semantics: the strings are the runs between delimiter bytes; the delimiter
+ * is not part of a string; a trailing fragment without a delimiter is a string; a buffer that ends in a delimiter has no
+ * extra empty string behind it; an empty buffer has no strings; consecutive delimiters give empty strings.  With D
+ * delimiter bytes in raw[0, size), the k-th of them (from 1) at p_k:
+ *   n = D + (size > 0 && raw[size - 1] != delim)
+ *   out_offsets[0] = 0,  out_offsets[k] = p_k - (k - 1) for 1 <= k <= D,  out_offsets[n] = size - D
+ *   out_text = raw without its delimiter bytes, size - D bytes (room for `size` bytes is always enough)
+ * so string i is out_text[out_offsets[i], out_offsets[i + 1]) and, in the buffer it came from,
+ *   raw[out_offsets[i] + i, out_offsets[i + 1] + i).
+ * out_text == NULL: nothing is copied, the offsets index raw itself and every string keeps its delimiter as its last
+ * byte: out_offsets[k] = p_k + 1, out_offsets[n] = size (for callers whose scanner tolerates the delimiter).
+ * out_n (required) receives n, also when n > offsets_cap.  out_offsets (nullable when offsets_cap == 0) has
+ * offsets_cap + 1 entries; only entries 0..min(n, offsets_cap) are written, nothing behind them.  size == 0 writes
+ * n = 0 and out_offsets[0] = 0.  delim is a byte value.  The pass is not in-place.
+ * flags: PIRE_HIP_RUN_ON_DEVICE -> every pointer is a device pointer and the call only enqueues on `stream`: three
+ *        kernels (count per tile, one-block scan, scatter), no atomics -- the same input gives the same bits --, 12 bytes
+ *        of scratch per tile from the stream-ordered allocator.  raw and out_text may have any alignment.
+ *        Otherwise host pointers: staged, synchronises.
+ * PIRE_HIP_EINVAL before any device is touched: delim > 255, null out_n, size > 0 with null raw, offsets_cap > 0 with
+ * null out_offsets, out_text[0, size) overlapping raw[0, size).
+ */
+int pire_hip_split(const void* raw, uint64_t size, uint32_t delim, uint32_t flags, void* out_text, uint64_t* out_offsets,
+                   uint64_t offsets_cap, uint64_t* out_n, void* stream);
+
+/*
+ * Raw bytes in, the matching lines out: pire_hip_split into scratch of the library's own, pire_hip_run_select on the
+ * result, and one small kernel that turns the hit list into byte ranges of the raw buffer.
+ * out_line_count (required)  n, the number of lines
+ * out_hits       (nullable)  [hit_cap] the numbers (from 0) of the selected lines, ascending
+ * out_hit_spans  (nullable)  [hit_cap][2] begin, end: hit k is raw[begin, end), its delimiter not included
+ * out_hit_masks  (nullable)  [hit_cap][W]
+ * want, hit_cap, out_hit_count (required): exactly pire_hip_select's; out_hit_spans and out_hit_masks need out_hits.
+ * flags: PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END | PIRE_HIP_RUN_GENERIC | PIRE_HIP_RUN_ON_DEVICE (every pointer a device
+ * pointer).  The call reads n back (8 bytes) between the split's scan and its scatter, to size the offsets: it
+ * synchronises `stream` once EVEN WITH PIRE_HIP_RUN_ON_DEVICE, and what it enqueues behind that is enqueue-only.
+ * PIRE_HIP_EINVAL before any device is touched: what pire_hip_select refuses, delim > 255, null out_line_count,
+ * size > 0 with null raw.  pire_hip_last_kernel() names the scan kernel.  Fewer than 2^32 lines.
+ */
+int pire_hip_run_lines_select(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
+                              const uint64_t* want, uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_hit_spans,
+                              uint64_t* out_hit_masks, uint64_t hit_cap, uint64_t* out_hit_count, void* stream);
+
 /*
  * Batched Runner over the table walked as a Pire::HalfFinalScanner (scanners/half_final.h:32-227).  A
  * HalfFinalScanner IS a Scanner (same Save() bytes, ingest it with pire_hip_table_create), but its Initialize and

@@ -184,7 +184,7 @@ public:
 		m_offsets = offsets;
 		m_n = n;
 		m_onDevice = false;
-		m_ran = false;
+		m_ran = m_lines = false;
 		return *this;
 	}
 
@@ -197,7 +197,7 @@ public:
 		m_len = m_stride = 0;
 		m_stream = stream;
 		m_onDevice = true;
-		m_ran = false;
+		m_ran = m_lines = false;
 		return *this;
 	}
 
@@ -211,7 +211,7 @@ public:
 		m_stride = stride;
 		m_stream = stream;
 		m_onDevice = true;
-		m_ran = false;
+		m_ran = m_lines = false;
 		return *this;
 	}
 
@@ -226,6 +226,29 @@ public:
 		}
 		return Run(m_ownText.data(), m_ownOffsets.data(), strings.size());
 	}
+
+	/*
+	 * A buffer as it was read -- lines with `delim` between them, host pointer -- cut into lines, scanned and selected on
+	 * the device (pire_hip_run_lines_select; getline's semantics: the delimiter is not part of a line, a trailing fragment
+	 * is one):
+	 *     run.Begin().RunLines(raw, size).End();
+	 *     run.HitSpans()    [2 * k], [2 * k + 1]: hit k is raw[begin, end)       run.LineCount()  lines in the buffer
+	 *     run.Hits()        the numbers of the selected lines, ascending         run.HitCount() / HitMasks() as after Select()
+	 * Select({..}) in front of them chooses regexps.  This form has hits only: States() / Finals() / MatchCounts() throw.
+	 */
+	BatchRunner& RunLines(const char* raw, size_t size, char delim = '\n')
+	{
+		m_text = raw;
+		m_offsets = nullptr;
+		m_n = 0;
+		m_len = size;
+		m_delim = uint8_t(delim);
+		m_onDevice = m_ran = m_selected = m_hitsFetched = false;
+		m_lines = true;
+		return *this;
+	}
+	uint64_t LineCount() { FetchHits(); return m_lineCount; }
+	const std::vector<uint64_t>& HitSpans() { FetchHits(); return m_hitSpans; }
 
 	/* RunHelper::State() per string (run.h:378). */
 	const std::vector<State>& States()
@@ -292,8 +315,9 @@ public:
 private:
 	void Reset()
 	{
-		m_selected = m_hitsFetched = m_haveWant = false;
-		m_hitCount = 0;
+		m_selected = m_hitsFetched = m_haveWant = m_lines = false;
+		m_hitCount = m_lineCount = 0;
+		m_delim = 0;
 		m_flags = 0;
 		m_text = nullptr;
 		m_offsets = nullptr;
@@ -304,6 +328,8 @@ private:
 
 	void Execute()
 	{
+		if (m_lines)
+			throw Pire::Error("pire_hip: RunLines() has hits, no states");
 		if (m_ran)
 			return;
 		if (!m_init.empty() && m_init.size() != m_n)
@@ -342,8 +368,36 @@ private:
 		m_ran = true;
 	}
 
+	/* RunLines(): one call; room for a hit on every line of 64 bytes or more, and a second call where there are more */
+	void ExecuteLines()
+	{
+		if (m_selected && m_ran)
+			return;
+		if (m_want.empty())
+			Select();
+		const size_t w = m_want.size();
+		for (size_t cap = m_len / 64 + 1024;; cap = m_hitCount) {
+			m_hits.resize(cap);
+			m_hitSpans.resize(cap * 2);
+			m_hitMasks.resize(cap * w);
+			Check(pire_hip_run_lines_select(m_table->Handle(), m_text, m_len, m_delim, m_flags, m_haveWant ? m_want.data() : nullptr,
+			                                &m_lineCount, m_hits.data(), m_hitSpans.data(), m_hitMasks.data(), cap, &m_hitCount,
+			                                nullptr));
+			if (m_hitCount <= cap)
+				break;
+		}
+		m_hits.resize(m_hitCount);
+		m_hitSpans.resize(m_hitCount * 2);
+		m_hitMasks.resize(m_hitCount * w);
+		m_ran = m_selected = m_hitsFetched = true;
+	}
+
 	void ExecuteSelect()
 	{
+		if (m_lines) {
+			ExecuteLines();
+			return;
+		}
 		const bool ranBefore = m_ran;
 		Execute();
 		if (m_selected && ranBefore)
@@ -434,9 +488,10 @@ private:
 	std::vector<char> m_final;
 	std::vector<uint64_t> m_counts;
 	DeviceBuffer m_devIdx, m_devFin, m_devCounts, m_devInit;
-	bool m_selected, m_hitsFetched, m_haveWant;
-	uint64_t m_hitCount;
-	std::vector<uint64_t> m_want, m_hits, m_hitMasks;
+	bool m_selected, m_hitsFetched, m_haveWant, m_lines;
+	uint8_t m_delim;
+	uint64_t m_hitCount, m_lineCount;
+	std::vector<uint64_t> m_want, m_hits, m_hitMasks, m_hitSpans;
 	DeviceBuffer m_devHits, m_devHitMasks, m_devHitCount, m_devWant;
 	ystring m_ownText;
 	std::vector<uint64_t> m_ownOffsets;

@@ -21,4 +21,6 @@ from .binding import (  # noqa: F401
     device_count,
     lib,
     lib_path,
+    split_device,
+    split_host,
 )

@@ -133,6 +133,7 @@ NONE = (1 << 64) - 1   # PIRE_HIP_SEGMENT_WARMUP_NONE / PIRE_HIP_SEGMENT_BUDGET_
 
 
 ABI_VERSION = 6   # include/pire_hip.h PIRE_HIP_ABI_VERSION
+SPLIT_TILE = 16384   # include/pire_hip.h PIRE_HIP_SPLIT_TILE_BYTES: the split pass cuts raw into tiles of this many bytes
 
 # every symbol include/pire_hip.h declares: (name, restype, argtypes)
 ABI = [
@@ -176,6 +177,10 @@ ABI = [
     ("pire_hip_run_select_strided", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_split", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                 C.c_void_p]),
+    ("pire_hip_run_lines_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_run_half_final", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_prefix", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_uint32,
@@ -310,6 +315,35 @@ def _check(rc: int):
 
 def _np_ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data
+
+
+# --- raw text into strings (pire_hip_split)
+def _raw_bytes(raw) -> np.ndarray:
+    return np.ascontiguousarray(np.frombuffer(raw, dtype=np.uint8) if isinstance(raw, (bytes, bytearray)) else raw, dtype=np.uint8)
+
+
+def split_host(raw, delim: int = 10, keep_delim: bool = False, offsets_cap: Optional[int] = None):
+    """pire_hip_split on host arrays: (text u8 -- None with keep_delim --, offsets u64[min(n, cap) + 1], n).  offsets_cap
+    None = room for every string: one call for n, one for the rest."""
+    raw = _raw_bytes(raw)
+    n = C.c_uint64(0)
+    ptr = raw.ctypes.data if raw.size else None
+    if offsets_cap is None:
+        _check(lib().pire_hip_split(ptr, raw.size, delim, 0, None, None, 0, C.byref(n), None))
+        offsets_cap = int(n.value)
+    text = None if keep_delim else np.zeros(max(raw.size, 1), dtype=np.uint8)
+    offsets = np.zeros(offsets_cap + 1, dtype=np.uint64)
+    _check(lib().pire_hip_split(ptr, raw.size, delim, 0, _np_ptr(text), offsets.ctypes.data, offsets_cap, C.byref(n), None))
+    k = min(int(n.value), offsets_cap)
+    delims = int(n.value) - (1 if raw.size and int(raw[-1]) != delim else 0)
+    return (None if text is None else text[:raw.size - delims]), offsets[:k + 1], int(n.value)
+
+
+def split_device(raw_ptr: int, size: int, out_n_ptr: int, delim: int = 10, out_text_ptr=0, out_offsets_ptr=0, offsets_cap=0,
+                 stream: int = 0):
+    """pire_hip_split with PIRE_HIP_RUN_ON_DEVICE: raw device addresses, only enqueues on `stream`."""
+    _check(lib().pire_hip_split(raw_ptr or None, size, delim, FLAG_ON_DEVICE, out_text_ptr or None, out_offsets_ptr or None,
+                                offsets_cap, out_n_ptr or None, stream or None))
 
 
 class Table:
@@ -602,6 +636,33 @@ class Table:
                                                  out_counts_ptr or None, want_ptr or None, out_masks_ptr or None,
                                                  out_hits_ptr or None, out_hit_masks_ptr or None, hit_cap,
                                                  out_hit_count_ptr or None, stream or None))
+
+    # --- raw bytes in, the matching lines out (pire_hip_run_lines_select): spans are uint64[hits, 2], begin / end in raw
+    def run_lines_select_host(self, raw, delim: int = 10, flags=FLAG_BEGIN | FLAG_END, want=None, hit_cap=None, hit_masks=True):
+        """pire_hip_run_lines_select on a host buffer: {"lines", "hits", "spans", "hit_masks", "count"}; hit_cap None = room for
+        a hit on every line (no more lines than bytes)."""
+        raw = _raw_bytes(raw)
+        wm = self.want_mask(want)
+        cap = raw.size if hit_cap is None else int(hit_cap)
+        w = self.mask_words
+        hits = np.zeros(cap, dtype=np.uint64)
+        spans = np.zeros((cap, 2), dtype=np.uint64)
+        masks = np.zeros((cap, w), dtype=np.uint64) if hit_masks else None
+        lines, cnt = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().pire_hip_run_lines_select(self._h, raw.ctypes.data if raw.size else None, raw.size, delim, flags & ~FLAG_ON_DEVICE,
+                                               _np_ptr(wm), C.byref(lines), hits.ctypes.data if cap else None,
+                                               spans.ctypes.data if cap else None, _np_ptr(masks) if cap else None, cap,
+                                               C.byref(cnt), None))
+        k = min(int(cnt.value), cap)
+        return {"lines": int(lines.value), "hits": hits[:k], "spans": spans[:k], "hit_masks": None if masks is None else masks[:k],
+                "count": int(cnt.value)}
+
+    def run_lines_select_device(self, raw_ptr: int, size: int, flags, out_line_count_ptr: int, out_hit_count_ptr: int, delim: int = 10,
+                                want_ptr=0, out_hits_ptr=0, out_hit_spans_ptr=0, out_hit_masks_ptr=0, hit_cap=0, stream: int = 0):
+        """pire_hip_run_lines_select on device pointers (synchronises `stream` once: the number of lines sizes its scratch)."""
+        _check(lib().pire_hip_run_lines_select(self._h, raw_ptr or None, size, delim, flags | FLAG_ON_DEVICE, want_ptr or None,
+                                               out_line_count_ptr or None, out_hits_ptr or None, out_hit_spans_ptr or None,
+                                               out_hit_masks_ptr or None, hit_cap, out_hit_count_ptr or None, stream or None))
 
     def run_half_final(self, text, offsets, flags=FLAG_BEGIN | FLAG_END):
         """The table walked as a Pire::HalfFinalScanner: (StateIndex, Final, Result[n, regexps]) for host strings."""

@@ -1730,6 +1730,191 @@ try {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
 
+// ---- raw text into strings (split.hip) -----------------------------------------------------------------------------------
+namespace {
+
+// What both split entry points refuse before any device is touched (`count`: out_n / out_line_count)
+int SplitArgsInvalid(const char* who, const void* raw, uint64_t size, uint32_t delim, const void* count, const char* countName)
+{
+	std::string what = delim > 255      ? "delim > 255"
+	                   : !count         ? std::string("null ") + countName
+	                   : size && !raw   ? "size > 0 with null raw"
+	                                    : "";
+	if (what.empty())
+		return PIRE_HIP_OK;
+	SetError(std::string(who) + ": " + what);
+	return PIRE_HIP_EINVAL;
+}
+
+// The number of strings, from the device to the host in the middle of a call: the stream is drained
+int ReadCount(const uint64_t* dev, uint64_t* host, hipStream_t stream)
+{
+	hipError_t e = hipMemcpyAsync(host, dev, 8, hipMemcpyDeviceToHost, stream);
+	if (e == hipSuccess)
+		e = hipStreamSynchronize(stream);
+	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "reading the number of strings back");
+}
+
+}  // namespace
+
+int pire_hip_split(const void* raw, uint64_t size, uint32_t delim, uint32_t flags, void* out_text, uint64_t* out_offsets,
+                   uint64_t offsets_cap, uint64_t* out_n, void* streamPtr)
+try {
+	if (int rc = SplitArgsInvalid("pire_hip_split", raw, size, delim, out_n, "out_n"))
+		return rc;
+	if (offsets_cap && !out_offsets) {
+		SetError("pire_hip_split: offsets_cap > 0 with null out_offsets");
+		return PIRE_HIP_EINVAL;
+	}
+	const uintptr_t r = reinterpret_cast<uintptr_t>(raw), o = reinterpret_cast<uintptr_t>(out_text);
+	if (out_text && size && o < r + size && r < o + size) {
+		SetError("pire_hip_split: out_text overlaps raw (the pass is not in-place)");
+		return PIRE_HIP_EINVAL;
+	}
+	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
+	if (!onDevice && size == 0) {
+		*out_n = 0;
+		if (out_offsets)
+			out_offsets[0] = 0;
+		return PIRE_HIP_OK;
+	}
+	BatchIO io(stream, onDevice);
+	const uint8_t* dRaw = nullptr;
+	if (int rc = io.In(static_cast<const uint8_t*>(raw), size_t(size), &dRaw))
+		return rc;
+	uint64_t n = 0;   // host pointers: the count comes back here first
+	uint64_t* dN = nullptr;
+	if (int rc = io.Result(onDevice ? out_n : &n, 1, 1, &dN))
+		return rc;
+	if (int rc = io.Ready())
+		return rc;
+	StreamScratch scratch(stream);
+	SplitPlan plan;
+	if (int rc = LaunchSplitCount(dRaw, size, delim, dN, stream, scratch, &plan))
+		return rc;
+	if (onDevice)
+		return LaunchSplitScatter(plan, out_text, out_offsets, offsets_cap, dN, stream);
+	// host pointers: n first -- it says how much there is to stage
+	if (int rc = ReadCount(dN, &n, stream))
+		return rc;
+	const uint64_t delims = n - (static_cast<const uint8_t*>(raw)[size - 1] != delim ? 1 : 0);
+	const uint64_t entries = std::min(n, offsets_cap);
+	uint8_t* dText = nullptr;
+	uint64_t* dOffsets = nullptr;
+	if (out_text)
+		if (int rc = io.Result(static_cast<uint8_t*>(out_text), size_t(size - delims), size_t(size - delims), &dText))
+			return rc;
+	if (out_offsets)
+		if (int rc = io.Result(out_offsets, size_t(entries) + 1, size_t(entries) + 1, &dOffsets))
+			return rc;
+	if (int rc = LaunchSplitScatter(plan, dText, dOffsets, entries, dN, stream))
+		return rc;
+	if (int rc = io.Finish())
+		return rc;
+	*out_n = n;
+	return PIRE_HIP_OK;
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_run_lines_select(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
+                              const uint64_t* want, uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_hit_spans,
+                              uint64_t* out_hit_masks, uint64_t hit_cap, uint64_t* out_hit_count, void* streamPtr)
+try {
+	if (int rc = SelectArgsInvalid(t, nullptr, false, 0, out_hits, out_hit_masks, hit_cap, out_hit_count))
+		return rc;
+	if (int rc = SplitArgsInvalid("pire_hip_run_lines_select", raw, size, delim, out_line_count, "out_line_count"))
+		return rc;
+	if (out_hit_spans && !out_hits) {
+		SetError("pire_hip_run_lines_select: out_hit_spans without out_hits");
+		return PIRE_HIP_EINVAL;
+	}
+	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
+	if (!onDevice && size == 0) {
+		*out_line_count = *out_hit_count = 0;
+		return PIRE_HIP_OK;
+	}
+	const uint32_t words = pire_hip_table_mask_words(t);
+	BatchIO io(stream, onDevice);
+	const uint8_t* dRaw = nullptr;
+	const uint64_t* dWant = nullptr;
+	if (int rc = io.In(static_cast<const uint8_t*>(raw), size_t(size), &dRaw))
+		return rc;
+	if (want)
+		if (int rc = io.In(want, size_t(words), &dWant))
+			return rc;
+	uint64_t n = 0, count = 0;   // host pointers: the counts come back here first
+	uint64_t *dN = nullptr, *dCount = nullptr, *dHits = nullptr, *dSpans = nullptr, *dHitMasks = nullptr;
+	if (int rc = io.Result(onDevice ? out_line_count : &n, 1, 1, &dN))
+		return rc;
+	if (int rc = io.Result(onDevice ? out_hit_count : &count, 1, 1, &dCount))
+		return rc;
+	if (int rc = io.Ready())
+		return rc;
+	// the split, into scratch that lives until the scan and the gather behind it are enqueued; n sizes the offsets
+	StreamScratch tiles(stream), text(stream), offsets(stream);
+	SplitPlan plan;
+	if (int rc = LaunchSplitCount(dRaw, size, delim, dN, stream, tiles, &plan))
+		return rc;
+	if (int rc = ReadCount(dN, &n, stream))
+		return rc;
+	if (n >= (1ull << 32)) {
+		SetError("pire_hip_run_lines_select: 2^32 lines or more in one call");
+		return PIRE_HIP_EUNSUPPORTED;
+	}
+	if (int rc = text.Alloc(size_t(size) + 16, "hipMallocAsync(split text)"))
+		return rc;
+	if (int rc = offsets.Alloc((size_t(n) + 1) * 8, "hipMallocAsync(split offsets)"))
+		return rc;
+	if (int rc = LaunchSplitScatter(plan, text.get(), offsets.as<uint64_t>(), n, dN, stream))
+		return rc;
+	const uint64_t cap = std::min<uint64_t>(hit_cap, n);   // n lines have at most n hits
+	if (out_hits && cap) {
+		if (int rc = io.Result(out_hits, size_t(cap), 0, &dHits))
+			return rc;
+		if (out_hit_spans)
+			if (int rc = io.Result(out_hit_spans, size_t(cap) * 2, 0, &dSpans))
+				return rc;
+		if (out_hit_masks)
+			if (int rc = io.Result(out_hit_masks, size_t(cap) * words, 0, &dHitMasks))
+				return rc;
+	}
+	if (n == 0) {
+		const hipError_t e = hipMemsetAsync(dCount, 0, 8, stream);
+		if (e != hipSuccess)
+			return HipFail(e, "hipMemsetAsync(hit count)");
+	} else {
+		const uint32_t runFlags = (flags & (PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END | PIRE_HIP_RUN_GENERIC)) | PIRE_HIP_RUN_ON_DEVICE;
+		if (int rc = pire_hip_run_select(t, text.get(), offsets.as<uint64_t>(), n, runFlags, nullptr, nullptr, nullptr, nullptr, dWant,
+		                                 nullptr, dHits, dHitMasks, dHits ? cap : 0, dCount, stream))
+			return rc;
+		if (dSpans)
+			if (int rc = LaunchSplitSpans(dHits, dCount, cap, offsets.as<uint64_t>(), dSpans, stream))
+				return rc;
+	}
+	if (int rc = io.Finish())
+		return rc;
+	if (onDevice)
+		return PIRE_HIP_OK;
+	*out_line_count = n;
+	*out_hit_count = count;
+	const uint64_t written = std::min<uint64_t>(count, dHits ? cap : 0);
+	if (written) {
+		hipError_t e = hipMemcpy(out_hits, dHits, size_t(written) * 8, hipMemcpyDeviceToHost);
+		if (e == hipSuccess && dSpans)
+			e = hipMemcpy(out_hit_spans, dSpans, size_t(written) * 16, hipMemcpyDeviceToHost);
+		if (e == hipSuccess && dHitMasks)
+			e = hipMemcpy(out_hit_masks, dHitMasks, size_t(written) * words * 8, hipMemcpyDeviceToHost);
+		if (e != hipSuccess)
+			return HipFail(e, "hipMemcpy(hits)");
+	}
+	return PIRE_HIP_OK;
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
 // ---- first-use self-tests of the entry points with actions (selftest.h) -------------------------------------------------
 namespace {
 

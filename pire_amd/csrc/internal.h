@@ -1064,6 +1064,26 @@ void FreeSelect(pire_hip_table* t);
 int LaunchSelect(const SelectDevice& image, uint32_t states, uint32_t words, const uint32_t* stateIdx, uint64_t n,
                  const uint64_t* want, uint64_t* outMasks, uint64_t* outHits, uint64_t* outHitMasks, uint64_t hitCap,
                  uint64_t* outHitCount, hipStream_t stream);
+// split.hip: raw text into strings (pire_hip_split).  Device pointers only, everything enqueued on `stream`.  The pass
+// comes in two halves because a caller may want the number of strings before it has room for their offsets:
+// LaunchSplitCount counts and scans (*outN = n; the tile prefixes stay in `scratch`, the caller's owner, which has to live
+// until the scatter is enqueued), LaunchSplitScatter writes offsets[0..min(n, cap)] and, where outText is not null, the text
+// without its delimiters.  LaunchSplitSpans: [begin, end) in the raw buffer of the first min(*hitCount, cap) hits.
+struct SplitPlan {
+	const uint8_t* raw;
+	uint32_t head;       // raw's address modulo 16: tiles and lanes are cut on the 16-byte grid, raw[0] is byte `head` of the first lane
+	uint32_t delim4;     // the delimiter in every byte
+	uint64_t size;
+	uint32_t tiles;
+	uint32_t* counts;    // [tiles] delimiters per tile
+	uint64_t* prefix;    // [tiles] delimiters in front of the tile
+};
+int LaunchSplitCount(const void* raw, uint64_t size, uint32_t delim, uint64_t* outN, hipStream_t stream, StreamScratch& scratch,
+                     SplitPlan* plan);
+int LaunchSplitScatter(const SplitPlan& plan, void* outText, uint64_t* outOffsets, uint64_t offsetsCap, const uint64_t* outN,
+                       hipStream_t stream);
+int LaunchSplitSpans(const uint64_t* hits, const uint64_t* hitCount, uint64_t cap, const uint64_t* offsets, uint64_t* spans,
+                     hipStream_t stream);
 void NoteKernel(const char* name, const char* symbol = nullptr);   // what pire_hip_last_kernel[_symbol]() report (thread local)
 bool RaggedActEligible(const ScanParams& p);
 int LaunchRaggedHalfFinal(const ScanParams& p, unsigned long long* workCounter, uint32_t* outResults, hipStream_t stream);
