@@ -537,6 +537,111 @@ __device__ __forceinline__ void TransposeTile(u32x4 (&r)[8], uint32_t lane)
 	}
 }
 
+// ---- the ring of two register tiles of the fixed-length kernels (tiled.hip, pair.hip, wide.hip) -----------------------
+// The pieces below are force-inlined; the emitted code of every kernel was compared with the parent's when they were
+// shared (profiles/tile_ring_isa.txt): do the same after any edit here.
+//
+// A tile is 128 bytes (one cache line) of each of the wave's 64 strings.  It is fetched with 8 x
+// global_load_dwordx4 in which EIGHT ADJACENT LANES COVER ONE WHOLE LINE: instruction j, lane l reads
+//     chunk (l & 7) of string  s0 + (l & ~7) + j        (16 bytes)
+// so every instruction touches 8 full lines instead of 64 partial ones.  Measured on MI355X
+// (profiles/r01_pmc_summary_strided_16w_nbuf3.txt): with one-line-per-lane loads the L1 (TCP) tag pipeline was the
+// binding unit -- TA busy 75 %, TA stalled by TC 56 %, 0.63 lane-accesses/clk/CU -- and `nt` could not be used
+// because each line was touched by 8 separate instructions.  With whole-line instructions the same bytes cost
+// 1/8 of the L1 accesses and stream with `nt`.
+// After the loads, lane 8g+k holds in register j chunk k of string 8g+j; an 8x8 transpose across each group of 8
+// lanes (TransposeTile, DPP only, no LDS) leaves lane 8g+j with chunks 0..7 of its own string in registers 0..7.
+//
+// The loads are issued from inline asm and waited for with hand-counted s_waitcnt vmcnt(N).  Reason (measured,
+// DESIGN.md section 6): hipcc's own wait insertion turns every loop-carried prefetch into `s_waitcnt vmcnt(0)` at
+// the tile boundary, which collapses an N-deep register pipeline to depth 1.  Counting is safe with foreign VMEM
+// ops in the queue: loads return in order among themselves, so "at most 8*k outstanding" implies every load issued
+// before the last k tiles has landed; extra compiler-issued ops only make the wait stricter.
+// "+v": the tile registers are updated IN PLACE, so the compiler has no reason to copy a slot that is in flight.
+//
+// LOW (the kernels with a warm-up inside the pass): `low` is the first byte of the text.  Only the warm-up tiles of the
+// very first record (the first load's lanes 0..7) lie below it; those lanes read from the record itself instead, and
+// what they read is never used.
+template <bool NT = true, bool LOW = false>
+__device__ __forceinline__ void IssueTile(u32x4 (&r)[8], uint32_t voff, uint64_t tileBase, uint64_t stride, uint64_t low = 0)
+{
+	static_assert(NT || !LOW, "plain loads below the text's first byte: no kernel asks for them");
+	uint32_t voff0 = voff;
+	if (LOW && tileBase < low)
+		voff0 += (threadIdx.x & 63) < 8 ? uint32_t(low - tileBase + 127) & ~127u : 0u;
+	const uint64_t b0 = tileBase, b1 = b0 + stride, b2 = b1 + stride, b3 = b2 + stride, b4 = b3 + stride,
+	               b5 = b4 + stride, b6 = b5 + stride, b7 = b6 + stride;
+	if constexpr (LOW)
+		asm volatile(
+			"global_load_dwordx4 %0, %17, %9 nt\n\t"
+			"global_load_dwordx4 %1, %8, %10 nt\n\t"
+			"global_load_dwordx4 %2, %8, %11 nt\n\t"
+			"global_load_dwordx4 %3, %8, %12 nt\n\t"
+			"global_load_dwordx4 %4, %8, %13 nt\n\t"
+			"global_load_dwordx4 %5, %8, %14 nt\n\t"
+			"global_load_dwordx4 %6, %8, %15 nt\n\t"
+			"global_load_dwordx4 %7, %8, %16 nt"
+			: "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7])
+			: "v"(voff), "s"(b0), "s"(b1), "s"(b2), "s"(b3), "s"(b4), "s"(b5), "s"(b6), "s"(b7), "v"(voff0));
+	else if constexpr (NT)
+		asm volatile(
+			"global_load_dwordx4 %0, %8, %9 nt\n\t"
+			"global_load_dwordx4 %1, %8, %10 nt\n\t"
+			"global_load_dwordx4 %2, %8, %11 nt\n\t"
+			"global_load_dwordx4 %3, %8, %12 nt\n\t"
+			"global_load_dwordx4 %4, %8, %13 nt\n\t"
+			"global_load_dwordx4 %5, %8, %14 nt\n\t"
+			"global_load_dwordx4 %6, %8, %15 nt\n\t"
+			"global_load_dwordx4 %7, %8, %16 nt"
+			: "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7])
+			: "v"(voff), "s"(b0), "s"(b1), "s"(b2), "s"(b3), "s"(b4), "s"(b5), "s"(b6), "s"(b7));
+	else
+		asm volatile(
+			"global_load_dwordx4 %0, %8, %9\n\t"
+			"global_load_dwordx4 %1, %8, %10\n\t"
+			"global_load_dwordx4 %2, %8, %11\n\t"
+			"global_load_dwordx4 %3, %8, %12\n\t"
+			"global_load_dwordx4 %4, %8, %13\n\t"
+			"global_load_dwordx4 %5, %8, %14\n\t"
+			"global_load_dwordx4 %6, %8, %15\n\t"
+			"global_load_dwordx4 %7, %8, %16"
+			: "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7])
+			: "v"(voff), "s"(b0), "s"(b1), "s"(b2), "s"(b3), "s"(b4), "s"(b5), "s"(b6), "s"(b7));
+}
+
+// Wait until at most TILES_BEHIND tiles issued after `r` are still in flight; names r so nothing reads it earlier.
+template <int TILES_BEHIND>
+__device__ __forceinline__ void WaitTile(u32x4 (&r)[8])
+{
+	asm volatile("s_waitcnt vmcnt(%8)"
+	             : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7])
+	             : "n"(TILES_BEHIND * 8));
+}
+
+// Keep the waves of a block in step.  Every STEP tiles a wave adds STEP to a block-wide progress counter (LDS) and compares
+// `waves` x its own tile count with the sum: a wave ahead of the block's average by more than a quarter tile drops its issue
+// priority, one behind raises it.  Without it the 16 waves of a block, which all do exactly the same amount of work,
+// finish up to 30 us apart (profiles/r02_tiled_block_stamps.log: age-ordered arbitration lets some waves run ahead all
+// the way) and the CU idles half empty at the end of a launch; with it 10 us.  Worth 1.3 % on the 2^20 x 4 KiB headline
+// (9 of 9 alternating pairs), 4.8 % with the single-pattern table, nothing from 8 tasks per wave up, -0.7 % on C++ text
+// (profiles/r02_tiled_equalise.log).
+template <uint32_t STEP>
+__device__ __forceinline__ void KeepInStep(uint32_t* prog, uint32_t& myTiles, uint32_t lane, uint32_t waves)
+{
+	uint32_t sum = 0;
+	if (lane == 0)
+		sum = atomicAdd(prog, STEP) + STEP;
+	sum = uint32_t(__builtin_amdgcn_readfirstlane(int(sum)));
+	myTiles += STEP;
+	constexpr uint32_t margin = 4 * STEP;   // in sixteenths of a tile (0 / 4 / 8: equal; 16, 32: less effect)
+	if (myTiles * waves > sum + margin)
+		__builtin_amdgcn_s_setprio(0);
+	else if (myTiles * waves + margin < sum)
+		__builtin_amdgcn_s_setprio(3);
+	else
+		__builtin_amdgcn_s_setprio(1);
+}
+
 // ---- window loads of the offset-batch kernels (ragged.hip, stream.hip) ------------------------------------------------
 // Both kernels fetch, per lane and iteration, one window of 128 bytes at an address of the lane's own.
 __device__ __forceinline__ void IssueTileLane(u32x4 (&r)[8], uint64_t src)
@@ -616,8 +721,7 @@ __device__ __forceinline__ void IssueTileGroup(u32x4 (&r)[8], uint64_t src, uint
 
 __device__ __forceinline__ void WaitAllLoads(u32x4 (&r)[8])
 {
-	asm volatile("s_waitcnt vmcnt(0)"
-	             : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7]));
+	WaitTile<0>(r);
 }
 
 
@@ -780,9 +884,7 @@ __device__ __forceinline__ void ShadowLookups(const u32x4 v, uint32_t& hs, u32x4
 		if constexpr (I >= SKIP && slot < kTransposeSlots) {
 			__builtin_amdgcn_sched_barrier(0);
 			if constexpr (WAIT && I == SKIP)
-				asm volatile("s_waitcnt vmcnt(0)"
-				             : "+v"(next[0]), "+v"(next[1]), "+v"(next[2]), "+v"(next[3]), "+v"(next[4]), "+v"(next[5]),
-				               "+v"(next[6]), "+v"(next[7]));
+				WaitTile<0>(next);
 			TransposeSlot<slot>(next, tmp);
 			__builtin_amdgcn_sched_barrier(0);
 		}
@@ -800,10 +902,6 @@ __device__ __forceinline__ void StepChunkShadow(const ScanParams& p, const uint8
 	if (hs == p.hot)
 		TrapChunk(p, lds, L, v, hs0, hs, cold, sampleLane);
 }
-
-// One pipeline phase of the register ring: refill the slot that was freed one phase ago with the tile NBUF-1
-// ahead (index clamped to the last tile, so the steady-state loop has no conditional loads), wait until the
-// current slot has landed, transpose it into lane-owns-string order, walk it.
 
 // ---- launch helpers --------------------------------------------------------------------------------------------------
 

@@ -401,6 +401,19 @@ int LaunchGeneric(const ScanParams& p0, hipStream_t stream)
 	return LaunchScan(ScanGenericKernel, p, ExactBlockThreads(p.n), L.total, stream);
 }
 
+int LaunchRemainder(const ScanParams& p, uint64_t done, hipStream_t stream)
+{
+	ScanParams tail = p;
+	tail.n = p.n - done;
+	tail.text = p.text + done * p.stride;
+	if (p.initIdx)
+		tail.initIdx = p.initIdx + done;
+	if (p.outIdx)
+		tail.outIdx = p.outIdx + done;
+	if (p.outFinal)
+		tail.outFinal = p.outFinal + done;
+	return LaunchGeneric(tail, stream);
+}
 
 int LaunchPrefix(const ScanParams& p0, bool longest, bool throughEnd, long long* outLen, hipStream_t stream,
                  unsigned long long* workCounter)

@@ -918,6 +918,8 @@ void FreeDeviceTable(DeviceTable* d);
 
 // tiled.hip / ragged.hip / exact.hip / corpus.hip
 int LaunchGeneric(const ScanParams& p, hipStream_t stream);
+// what a kernel of whole tasks leaves over: strings [done, p.n) of a fixed-length batch through the generic kernel
+int LaunchRemainder(const ScanParams& p, uint64_t done, hipStream_t stream);
 int LaunchTiled(const ScanParams& p, hipStream_t stream);
 // wide.hip: fixed-length records through the class-indexed walk (tables whose scans keep leaving the dense rows)
 bool WideWanted(const ScanParams& p, const pire_hip_config& cfg);

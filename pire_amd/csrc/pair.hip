@@ -97,37 +97,6 @@ __device__ __forceinline__ void PairStepChunk(const PairParams& q, const PairSid
 	}
 }
 
-template <bool NT>
-__device__ __forceinline__ void PairIssueTile(u32x4 (&r)[8], uint32_t voff, uint64_t tileBase, uint64_t stride, uint64_t low = 0)
-{
-	// `low`: the first byte of the text.  Only the warm-up tiles of the very first record (the first load's lanes 0..7)
-	// lie below it (SEG); those lanes read from the record itself instead, and what they read is never used.
-	uint32_t voff0 = voff;
-	if (tileBase < low)
-		voff0 += (threadIdx.x & 63) < 8 ? uint32_t(low - tileBase + 127) & ~127u : 0u;
-	const uint64_t b0 = tileBase, b1 = tileBase + stride, b2 = b1 + stride, b3 = b2 + stride, b4 = b3 + stride,
-	               b5 = b4 + stride, b6 = b5 + stride, b7 = b6 + stride;
-	asm volatile(
-		"global_load_dwordx4 %0, %17, %9 nt\n\t"
-		"global_load_dwordx4 %1, %8, %10 nt\n\t"
-		"global_load_dwordx4 %2, %8, %11 nt\n\t"
-		"global_load_dwordx4 %3, %8, %12 nt\n\t"
-		"global_load_dwordx4 %4, %8, %13 nt\n\t"
-		"global_load_dwordx4 %5, %8, %14 nt\n\t"
-		"global_load_dwordx4 %6, %8, %15 nt\n\t"
-		"global_load_dwordx4 %7, %8, %16 nt"
-		: "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7])
-		: "v"(voff), "s"(b0), "s"(b1), "s"(b2), "s"(b3), "s"(b4), "s"(b5), "s"(b6), "s"(b7), "v"(voff0));
-}
-
-template <int BEHIND>
-__device__ __forceinline__ void PairWaitTile(u32x4 (&r)[8])
-{
-	asm volatile("s_waitcnt vmcnt(%8)"
-	             : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7])
-	             : "n"(BEHIND * 8));
-}
-
 // Copy a table's dense rows into LDS, cutting ids >= `hot` to the trap id `hot` (table A: 254 rows of its 255).
 __device__ inline void PairLoadRows(uint8_t* dst, const uint8_t* src, uint32_t srcHot, uint32_t hot)
 {
@@ -191,7 +160,7 @@ __global__ __launch_bounds__(1024, 4) void ScanPairTiledKernel(PairParams q)
 	ZeroTile(b);
 	bool primed = firstTask < ntasks;
 	if (primed)
-		PairIssueTile<true>(a, voff, Uniform64(text + firstTask * 64 * pa.stride), pa.stride, low);
+		IssueTile<true, true>(a, voff, Uniform64(text + firstTask * 64 * pa.stride), pa.stride, low);
 	PairLoadRows(lds, pa.hotRows, pa.hot, A.hot);
 	if (!SEG)
 		PairLoadRows(lds + kPairBaseB, pb.hotRows, pb.hot, B.hot);
@@ -205,7 +174,7 @@ __global__ __launch_bounds__(1024, 4) void ScanPairTiledKernel(PairParams q)
 		if (!SEG)
 			reinterpret_cast<uint16_t*>(tail + 512 + 528)[i] = pb.cls[i];
 	}
-	// block-wide progress counter: the waves of a block are kept in step by issue priority, as in the tiled kernel
+	// block-wide progress counter: the waves of a block are kept in step by issue priority (device_common.h KeepInStep)
 	uint32_t* prog = reinterpret_cast<uint32_t*>(tail + 512 + 2 * 528);   // (SEG leaves the B halves of the tail unused)
 	if (threadIdx.x == 0)
 		*prog = 0;
@@ -225,7 +194,7 @@ __global__ __launch_bounds__(1024, 4) void ScanPairTiledKernel(PairParams q)
 		uint32_t ha = ca < A.hot ? ca : A.hot, hb = cb < B.hot ? cb : B.hot;
 		bool done = false;
 		if (!primed)
-			PairIssueTile<true>(a, voff, rowBase, pa.stride, low);
+			IssueTile<true, true>(a, voff, rowBase, pa.stride, low);
 		for (uint32_t t = 0; t < ntiles && !done; t += 2) {
 			if (SEG && t == warm) {   // the segment's first byte: these two states are the guesses
 				ca = ha != A.hot ? ha : ca;
@@ -239,27 +208,15 @@ __global__ __launch_bounds__(1024, 4) void ScanPairTiledKernel(PairParams q)
 				q.guessA[s] = ca;
 				q.guessB[s] = cb;
 			}
-			{
-				uint32_t sum = 0;
-				if (lane == 0)
-					sum = atomicAdd(prog, 2u) + 2;
-				sum = uint32_t(__builtin_amdgcn_readfirstlane(int(sum)));
-				myTiles += 2;
-				if (myTiles * wavesPerBlock > sum + 8)
-					__builtin_amdgcn_s_setprio(0);
-				else if (myTiles * wavesPerBlock + 8 < sum)
-					__builtin_amdgcn_s_setprio(3);
-				else
-					__builtin_amdgcn_s_setprio(1);
-			}
-			PairIssueTile<true>(b, voff, rowBase + uint64_t(t + 1) * 128, pa.stride, low);
-			PairWaitTile<1>(a);
+			KeepInStep<2>(prog, myTiles, lane, wavesPerBlock);
+			IssueTile<true, true>(b, voff, rowBase + uint64_t(t + 1) * 128, pa.stride, low);
+			WaitTile<1>(a);
 			TransposeTile(a, lane);
 #pragma unroll
 			for (int k = 0; k < 8; ++k)
 				PairStepChunk<SEG>(q, A, B, a[k], ha, ca, hb, cb);
-			PairIssueTile<true>(a, voff, t + 2 < ntiles ? rowBase + uint64_t(t + 2) * 128 : chainBase, pa.stride, low);
-			PairWaitTile<1>(b);
+			IssueTile<true, true>(a, voff, t + 2 < ntiles ? rowBase + uint64_t(t + 2) * 128 : chainBase, pa.stride, low);
+			WaitTile<1>(b);
 			TransposeTile(b, lane);
 #pragma unroll
 			for (int k = 0; k < 8; ++k)
@@ -271,7 +228,7 @@ __global__ __launch_bounds__(1024, 4) void ScanPairTiledKernel(PairParams q)
 		}
 		primed = hasNext && !done;   // an early-out leaves some other tile in slot a: re-prime then
 		if (done)
-			PairWaitTile<0>(a);
+			WaitTile<0>(a);
 		uint32_t sa = ha != A.hot ? ha : ca, sb = hb != B.hot ? hb : cb;
 		if (!done) {
 			const uint8_t* base = pa.text + s * pa.stride;
@@ -292,8 +249,8 @@ __global__ __launch_bounds__(1024, 4) void ScanPairTiledKernel(PairParams q)
 		if (!SEG && pa.outFinal)
 			pa.outFinal[s] = ((rawA.y | rawB.y) >> 28) & kFinal;
 	}
-	PairWaitTile<0>(a);
-	PairWaitTile<0>(b);
+	WaitTile<0>(a);
+	WaitTile<0>(b);
 }
 
 // Whole pairs of 128-byte tiles (the ring of two), at least one; len need NOT be a multiple of 256 or of 128: the kernel walks

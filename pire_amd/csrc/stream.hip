@@ -213,9 +213,8 @@ __device__ __forceinline__ bool StreamPhase(const ScanParams& p, uint8_t* lds, c
 	// (the sum modulo 2^32 FIRST: in a sub-task's first phase wpos is -128 mod 2^32 for the lanes whose first line is line 0)
 	IssueTileGroup(nxt, S.dataEnd > S.wpos + 128u ? lineBase + uint64_t(uint32_t(S.wpos + 128u)) : reinterpret_cast<uint64_t>(p.hotRows), lane);
 	// at most the 8 loads just issued may still be out: loads return in order, whatever else is in the queue only makes
-	// the wait stricter (tiled.hip)
-	asm volatile("s_waitcnt vmcnt(8)"
-	             : "+v"(cur[0]), "+v"(cur[1]), "+v"(cur[2]), "+v"(cur[3]), "+v"(cur[4]), "+v"(cur[5]), "+v"(cur[6]), "+v"(cur[7]));
+	// the wait stricter (device_common.h, the ring of two register tiles)
+	WaitTile<1>(cur);
 	TransposeTile(cur, lane);
 	if (lane == (iter & 63) && S.live) {   // visit sample, as in the tiled kernel
 		if constexpr (WIDE != 0)

@@ -11,64 +11,7 @@ namespace pirehip {
 // No LDS staging: all of the LDS is left for the table (profiles/micro_loadpath_r01.log: the register path streams
 // as fast as a fully coalesced read).
 
-// ---- tile loads -------------------------------------------------------------------------------------------
-// A tile is 128 bytes (one cache line) of each of the wave's 64 strings.  It is fetched with 8 x
-// global_load_dwordx4 in which EIGHT ADJACENT LANES COVER ONE WHOLE LINE: instruction j, lane l reads
-//     chunk (l & 7) of string  s0 + (l & ~7) + j        (16 bytes)
-// so every instruction touches 8 full lines instead of 64 partial ones.  Measured on MI355X
-// (profiles/r01_pmc_summary_strided_16w_nbuf3.txt): with one-line-per-lane loads the L1 (TCP) tag pipeline was the
-// binding unit -- TA busy 75 %, TA stalled by TC 56 %, 0.63 lane-accesses/clk/CU -- and `nt` could not be used
-// because each line was touched by 8 separate instructions.  With whole-line instructions the same bytes cost
-// 1/8 of the L1 accesses and stream with `nt`.
-// After the loads, lane 8g+k holds in register j chunk k of string 8g+j; an 8x8 transpose across each group of 8
-// lanes (TransposeTile, DPP only, no LDS) leaves lane 8g+j with chunks 0..7 of its own string in registers 0..7.
-//
-// The loads are issued from inline asm and waited for with hand-counted s_waitcnt vmcnt(N).  Reason (measured,
-// DESIGN.md section 6): hipcc's own wait insertion turns every loop-carried prefetch into `s_waitcnt vmcnt(0)` at
-// the tile boundary, which collapses an N-deep register pipeline to depth 1.  Counting is safe with foreign VMEM
-// ops in the queue: loads return in order among themselves, so "at most 8*k outstanding" implies every load issued
-// before the last k tiles has landed; extra compiler-issued ops only make the wait stricter.
-// "+v": the tile registers are updated IN PLACE, so the compiler has no reason to copy a slot that is in flight.
-template <bool NT>
-__device__ __forceinline__ void IssueTile(u32x4 (&r)[8], uint32_t voff, uint64_t tileBase, uint64_t stride)
-{
-	const uint64_t b0 = tileBase, b1 = b0 + stride, b2 = b1 + stride, b3 = b2 + stride, b4 = b3 + stride,
-	               b5 = b4 + stride, b6 = b5 + stride, b7 = b6 + stride;
-	if (NT)
-		asm volatile(
-			"global_load_dwordx4 %0, %8, %9 nt\n\t"
-			"global_load_dwordx4 %1, %8, %10 nt\n\t"
-			"global_load_dwordx4 %2, %8, %11 nt\n\t"
-			"global_load_dwordx4 %3, %8, %12 nt\n\t"
-			"global_load_dwordx4 %4, %8, %13 nt\n\t"
-			"global_load_dwordx4 %5, %8, %14 nt\n\t"
-			"global_load_dwordx4 %6, %8, %15 nt\n\t"
-			"global_load_dwordx4 %7, %8, %16 nt"
-			: "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7])
-			: "v"(voff), "s"(b0), "s"(b1), "s"(b2), "s"(b3), "s"(b4), "s"(b5), "s"(b6), "s"(b7));
-	else
-		asm volatile(
-			"global_load_dwordx4 %0, %8, %9\n\t"
-			"global_load_dwordx4 %1, %8, %10\n\t"
-			"global_load_dwordx4 %2, %8, %11\n\t"
-			"global_load_dwordx4 %3, %8, %12\n\t"
-			"global_load_dwordx4 %4, %8, %13\n\t"
-			"global_load_dwordx4 %5, %8, %14\n\t"
-			"global_load_dwordx4 %6, %8, %15\n\t"
-			"global_load_dwordx4 %7, %8, %16"
-			: "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7])
-			: "v"(voff), "s"(b0), "s"(b1), "s"(b2), "s"(b3), "s"(b4), "s"(b5), "s"(b6), "s"(b7));
-}
-
-// Wait until at most TILES_BEHIND tiles issued after `r` are still in flight; names r so nothing reads it earlier.
-template <int TILES_BEHIND>
-__device__ __forceinline__ void WaitTile(u32x4 (&r)[8])
-{
-	asm volatile("s_waitcnt vmcnt(%8)"
-	             : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7])
-	             : "n"(TILES_BEHIND * 8));
-}
-
+// (IssueTile / WaitTile / KeepInStep, the ring's pieces: device_common.h, shared with the pair and the wide kernels.)
 // (Butterfly4 / ButterflyQuad4 / TransposeTile: device_common.h, shared with the ragged kernel.)
 
 // The hot rows sit at LDS byte address 0 (the kernels declare no static __shared__, so the dynamic region
@@ -93,39 +36,23 @@ __device__ __forceinline__ bool AllAbsorbing(const ScanParams& p, const uint8_t*
 }
 
 
-// EQ: keep the waves of a block in step.  Every tile a wave adds 1 to a block-wide progress counter (LDS) and compares
-// 16 x its own tile count with the sum: a wave ahead of the block's average by more than a quarter tile drops its issue
-// priority, one behind raises it.  Without it the 16 waves of a block, which all do exactly the same amount of work,
-// finish up to 30 us apart (profiles/r02_tiled_block_stamps.log: age-ordered arbitration lets some waves run ahead all
-// the way) and the CU idles half empty at the end of a launch; with it 10 us.  Worth 1.3 % on the 2^20 x 4 KiB headline
-// (9 of 9 alternating pairs), 4.8 % with the single-pattern table, nothing from 8 tasks per wave up, -0.7 % on C++ text
-// (profiles/r02_tiled_equalise.log).
-template <int NBUF, bool NT, int ROT, bool EQ = false>
+// One phase of the ring: request the tile behind the one in `cur` into the slot walked one phase ago, wait for `cur`,
+// transpose it, walk it.  EQ: the waves of a block kept in step (device_common.h KeepInStep).  LOW: the segment kernel's
+// loads (IssueTile), which the debug knobs of a -DPIRE_HIP_TUNING build then reach too: harmless.
+template <int NBUF, bool NT, int ROT, bool EQ = false, bool LOW = false>
 __device__ __forceinline__ void Phase(const ScanParams& p, const uint8_t* lds, const LdsLayout& L, uint64_t rowBase,
                                       uint64_t chainBase, uint32_t voff, uint64_t istride, uint32_t lane, uint32_t t,
                                       uint32_t lastTile, u32x4 (&cur)[8], u32x4 (&refill)[8], uint32_t& hs, uint32_t& cold,
-                                      uint32_t* prog = nullptr, uint32_t* myTiles = nullptr)
+                                      uint32_t* prog = nullptr, uint32_t* myTiles = nullptr, uint64_t low = 0)
 {
-	if (EQ) {
-		uint32_t sum = 0;
-		if (lane == 0)
-			sum = atomicAdd(prog, 1u) + 1;
-		sum = uint32_t(__builtin_amdgcn_readfirstlane(int(sum)));
-		const uint32_t mine = ++*myTiles;
-		constexpr uint32_t margin = 4;   // in sixteenths of a tile (0 / 4 / 8: equal; 16, 32: less effect)
-		if (mine * (blockDim.x >> 6) > sum + margin)
-			__builtin_amdgcn_s_setprio(0);
-		else if (mine * (blockDim.x >> 6) + margin < sum)
-			__builtin_amdgcn_s_setprio(3);
-		else
-			__builtin_amdgcn_s_setprio(1);
-	}
+	if (EQ)
+		KeepInStep<1>(prog, *myTiles, lane, blockDim.x >> 6);
 	// Refill target: the next tile of this task, or -- on the task's last tile -- tile 0 of the wave's NEXT task
 	// (chainBase; equals this task's last tile when there is nothing to chain to), so that neither the HBM
 	// latency of a task's first tile nor a duplicate load of its last tile is ever paid.
 	const uint64_t ahead = t < lastTile ? rowBase + uint64_t(t + 1) * 128 : chainBase;
 	if (!(p.flags & kDebugNoRefill))   // measurement knob only (PIRE_HIP_DEBUG_NOLOAD): walk stale registers
-		IssueTile<NT>(refill, voff, ahead, istride);
+		IssueTile<NT, LOW>(refill, voff, ahead, istride, low);
 	WaitTile<NBUF - 1>(cur);
 	if (!(p.flags & kDebugNoTranspose))
 		TransposeTile(cur, lane);
@@ -149,20 +76,8 @@ __device__ __forceinline__ void PhaseShadow(const ScanParams& p, const uint8_t* 
                                             uint32_t lastTile, u32x4 (&cur)[8], u32x4 (&next)[8], uint32_t& hs, uint32_t& cold,
                                             uint32_t* prog, uint32_t* myTiles)
 {
-	if (EQ) {
-		uint32_t sum = 0;
-		if (lane == 0)
-			sum = atomicAdd(prog, 1u) + 1;
-		sum = uint32_t(__builtin_amdgcn_readfirstlane(int(sum)));
-		const uint32_t mine = ++*myTiles;
-		constexpr uint32_t margin = 4;   // in sixteenths of a tile
-		if (mine * (blockDim.x >> 6) > sum + margin)
-			__builtin_amdgcn_s_setprio(0);
-		else if (mine * (blockDim.x >> 6) + margin < sum)
-			__builtin_amdgcn_s_setprio(3);
-		else
-			__builtin_amdgcn_s_setprio(1);
-	}
+	if (EQ)
+		KeepInStep<1>(prog, *myTiles, lane, blockDim.x >> 6);
 	const uint64_t ahead = t < lastTile ? rowBase + uint64_t(t + 1) * 128 : chainBase;
 	IssueTile<NT>(next, voff, ahead, istride);
 	if (lane == (t & 63))   // visit sample: one lane per wave per tile, rotating
@@ -314,64 +229,13 @@ __global__ __launch_bounds__(WAVES * 64, MINW) void ScanTiledKernel(ScanParams p
 // start state, and the one record whose warm-up would lie in front of the text reads its own bytes for those tiles.
 // One launch instead of a ragged warm-up batch plus the tiled pass: what a table with ONE mode -- e.g. the reference's
 // benchmark corpus as one string -- still paid in round 3's first version of the fused scan.
-// A kernel of its own (a trimmed copy of ScanTiledKernel's loop: shipped variant only, even tile counts only) so that
-// the headline kernel's code is what it was.
+// A kernel of its own: ScanTiledKernel's loop for the shipped variant and even tile counts only, with the warm-up in it.
 struct TiledSegParams {
 	ScanParams p;
 	uint32_t warmTiles;
 	const uint32_t* segJ;
 	uint32_t* guess;
 };
-
-__device__ __forceinline__ void IssueTileLow(u32x4 (&r)[8], uint32_t voff, uint64_t tileBase, uint64_t stride, uint64_t low)
-{
-	// only the warm-up tiles of the very first record (the first load's lanes 0..7) lie below `low`, the first byte of
-	// the text: those lanes read from the record itself instead, and what they read is never used
-	uint32_t voff0 = voff;
-	if (tileBase < low)
-		voff0 += (threadIdx.x & 63) < 8 ? uint32_t(low - tileBase + 127) & ~127u : 0u;
-	const uint64_t b0 = tileBase, b1 = b0 + stride, b2 = b1 + stride, b3 = b2 + stride, b4 = b3 + stride,
-	               b5 = b4 + stride, b6 = b5 + stride, b7 = b6 + stride;
-	asm volatile(
-		"global_load_dwordx4 %0, %17, %9 nt\n\t"
-		"global_load_dwordx4 %1, %8, %10 nt\n\t"
-		"global_load_dwordx4 %2, %8, %11 nt\n\t"
-		"global_load_dwordx4 %3, %8, %12 nt\n\t"
-		"global_load_dwordx4 %4, %8, %13 nt\n\t"
-		"global_load_dwordx4 %5, %8, %14 nt\n\t"
-		"global_load_dwordx4 %6, %8, %15 nt\n\t"
-		"global_load_dwordx4 %7, %8, %16 nt"
-		: "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7])
-		: "v"(voff), "s"(b0), "s"(b1), "s"(b2), "s"(b3), "s"(b4), "s"(b5), "s"(b6), "s"(b7), "v"(voff0));
-}
-
-__device__ __forceinline__ void PhaseSeg(const ScanParams& p, const uint8_t* lds, const LdsLayout& L, uint64_t rowBase,
-                                         uint64_t chainBase, uint32_t voff, uint64_t istride, uint64_t low, uint32_t lane,
-                                         uint32_t t, uint32_t lastTile, u32x4 (&cur)[8], u32x4 (&refill)[8], uint32_t& hs,
-                                         uint32_t& cold, uint32_t* prog, uint32_t& myTiles)
-{
-	{   // the waves of a block kept in step (EQ, above)
-		uint32_t sum = 0;
-		if (lane == 0)
-			sum = atomicAdd(prog, 1u) + 1;
-		sum = uint32_t(__builtin_amdgcn_readfirstlane(int(sum)));
-		const uint32_t mine = ++myTiles;
-		constexpr uint32_t margin = 4;
-		if (mine * (blockDim.x >> 6) > sum + margin)
-			__builtin_amdgcn_s_setprio(0);
-		else if (mine * (blockDim.x >> 6) + margin < sum)
-			__builtin_amdgcn_s_setprio(3);
-		else
-			__builtin_amdgcn_s_setprio(1);
-	}
-	const uint64_t ahead = t < lastTile ? rowBase + uint64_t(t + 1) * 128 : chainBase;
-	IssueTileLow(refill, voff, ahead, istride, low);
-	WaitTile<1>(cur);
-	TransposeTile(cur, lane);
-	if (lane == (t & 63))   // visit sample: one lane per wave per tile, rotating
-		atomicAdd(reinterpret_cast<uint32_t*>(const_cast<uint8_t*>(lds) + L.histOff) + hs, 1u);
-	StepTile<0>(p, lds, L, cur, hs, cold, t);
-}
 
 __global__ __launch_bounds__(1024, 4) void ScanTiledSegKernel(TiledSegParams q)
 {
@@ -398,7 +262,7 @@ __global__ __launch_bounds__(1024, 4) void ScanTiledSegKernel(TiledSegParams q)
 	const uint64_t firstTask = uint64_t(blockIdx.x) * wavesPerBlock + wave;
 	bool primed = firstTask < ntasks;
 	if (primed)
-		IssueTileLow(a, voff, Uniform64(text + firstTask * 64 * p.stride), istride, low);
+		IssueTile<true, true>(a, voff, Uniform64(text + firstTask * 64 * p.stride), istride, low);
 	LoadTableToLds(p, lds, L);
 	for (uint64_t task = firstTask; task < ntasks; task += taskStep) {
 		const uint64_t s0 = task * 64;
@@ -410,7 +274,7 @@ __global__ __launch_bounds__(1024, 4) void ScanTiledSegKernel(TiledSegParams q)
 		uint32_t hs = cold < p.hot ? cold : p.hot;
 		bool done = false;
 		if (!primed)
-			IssueTileLow(a, voff, rowBase, istride, low);
+			IssueTile<true, true>(a, voff, rowBase, istride, low);
 		for (uint32_t t = 0; t < ntiles && !done; t += 2) {
 			if (t == warm) {   // the segment's first byte: this state is the guess
 				uint32_t st = hs != p.hot ? hs : cold;
@@ -420,8 +284,8 @@ __global__ __launch_bounds__(1024, 4) void ScanTiledSegKernel(TiledSegParams q)
 				cold = st;
 				hs = st < p.hot ? st : p.hot;
 			}
-			PhaseSeg(p, lds, L, rowBase, chainBase, voff, istride, low, lane, t, lastTile, a, b, hs, cold, prog, myTiles);
-			PhaseSeg(p, lds, L, rowBase, chainBase, voff, istride, low, lane, t + 1, lastTile, b, a, hs, cold, prog, myTiles);
+			Phase<2, true, 0, true, /*LOW*/ true>(p, lds, L, rowBase, chainBase, voff, istride, lane, t, lastTile, a, b, hs, cold, prog, &myTiles, low);
+			Phase<2, true, 0, true, /*LOW*/ true>(p, lds, L, rowBase, chainBase, voff, istride, lane, t + 1, lastTile, b, a, hs, cold, prog, &myTiles, low);
 			done = t >= warm && AllAbsorbing(p, lds, L, hs);
 		}
 		primed = hasNext && !done;   // an early-out leaves some other tile in slot a: re-prime then
@@ -583,16 +447,7 @@ int LaunchTiled(const ScanParams& p, hipStream_t stream)
 #endif
 	if (rc != PIRE_HIP_OK || q.n == p.n)
 		return rc;
-	ScanParams tail = p;
-	tail.n = p.n - q.n;
-	tail.text = p.text + q.n * p.stride;
-	if (p.initIdx)
-		tail.initIdx = p.initIdx + q.n;
-	if (p.outIdx)
-		tail.outIdx = p.outIdx + q.n;
-	if (p.outFinal)
-		tail.outFinal = p.outFinal + q.n;
-	return LaunchGeneric(tail, stream);
+	return LaunchRemainder(p, q.n, stream);
 }
 
 

@@ -13,40 +13,13 @@
 // WideLayout: 1 700 states at 44 letters, 2 040 at 34).  Targets without a row lead to an absorbing escape row (id ==
 // wide); a lane found there after a chunk is re-walked from the chunk's first byte, one load per byte -- its row in LDS
 // while its state has one, the exact table in memory (u16 entries when the ids fit: half the cache footprint) while it
-// has none.  Bit-exact for any table and any ranking, like every kernel of the path.  Text path, task numbering, wave
-// levelling: tiled.hip's.
+// has none.  Bit-exact for any table and any ranking, like every kernel of the path.  Text path and wave levelling: the
+// tiled kernel's (device_common.h, the ring of two register tiles); task numbering: tiled.hip's kSpreadTasks form.
 
 #include "device_common.h"
 #include "wide_common.h"
 
 namespace pirehip {
-
-// Whole-line loads of one 128-byte tile of 64 strings (tiled.hip IssueTile; a copy of its own, like pair.hip's, so that
-// the headline kernel's translation unit stays what it was measured as)
-__device__ __forceinline__ void WideIssueTile(u32x4 (&r)[8], uint32_t voff, uint64_t tileBase, uint64_t stride)
-{
-	const uint64_t b0 = tileBase, b1 = b0 + stride, b2 = b1 + stride, b3 = b2 + stride, b4 = b3 + stride,
-	               b5 = b4 + stride, b6 = b5 + stride, b7 = b6 + stride;
-	asm volatile(
-		"global_load_dwordx4 %0, %8, %9 nt\n\t"
-		"global_load_dwordx4 %1, %8, %10 nt\n\t"
-		"global_load_dwordx4 %2, %8, %11 nt\n\t"
-		"global_load_dwordx4 %3, %8, %12 nt\n\t"
-		"global_load_dwordx4 %4, %8, %13 nt\n\t"
-		"global_load_dwordx4 %5, %8, %14 nt\n\t"
-		"global_load_dwordx4 %6, %8, %15 nt\n\t"
-		"global_load_dwordx4 %7, %8, %16 nt"
-		: "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7])
-		: "v"(voff), "s"(b0), "s"(b1), "s"(b2), "s"(b3), "s"(b4), "s"(b5), "s"(b6), "s"(b7));
-}
-
-template <int TILES_BEHIND>
-__device__ __forceinline__ void WideWaitTile(u32x4 (&r)[8])
-{
-	asm volatile("s_waitcnt vmcnt(%8)"
-	             : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7])
-	             : "n"(TILES_BEHIND * 8));
-}
 
 template <bool N16, bool ZIP>
 __device__ __forceinline__ void WidePhase(const ScanParams& p, uint8_t* lds, const WideLayout& W, const WideConst& K, uint64_t rowBase,
@@ -54,23 +27,10 @@ __device__ __forceinline__ void WidePhase(const ScanParams& p, uint8_t* lds, con
                                           uint32_t lastTile, u32x4 (&cur)[8], u32x4 (&refill)[8], uint32_t& st, uint32_t& cold,
                                           uint32_t* prog, uint32_t& myTiles)
 {
-	{   // the waves of a block kept in step (tiled.hip, EQ)
-		uint32_t sum = 0;
-		if (lane == 0)
-			sum = atomicAdd(prog, 1u) + 1;
-		sum = uint32_t(__builtin_amdgcn_readfirstlane(int(sum)));
-		const uint32_t mine = ++myTiles;
-		constexpr uint32_t margin = 4;
-		if (mine * (blockDim.x >> 6) > sum + margin)
-			__builtin_amdgcn_s_setprio(0);
-		else if (mine * (blockDim.x >> 6) + margin < sum)
-			__builtin_amdgcn_s_setprio(3);
-		else
-			__builtin_amdgcn_s_setprio(1);
-	}
+	KeepInStep<1>(prog, myTiles, lane, blockDim.x >> 6);
 	const uint64_t ahead = t < lastTile ? rowBase + uint64_t(t + 1) * 128 : chainBase;
-	WideIssueTile(refill, voff, ahead, istride);
-	WideWaitTile<1>(cur);
+	IssueTile(refill, voff, ahead, istride);
+	WaitTile<1>(cur);
 	TransposeTile(cur, lane);
 #pragma unroll
 	for (int k = 0; k < 8; ++k)
@@ -115,7 +75,7 @@ __global__ __launch_bounds__(1024, 4) void ScanWideKernel(ScanParams p)
 	const uint64_t firstTask = uint64_t(wave) * gridDim.x + blockIdx.x;
 	bool primed = firstTask < ntasks;
 	if (primed)   // the first tile is on its way while the table is copied
-		WideIssueTile(a, voff, Uniform64(reinterpret_cast<uint64_t>(p.text) + firstTask * 64 * p.stride), istride);
+		IssueTile(a, voff, Uniform64(reinterpret_cast<uint64_t>(p.text) + firstTask * 64 * p.stride), istride);
 	LoadWideToLds(p, lds, W);
 	for (uint64_t task = firstTask; task < ntasks; task += taskStep) {
 		const uint64_t s0 = task * 64;
@@ -128,7 +88,7 @@ __global__ __launch_bounds__(1024, 4) void ScanWideKernel(ScanParams p)
 		uint32_t st = cold < p.wide ? cold : p.wide;   // the walk's state: a device id with a row, or `wide` = the escape row
 		bool done = false;
 		if (!primed)
-			WideIssueTile(a, voff, rowBase, istride);
+			IssueTile(a, voff, rowBase, istride);
 		for (uint32_t t = 0; t < paired && !done; t += 2) {
 			WidePhase<N16, ZIP>(p, lds, W, K, rowBase, chainBase, voff, istride, lane, t, lastTile, a, b, st, cold, prog, myTiles);
 			WidePhase<N16, ZIP>(p, lds, W, K, rowBase, chainBase, voff, istride, lane, t + 1, lastTile, b, a, st, cold, prog, myTiles);
@@ -141,18 +101,18 @@ __global__ __launch_bounds__(1024, 4) void ScanWideKernel(ScanParams p)
 			// absorbing state: 557 of 2^20 strings wrong; tests/test_wide.py test_early_out_between_chained_tasks).
 #if !defined(PIRE_EXP) || PIRE_EXP != 2
 			if (done)
-				WideWaitTile<0>(a);
+				WaitTile<0>(a);
 #endif
 		}
 		primed = hasNext && !done;   // an early-out left some other tile in slot a: re-prime then
 #if defined(PIRE_EXP) && PIRE_EXP == 2   // (round 5's form, kept for the regression test's own test: make exp N=2)
 		if (done)
-			WideWaitTile<0>(a);
+			WaitTile<0>(a);
 #endif
 		if (!done && !chain) {
 			// the odd last tile (ntiles >= 3 here): requested into slot a by the last phase of the loop, walked with nothing
 			// on its way behind it
-			WideWaitTile<0>(a);
+			WaitTile<0>(a);
 			TransposeTile(a, lane);
 #pragma unroll
 			for (int k = 0; k < 8; ++k)
@@ -166,8 +126,8 @@ __global__ __launch_bounds__(1024, 4) void ScanWideKernel(ScanParams p)
 		}
 		Finish(p, lds, L, s, true, end);
 	}
-	WideWaitTile<0>(a);
-	WideWaitTile<0>(b);
+	WaitTile<0>(a);
+	WaitTile<0>(b);
 	// (for the build's audit, which follows every way out of the task loop until all loads are waited for: nothing is on its way
 	// here -- the loops above wait for what they request before they are left -- and this says so where the walker can see it)
 	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -196,8 +156,8 @@ __global__ __launch_bounds__(1024, 4) void ScanWide2Kernel(ScanParams p)
 	ZeroTile(a);
 	ZeroTile(b);
 	uint32_t* prog = reinterpret_cast<uint32_t*>(lds + W.progOff);
-	uint32_t myTiles = 0;
 	uint32_t direct = 0;   // wave-uniform: the last chunk left the rows, the next ones skip the attempt on the rows alone (WideChunk2)
+	uint32_t myTiles = 0;
 	// tasks go round the blocks before they go round a block's waves: a batch with fewer tasks than wave slots then puts a few
 	// waves on every CU instead of sixteen on some (2^18 strings, two per lane: 2.1 TB/s on half the CUs)
 	const uint64_t taskStep = uint64_t(gridDim.x) * 16;
@@ -211,24 +171,11 @@ __global__ __launch_bounds__(1024, 4) void ScanWide2Kernel(ScanParams p)
 		uint32_t sa = colda < p.wide ? colda : p.wide, sb = coldb < p.wide ? coldb : p.wide;
 		bool done = false;
 		for (uint32_t t = 0; t < ntiles && !done; ++t) {
-			{   // the waves of a block kept in step (tiled.hip, EQ)
-				uint32_t sum = 0;
-				if (lane == 0)
-					sum = atomicAdd(prog, 1u) + 1;
-				sum = uint32_t(__builtin_amdgcn_readfirstlane(int(sum)));
-				const uint32_t mine = ++myTiles;
-				constexpr uint32_t margin = 4;
-				if (mine * (blockDim.x >> 6) > sum + margin)
-					__builtin_amdgcn_s_setprio(0);
-				else if (mine * (blockDim.x >> 6) + margin < sum)
-					__builtin_amdgcn_s_setprio(3);
-				else
-					__builtin_amdgcn_s_setprio(1);
-			}
-			WideIssueTile(a, voff, baseA + uint64_t(t) * 128, istride);
-			WideIssueTile(b, voff, baseB + uint64_t(t) * 128, istride);
-			WideWaitTile<0>(a);
-			WideWaitTile<0>(b);
+			KeepInStep<1>(prog, myTiles, lane, blockDim.x >> 6);
+			IssueTile(a, voff, baseA + uint64_t(t) * 128, istride);
+			IssueTile(b, voff, baseB + uint64_t(t) * 128, istride);
+			WaitTile<0>(a);
+			WaitTile<0>(b);
 			TransposeTile(a, lane);
 			TransposeTile(b, lane);
 			// (written out: with the zipped step's larger body hipcc left the loop rolled and both tiles in scratch)
@@ -327,16 +274,7 @@ int LaunchWide(const ScanParams& p, hipStream_t stream)
 	}
 	if (rc != PIRE_HIP_OK || q.n == p.n)
 		return rc;
-	ScanParams tail = p;
-	tail.n = p.n - q.n;
-	tail.text = p.text + q.n * p.stride;
-	if (p.initIdx)
-		tail.initIdx = p.initIdx + q.n;
-	if (p.outIdx)
-		tail.outIdx = p.outIdx + q.n;
-	if (p.outFinal)
-		tail.outFinal = p.outFinal + q.n;
-	return LaunchGeneric(tail, stream);
+	return LaunchRemainder(p, q.n, stream);
 }
 
 }  // namespace pirehip
