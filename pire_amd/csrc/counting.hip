@@ -699,10 +699,7 @@ __global__ __launch_bounds__(RMAX > 8 ? 512 : 1024) void CountingKernel(Counting
 #pragma unroll 1
 			for (int i = 0; i < 16; ++i) {
 				step(v.x & 0xFF);
-				v.x = __builtin_amdgcn_alignbit(v.y, v.x, 8);
-				v.y = __builtin_amdgcn_alignbit(v.z, v.y, 8);
-				v.z = __builtin_amdgcn_alignbit(v.w, v.z, 8);
-				v.w >>= 8;
+				NextByte(v);
 			}
 		}
 		for (; ptr < end; ++ptr)
@@ -836,10 +833,7 @@ __global__ __launch_bounds__(256) void CaptureKernel(CountingParams p)
 #pragma unroll 1
 			for (int i = 0; i < 16; ++i) {
 				step(v.x & 0xFF);
-				v.x = __builtin_amdgcn_alignbit(v.y, v.x, 8);
-				v.y = __builtin_amdgcn_alignbit(v.z, v.y, 8);
-				v.z = __builtin_amdgcn_alignbit(v.w, v.z, 8);
-				v.w >>= 8;
+				NextByte(v);
 			}
 		}
 		for (; ptr < stop; ++ptr)

@@ -31,6 +31,7 @@
 #include <cstring>
 
 #include "internal.h"
+#include "walk.h"   // NextByte, ForBytes
 
 namespace pirehip {
 
@@ -185,22 +186,13 @@ __device__ __forceinline__ uint32_t DenseChunk(const uint8_t* lds, const LdsLayo
 __device__ __forceinline__ uint32_t DenseBytes(const uint8_t* lds, const LdsLayout& L, u32x4 v, uint32_t skip, uint32_t count,
                                                uint32_t& st)
 {
-	for (uint32_t i = 0; i < skip; ++i) {
-		v.x = __builtin_amdgcn_alignbit(v.y, v.x, 8);
-		v.y = __builtin_amdgcn_alignbit(v.z, v.y, 8);
-		v.z = __builtin_amdgcn_alignbit(v.w, v.z, 8);
-		v.w >>= 8;
-	}
+	for (uint32_t i = 0; i < skip; ++i)
+		NextByte(v);
 	uint32_t mx = 0;
-#pragma unroll 1
-	for (uint32_t i = 0; i < count; ++i) {
-		st = lds[st * L.pitch + (v.x & 0xFFu)];
+	ForBytes<Trips::PerLane>(v, count, [&](uint32_t byte, uint32_t) __attribute__((always_inline)) {
+		st = lds[st * L.pitch + byte];
 		mx = mx > st ? mx : st;
-		v.x = __builtin_amdgcn_alignbit(v.y, v.x, 8);
-		v.y = __builtin_amdgcn_alignbit(v.z, v.y, 8);
-		v.z = __builtin_amdgcn_alignbit(v.w, v.z, 8);
-		v.w >>= 8;
-	}
+	});
 	return mx;
 }
 
@@ -344,53 +336,64 @@ __device__ __forceinline__ uint32_t CompactChunk(const ScanParams& p, const LdsL
 	return LdsU16((row << 2) + p.letters * 2);
 }
 
-// Same for the first `count` (1..15) bytes of v, rolled.
+// Same for the first `count` (1..15) bytes of v, rolled.  (Not CompactChunk with a count: that one takes a dword per trip
+// with its four class lookups hoisted, this one a byte per trip -- measured, and kept as two loops.)
 __device__ __forceinline__ uint32_t CompactPartial(const ScanParams& p, const LdsLayout& L, u32x4 v, uint32_t st,
                                                    uint32_t count)
 {
 	const uint32_t pitch = CompactPitch(p.letters);
 	uint32_t row = (L.compactOff >> 2) + st * (pitch >> 2);
 	const uint32_t clsBase = L.cls8Off;
-#pragma unroll 1
-	for (uint32_t i = 0; __any(i < count); ++i) {
-		const uint32_t c = HotLookup(__builtin_amdgcn_perm(clsBase, v.x, 0x0c060500u));
+	ForBytes<Trips::Levelled>(v, count, [&](uint32_t byte, uint32_t i) __attribute__((always_inline)) {
+		const uint32_t c = HotLookup(clsBase | byte);
 		const uint32_t nr = LdsU16((row << 2) + c);
 		row = i < count ? nr : row;
-		v.x = __builtin_amdgcn_alignbit(v.y, v.x, 8);
-		v.y = __builtin_amdgcn_alignbit(v.z, v.y, 8);
-		v.z = __builtin_amdgcn_alignbit(v.w, v.z, 8);
-		v.w >>= 8;
-	}
+	});
 	return LdsU16((row << 2) + p.letters * 2);
 }
 
-// Exact re-walk of one 16-byte chunk for the lanes that trapped.  Deliberately a rolled loop (the chunk is shifted
-// through as a 128-bit value): this is the cold path, and keeping it small keeps the hot loop dense in the I-cache.
-__device__ __forceinline__ uint32_t SlowChunk(const ScanParams& p, const uint8_t* lds, const LdsLayout& L, u32x4 v,
-                                           uint32_t st)
+// Exact re-walk of the leading bytes of the chunk `v` through SlowStep: the one loop behind every such walk of the dense
+// rows' kernels.  Trips::Sixteen -- the whole chunk, for the lanes that trapped; Levelled -- the first `count` (0..15) bytes
+// of a string's last chunk, lanes with a smaller count idle; PerLane -- a sample lane on its way to its drawn byte.
+// Deliberately a rolled loop (ForBytes: the chunk is shifted through as a 128-bit value): this is the cold path, and
+// keeping it small keeps the hot loop dense in the I-cache.
+template <Trips T>
+__device__ __forceinline__ uint32_t SlowBytes(const ScanParams& p, const uint8_t* lds, const LdsLayout& L, const u32x4 v,
+                                              uint32_t st, uint32_t count = 16u)
 {
-#pragma unroll 1
-	for (int i = 0; i < 16; ++i) {
-		st = SlowStep(p, lds, L, st, v.x & 0xFF);
-		v.x = __builtin_amdgcn_alignbit(v.y, v.x, 8);
-		v.y = __builtin_amdgcn_alignbit(v.z, v.y, 8);
-		v.z = __builtin_amdgcn_alignbit(v.w, v.z, 8);
-		v.w >>= 8;
-	}
+	ForBytes<T>(v, count, [&](uint32_t byte, uint32_t i) __attribute__((always_inline)) {
+		if (T != Trips::Levelled || i < count)
+			st = SlowStep(p, lds, L, st, byte);
+	});
 	return st;
 }
 
-// A lane left the dense rows somewhere in the chunk `v` (hs == p.hot after it): exact re-walk from the chunk's start
-// state, through the compact rows in LDS when the state has one, through the full table in HBM when that escapes too.
-__device__ __forceinline__ void TrapChunk(const ScanParams& p, const uint8_t* lds, const LdsLayout& L, const u32x4 v,
-                                          uint32_t hs0, uint32_t& hs, uint32_t& cold, uint32_t sampleLane)
+// The state after the chunk `v` (PARTIAL: after its first `count`, 1..15, bytes) from state st0, exactly: through the
+// compact rows in LDS when the state has one, through the full table in HBM when that escapes too.
+template <bool PARTIAL>
+__device__ __forceinline__ uint32_t ExactChunk(const ScanParams& p, const uint8_t* lds, const LdsLayout& L, const u32x4 v,
+                                               uint32_t st0, uint32_t count)
 {
-	const uint32_t st0 = hs0 != p.hot ? hs0 : cold;
 	uint32_t f = p.compact;
 	if (st0 < p.compact)
-		f = CompactChunk(p, L, v, st0);
+		f = PARTIAL ? CompactPartial(p, L, v, st0, count) : CompactChunk(p, L, v, st0);
 	if (f == p.compact)
-		f = SlowChunk(p, lds, L, v, st0);
+		f = SlowBytes<PARTIAL ? Trips::Levelled : Trips::Sixteen>(p, lds, L, v, st0, count);
+	return f;
+}
+
+// A lane left the dense rows somewhere in the chunk `v` (hs == p.hot after it): exact re-walk from the chunk's start
+// state.
+// PARTIAL: the chunk is a string's last, only its first `count` (1..15) bytes are walked (the ragged kernel's StepPartial).
+// The two forms differ in their samples, and in nothing else: the whole chunk draws its step as hash >> 28 and counts a
+// chunk that ENDS outside the rows in the trap-signal slot (kLdsTrapSlot); the partial one draws hash >> 28 modulo count
+// and never touches that slot.  (Both as they were while the two were separate copies; kept, not chosen.)
+template <bool PARTIAL = false>
+__device__ __forceinline__ void TrapChunk(const ScanParams& p, const uint8_t* lds, const LdsLayout& L, const u32x4 v,
+                                          uint32_t hs0, uint32_t& hs, uint32_t& cold, uint32_t sampleLane, uint32_t count = 16u)
+{
+	const uint32_t st0 = hs0 != p.hot ? hs0 : cold;
+	const uint32_t f = ExactChunk<PARTIAL>(p, lds, L, v, st0, count);
 	if (f < p.hot) {
 		hs = f;
 	} else {
@@ -403,23 +406,16 @@ __device__ __forceinline__ void TrapChunk(const ScanParams& p, const uint8_t* ld
 	// drawn from the chunk's place and the block's number, walked to exactly -- if it has no dense row.  (Rounds 1-5 told the
 	// state the chunk ENDS in, if that has none: a state the walk passes through on its way back into the rows was never
 	// seen, nor one that lives at a fixed offset of every record -- 4.0 % of the lookups of URL records outside the 255 rows
-	// where 0.5 % need be, tools/ranking_quality_records.py.)  The trap signal counts chunks that end outside the rows, as before.
+	// where 0.5 % need be, tools/ranking_quality_records.py; and of a partial chunk that is the state the STRING ends in, which
+	// nothing looks up: rounds 2-5 gave rows to those.)  The trap signal counts chunks that end outside the rows, as before.
 	if ((threadIdx.x & 63) == sampleLane && !(p.flags & kDebugNoColdCount)) {
-		const uint32_t step = ((sampleLane + blockIdx.x * 0x632BE5ABu) * 0x9E3779B1u) >> 28;
-		uint32_t s = st0;
-		u32x4 w = v;
-#pragma unroll 1
-		for (uint32_t i = 0; i < step; ++i) {
-			s = SlowStep(p, lds, L, s, w.x & 0xFF);
-			w.x = __builtin_amdgcn_alignbit(w.y, w.x, 8);
-			w.y = __builtin_amdgcn_alignbit(w.z, w.y, 8);
-			w.z = __builtin_amdgcn_alignbit(w.w, w.z, 8);
-			w.w >>= 8;
-		}
+		const uint32_t draw = ((sampleLane + blockIdx.x * 0x632BE5ABu) * 0x9E3779B1u) >> 28;
+		const uint32_t s = SlowBytes<Trips::PerLane>(p, lds, L, v, st0, PARTIAL ? draw % count : draw);
 		if (s >= p.hot)
 			atomicAdd(&p.visitCold[s], 1u);
-		if (f >= p.hot)
-			atomicAdd(reinterpret_cast<uint32_t*>(const_cast<uint8_t*>(lds) + L.histOff) + kLdsTrapSlot, 1u);
+		if constexpr (!PARTIAL)
+			if (f >= p.hot)
+				atomicAdd(reinterpret_cast<uint32_t*>(const_cast<uint8_t*>(lds) + L.histOff) + kLdsTrapSlot, 1u);
 	}
 }
 

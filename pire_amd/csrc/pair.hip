@@ -50,14 +50,7 @@ __device__ __forceinline__ uint32_t PairSlowStep(const ScanParams& p, const Pair
 
 __device__ __forceinline__ uint32_t PairSlowChunk(const ScanParams& p, const PairSide& S, u32x4 v, uint32_t st)
 {
-#pragma unroll 1
-	for (int i = 0; i < 16; ++i) {
-		st = PairSlowStep(p, S, st, v.x & 0xFF);
-		v.x = __builtin_amdgcn_alignbit(v.y, v.x, 8);
-		v.y = __builtin_amdgcn_alignbit(v.z, v.y, 8);
-		v.z = __builtin_amdgcn_alignbit(v.w, v.z, 8);
-		v.w >>= 8;
-	}
+	ForBytes<Trips::Sixteen>(v, 16u, [&](uint32_t byte, uint32_t) __attribute__((always_inline)) { st = PairSlowStep(p, S, st, byte); });
 	return st;
 }
 

@@ -49,22 +49,6 @@ static_assert(kRaggedFinBytes + sizeof(RaggedWork) == kRaggedLdsExtra, "LDS budg
 
 // (IssueTileLane / IssueTileGroup / WaitAllLoads: device_common.h, shared with the stream kernel.)
 
-// Exact walk of the first `count` (0..15) bytes of v; lanes with a smaller count idle (one rolled loop per wave).
-__device__ __forceinline__ uint32_t SlowPartial(const ScanParams& p, const uint8_t* lds, const LdsLayout& L, u32x4 v,
-                                                uint32_t st, uint32_t count)
-{
-#pragma unroll 1
-	for (uint32_t i = 0; __any(i < count); ++i) {
-		if (i < count)
-			st = SlowStep(p, lds, L, st, v.x & 0xFF);
-		v.x = __builtin_amdgcn_alignbit(v.y, v.x, 8);
-		v.y = __builtin_amdgcn_alignbit(v.z, v.y, 8);
-		v.z = __builtin_amdgcn_alignbit(v.w, v.z, 8);
-		v.w >>= 8;
-	}
-	return st;
-}
-
 // The first `count` (0..15) bytes of v through the LDS fast path: the whole chunk is walked, unrolled like StepChunk,
 // and the state after byte `count` is kept (v_cmp + v_cndmask per byte, no loop, no branches); lanes with count == 0
 // keep their state.  What the walk reads past `count` is ignored.  Exact re-walk on a trap like StepChunk.
@@ -88,37 +72,8 @@ __device__ __forceinline__ void StepPartial(const ScanParams& p, const uint8_t* 
 		}
 	}
 	hs = snap;
-	if (count != 0 && hs == p.hot && !(p.flags & kDebugNoTrap)) {
-		const uint32_t st0 = hs0 != p.hot ? hs0 : cold;
-		uint32_t f = p.compact;
-		if (st0 < p.compact)
-			f = CompactPartial(p, L, v, st0, count);
-		if (f == p.compact)
-			f = SlowPartial(p, lds, L, v, st0, count);
-		if (f < p.hot) {
-			hs = f;
-		} else {
-			hs = p.hot;
-			cold = f;
-		}
-		// (the sample: the state in front of a drawn one of the chunk's `count` steps, as TrapChunk's -- not the state behind
-		// the last one: that is the state the STRING ends in, which nothing looks up; rounds 2-5 gave rows to those)
-		if ((threadIdx.x & 63) == sampleLane && !(p.flags & kDebugNoColdCount)) {
-			const uint32_t step = (((sampleLane + blockIdx.x * 0x632BE5ABu) * 0x9E3779B1u) >> 28) % count;
-			uint32_t s = st0;
-			u32x4 w = v;
-#pragma unroll 1
-			for (uint32_t i = 0; i < step; ++i) {
-				s = SlowStep(p, lds, L, s, w.x & 0xFF);
-				w.x = __builtin_amdgcn_alignbit(w.y, w.x, 8);
-				w.y = __builtin_amdgcn_alignbit(w.z, w.y, 8);
-				w.z = __builtin_amdgcn_alignbit(w.w, w.z, 8);
-				w.w >>= 8;
-			}
-			if (s >= p.hot)
-				atomicAdd(&p.visitCold[s], 1u);
-		}
-	}
+	if (count != 0 && hs == p.hot && !(p.flags & kDebugNoTrap))
+		TrapChunk<true>(p, lds, L, v, hs0, hs, cold, sampleLane, count);
 }
 
 // ------------------------------------------------------------------------------------------ scans with actions
@@ -490,26 +445,8 @@ struct CaptureAct {
 	}
 };
 
-// Exact walk of the first `count` (<= 16) bytes of v with the action after every step; `addr` is the address of
-// byte 0.  Rolled: this is the cold path.
-template <class Act>
-__device__ __forceinline__ uint32_t ActBytes(const ScanParams& p, const uint8_t* lds, const LdsLayout& L, u32x4 v,
-                                             uint32_t st, uint32_t count, const Act& act, typename Act::Lane& al,
-                                             uint64_t addr)
-{
-#pragma unroll 1
-	for (uint32_t i = 0; i < count; ++i) {
-		st = SlowStep(p, lds, L, st, v.x & 0xFF);
-		act.Step(p, lds, L, al, st, addr + i + 1);
-		v.x = __builtin_amdgcn_alignbit(v.y, v.x, 8);
-		v.y = __builtin_amdgcn_alignbit(v.z, v.y, 8);
-		v.z = __builtin_amdgcn_alignbit(v.w, v.z, 8);
-		v.w >>= 8;
-	}
-	return st;
-}
-
-// The same for a chunk that stayed inside the dense rows (the usual reason for a re-walk: it touched a Final state):
+// A chunk that stayed inside the dense rows but touched a state the action cares about (the usual reason for a re-walk:
+// it touched a Final state): its first `count` (<= 16) bytes again, `addr` the address of byte 0,
 // LDS only, one compare per step on top of the lookup, the action only where the compare says so.
 template <class Act>
 __device__ __forceinline__ uint32_t ActHotBytes(const ScanParams& p, const uint8_t* lds, const LdsLayout& L,
@@ -537,95 +474,75 @@ __device__ __forceinline__ uint32_t ActHotBytes(const ScanParams& p, const uint8
 }
 
 // StepChunk with the visit test: 16 bytes through the dense rows, keeping the largest id seen.
-template <class Act>
+// PARTIAL: StepPartial with it -- a string's last chunk, only the first `count` (0..15) steps count (else count == 16).
+// The two fast paths are two instruction sequences on purpose (these kernels are timed on them): the whole chunk folds
+// its ids pairwise into v_max3, the partial one takes a predicated max and the snapshot, and skips the 16th lookup.
+template <class Act, bool PARTIAL>
 __device__ __forceinline__ void StepChunkAct(const ScanParams& p, const uint8_t* lds, const LdsLayout& L, const u32x4 v,
-                                             uint32_t& hs, uint32_t& cold, const uint8_t* area, const Act& act,
+                                             uint32_t count, uint32_t& hs, uint32_t& cold, const uint8_t* area, const Act& act,
                                              typename Act::Lane& al, uint64_t addr)
 {
 	const uint32_t hs0 = hs;
 	uint32_t h = hs, m = 0;
+	if constexpr (PARTIAL) {
+		uint32_t snap = hs;
 #pragma unroll
-	for (int w = 0; w < 4; ++w) {
-		const uint32_t x = v[w];
-		h = HotLookup(__builtin_amdgcn_perm(h, x, 0x0c0c0400u));
-		const uint32_t h1 = h;
-		h = HotLookup(__builtin_amdgcn_perm(h, x, 0x0c0c0401u));
-		m = max(m, max(h1, h));
-		h = HotLookup(__builtin_amdgcn_perm(h, x, 0x0c0c0402u));
-		const uint32_t h3 = h;
-		h = HotLookup(__builtin_amdgcn_perm(h, x, 0x0c0c0403u));
-		m = max(m, max(h3, h));
+		for (int w = 0; w < 4; ++w) {
+			const uint32_t x = v[w];
+#pragma unroll
+			for (int j = 0; j < 4; ++j) {
+				if (w == 3 && j == 3)
+					break;
+				h = HotLookup(__builtin_amdgcn_perm(h, x, 0x0c0c0400u + uint32_t(j)));
+				const bool in = count >= uint32_t(4 * w + j + 1);
+				m = max(m, in ? h : 0u);
+				snap = count == uint32_t(4 * w + j + 1) ? h : snap;
+			}
+		}
+		hs = snap;
+	} else {
+#pragma unroll
+		for (int w = 0; w < 4; ++w) {
+			const uint32_t x = v[w];
+			h = HotLookup(__builtin_amdgcn_perm(h, x, 0x0c0c0400u));
+			const uint32_t h1 = h;
+			h = HotLookup(__builtin_amdgcn_perm(h, x, 0x0c0c0401u));
+			m = max(m, max(h1, h));
+			h = HotLookup(__builtin_amdgcn_perm(h, x, 0x0c0c0402u));
+			const uint32_t h3 = h;
+			h = HotLookup(__builtin_amdgcn_perm(h, x, 0x0c0c0403u));
+			m = max(m, max(h3, h));
+		}
+		hs = h;
 	}
-	hs = h;
-	if (m >= act.Threshold(p) && act.Wants(al) && !(p.flags & kDebugNoTrap)) {
+	if ((!PARTIAL || count != 0) && m >= act.Threshold(p) && act.Wants(al) && !(p.flags & kDebugNoTrap)) {
 		if (m < p.hot) {
-			(void)ActHotBytes(p, lds, L, area, v, hs0, 16u, act, al, addr);   // ends in h again
+			(void)ActHotBytes(p, lds, L, area, v, hs0, count, act, al, addr);   // ends in hs again
 		} else {
 			const uint32_t st0 = hs0 != p.hot ? hs0 : cold;
-			uint32_t st;
+			uint32_t st = st0;
 			if (p.actDist && p.actDist[st0] > 16) {
 				// the chunk left the dense rows but cannot reach a state the action cares about: the plain
 				// trap path (compact rows in LDS first) moves the state on, there is nothing else to do
-				st = p.compact;
-				if (st0 < p.compact)
-					st = CompactChunk(p, L, v, st0);
-				if (st == p.compact)
-					st = SlowChunk(p, lds, L, v, st0);
+				st = ExactChunk<PARTIAL>(p, lds, L, v, st0, count);
 			} else {
-				st = ActBytes(p, lds, L, v, st0, 16u, act, al, addr);
+				// the exact walk with the action after every step (rolled: this is the cold path)
+				ForBytes<Trips::PerLane>(v, count, [&](uint32_t byte, uint32_t i) __attribute__((always_inline)) {
+					st = SlowStep(p, lds, L, st, byte);
+					act.Step(p, lds, L, al, st, addr + i + 1);
+				});
 			}
 			hs = st < p.hot ? st : p.hot;
 			cold = st;
 			// tell pire_hip_table_adapt() which rows deserve LDS, sampled like TrapChunk's.  (Round 5: the walks with actions
 			// left no samples, so a caller of the prefix searches alone never saw its table adapt -- and 13 states of set_a
 			// without a dense row on log lines cost the searches 40 %: 1.65 against 2.35 TB/s, profiles/r05_prefix_sizes*.log.)
-			if (st >= p.hot && (threadIdx.x & 63) == ((uint32_t(addr) >> 4) & 63u)) {
-				atomicAdd(&p.visitCold[st], 1u);
-				atomicAdd(reinterpret_cast<uint32_t*>(const_cast<uint8_t*>(lds) + L.histOff) + kLdsTrapSlot, 1u);
-			}
-		}
-	}
-}
-
-// StepPartial with the visit test: only the first `count` steps count.
-template <class Act>
-__device__ __forceinline__ void StepPartialAct(const ScanParams& p, const uint8_t* lds, const LdsLayout& L, const u32x4 v,
-                                               uint32_t count, uint32_t& hs, uint32_t& cold, const uint8_t* area,
-                                               const Act& act, typename Act::Lane& al, uint64_t addr)
-{
-	const uint32_t hs0 = hs;
-	uint32_t h = hs, snap = hs, m = 0;
-#pragma unroll
-	for (int w = 0; w < 4; ++w) {
-		const uint32_t x = v[w];
-#pragma unroll
-		for (int j = 0; j < 4; ++j) {
-			if (w == 3 && j == 3)
-				break;
-			h = HotLookup(__builtin_amdgcn_perm(h, x, 0x0c0c0400u + uint32_t(j)));
-			const bool in = count >= uint32_t(4 * w + j + 1);
-			m = max(m, in ? h : 0u);
-			snap = count == uint32_t(4 * w + j + 1) ? h : snap;
-		}
-	}
-	hs = snap;
-	if (count != 0 && m >= act.Threshold(p) && act.Wants(al) && !(p.flags & kDebugNoTrap)) {
-		if (m < p.hot) {
-			(void)ActHotBytes(p, lds, L, area, v, hs0, count, act, al, addr);
-		} else {
-			const uint32_t st0 = hs0 != p.hot ? hs0 : cold;
-			uint32_t st;
-			if (p.actDist && p.actDist[st0] > 16) {
-				st = p.compact;
-				if (st0 < p.compact)
-					st = CompactPartial(p, L, v, st0, count);
-				if (st == p.compact)
-					st = SlowPartial(p, lds, L, v, st0, count);
-			} else {
-				st = ActBytes(p, lds, L, v, st0, count, act, al, addr);
-			}
-			hs = st < p.hot ? st : p.hot;
-			cold = st;
+			// Whole chunks only: a partial one never left a sample here, nor bumped the trap signal (as TrapChunk<true>).
+			if constexpr (!PARTIAL)
+				if (st >= p.hot && (threadIdx.x & 63) == ((uint32_t(addr) >> 4) & 63u)) {
+					atomicAdd(&p.visitCold[st], 1u);
+					atomicAdd(reinterpret_cast<uint32_t*>(const_cast<uint8_t*>(lds) + L.histOff) + kLdsTrapSlot, 1u);
+				}
 		}
 	}
 }
@@ -786,27 +703,19 @@ __device__ __forceinline__ uint32_t WideActBytes(const ScanParams& p, const uint
                                                  uint64_t addr, uint32_t sampleStep, uint32_t& sampleSid)
 {
 	sampleSid = 0;
-#pragma unroll 1
-	for (uint32_t i = 0; i < count; ++i) {
+	ForBytes<Trips::PerLane>(v, count, [&](uint32_t byte, uint32_t i) __attribute__((always_inline)) {
 		if (i == sampleStep)
 			sampleSid = sid;   // the state whose row (or table line) this step looks up: what the ranking counts
-		const uint32_t c2 = HotLookup(v.x & 0xFFu);
-		uint32_t next = WideEntry<ZIP>(sid < p.wide ? sid : p.wide, K, c2);
-		bool look = true;
-		if (next == p.wide) {
-			next = WideNextC2<true>(p, sid, c2);
-			asm volatile("" : "+v"(next));   // (the wait belongs in here)
-		} else {
+		const uint32_t next = WideExactStep<true, ZIP>(p, K, sid, HotLookup(byte));
+		// the step went through the table in memory iff it starts or ends outside the tier (a row's entry says "no row" only of
+		// a target without one): the image says nothing of such a step, so the action looks
+		bool look = sid >= p.wide || next >= p.wide;
+		if (!look)
 			look = WideIsFlagged<ZIP, Act::kWideMask>(WideFlaggedBits<ZIP>(next, K), next, K);
-		}
 		sid = next;
 		if (look)
 			act.Step(p, lds, L, al, sid, addr + i + 1);
-		v.x = __builtin_amdgcn_alignbit(v.y, v.x, 8);
-		v.y = __builtin_amdgcn_alignbit(v.z, v.y, 8);
-		v.z = __builtin_amdgcn_alignbit(v.w, v.z, 8);
-		v.w >>= 8;
-	}
+	});
 	return sid;
 }
 
@@ -1002,8 +911,8 @@ __device__ __forceinline__ bool RaggedPhase(const ScanParams& p, uint8_t* lds, c
 					if constexpr (Act::kActive && WIDE != 0)
 						WideChunkAct<Act, WIDE == 3, false>(p, lds, L, W, K, cur[k], 16u, S.hs, S.cold, act, al, S.pos + 16u * k);
 					else if constexpr (Act::kActive)
-						StepChunkAct(p, lds, L, cur[k], S.hs, S.cold, reinterpret_cast<const uint8_t*>(finHot), act, al,
-						             S.pos + 16u * k);
+						StepChunkAct<Act, false>(p, lds, L, cur[k], 16u, S.hs, S.cold, reinterpret_cast<const uint8_t*>(finHot), act, al,
+						                         S.pos + 16u * k);
 					else if constexpr (WIDE != 0)
 						WideChunk<WIDE >= 2, WIDE == 3>(p, lds, W, K, cur[k], S.hs, S.cold, (iter * 8 + k) & 63);
 					else
@@ -1021,67 +930,44 @@ __device__ __forceinline__ bool RaggedPhase(const ScanParams& p, uint8_t* lds, c
 				if constexpr (Act::kActive && WIDE != 0)
 					WideChunkAct<Act, WIDE == 3, true>(p, lds, L, W, K, v, tail, S.hs, S.cold, act, al, S.pos + 16u * full);
 				else if constexpr (Act::kActive)
-					StepPartialAct(p, lds, L, v, tail, S.hs, S.cold, reinterpret_cast<const uint8_t*>(finHot), act, al,
-					               S.pos + 16u * full);
+					StepChunkAct<Act, true>(p, lds, L, v, tail, S.hs, S.cold, reinterpret_cast<const uint8_t*>(finHot), act, al,
+					                        S.pos + 16u * full);
 				else if constexpr (WIDE != 0)
 					WidePartial<WIDE >= 2, WIDE == 3>(p, K, v, tail, S.hs, S.cold);
 				else
 					StepPartial(p, lds, L, v, tail, S.hs, S.cold, (iter + 32) & 63);
 			}
-			if constexpr (WIDE == 0 && kDrawn) {
-				// The dense rows' sample, drawn like the wide walk's (above): the state in front of one byte of one lane's window,
-				// walked to exactly, if it has a dense row; which states are looked up WITHOUT one the re-walks say, fairly too since
-				// round 6 (device_common.h TrapChunk), one sample per 1 024 lane-steps of theirs.  (Rounds 2-5: the state a window STARTS
-				// in, and of a chunk that left the rows the state it ENDS in if that has no row -- on a URL batch the first is the
+			if constexpr (kDrawn) {
+				// The drawn byte's sample (above): the drawn lane walks the drawn chunk again from the state in front of it, exactly, up
+				// to the drawn byte, and counts the state it finds there.
+				// The dense rows': if that state has a dense row; which states are looked up WITHOUT one the re-walks say, fairly too
+				// since round 6 (device_common.h TrapChunk), one sample per 1 024 lane-steps of theirs.  (Rounds 2-5: the state a window
+				// STARTS in, and of a chunk that left the rows the state it ENDS in if that has no row -- on a URL batch the first is the
 				// start state every time and the second misses every state the walk passes through on its way back into the rows:
 				// a state with 4.6 % of all lookups stood outside the 255 rows for good, 17 % of the steps there where 2 % need be;
-				// tools/ranking_quality.py ... dense.)
-				// (every fourth iteration, four times the weight: the dense walk's iteration is short, and a lane walking up to 15
-				// steps alone at its end was 6-8 % of it -- 2 140 -> 2 013 GB/s on set_a's URL batch when every iteration drew)
-				if (sampleLaneHere && sampleAt < nbl && (iter & 3u) == 0) {
+				// tools/ranking_quality.py ... dense.)  Every fourth iteration, four times the weight: the dense walk's iteration is
+				// short, and a lane walking up to 15 steps alone at its end was 6-8 % of it -- 2 140 -> 2 013 GB/s on set_a's URL batch
+				// when every iteration drew.
+				// The wide walk's: every iteration; a state outside the tier is counted as "outside" here; WHICH state it is the re-walks
+				// say -- WideTrapChunk, one sample per 1 024 lane-steps outside the tier where this one stands for 8 192 --, and the
+				// walks with actions.
+				if (sampleLaneHere && sampleAt < nbl && (WIDE != 0 || (iter & 3u) == 0)) {
+					uint32_t st = sampleFrom;   // (device) id of the state in front of the chunk
 					u32x4 v = cur[0];
 #pragma unroll
 					for (int k = 1; k < 8; ++k)
 						if (sampleChunk == uint32_t(k))
 							v = cur[k];
-					uint32_t st = sampleFrom;
-#pragma unroll 1
-					for (uint32_t i = 0; i < (sampleAt & 15u); ++i) {
-						st = SlowStep(p, lds, L, st, v.x & 0xFFu);
-						v.x = __builtin_amdgcn_alignbit(v.y, v.x, 8);
-						v.y = __builtin_amdgcn_alignbit(v.z, v.y, 8);
-						v.z = __builtin_amdgcn_alignbit(v.w, v.z, 8);
-						v.w >>= 8;
-					}
-					if (st < p.hot)   // (a state without a row: the re-walks say which, device_common.h TrapChunk)
+					ForBytes<Trips::PerLane>(v, sampleAt & 15u, [&](uint32_t byte, uint32_t) __attribute__((always_inline)) {
+						if constexpr (WIDE != 0)
+							st = WideExactStep<WIDE >= 2, WIDE == 3>(p, K, st, HotLookup(byte));
+						else
+							st = SlowStep(p, lds, L, st, byte);
+					});
+					if constexpr (WIDE != 0)
+						WideSample<WIDE == 3>(p, lds, W, st < p.wide ? st : p.wide);
+					else if (st < p.hot)   // (a state without a row: the re-walks say which)
 						atomicAdd(reinterpret_cast<uint32_t*>(lds + L.histOff) + st, 4u);
-				}
-			}
-			if constexpr (WIDE != 0) {
-				if (sampleLaneHere && sampleAt < nbl) {
-					u32x4 v = cur[0];
-#pragma unroll
-					for (int k = 1; k < 8; ++k)
-						if (sampleChunk == uint32_t(k))
-							v = cur[k];
-					uint32_t sid = sampleFrom;   // device id of the state in front of the chunk
-#pragma unroll 1
-					for (uint32_t i = 0; i < (sampleAt & 15u); ++i) {
-						const uint32_t c2 = HotLookup(v.x & 0xFFu);
-						uint32_t next = WideEntry<WIDE == 3>(sid < p.wide ? sid : p.wide, K, c2);
-						if (next == p.wide) {
-							next = WideNextC2<WIDE >= 2>(p, sid, c2);
-							asm volatile("" : "+v"(next));   // (the wait belongs in here)
-						}
-						sid = next;
-						v.x = __builtin_amdgcn_alignbit(v.y, v.x, 8);
-						v.y = __builtin_amdgcn_alignbit(v.z, v.y, 8);
-						v.z = __builtin_amdgcn_alignbit(v.w, v.z, 8);
-						v.w >>= 8;
-					}
-					// (a state outside the tier is counted as "outside" here; WHICH state it is the re-walks say -- WideTrapChunk, one
-					// sample per 1 024 lane-steps outside the tier where this one stands for 8 192 --, and the walks with actions below)
-					WideSample<WIDE == 3>(p, lds, W, sid < p.wide ? sid : p.wide);
 				}
 			}
 		}

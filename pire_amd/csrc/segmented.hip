@@ -412,16 +412,10 @@ __global__ __launch_bounds__(1024) void SegmentHalfFinalKernel(ScanParams p, Seg
 				hs = h;
 				if (m >= p.hotFinalLo) {
 					uint32_t w = hs0 != p.hot ? hs0 : cold;
-					u32x4 u = v;
-#pragma unroll 1
-					for (int i = 0; i < 16; ++i) {
-						w = SlowStep(p, lds, L, w, u.x & 0xFF);
+					ForBytes<Trips::Sixteen>(v, 16u, [&](uint32_t byte, uint32_t) __attribute__((always_inline)) {
+						w = SlowStep(p, lds, L, w, byte);
 						take(w);
-						u.x = __builtin_amdgcn_alignbit(u.y, u.x, 8);
-						u.y = __builtin_amdgcn_alignbit(u.z, u.y, 8);
-						u.z = __builtin_amdgcn_alignbit(u.w, u.z, 8);
-						u.w >>= 8;
-					}
+					});
 					hs = w < p.hot ? w : p.hot;
 					cold = w;
 				}

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "walk.h"
 
 namespace pirehip {
 
@@ -296,10 +297,7 @@ __global__ __launch_bounds__(1024) void SlowScanKernel(SlowParams p)
 #pragma unroll 1
 			for (int i = 0; i < 16; ++i) {
 				lane.Step(masks, single, p.letters, ldsLetter[v.x & 0xFF]);
-				v.x = __builtin_amdgcn_alignbit(v.y, v.x, 8);
-				v.y = __builtin_amdgcn_alignbit(v.z, v.y, 8);
-				v.z = __builtin_amdgcn_alignbit(v.w, v.z, 8);
-				v.w >>= 8;
+				NextByte(v);
 			}
 		}
 		for (; ptr < end; ++ptr)

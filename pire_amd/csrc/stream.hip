@@ -260,7 +260,7 @@ __device__ __forceinline__ bool StreamPhase(const ScanParams& p, uint8_t* lds, c
 				if (h == p.hot && S.live) {
 					// TrapChunk without the compact tier (its LDS holds the string positions here): the chunk again through the
 					// full table, the cold end state sampled for pire_hip_table_adapt()
-					const uint32_t f = SlowChunk(p, lds, L, cur[k], hs0 != p.hot ? hs0 : S.cold);
+					const uint32_t f = SlowBytes<Trips::Sixteen>(p, lds, L, cur[k], hs0 != p.hot ? hs0 : S.cold);
 					S.hs = f < p.hot ? f : p.hot;
 					S.cold = f;
 					if (f >= p.hot && lane == ((iter * 8 + k) & 63)) {

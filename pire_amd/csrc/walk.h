@@ -17,6 +17,33 @@ namespace pirehip {
 
 typedef uint32_t walk_u32x4 __attribute__((ext_vector_type(4)));
 
+// The 16-byte block `v` (any vector of four dwords: u32x4, uint4) one byte down: byte k + 1 becomes byte k.
+template <class V>
+__device__ __forceinline__ void NextByte(V& v)
+{
+	v.x = __builtin_amdgcn_alignbit(v.y, v.x, 8);
+	v.y = __builtin_amdgcn_alignbit(v.z, v.y, 8);
+	v.z = __builtin_amdgcn_alignbit(v.w, v.z, 8);
+	v.w >>= 8;
+}
+
+// The exact re-walks' loop: `step(byte, i)` for the leading bytes of a block, in order.  ROLLED whatever the form (these are
+// cold paths, instantiated once per unrolled chunk of their callers, and have to stay small in the instruction cache).
+//   Sixteen   the whole block, a constant 16 trips
+//   Levelled  the wave makes max(count) trips together; `step` itself asks whether trip i is one of its lane's (i < count)
+//   PerLane   a lane's own `count` trips
+enum class Trips { Sixteen, Levelled, PerLane };
+
+template <Trips T, class V, class Step>
+__device__ __forceinline__ void ForBytes(V v, uint32_t count, Step&& step)
+{
+#pragma unroll 1
+	for (uint32_t i = 0; T == Trips::Sixteen ? i < 16u : T == Trips::Levelled ? bool(__any(i < count)) : i < count; ++i) {
+		step(v.x & 0xFFu, i);
+		NextByte(v);
+	}
+}
+
 // Block feeder: hands the 16-byte blocks that hold [ptr, end) to `block(v, skip, count)` in order -- bytes
 // [skip, skip + count) of v belong to the string (only the first block can have skip > 0, only the last count < 16 -
 // skip) -- reading line-aligned tiles as described above.  `block` returns false to stop early.
@@ -63,20 +90,13 @@ __device__ __forceinline__ void WalkBlocks(const uint8_t* ptr, const uint8_t* en
 template <class Step>
 __device__ __forceinline__ bool BlockBytes(walk_u32x4 v, uint32_t skip, uint32_t count, Step&& step)
 {
-	for (uint32_t i = 0; i < skip; ++i) {
-		v.x = __builtin_amdgcn_alignbit(v.y, v.x, 8);
-		v.y = __builtin_amdgcn_alignbit(v.z, v.y, 8);
-		v.z = __builtin_amdgcn_alignbit(v.w, v.z, 8);
-		v.w >>= 8;
-	}
+	for (uint32_t i = 0; i < skip; ++i)
+		NextByte(v);
 #pragma unroll 1
 	for (uint32_t i = 0; i < count; ++i) {
 		if (!step(v.x & 0xFFu))
 			return false;
-		v.x = __builtin_amdgcn_alignbit(v.y, v.x, 8);
-		v.y = __builtin_amdgcn_alignbit(v.z, v.y, 8);
-		v.z = __builtin_amdgcn_alignbit(v.w, v.z, 8);
-		v.w >>= 8;
+		NextByte(v);
 	}
 	return true;
 }

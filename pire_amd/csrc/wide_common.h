@@ -94,6 +94,21 @@ __device__ __forceinline__ uint32_t WideNextC2(const ScanParams& p, uint32_t st,
 	return p.nextPerm[size_t(st) * p.letters + (c2 >> 1)];
 }
 
+// One exact step from the state with device id `sid` (c2: the byte's doubled class): its row's entry -- a state without a row
+// reads the escape row, "no row" -- and, for the lanes that entry sends outside the rows or that are there already, ONE load
+// from the table in memory.  The owner of that step for every exact re-walk of this walk but WideTrapChunk2's, which puts two
+// chains' loads behind one wait on purpose.
+template <bool N16, bool ZIP>
+__device__ __forceinline__ uint32_t WideExactStep(const ScanParams& p, const WideConst& K, uint32_t sid, uint32_t c2)
+{
+	uint32_t next = WideEntry<ZIP>(sid < p.wide ? sid : p.wide, K, c2);
+	if (next == p.wide) {
+		next = WideNextC2<N16>(p, sid, c2);
+		asm volatile("" : "+v"(next));   // (the wait belongs in here: left to the join it is a vmcnt(0) every lane passes)
+	}
+	return next;
+}
+
 // A lane sits in the escape row after the 16 bytes `v`: walk them again from the state it was in before them, exactly,
 // device ids all the way: the row's entry in LDS, and ONE load from the table in memory in the steps in which that entry
 // says "no row" -- for a lane that leaves the rows with this step and for one that is outside them already alike (the
@@ -154,14 +169,7 @@ __device__ __forceinline__ void WideTrapChunk(const ScanParams& p, uint8_t* lds,
 				if (out && (threadIdx.x & 63) == uint32_t(__ffsll(m)) - 1u)
 					atomicAdd(&p.visitCold[sid], uint32_t(__popcll(m)));   // (see above: the step's lanes outside the rows)
 			}
-			// the row's entry (a state without a row reads the escape row: "no row") ...
-			const uint32_t e = WideEntry<ZIP>(sid < p.wide ? sid : p.wide, K, c2);
-			uint32_t next = e;
-			if (e == p.wide) {   // ... and, for the lanes it sends outside the rows or that are there already, the table in memory
-				next = WideNextC2<N16>(p, sid, c2);
-				asm volatile("" : "+v"(next));   // (the wait belongs in here: left to the join it is a vmcnt(0) every lane passes)
-			}
-			sid = next;
+			sid = WideExactStep<N16, ZIP>(p, K, sid, c2);
 			c2 = c2n;
 		}
 	}
@@ -352,16 +360,10 @@ __device__ __forceinline__ void WidePartial(const ScanParams& p, const WideConst
 	st = snap;
 	if (count != 0 && st == p.wide) {
 		uint32_t sid = st0 < p.wide ? st0 : cold;
-		u32x4 t = v;
-#pragma unroll 1
-		for (uint32_t i = 0; __any(i < count); ++i) {
+		ForBytes<Trips::Levelled>(v, count, [&](uint32_t byte, uint32_t i) __attribute__((always_inline)) {
 			if (i < count)
-				sid = WideNext<N16>(p, sid, HotLookup(t.x & 0xFFu) >> 1);
-			t.x = __builtin_amdgcn_alignbit(t.y, t.x, 8);
-			t.y = __builtin_amdgcn_alignbit(t.z, t.y, 8);
-			t.z = __builtin_amdgcn_alignbit(t.w, t.z, 8);
-			t.w >>= 8;
-		}
+				sid = WideNext<N16>(p, sid, HotLookup(byte) >> 1);
+		});
 		st = sid < p.wide ? sid : p.wide;
 		cold = sid;
 	}

@@ -192,3 +192,89 @@ def test_ragged_half_final_with_counters_that_do_not_pack():
             xi, xf, xr = t.run_half_final(text, offs, flags=flags | pb.FLAG_GENERIC)
             assert (xr == orr).all()
         assert orr.sum() > 0
+
+
+def _tail_lengths():
+    """Every residue 0..15 mod 16 behind 0, 1 and 8 whole chunks, the window cut, and the smallest partial chunks."""
+    return list(range(0, 16)) + list(range(16, 32)) + list(range(128, 144)) + [127, 128, 129, 1, 17]
+
+
+def _tail_batch(labels, filler, n=512):
+    """n strings of the lengths above, a label written so that it ENDS in the string's partial last chunk -- in its last
+    1..15 bytes, every place in turn -- where it fits; the trap or the Final state then falls into that chunk."""
+    lens, a = _tail_lengths(), np.frombuffer(filler, dtype=np.uint8)
+    rng = np.random.RandomState(23)
+    out = []
+    for i in range(n):
+        k = lens[i % len(lens)]
+        s = bytearray(a[rng.randint(0, len(a), size=k)].tobytes())
+        tail = k % 16
+        w = labels[(i // len(lens) + i) % len(labels)]
+        if tail:
+            end = k - (i // len(lens)) % tail
+            if len(w) <= end:
+                s[end - len(w):end] = w
+        out.append(bytes(s))
+    return out
+
+
+def test_every_partial_last_chunk_on_dense_and_wide_rows(cfg):
+    """The <= 15 bytes behind a string's last whole chunk (StepPartial, StepChunkAct<.., true>, WidePartial,
+    WideChunkAct<.., true> and the exact re-walks behind them): every length 0..15, 16..31, 128..143 and 127..129, the
+    match or the step out of the rows in the last 1..15 bytes.  Plain scan, half-final counting, both prefix searches and
+    the capture, on a small table and on a dictionary that leaves the dense rows (there also on the wide rows), against
+    the oracle and the one-string-per-lane kernels."""
+    import pire_amd
+    from pire_amd import binding as pb
+    from pire_amd import workloads as W
+
+    cfg.set(auto_adapt=0, zip_variant=0)
+    g = H.golden()
+    small = [c for c in g["half_final"] if c["regexps"] <= 8][0]
+    entry = W.wide_set("dict_1k")
+    words = W.dictionary_words(entry)
+    longw = [w for w in words if len(w) >= 8][:40] or words[:40]
+    dict_strings = _tail_batch(longw, b"abcdefghijklmnopqrstuvwxyz ")
+    # the smallest partial chunks: one byte; 17 bytes whose 17th is byte k + 1 of a word, k = 1..16 -- the walk goes one
+    # state deeper into the dictionary with every byte of a word, so for one k the step out of the dense rows IS byte 17
+    w17 = max(words, key=len)
+    dict_strings += [w17[:1]] + [b" " * (16 - k) + w17[:k + 1] for k in range(1, 17) if len(w17) > k]
+    tables = [("small", H.load_blob(small["blob"]), _tail_batch([b"abcde", b"w a", b"e"], b"abcde w"), (0,)),
+              ("dict_1k", W.load_blob(entry["blob"]), dict_strings, (0, 2))]
+    for name, blob, strings, variants in tables:
+        assert len(strings) >= 512 and {len(s) for s in strings} >= set(_tail_lengths())
+        t, o = pire_amd.Table(blob), ob.OracleScanner(blob)
+        text, offs = H.pack(strings)
+        wi, wf = o.run(text, offs)
+        whf = {fl: o.run_half_final(text, offs, flags=fl) for fl in (3, 0)}
+        wpre = {(lg, te): o.prefix(text, offs, lg, True, te) for lg in (True, False) for te in (True, False)}
+        for variant in variants:
+            cfg.set(walk_variant=variant, ragged_act_always=1, no_ragged_act=0)
+            for generic in (0, pb.FLAG_GENERIC):
+                gi, gf = t.run(text, offs, flags=3 | generic)
+                assert (gi == wi).all() and (gf == wf).all(), (name, variant, generic, np.nonzero(gi != wi)[0][:8])
+                for fl, want in whf.items():
+                    got = t.run_half_final(text, offs, flags=fl | generic)
+                    assert generic or pb.last_kernel().startswith("ragged_half_final"), pb.last_kernel()
+                    assert all((x == y).all() for x, y in zip(want, got)), (name, variant, generic, fl)
+                for (lg, te), want in wpre.items():
+                    got = t.prefix(text, offs, lg, True, te, generic=bool(generic))
+                    assert generic or pb.last_kernel().startswith("ragged_prefix"), pb.last_kernel()
+                    assert (got == want).all(), (name, variant, generic, lg, te, np.nonzero(got != want)[0][:8])
+        assert whf[3][2].sum() > 0 and any((w >= 0).any() for w in wpre.values()), name
+    assert (wi != wi[0]).any()
+    cfg.set(walk_variant=0)
+    for case in g.get("capturing", [])[:1]:
+        blob = H.load_blob(case["blob"])
+        t, o = pire_amd.CountingTable(blob, 0), ob.OracleCountingScanner(blob, 0)
+        pool = [bytes.fromhex(h) for h in case["strings_hex"][:5]]
+        strings = _tail_batch([p for p in pool if p] or [b"x"], b"google_id ='\";x1/")
+        want = o.capture(*ob.pack_strings(strings))
+        cfg.set(ragged_act_always=1, no_ragged_act=0)
+        got = t.capture(*H.pack(strings))
+        assert pb.last_kernel() == ("ragged_capture" if t.LettersCount <= 127 else pb.last_kernel())
+        assert all((x == y).all() for x, y in zip(want, got))
+        cfg.set(ragged_act_always=0, no_ragged_act=1)
+        lane = t.capture(*H.pack(strings))
+        assert not pb.last_kernel().startswith("ragged"), pb.last_kernel()
+        assert all((x == y).all() for x, y in zip(want, lane))
