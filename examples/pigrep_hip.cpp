@@ -23,16 +23,24 @@ namespace {
 
 // The stream as it is, in one buffer: cutting it into lines (getline semantics: the newline is not part of the line, a
 // trailing fragment without newline is a line, an empty stream has no lines), scanning them and picking the lines that
-// matched all happen on the GPU; what comes back is the byte range of every hit.
+// matched all happen on the GPU; what comes back is the text of the hits, a newline behind each: the output itself.
 void GrepStream(std::istream& in, const Pire::Hip::Table<Pire::Scanner>& table, const std::string& prefix)
 {
 	const std::string raw((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
 	if (raw.empty())
 		return;
 	Pire::Hip::BatchRunner<Pire::Scanner> run(table);
-	const std::vector<uint64_t>& spans = run.Begin().RunLines(raw.data(), raw.size()).End().HitSpans();
-	for (size_t k = 0; k + 1 < spans.size(); k += 2)
-		std::cout << prefix << raw.substr(spans[k], spans[k + 1] - spans[k]) << std::endl;
+	const std::string& hits = run.Begin().RunLines(raw.data(), raw.size()).End().HitText();
+	if (prefix.empty()) {
+		std::cout.write(hits.data(), std::streamsize(hits.size()));
+	} else {
+		const std::vector<uint64_t>& offsets = run.HitTextOffsets();
+		for (size_t k = 0; k + 1 < offsets.size(); ++k) {
+			std::cout << prefix;
+			std::cout.write(hits.data() + offsets[k], std::streamsize(offsets[k + 1] - offsets[k]));
+		}
+	}
+	std::cout.flush();
 }
 
 void Usage()

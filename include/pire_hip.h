@@ -521,6 +521,74 @@ int pire_hip_run_lines_select(pire_hip_table* t, const void* raw, uint64_t size,
                               const uint64_t* want, uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_hit_spans,
                               uint64_t* out_hit_masks, uint64_t hit_cap, uint64_t* out_hit_count, void* stream);
 
+/* ---- the selected strings gathered into a batch, on the device ------------------------------------------------ */
+
+/* The copy pass cuts out_text into tiles of this many bytes, on the 16-byte grid of out_text's address (tests aim at its edges). */
+#define PIRE_HIP_GATHER_TILE_BYTES 16384u
+#define PIRE_HIP_GATHER_NO_TAIL (~0u)
+
+/*
+ * From a hit list to bytes: the listed strings of a batch, back to back, as text + offsets -- the input form of every scan
+ * entry point, so that a second scanner runs on the survivors of a first one without the text leaving the device; with a
+ * tail byte behind every string it is grep's output buffer, and the inverse of pire_hip_split.
+ *   k   = min(idx_count ? *idx_count : idx_cap, idx_cap)               the number of strings copied
+ *   s_j = idx ? idx[j] : j                    for j < k                 the source of output string j:
+ *                                                                       text[offsets[s_j], offsets[s_j + 1])
+ *   a   = (tail != PIRE_HIP_GATHER_NO_TAIL)                             one byte `tail` behind every string, or none
+ *   L_j = offsets[s_j + 1] - offsets[s_j] + a
+ *   out_offsets[0] = 0,  out_offsets[j + 1] = L_0 + ... + L_j
+ *   out_text[out_offsets[j], out_offsets[j + 1]) = the string, then the byte `tail` if a
+ *   *out_bytes = out_offsets[k]
+ * idx need not be ascending or distinct (the hit lists of pire_hip_select are; a caller's own order is legal).  With a tail
+ * every output string keeps it as its last byte: the convention of pire_hip_split's out_text == NULL form.
+ * out_bytes (required) receives the whole total, also when it exceeds text_cap; only bytes of out_text at positions
+ * < text_cap are written, nothing behind them.  out_offsets has idx_cap + 1 entries; entries 0..k are written, nothing
+ * behind them.  idx_cap == 0 or k == 0 writes *out_bytes = 0 and out_offsets[0] = 0 (where out_offsets is not null).
+ * idx_cap < 2^32.
+ * pire_hip_gather_spans: the source of output string j is raw[spans[2j], spans[2j + 1]) -- what out_hit_spans of
+ * pire_hip_run_lines_select holds; k and the rest as above with span_count / span_cap.  A range with end < begin or
+ * end > size is out of range.
+ * An index s_j >= n, or a span out of range: with host pointers PIRE_HIP_EINVAL and nothing is written; with
+ * PIRE_HIP_RUN_ON_DEVICE it contributes an empty string (and its tail) and reads nothing.
+ * flags: PIRE_HIP_RUN_ON_DEVICE -> every pointer (idx_count included) is a device pointer and the call only enqueues on
+ *        `stream`: four kernels (lengths per tile of 1 024 strings, one-block scan, offsets, copy), no atomics -- the same
+ *        input gives the same bits --, and no allocation of any kind: the pass needs no scratch (the per-tile sums wait
+ *        in entries of out_offsets that it overwrites last), so calls right behind one another on a busy stream only
+ *        enqueue, each of them.  The copy
+ *        pass divides its work by OUTPUT BYTES: a string of megabytes spreads over as many blocks as it has tiles, empty
+ *        strings cost nothing.  Device text is read under the rule stated at PIRE_HIP_RUN_ON_DEVICE.  text, raw and
+ *        out_text may have any alignment.
+ *        Otherwise host pointers: staged, synchronises.
+ * The pass is not in place: out_text must not overlap the source.  That is refused where the host can tell: in the spans
+ * form (out_text[0, text_cap) against raw[0, size)) and with host pointers (against text[0, offsets[n])).
+ * PIRE_HIP_EINVAL before any device is touched: null out_bytes, tail > 255 (and not PIRE_HIP_GATHER_NO_TAIL), idx_cap > 0
+ * with null offsets (span_cap > 0 with null spans), idx_cap > 0 with null out_offsets, text_cap > 0 with null out_text,
+ * idx_cap > n without idx, 2^32 strings or more, out_text overlaps the source.
+ * pire_hip_last_kernel() is not changed by a gather.  No first-use self-test (as pire_hip_split).
+ */
+int pire_hip_gather(const void* text, const uint64_t* offsets, uint64_t n,
+                    const uint64_t* idx, const uint64_t* idx_count, uint64_t idx_cap, uint32_t tail, uint32_t flags,
+                    void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes, void* stream);
+
+int pire_hip_gather_spans(const void* raw, uint64_t size,
+                          const uint64_t* spans, const uint64_t* span_count, uint64_t span_cap, uint32_t tail, uint32_t flags,
+                          void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes, void* stream);
+
+/*
+ * pire_hip_run_lines_select followed by the gather of the selected lines from raw, behind one call: raw bytes in, the
+ * matching lines out AS BYTES.  With tail = delim the bytes in out_text are exactly what `grep` prints for the buffer.
+ * out_line_count, want, out_hits (nullable: the library keeps the hit list to itself), hit_cap, out_hit_count: as
+ * pire_hip_run_lines_select; k = min(*out_hit_count, hit_cap) lines are gathered.  out_text, text_cap, out_offsets
+ * (hit_cap + 1 entries), out_bytes: as pire_hip_gather.  flags as pire_hip_run_lines_select; it synchronises `stream`
+ * once, for the same reason and at the same place, and adds no second wait.  It refuses what pire_hip_run_lines_select
+ * refuses (hit_cap > 0 with null out_hits excepted) and what pire_hip_gather refuses of its outputs.
+ * pire_hip_last_kernel() names the scan kernel.
+ */
+int pire_hip_run_lines_gather(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
+                              const uint64_t* want, uint32_t tail, uint64_t* out_line_count,
+                              uint64_t* out_hits, uint64_t hit_cap, uint64_t* out_hit_count,
+                              void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes, void* stream);
+
 /*
  * Batched Runner over the table walked as a Pire::HalfFinalScanner (scanners/half_final.h:32-227).  A
  * HalfFinalScanner IS a Scanner (same Save() bytes, ingest it with pire_hip_table_create), but its Initialize and

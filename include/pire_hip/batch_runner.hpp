@@ -234,6 +234,8 @@ public:
 	 *     run.Begin().RunLines(raw, size).End();
 	 *     run.HitSpans()    [2 * k], [2 * k + 1]: hit k is raw[begin, end)       run.LineCount()  lines in the buffer
 	 *     run.Hits()        the numbers of the selected lines, ascending         run.HitCount() / HitMasks() as after Select()
+	 *     run.HitText()     the selected lines back to back, '\n' (or the byte given) behind each: grep's output, gathered on
+	 *                       the device (pire_hip_run_lines_gather)       run.HitTextOffsets()  hit k is HitText()[o[k], o[k + 1])
 	 * Select({..}) in front of them chooses regexps.  This form has hits only: States() / Finals() / MatchCounts() throw.
 	 */
 	BatchRunner& RunLines(const char* raw, size_t size, char delim = '\n')
@@ -243,12 +245,22 @@ public:
 		m_n = 0;
 		m_len = size;
 		m_delim = uint8_t(delim);
-		m_onDevice = m_ran = m_selected = m_hitsFetched = false;
+		m_onDevice = m_ran = m_selected = m_hitsFetched = m_textFetched = false;
 		m_lines = true;
 		return *this;
 	}
 	uint64_t LineCount() { FetchHits(); return m_lineCount; }
 	const std::vector<uint64_t>& HitSpans() { FetchHits(); return m_hitSpans; }
+	/* Fetched lazily, like HitSpans(); the offsets are those of the text fetched last ('\n' where none was).  The text comes from
+	 * a call of its own (pire_hip_run_lines_gather: split, scan, select, gather): HitText() after HitSpans() / Hits() scans the
+	 * buffer a second time -- ask for the one or the other. */
+	const std::string& HitText(char tail = '\n') { FetchHitText(tail); return m_hitText; }
+	const std::vector<uint64_t>& HitTextOffsets()
+	{
+		if (!m_textFetched)
+			FetchHitText('\n');
+		return m_hitTextOffsets;
+	}
 
 	/* RunHelper::State() per string (run.h:378). */
 	const std::vector<State>& States()
@@ -298,7 +310,7 @@ public:
 		for (size_t i = 0; i < want.size(); ++i)
 			if (want[i] < m_want.size() * 64)
 				m_want[want[i] / 64] |= uint64_t(1) << (want[i] % 64);
-		m_selected = m_hitsFetched = false;
+		m_selected = m_hitsFetched = m_textFetched = false;
 		return *this;
 	}
 	size_t MaskWords() const { return pire_hip_table_mask_words(m_table->Handle()); }
@@ -315,9 +327,10 @@ public:
 private:
 	void Reset()
 	{
-		m_selected = m_hitsFetched = m_haveWant = m_lines = false;
+		m_selected = m_hitsFetched = m_haveWant = m_lines = m_textFetched = false;
 		m_hitCount = m_lineCount = 0;
 		m_delim = 0;
+		m_textTail = '\n';
 		m_flags = 0;
 		m_text = nullptr;
 		m_offsets = nullptr;
@@ -390,6 +403,32 @@ private:
 		m_hitSpans.resize(m_hitCount * 2);
 		m_hitMasks.resize(m_hitCount * w);
 		m_ran = m_selected = m_hitsFetched = true;
+	}
+
+	/* RunLines(): the selected lines as bytes; room for every byte they can have, the grow-and-retry of ExecuteLines() on the
+	 * number of hits */
+	void FetchHitText(char tail)
+	{
+		if (!m_lines)
+			throw Pire::Error("pire_hip: HitText() follows RunLines()");
+		if (m_textFetched && m_textTail == tail)
+			return;
+		if (m_want.empty())
+			Select();
+		uint64_t count = 0, bytes = 0;
+		for (size_t cap = m_selected && m_ran ? size_t(m_hitCount) : m_len / 64 + 1024;; cap = count) {
+			m_hitTextOffsets.resize(cap + 1);
+			m_hitText.resize(m_len + cap + 1);
+			Check(pire_hip_run_lines_gather(m_table->Handle(), m_text, m_len, m_delim, m_flags, m_haveWant ? m_want.data() : nullptr,
+			                                uint8_t(tail), &m_lineCount, nullptr, cap, &count, &m_hitText[0], m_hitText.size(),
+			                                m_hitTextOffsets.data(), &bytes, nullptr));
+			if (count <= cap && bytes <= m_hitText.size())
+				break;
+		}
+		m_hitText.resize(bytes);
+		m_hitTextOffsets.resize(count + 1);
+		m_textTail = tail;
+		m_textFetched = true;
 	}
 
 	void ExecuteSelect()
@@ -488,8 +527,11 @@ private:
 	std::vector<char> m_final;
 	std::vector<uint64_t> m_counts;
 	DeviceBuffer m_devIdx, m_devFin, m_devCounts, m_devInit;
-	bool m_selected, m_hitsFetched, m_haveWant, m_lines;
+	bool m_selected, m_hitsFetched, m_haveWant, m_lines, m_textFetched;
 	uint8_t m_delim;
+	char m_textTail;
+	std::string m_hitText;
+	std::vector<uint64_t> m_hitTextOffsets;
 	uint64_t m_hitCount, m_lineCount;
 	std::vector<uint64_t> m_want, m_hits, m_hitMasks, m_hitSpans;
 	DeviceBuffer m_devHits, m_devHitMasks, m_devHitCount, m_devWant;

@@ -134,6 +134,8 @@ NONE = (1 << 64) - 1   # PIRE_HIP_SEGMENT_WARMUP_NONE / PIRE_HIP_SEGMENT_BUDGET_
 
 ABI_VERSION = 6   # include/pire_hip.h PIRE_HIP_ABI_VERSION
 SPLIT_TILE = 16384   # include/pire_hip.h PIRE_HIP_SPLIT_TILE_BYTES: the split pass cuts raw into tiles of this many bytes
+GATHER_TILE = 16384   # include/pire_hip.h PIRE_HIP_GATHER_TILE_BYTES: the gather's copy pass cuts out_text into tiles of this many bytes
+NO_TAIL = (1 << 32) - 1   # include/pire_hip.h PIRE_HIP_GATHER_NO_TAIL: no byte behind the gathered strings
 
 # every symbol include/pire_hip.h declares: (name, restype, argtypes)
 ABI = [
@@ -181,6 +183,13 @@ ABI = [
                                  C.c_void_p]),
     ("pire_hip_run_lines_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                  C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_gather_spans", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                        C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_run_lines_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                            C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
     ("pire_hip_run_half_final", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_prefix", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_uint32,
@@ -344,6 +353,56 @@ def split_device(raw_ptr: int, size: int, out_n_ptr: int, delim: int = 10, out_t
     """pire_hip_split with PIRE_HIP_RUN_ON_DEVICE: raw device addresses, only enqueues on `stream`."""
     _check(lib().pire_hip_split(raw_ptr or None, size, delim, FLAG_ON_DEVICE, out_text_ptr or None, out_offsets_ptr or None,
                                 offsets_cap, out_n_ptr or None, stream or None))
+
+
+# --- the listed strings of a batch back to back (pire_hip_gather / pire_hip_gather_spans)
+def _tail(tail) -> int:
+    return NO_TAIL if tail is None else int(tail)
+
+
+def gather_host(text, offsets=None, idx=None, tail=None, spans=None, text_cap: Optional[int] = None):
+    """pire_hip_gather on host arrays -- or, with spans (uint64[k, 2], begin / end in `text`), pire_hip_gather_spans:
+    (out_text u8[min(total, text_cap)], out_offsets u64[k + 1], total).  tail None = no byte behind the strings; text_cap
+    None = room for everything (the sources' lengths are the host's to add up)."""
+    text = _raw_bytes(text)
+    a = 0 if tail is None else 1
+    if spans is not None:
+        spans = np.ascontiguousarray(spans, dtype=np.uint64).reshape(-1, 2)
+        k = len(spans)
+        room = int((spans[:, 1] - spans[:, 0]).sum()) + a * k if text_cap is None else int(text_cap)
+    else:
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        idx = None if idx is None else np.ascontiguousarray(idx, dtype=np.uint64)
+        k = len(offsets) - 1 if idx is None else len(idx)
+        src = np.arange(k, dtype=np.int64) if idx is None else idx.astype(np.int64)
+        room = int((offsets[src + 1] - offsets[src]).sum()) + a * k if text_cap is None else int(text_cap)
+    out = np.zeros(max(room, 1), dtype=np.uint8)
+    out_offsets = np.zeros(k + 1, dtype=np.uint64)
+    total = C.c_uint64(0)
+    tptr = text.ctypes.data if text.size else None
+    if spans is not None:
+        _check(lib().pire_hip_gather_spans(tptr, text.size, spans.ctypes.data if k else None, None, k, _tail(tail), 0,
+                                           out.ctypes.data if room else None, room, out_offsets.ctypes.data, C.byref(total), None))
+    else:
+        _check(lib().pire_hip_gather(tptr, offsets.ctypes.data, len(offsets) - 1, _np_ptr(idx) if k else None, None, k, _tail(tail), 0,
+                                     out.ctypes.data if room else None, room, out_offsets.ctypes.data, C.byref(total), None))
+    return out[:min(int(total.value), room)], out_offsets, int(total.value)
+
+
+def gather_device(text_ptr: int, offsets_ptr: int, n: int, out_bytes_ptr: int, idx_ptr=0, idx_count_ptr=0, idx_cap=0, tail=None,
+                  out_text_ptr=0, text_cap=0, out_offsets_ptr=0, stream: int = 0):
+    """pire_hip_gather with PIRE_HIP_RUN_ON_DEVICE: raw device addresses, only enqueues on `stream`."""
+    _check(lib().pire_hip_gather(text_ptr or None, offsets_ptr or None, n, idx_ptr or None, idx_count_ptr or None, idx_cap, _tail(tail),
+                                 FLAG_ON_DEVICE, out_text_ptr or None, text_cap, out_offsets_ptr or None, out_bytes_ptr or None,
+                                 stream or None))
+
+
+def gather_spans_device(raw_ptr: int, size: int, spans_ptr: int, out_bytes_ptr: int, span_count_ptr=0, span_cap=0, tail=None,
+                        out_text_ptr=0, text_cap=0, out_offsets_ptr=0, stream: int = 0):
+    """pire_hip_gather_spans with PIRE_HIP_RUN_ON_DEVICE: raw device addresses, only enqueues on `stream`."""
+    _check(lib().pire_hip_gather_spans(raw_ptr or None, size, spans_ptr or None, span_count_ptr or None, span_cap, _tail(tail),
+                                       FLAG_ON_DEVICE, out_text_ptr or None, text_cap, out_offsets_ptr or None, out_bytes_ptr or None,
+                                       stream or None))
 
 
 class Table:
@@ -663,6 +722,36 @@ class Table:
         _check(lib().pire_hip_run_lines_select(self._h, raw_ptr or None, size, delim, flags | FLAG_ON_DEVICE, want_ptr or None,
                                                out_line_count_ptr or None, out_hits_ptr or None, out_hit_spans_ptr or None,
                                                out_hit_masks_ptr or None, hit_cap, out_hit_count_ptr or None, stream or None))
+
+    # --- raw bytes in, the matching lines out as bytes (pire_hip_run_lines_gather)
+    def run_lines_gather_host(self, raw, delim: int = 10, flags=FLAG_BEGIN | FLAG_END, want=None, tail=-1, hit_cap=None,
+                              text_cap=None):
+        """pire_hip_run_lines_gather on a host buffer: {"lines", "hits", "count", "text", "offsets", "bytes"}.  tail -1 = the
+        delimiter (grep's output), None = none; hit_cap None = room for a hit on every line, text_cap None = for all of them."""
+        raw = _raw_bytes(raw)
+        wm = self.want_mask(want)
+        cap = raw.size if hit_cap is None else int(hit_cap)
+        room = raw.size + cap if text_cap is None else int(text_cap)
+        hits = np.zeros(cap, dtype=np.uint64)
+        text = np.zeros(max(room, 1), dtype=np.uint8)
+        offsets = np.zeros(cap + 1, dtype=np.uint64)
+        lines, cnt, total = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().pire_hip_run_lines_gather(self._h, raw.ctypes.data if raw.size else None, raw.size, delim, flags & ~FLAG_ON_DEVICE,
+                                               _np_ptr(wm), _tail(delim if tail == -1 else tail), C.byref(lines),
+                                               hits.ctypes.data if cap else None, cap, C.byref(cnt), text.ctypes.data if room else None,
+                                               room, offsets.ctypes.data, C.byref(total), None))
+        k = min(int(cnt.value), cap)
+        return {"lines": int(lines.value), "hits": hits[:k], "count": int(cnt.value), "text": text[:min(int(total.value), room)],
+                "offsets": offsets[:k + 1], "bytes": int(total.value)}
+
+    def run_lines_gather_device(self, raw_ptr: int, size: int, flags, out_line_count_ptr: int, out_hit_count_ptr: int,
+                                out_bytes_ptr: int, delim: int = 10, tail=-1, want_ptr=0, out_hits_ptr=0, hit_cap=0, out_text_ptr=0,
+                                text_cap=0, out_offsets_ptr=0, stream: int = 0):
+        """pire_hip_run_lines_gather on device pointers (synchronises `stream` once, as run_lines_select_device does)."""
+        _check(lib().pire_hip_run_lines_gather(self._h, raw_ptr or None, size, delim, flags | FLAG_ON_DEVICE, want_ptr or None,
+                                               _tail(delim if tail == -1 else tail), out_line_count_ptr or None, out_hits_ptr or None,
+                                               hit_cap, out_hit_count_ptr or None, out_text_ptr or None, text_cap,
+                                               out_offsets_ptr or None, out_bytes_ptr or None, stream or None))
 
     def run_half_final(self, text, offsets, flags=FLAG_BEGIN | FLAG_END):
         """The table walked as a Pire::HalfFinalScanner: (StateIndex, Final, Result[n, regexps]) for host strings."""

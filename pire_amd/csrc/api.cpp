@@ -1818,22 +1818,79 @@ try {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
 
-int pire_hip_run_lines_select(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
-                              const uint64_t* want, uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_hit_spans,
-                              uint64_t* out_hit_masks, uint64_t hit_cap, uint64_t* out_hit_count, void* streamPtr)
-try {
-	if (int rc = SelectArgsInvalid(t, nullptr, false, 0, out_hits, out_hit_masks, hit_cap, out_hit_count))
+namespace {
+
+// What pire_hip_run_lines_gather adds to pire_hip_run_lines_select: where the bytes of the selected lines go
+struct LinesGather {
+	uint32_t tail;
+	void* outText;
+	uint64_t textCap;
+	uint64_t* outOffsets;
+	uint64_t* outBytes;
+};
+
+// What the gather entry points refuse of their outputs before any device is touched.  capAlias: what this entry point
+// calls idx_cap where it has another name for it (the message names both), else nullptr.
+int GatherOutputsInvalid(const char* who, const char* capAlias, uint64_t cap, uint32_t tail, const void* outText, uint64_t textCap,
+                         const void* outOffsets, const void* outBytes)
+{
+	const char* what = !outBytes                                      ? "null out_bytes"
+	                   : tail != PIRE_HIP_GATHER_NO_TAIL && tail > 255 ? "tail > 255"
+	                   : cap && !outOffsets                            ? "idx_cap > 0 with null out_offsets"
+	                   : textCap && !outText                           ? "text_cap > 0 with null out_text"
+	                                                                   : nullptr;
+	if (!what)
+		return PIRE_HIP_OK;
+	const bool aliased = capAlias && cap && !outOffsets && outBytes && !(tail != PIRE_HIP_GATHER_NO_TAIL && tail > 255);
+	SetError(std::string(who) + ": " + what + (aliased ? std::string(" (idx_cap = ") + capAlias + ")" : ""));
+	return PIRE_HIP_EINVAL;
+}
+
+int GatherRefuse(const char* who, const char* what)
+{
+	SetError(std::string(who) + ": " + what);
+	return PIRE_HIP_EINVAL;
+}
+
+int GatherOverlaps(const char* who, const void* source, uint64_t size, const void* outText, uint64_t textCap)
+{
+	const uintptr_t r = reinterpret_cast<uintptr_t>(source), o = reinterpret_cast<uintptr_t>(outText);
+	if (!(outText && size && textCap && o < r + size && r < o + textCap))
+		return PIRE_HIP_OK;
+	SetError(std::string(who) + ": out_text overlaps the source (the pass is not in-place)");
+	return PIRE_HIP_EINVAL;
+}
+
+int RunLinesImpl(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags, const uint64_t* want,
+                 uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_hit_spans, uint64_t* out_hit_masks, uint64_t hit_cap,
+                 uint64_t* out_hit_count, void* streamPtr, const LinesGather* gather)
+{
+	const char* who = gather ? "pire_hip_run_lines_gather" : "pire_hip_run_lines_select";
+	// (the gather form keeps the hit list to itself where the caller has no array for it)
+	if (int rc = SelectArgsInvalid(t, nullptr, false, 0, out_hits, out_hit_masks, gather && !out_hits ? 0 : hit_cap, out_hit_count))
 		return rc;
-	if (int rc = SplitArgsInvalid("pire_hip_run_lines_select", raw, size, delim, out_line_count, "out_line_count"))
+	if (int rc = SplitArgsInvalid(who, raw, size, delim, out_line_count, "out_line_count"))
 		return rc;
 	if (out_hit_spans && !out_hits) {
 		SetError("pire_hip_run_lines_select: out_hit_spans without out_hits");
 		return PIRE_HIP_EINVAL;
 	}
+	if (gather) {
+		if (int rc = GatherOutputsInvalid(who, "hit_cap", hit_cap, gather->tail, gather->outText, gather->textCap, gather->outOffsets,
+		                                  gather->outBytes))
+			return rc;
+		if (int rc = GatherOverlaps(who, raw, size, gather->outText, gather->textCap))
+			return rc;
+	}
 	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
 	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
 	if (!onDevice && size == 0) {
 		*out_line_count = *out_hit_count = 0;
+		if (gather) {
+			*gather->outBytes = 0;
+			if (gather->outOffsets)
+				gather->outOffsets[0] = 0;
+		}
 		return PIRE_HIP_OK;
 	}
 	const uint32_t words = pire_hip_table_mask_words(t);
@@ -1845,23 +1902,28 @@ try {
 	if (want)
 		if (int rc = io.In(want, size_t(words), &dWant))
 			return rc;
-	uint64_t n = 0, count = 0;   // host pointers: the counts come back here first
+	uint64_t n = 0, count = 0, bytes = 0;   // host pointers: the counts come back here first
 	uint64_t *dN = nullptr, *dCount = nullptr, *dHits = nullptr, *dSpans = nullptr, *dHitMasks = nullptr;
+	uint64_t *dBytes = nullptr, *dOutOffsets = nullptr;
+	uint8_t* dOutText = nullptr;
 	if (int rc = io.Result(onDevice ? out_line_count : &n, 1, 1, &dN))
 		return rc;
 	if (int rc = io.Result(onDevice ? out_hit_count : &count, 1, 1, &dCount))
 		return rc;
+	if (gather)
+		if (int rc = io.Result(onDevice ? gather->outBytes : &bytes, 1, 1, &dBytes))
+			return rc;
 	if (int rc = io.Ready())
 		return rc;
 	// the split, into scratch that lives until the scan and the gather behind it are enqueued; n sizes the offsets
-	StreamScratch tiles(stream), text(stream), offsets(stream);
+	StreamScratch tiles(stream), text(stream), offsets(stream), ownHits(stream), ownSpans(stream);
 	SplitPlan plan;
 	if (int rc = LaunchSplitCount(dRaw, size, delim, dN, stream, tiles, &plan))
 		return rc;
 	if (int rc = ReadCount(dN, &n, stream))
 		return rc;
 	if (n >= (1ull << 32)) {
-		SetError("pire_hip_run_lines_select: 2^32 lines or more in one call");
+		SetError(std::string(who) + ": 2^32 lines or more in one call");
 		return PIRE_HIP_EUNSUPPORTED;
 	}
 	if (int rc = text.Alloc(size_t(size) + 16, "hipMallocAsync(split text)"))
@@ -1881,6 +1943,26 @@ try {
 			if (int rc = io.Result(out_hit_masks, size_t(cap) * words, 0, &dHitMasks))
 				return rc;
 	}
+	uint64_t textRoom = 0;   // of out_text: the k lines and their tails are size + k bytes at most
+	if (gather && cap) {
+		if (!dHits) {
+			if (int rc = ownHits.Alloc(size_t(cap) * 8, "hipMallocAsync(hits)"))
+				return rc;
+			dHits = ownHits.as<uint64_t>();
+		}
+		if (!dSpans) {
+			if (int rc = ownSpans.Alloc(size_t(cap) * 16, "hipMallocAsync(hit spans)"))
+				return rc;
+			dSpans = ownSpans.as<uint64_t>();
+		}
+		textRoom = std::min(gather->textCap, size + cap);
+		if (textRoom)
+			if (int rc = io.Result(static_cast<uint8_t*>(gather->outText), size_t(textRoom), 0, &dOutText))
+				return rc;
+	}
+	if (gather && gather->outOffsets)
+		if (int rc = io.Result(gather->outOffsets, size_t(cap) + 1, 0, &dOutOffsets))
+			return rc;
 	if (n == 0) {
 		const hipError_t e = hipMemsetAsync(dCount, 0, 8, stream);
 		if (e != hipSuccess)
@@ -1894,6 +1976,12 @@ try {
 			if (int rc = LaunchSplitSpans(dHits, dCount, cap, offsets.as<uint64_t>(), dSpans, stream))
 				return rc;
 	}
+	if (gather) {
+		// straight from raw, through the spans (cap == 0: *out_bytes = 0 and out_offsets[0] = 0, nothing is read)
+		const GatherSource src = {dRaw, nullptr, 0, nullptr, dSpans, size};
+		if (int rc = LaunchGather(src, dCount, cap, gather->tail, dOutText, textRoom, dOutOffsets, dBytes, kGatherTotalUnknown, stream))
+			return rc;
+	}
 	if (int rc = io.Finish())
 		return rc;
 	if (onDevice)
@@ -1901,16 +1989,151 @@ try {
 	*out_line_count = n;
 	*out_hit_count = count;
 	const uint64_t written = std::min<uint64_t>(count, dHits ? cap : 0);
-	if (written) {
-		hipError_t e = hipMemcpy(out_hits, dHits, size_t(written) * 8, hipMemcpyDeviceToHost);
-		if (e == hipSuccess && dSpans)
+	hipError_t e = hipSuccess;
+	if (written && out_hits) {
+		e = hipMemcpy(out_hits, dHits, size_t(written) * 8, hipMemcpyDeviceToHost);
+		if (e == hipSuccess && out_hit_spans)
 			e = hipMemcpy(out_hit_spans, dSpans, size_t(written) * 16, hipMemcpyDeviceToHost);
 		if (e == hipSuccess && dHitMasks)
 			e = hipMemcpy(out_hit_masks, dHitMasks, size_t(written) * words * 8, hipMemcpyDeviceToHost);
-		if (e != hipSuccess)
-			return HipFail(e, "hipMemcpy(hits)");
 	}
-	return PIRE_HIP_OK;
+	if (gather) {
+		*gather->outBytes = bytes;
+		if (e == hipSuccess && dOutOffsets)
+			e = hipMemcpy(gather->outOffsets, dOutOffsets, (size_t(written) + 1) * 8, hipMemcpyDeviceToHost);
+		if (e == hipSuccess && std::min(bytes, textRoom))
+			e = hipMemcpy(gather->outText, dOutText, size_t(std::min(bytes, textRoom)), hipMemcpyDeviceToHost);
+	}
+	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(hits)");
+}
+
+// Both gather entry points behind their checks.  spans == nullptr: text + offsets[n + 1] + idx; else raw = text, `size` bytes.
+int GatherImpl(const char* who, const void* text, const uint64_t* offsets, uint64_t n, const uint64_t* idx, const uint64_t* spans,
+               uint64_t size, const uint64_t* count, uint64_t cap, uint32_t tail, uint32_t flags, void* outText, uint64_t textCap,
+               uint64_t* outOffsets, uint64_t* outBytes, void* streamPtr)
+{
+	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+	if (flags & PIRE_HIP_RUN_ON_DEVICE) {
+		const GatherSource src = {static_cast<const uint8_t*>(text), offsets, n, idx, spans, size};
+		return LaunchGather(src, count, cap, tail, outText, textCap, outOffsets, outBytes, kGatherTotalUnknown, stream);
+	}
+	// the host's own look at what it is asked to copy: total = the bytes of the k strings and their tails (offsets that
+	// decrease make it meaningless -- BatchIO::Text refuses them below, before anything is written)
+	const uint64_t k = std::min(count ? *count : cap, cap);
+	uint64_t total = tail != PIRE_HIP_GATHER_NO_TAIL ? k : 0;
+	if (spans) {
+		for (uint64_t j = 0; j < k; ++j) {
+			if (spans[2 * j] > spans[2 * j + 1] || spans[2 * j + 1] > size)
+				return GatherRefuse(who, "span out of range");
+			total += spans[2 * j + 1] - spans[2 * j];
+		}
+	} else {
+		for (uint64_t j = 0; j < k; ++j) {
+			const uint64_t s = idx ? idx[j] : j;
+			if (s >= n)
+				return GatherRefuse(who, "index out of range");
+			total += offsets[s + 1] - offsets[s];
+		}
+		if (k)
+			if (int rc = GatherOverlaps(who, text, offsets[n], outText, textCap))
+				return rc;
+	}
+	if (k == 0) {
+		*outBytes = 0;
+		if (outOffsets)
+			outOffsets[0] = 0;
+		return PIRE_HIP_OK;
+	}
+	BatchIO io(stream, false);
+	GatherSource src = {nullptr, nullptr, n, nullptr, nullptr, size};
+	if (spans) {
+		if (int rc = io.In(static_cast<const uint8_t*>(text), size_t(size), &src.text))
+			return rc;
+		if (int rc = io.In(spans, size_t(k) * 2, &src.spans))
+			return rc;
+	} else {
+		if (int rc = io.Text(text, offsets, n, 0, 0, &src.text, &src.offsets))
+			return rc;
+		if (idx)
+			if (int rc = io.In(idx, size_t(k), &src.idx))
+				return rc;
+	}
+	uint64_t *dBytes = nullptr, *dOutOffsets = nullptr;
+	uint8_t* dOutText = nullptr;
+	const uint64_t room = std::min(total, textCap);
+	if (int rc = io.Result(outBytes, 1, 1, &dBytes))
+		return rc;
+	if (int rc = io.Result(outOffsets, size_t(k) + 1, size_t(k) + 1, &dOutOffsets))
+		return rc;
+	if (room)
+		if (int rc = io.Result(static_cast<uint8_t*>(outText), size_t(room), size_t(room), &dOutText))
+			return rc;
+	if (int rc = io.Ready())
+		return rc;
+	if (int rc = LaunchGather(src, nullptr, k, tail, dOutText, room, dOutOffsets, dBytes, total, stream))
+		return rc;
+	return io.Finish();
+}
+
+}  // namespace
+
+int pire_hip_run_lines_select(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
+                              const uint64_t* want, uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_hit_spans,
+                              uint64_t* out_hit_masks, uint64_t hit_cap, uint64_t* out_hit_count, void* stream)
+try {
+	return RunLinesImpl(t, raw, size, delim, flags, want, out_line_count, out_hits, out_hit_spans, out_hit_masks, hit_cap,
+	                    out_hit_count, stream, nullptr);
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+// ---- the selected strings gathered into a batch (gather.hip) -------------------------------------------------------------
+int pire_hip_gather(const void* text, const uint64_t* offsets, uint64_t n, const uint64_t* idx, const uint64_t* idx_count,
+                    uint64_t idx_cap, uint32_t tail, uint32_t flags, void* out_text, uint64_t text_cap, uint64_t* out_offsets,
+                    uint64_t* out_bytes, void* stream)
+try {
+	const char* who = "pire_hip_gather";
+	if (int rc = GatherOutputsInvalid(who, nullptr, idx_cap, tail, out_text, text_cap, out_offsets, out_bytes))
+		return rc;
+	if (idx_cap && !offsets)
+		return GatherRefuse(who, "idx_cap > 0 with null offsets");
+	if (idx_cap > n && !idx)
+		return GatherRefuse(who, "idx_cap > n without idx");
+	if (idx_cap >= (1ull << 32))
+		return GatherRefuse(who, "2^32 strings or more in one call");
+	return GatherImpl(who, text, offsets, n, idx, nullptr, 0, idx_count, idx_cap, tail, flags, out_text, text_cap, out_offsets,
+	                  out_bytes, stream);
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_gather_spans(const void* raw, uint64_t size, const uint64_t* spans, const uint64_t* span_count, uint64_t span_cap,
+                          uint32_t tail, uint32_t flags, void* out_text, uint64_t text_cap, uint64_t* out_offsets,
+                          uint64_t* out_bytes, void* stream)
+try {
+	const char* who = "pire_hip_gather_spans";
+	if (int rc = GatherOutputsInvalid(who, "span_cap", span_cap, tail, out_text, text_cap, out_offsets, out_bytes))
+		return rc;
+	if (span_cap && !spans)
+		return GatherRefuse(who, "span_cap > 0 with null spans");
+	if (span_cap >= (1ull << 32))
+		return GatherRefuse(who, "2^32 strings or more in one call");
+	if (int rc = GatherOverlaps(who, raw, size, out_text, text_cap))
+		return rc;
+	return GatherImpl(who, raw, nullptr, 0, nullptr, spans, size, span_count, span_cap, tail, flags, out_text, text_cap,
+	                  out_offsets, out_bytes, stream);
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_run_lines_gather(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
+                              const uint64_t* want, uint32_t tail, uint64_t* out_line_count, uint64_t* out_hits, uint64_t hit_cap,
+                              uint64_t* out_hit_count, void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes,
+                              void* stream)
+try {
+	const LinesGather gather = {tail, out_text, text_cap, out_offsets, out_bytes};
+	return RunLinesImpl(t, raw, size, delim, flags, want, out_line_count, out_hits, nullptr, nullptr, hit_cap, out_hit_count, stream,
+	                    &gather);
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }

@@ -1086,6 +1086,22 @@ int LaunchSplitScatter(const SplitPlan& plan, void* outText, uint64_t* outOffset
                        hipStream_t stream);
 int LaunchSplitSpans(const uint64_t* hits, const uint64_t* hitCount, uint64_t cap, const uint64_t* offsets, uint64_t* spans,
                      hipStream_t stream);
+// gather.hip: the listed strings of a batch back to back (pire_hip_gather).  Device pointers only, four kernels enqueued on
+// `stream`, no scratch and no allocation (outOffsets, cap + 1 entries, is required where cap > 0).  Where the source ranges come from:
+// spans != nullptr -> raw[spans[2j], spans[2j + 1]) with raw = text and `size` its length; else offsets + idx (nullable:
+// the identity) over n strings.  hostTotal: the total where the host knows it (it sizes the copy pass's grid exactly),
+// kGatherTotalUnknown where it does not (the grid then comes from textCap, and blocks beyond *outBytes leave).
+struct GatherSource {
+	const uint8_t* text;
+	const uint64_t* offsets;
+	uint64_t n;
+	const uint64_t* idx;
+	const uint64_t* spans;
+	uint64_t size;
+};
+constexpr uint64_t kGatherTotalUnknown = ~0ull;
+int LaunchGather(const GatherSource& src, const uint64_t* count, uint64_t cap, uint32_t tail, void* outText, uint64_t textCap,
+                 uint64_t* outOffsets, uint64_t* outBytes, uint64_t hostTotal, hipStream_t stream);
 void NoteKernel(const char* name, const char* symbol = nullptr);   // what pire_hip_last_kernel[_symbol]() report (thread local)
 bool RaggedActEligible(const ScanParams& p);
 int LaunchRaggedHalfFinal(const ScanParams& p, unsigned long long* workCounter, uint32_t* outResults, hipStream_t stream);
