@@ -876,6 +876,74 @@ int pire_hip_counting_run(pire_hip_counting_table* t, int kind, const void* text
 int pire_hip_capture_run(pire_hip_counting_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
                          uint32_t* out_state_idx, uint8_t* out_final, int64_t* out_begin, int64_t* out_end, void* stream);
 
+/* ---- the captured substrings, on the device ------------------------------------------------------------------- */
+
+/*
+ * From capture positions to byte ranges: the strings that captured, as a compacted, ascending list, and where their
+ * captured text lies -- the input of pire_hip_gather_spans.  It takes no table and no text: it reads what
+ * pire_hip_capture_run wrote (begin, end, final of the same n strings, offsets[n + 1]), behind any of the capture kernels.
+ *   B           = (flags & PIRE_HIP_RUN_BEGIN) ? 1 : 0          the BeginMark step is counted (capture.h:96-116)
+ *   len_i       = offsets[i + 1] - offsets[i]
+ *   captured(i) = begin[i] >= 0 && end[i] >= 0                    State::Captured(), capture.h:61
+ *   selected(i) = captured(i) && (!need_final || final[i] != 0)
+ *   b_i         = clamp(begin[i] - B, 0, len_i)
+ *   e_i         = clamp(end[i]   - B, b_i, len_i)
+ *   span(i)     = [offsets[i] + b_i, offsets[i] + e_i)            a byte range of `text`
+ * out_hits[hit_cap] (nullable): the indices of the selected strings, ascending.  out_spans[hit_cap][2] (nullable, and it
+ * does not need out_hits): their spans.  *out_hit_count (required): the number of selected strings, also when it exceeds
+ * hit_cap; only the first min(count, hit_cap) entries are written, nothing behind them.  n == 0 writes a count of 0.
+ * n < 2^32.
+ * The clamp: for a well-formed capture the span is exactly the reference's [str + Begin() - 1, str + End() - 1)
+ * (capture_ut.cpp:85-91), [str + Begin(), str + End()) for a runner that never called Begin().  That helper is undefined
+ * where an action fires on the BeginMark step (begin == 0 under Begin()) and where end < begin; a device pass must not
+ * be.  Such a string is still captured, as the reference says: it stays in the list, its range clamped into the string,
+ * possibly empty.  So a span never leaves [offsets[i], offsets[i + 1]], whatever int64 the ON_DEVICE form is given.
+ * flags: PIRE_HIP_RUN_BEGIN -> the flag the capture call was made with.  PIRE_HIP_RUN_ON_DEVICE -> every pointer is a
+ *        device pointer and the call only enqueues on `stream`: three kernels (classify per tile of 1 024 strings, the
+ *        one-block scan of pire_hip_select, scatter), no atomics -- the same input gives the same bits.  Scratch
+ *        (n / 8 + n / 256 bytes) comes from the stream-ordered allocator: the rule and the capture-mode caveat stated at
+ *        pire_hip_select.  Otherwise host pointers: staged, synchronises.
+ * PIRE_HIP_EINVAL before any device is touched: null out_hit_count; n > 0 with null offsets, begin or end; need_final
+ * with null final; hit_cap > 0 with null out_hits and null out_spans; n >= 2^32.
+ * pire_hip_last_kernel() is not changed by the pass.  No first-use self-test (as pire_hip_select).
+ */
+int pire_hip_capture_select(const uint64_t* offsets, uint64_t n, uint32_t flags,
+                            const int64_t* begin, const int64_t* end, const uint8_t* final, int need_final,
+                            uint64_t* out_hits, uint64_t* out_spans, uint64_t hit_cap, uint64_t* out_hit_count, void* stream);
+
+/*
+ * pire_hip_capture_run followed by pire_hip_capture_select on the same stream.  t .. flags (BEGIN / END / ON_DEVICE /
+ * GENERIC): as pire_hip_capture_run; the pass gets flags & PIRE_HIP_RUN_BEGIN.  out_state_idx, out_final, out_begin and
+ * out_end are all nullable here: what the pass needs and the caller has no array for lives in stream-ordered scratch of
+ * the library's own.  With host pointers the text is staged once, and scan and pass run on the staged copy before
+ * anything comes back.  It refuses what pire_hip_capture_run refuses (the null position arrays excepted) and what
+ * pire_hip_capture_select refuses.  pire_hip_last_kernel() names the capture kernel.
+ */
+int pire_hip_capture_run_select(pire_hip_counting_table* t, const void* text, const uint64_t* offsets, uint64_t n,
+                                uint32_t flags, int need_final,
+                                uint32_t* out_state_idx, uint8_t* out_final, int64_t* out_begin, int64_t* out_end,
+                                uint64_t* out_hits, uint64_t* out_spans, uint64_t hit_cap, uint64_t* out_hit_count,
+                                void* stream);
+
+/*
+ * Raw bytes in, the captured field of every line that captured out: pire_hip_run_lines_gather for a capturing scanner
+ * (`grep -o` with one pair of parentheses).  The split into scratch, the capture scan on the lines, the pass -- its
+ * spans counted in raw: line i of the split buffer lies i bytes further into raw --, the gather from raw through them.
+ * out_line_count, delim, the one synchronisation of `stream` and the refusal of 2^32 lines (PIRE_HIP_EUNSUPPORTED): as
+ * pire_hip_run_lines_select.  out_hits (nullable): the numbers of the lines that captured; out_spans (nullable): byte
+ * ranges of raw; need_final, hit_cap, out_hit_count: as pire_hip_capture_select.  tail, out_text, text_cap, out_offsets
+ * (hit_cap + 1 entries), out_bytes: as pire_hip_gather_spans.  All four gather outputs null (text_cap == 0): spans only,
+ * the gather is skipped; any other combination of nulls is what pire_hip_gather refuses.  Host pointers with size == 0:
+ * zeros (out_offsets[0] = 0 where it is not null), no device is touched.  It also refuses delim > 255, null
+ * out_line_count, size > 0 with null raw, out_text overlapping raw, and what pire_hip_capture_select refuses.
+ */
+int pire_hip_capture_lines_gather(pire_hip_counting_table* t, const void* raw, uint64_t size, uint32_t delim,
+                                  uint32_t flags, int need_final, uint32_t tail,
+                                  uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_spans,
+                                  uint64_t hit_cap, uint64_t* out_hit_count,
+                                  void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes,
+                                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

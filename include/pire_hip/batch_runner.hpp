@@ -970,12 +970,20 @@ private:
  * per string State::Captured(), Begin(), End() and Final after Initialize + Begin() + Run() + End(), as
  * tests/capture_ut.cpp:75-83 drives it.  The captured text of string i is
  * [text + offsets[i] + Begin(i) - 1, text + offsets[i] + End(i) - 1) (capture_ut.cpp:85-91).
+ * The captured substrings without a loop on the host (include/pire_hip.h, "the captured substrings, on the device"):
+ *     run.Begin().Run(text, offsets, n).End();      run.CapturedLines()  the strings that captured, ascending
+ *                                                   run.CapturedSpans()  [begin, end) of their captured text in `text`, 2 per string
+ *     run.Begin().RunLines(raw, size).End();        the same per line of raw (spans: byte ranges of raw), and
+ *     run.CapturedText()                            the captured fields back to back, '\n' (or the byte given) behind each:
+ *                                                   `grep -o` with one pair of parentheses, gathered on the device
+ *     run.CapturedTextOffsets()                     field k is CapturedText()[o[k], o[k + 1])
  */
 #ifdef PIRE_EXTRA_CAPTURE_H
 class CaptureBatchRunner {
 public:
 	explicit CaptureBatchRunner(const Pire::CapturingScanner& sc)
-	    : m_table(nullptr), m_flags(0), m_text(nullptr), m_offsets(nullptr), m_n(0), m_ran(false)
+	    : m_table(nullptr), m_flags(0), m_text(nullptr), m_offsets(nullptr), m_n(0), m_ran(false), m_lines(false), m_len(0),
+	      m_delim('\n'), m_listed(false), m_textFetched(false), m_textTail('\n'), m_lineCount(0)
 	{
 		std::ostringstream out;
 		sc.Save(&out);                                    // LoadedScanner::Save, scanner_io.cpp:172-189
@@ -991,7 +999,17 @@ public:
 		m_text = text;
 		m_offsets = offsets;
 		m_n = n;
-		m_ran = false;
+		m_ran = m_lines = m_listed = m_textFetched = false;
+		return *this;
+	}
+	/* One raw buffer, cut into lines at `delim` on the device; the accessors per string do not follow it */
+	CaptureBatchRunner& RunLines(const char* raw, size_t size, char delim = '\n')
+	{
+		m_text = raw;
+		m_len = size;
+		m_delim = uint8_t(delim);
+		m_lines = true;
+		m_ran = m_listed = m_textFetched = false;
 		return *this;
 	}
 	CaptureBatchRunner& Run(const std::vector<ystring>& strings)
@@ -1011,9 +1029,22 @@ public:
 	bool Final(size_t i) { Execute(); return m_final[i] != 0; }
 	size_t StateIndex(size_t i) { Execute(); return m_idx[i]; }
 
+	const std::vector<uint64_t>& CapturedLines() { FetchList(); return m_hits; }
+	const std::vector<uint64_t>& CapturedSpans() { FetchList(); return m_spans; }
+	size_t LineCount() { FetchList(); return size_t(m_lineCount); }
+	const std::string& CapturedText(char tail = '\n') { FetchText(tail); return m_capturedText; }
+	const std::vector<uint64_t>& CapturedTextOffsets()
+	{
+		if (!m_textFetched)
+			FetchText('\n');
+		return m_capturedOffsets;
+	}
+
 private:
 	void Execute()
 	{
+		if (m_lines)
+			throw Pire::Error("pire_hip: the accessors per string follow Run(), not RunLines()");
 		if (m_ran)
 			return;
 		m_idx.assign(m_n, 0);
@@ -1024,6 +1055,67 @@ private:
 		Check(pire_hip_capture_run(m_table, m_text, m_n ? m_offsets : kNoOffsets, m_n, m_flags, m_idx.data(), m_final.data(),
 		                           m_begin.data(), m_end.data(), nullptr));
 		m_ran = true;
+	}
+
+	/* The list of the strings (lines) that captured and their spans: one call -- for RunLines() with room for a capture on
+	 * every line of 64 bytes or more, and a second call where there are more */
+	void FetchList()
+	{
+		if (m_listed)
+			return;
+		uint64_t count = 0;
+		if (!m_lines) {
+			m_idx.assign(m_n, 0);
+			m_final.assign(m_n, 0);
+			m_begin.assign(m_n, -1);
+			m_end.assign(m_n, -1);
+			m_hits.resize(m_n);
+			m_spans.resize(m_n * 2);
+			static const uint64_t kNoOffsets[1] = {0};
+			Check(pire_hip_capture_run_select(m_table, m_text, m_n ? m_offsets : kNoOffsets, m_n, m_flags, 0, m_idx.data(), m_final.data(),
+			                                  m_begin.data(), m_end.data(), m_hits.data(), m_spans.data(), m_n, &count, nullptr));
+			m_lineCount = m_n;
+			m_ran = true;
+		} else {
+			for (size_t cap = m_len / 64 + 1024;; cap = count) {
+				m_hits.resize(cap);
+				m_spans.resize(cap * 2);
+				Check(pire_hip_capture_lines_gather(m_table, m_text, m_len, m_delim, m_flags, 0, PIRE_HIP_GATHER_NO_TAIL, &m_lineCount,
+				                                    m_hits.data(), m_spans.data(), cap, &count, nullptr, 0, nullptr, nullptr, nullptr));
+				if (count <= cap)
+					break;
+			}
+		}
+		m_hits.resize(count);
+		m_spans.resize(count * 2);
+		m_listed = true;
+	}
+
+	/* RunLines(): the captured fields as bytes (and the list with them); the grow-and-retry of FetchList() */
+	void FetchText(char tail)
+	{
+		if (!m_lines)
+			throw Pire::Error("pire_hip: CapturedText() follows RunLines()");
+		if (m_textFetched && m_textTail == tail)
+			return;
+		uint64_t count = 0, bytes = 0;
+		for (size_t cap = m_listed ? m_hits.size() : m_len / 64 + 1024;; cap = count) {
+			m_hits.resize(cap);
+			m_spans.resize(cap * 2);
+			m_capturedOffsets.resize(cap + 1);
+			m_capturedText.resize(m_len + cap + 1);
+			Check(pire_hip_capture_lines_gather(m_table, m_text, m_len, m_delim, m_flags, 0, uint8_t(tail), &m_lineCount, m_hits.data(),
+			                                    m_spans.data(), cap, &count, &m_capturedText[0], m_capturedText.size(),
+			                                    m_capturedOffsets.data(), &bytes, nullptr));
+			if (count <= cap && bytes <= m_capturedText.size())
+				break;
+		}
+		m_hits.resize(count);
+		m_spans.resize(count * 2);
+		m_capturedText.resize(bytes);
+		m_capturedOffsets.resize(count + 1);
+		m_textTail = tail;
+		m_listed = m_textFetched = true;
 	}
 
 	CaptureBatchRunner(const CaptureBatchRunner&);
@@ -1039,6 +1131,14 @@ private:
 	std::vector<int64_t> m_begin, m_end;
 	ystring m_ownText;
 	std::vector<uint64_t> m_ownOffsets;
+	bool m_lines;                 // RunLines(): m_text is the raw buffer of m_len bytes
+	size_t m_len;
+	uint8_t m_delim;
+	bool m_listed, m_textFetched;
+	char m_textTail;
+	uint64_t m_lineCount;
+	std::vector<uint64_t> m_hits, m_spans, m_capturedOffsets;
+	std::string m_capturedText;
 };
 #endif  // PIRE_EXTRA_CAPTURE_H
 

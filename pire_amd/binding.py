@@ -211,6 +211,14 @@ ABI = [
                                         C.c_void_p, C.c_void_p]),
     ("pire_hip_capture_run", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_capture_select", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_capture_run_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                              C.c_void_p]),
+    ("pire_hip_capture_lines_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_multi_create", C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
     ("pire_hip_multi_destroy", None, [C.c_void_p]),
     ("pire_hip_multi_device_count", C.c_int, [C.c_void_p]),
@@ -403,6 +411,35 @@ def gather_spans_device(raw_ptr: int, size: int, spans_ptr: int, out_bytes_ptr: 
     _check(lib().pire_hip_gather_spans(raw_ptr or None, size, spans_ptr or None, span_count_ptr or None, span_cap, _tail(tail),
                                        FLAG_ON_DEVICE, out_text_ptr or None, text_cap, out_offsets_ptr or None, out_bytes_ptr or None,
                                        stream or None))
+
+
+# --- from capture positions to byte ranges (pire_hip_capture_select)
+def capture_select_host(offsets, begin, end, final=None, flags=FLAG_BEGIN, need_final=False, hit_cap: Optional[int] = None,
+                        want_hits=True, want_spans=True):
+    """pire_hip_capture_select on host arrays: (hits u64[k] or None, spans u64[k, 2] or None, count), k = min(count, hit_cap).
+    flags: FLAG_BEGIN where the capture call had it; hit_cap None = room for every string."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    begin = np.ascontiguousarray(begin, dtype=np.int64)
+    end = np.ascontiguousarray(end, dtype=np.int64)
+    final = None if final is None else np.ascontiguousarray(final, dtype=np.uint8)
+    n = len(offsets) - 1
+    cap = n if hit_cap is None else int(hit_cap)
+    hits = np.zeros(cap, dtype=np.uint64) if want_hits else None
+    spans = np.zeros((cap, 2), dtype=np.uint64) if want_spans else None
+    cnt = C.c_uint64(0)
+    _check(lib().pire_hip_capture_select(offsets.ctypes.data, n, flags & FLAG_BEGIN, begin.ctypes.data if n else None,
+                                         end.ctypes.data if n else None, _np_ptr(final), int(bool(need_final)),
+                                         _np_ptr(hits) if cap else None, _np_ptr(spans) if cap else None, cap, C.byref(cnt), None))
+    k = min(int(cnt.value), cap)
+    return (None if hits is None else hits[:k]), (None if spans is None else spans[:k]), int(cnt.value)
+
+
+def capture_select_device(offsets_ptr: int, n: int, flags, begin_ptr: int, end_ptr: int, out_hit_count_ptr: int, final_ptr=0,
+                          need_final=False, out_hits_ptr=0, out_spans_ptr=0, hit_cap=0, stream: int = 0):
+    """pire_hip_capture_select with PIRE_HIP_RUN_ON_DEVICE: raw device addresses, only enqueues on `stream`."""
+    _check(lib().pire_hip_capture_select(offsets_ptr or None, n, (flags & FLAG_BEGIN) | FLAG_ON_DEVICE, begin_ptr or None,
+                                         end_ptr or None, final_ptr or None, int(bool(need_final)), out_hits_ptr or None,
+                                         out_spans_ptr or None, hit_cap, out_hit_count_ptr or None, stream or None))
 
 
 class Table:
@@ -951,6 +988,73 @@ class CountingTable:
         _check(lib().pire_hip_capture_run(self._h, text_ptr or None, offsets_ptr or None, n, flags | FLAG_ON_DEVICE,
                                           out_idx_ptr or None, out_final_ptr or None, out_begin_ptr or None,
                                           out_end_ptr or None, stream or None))
+
+    # --- the captured substrings as byte ranges (pire_hip_capture_run_select, pire_hip_capture_lines_gather)
+    def capture_select(self, text, offsets, flags=FLAG_BEGIN | FLAG_END, need_final=False, hit_cap: Optional[int] = None,
+                       positions=True):
+        """pire_hip_capture_run_select on host strings: {"hits", "spans", "count"} and, with positions, {"idx", "final",
+        "begin", "end"}; without, the library keeps those arrays to itself.  hit_cap None = room for every string."""
+        text = _raw_bytes(text)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        cap = n if hit_cap is None else int(hit_cap)
+        idx, fin = (np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint8)) if positions else (None, None)
+        b, e = (np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64)) if positions else (None, None)
+        hits = np.zeros(cap, dtype=np.uint64)
+        spans = np.zeros((cap, 2), dtype=np.uint64)
+        cnt = C.c_uint64(0)
+        _check(lib().pire_hip_capture_run_select(self._h, text.ctypes.data if text.size else None, offsets.ctypes.data, n,
+                                                 flags & ~FLAG_ON_DEVICE, int(bool(need_final)), _np_ptr(idx), _np_ptr(fin), _np_ptr(b),
+                                                 _np_ptr(e), hits.ctypes.data if cap else None, spans.ctypes.data if cap else None, cap,
+                                                 C.byref(cnt), None))
+        k = min(int(cnt.value), cap)
+        out = {"hits": hits[:k], "spans": spans[:k], "count": int(cnt.value)}
+        if positions:
+            out.update(idx=idx, final=fin, begin=b, end=e)
+        return out
+
+    def capture_select_device(self, text_ptr: int, offsets_ptr: int, n: int, flags, out_hit_count_ptr: int, need_final=False,
+                              out_idx_ptr=0, out_final_ptr=0, out_begin_ptr=0, out_end_ptr=0, out_hits_ptr=0, out_spans_ptr=0,
+                              hit_cap=0, stream: int = 0):
+        """pire_hip_capture_run_select on device pointers: only enqueues on `stream`."""
+        _check(lib().pire_hip_capture_run_select(self._h, text_ptr or None, offsets_ptr or None, n, flags | FLAG_ON_DEVICE,
+                                                 int(bool(need_final)), out_idx_ptr or None, out_final_ptr or None,
+                                                 out_begin_ptr or None, out_end_ptr or None, out_hits_ptr or None,
+                                                 out_spans_ptr or None, hit_cap, out_hit_count_ptr or None, stream or None))
+
+    def capture_lines_gather_host(self, raw, delim: int = 10, flags=FLAG_BEGIN | FLAG_END, need_final=False, tail=-1,
+                                  hit_cap=None, text_cap=None, gather=True):
+        """pire_hip_capture_lines_gather on a host buffer: {"lines", "hits", "spans", "count"} and, with gather, {"text",
+        "offsets", "bytes"}.  tail -1 = the delimiter, None = none; hit_cap None = room for a hit on every line, text_cap None
+        = for all of them."""
+        raw = _raw_bytes(raw)
+        cap = raw.size if hit_cap is None else int(hit_cap)
+        room = (raw.size + cap if text_cap is None else int(text_cap)) if gather else 0
+        hits = np.zeros(cap, dtype=np.uint64)
+        spans = np.zeros((cap, 2), dtype=np.uint64)
+        text = np.zeros(max(room, 1), dtype=np.uint8)
+        offsets = np.zeros(cap + 1, dtype=np.uint64)
+        lines, cnt, total = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().pire_hip_capture_lines_gather(self._h, raw.ctypes.data if raw.size else None, raw.size, delim,
+                                                   flags & ~FLAG_ON_DEVICE, int(bool(need_final)), _tail(delim if tail == -1 else tail),
+                                                   C.byref(lines), hits.ctypes.data if cap else None, spans.ctypes.data if cap else None,
+                                                   cap, C.byref(cnt), text.ctypes.data if room else None, room,
+                                                   offsets.ctypes.data if gather else None, C.byref(total) if gather else None, None))
+        k = min(int(cnt.value), cap)
+        out = {"lines": int(lines.value), "hits": hits[:k], "spans": spans[:k], "count": int(cnt.value)}
+        if gather:
+            out.update(text=text[:min(int(total.value), room)], offsets=offsets[:k + 1], bytes=int(total.value))
+        return out
+
+    def capture_lines_gather_device(self, raw_ptr: int, size: int, flags, out_line_count_ptr: int, out_hit_count_ptr: int,
+                                    out_bytes_ptr=0, delim: int = 10, need_final=False, tail=-1, out_hits_ptr=0, out_spans_ptr=0,
+                                    hit_cap=0, out_text_ptr=0, text_cap=0, out_offsets_ptr=0, stream: int = 0):
+        """pire_hip_capture_lines_gather on device pointers (synchronises `stream` once, as run_lines_select_device does)."""
+        _check(lib().pire_hip_capture_lines_gather(self._h, raw_ptr or None, size, delim, flags | FLAG_ON_DEVICE,
+                                                   int(bool(need_final)), _tail(delim if tail == -1 else tail),
+                                                   out_line_count_ptr or None, out_hits_ptr or None, out_spans_ptr or None, hit_cap,
+                                                   out_hit_count_ptr or None, out_text_ptr or None, text_cap,
+                                                   out_offsets_ptr or None, out_bytes_ptr or None, stream or None))
 
     def run_device(self, text_ptr: int, offsets_ptr: int, n: int, flags, out_idx_ptr=0, out_results_ptr=0, stream: int = 0):
         _check(lib().pire_hip_counting_run(self._h, self.kind, text_ptr or None, offsets_ptr or None, n,

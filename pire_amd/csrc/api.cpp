@@ -2138,6 +2138,130 @@ try {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
 
+// ---- raw bytes in, the captured field of every line out (split.hip, counting.hip, capture_select.hip, gather.hip) ---------
+// The frame of RunLinesImpl around a capturing scanner: the split into scratch, the capture scan on the lines, the pass
+// with shift = 1 (string i of the split buffer lies i bytes further into raw), the gather from raw through its spans.
+int pire_hip_capture_lines_gather(pire_hip_counting_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
+                                  int need_final, uint32_t tail, uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_spans,
+                                  uint64_t hit_cap, uint64_t* out_hit_count, void* out_text, uint64_t text_cap,
+                                  uint64_t* out_offsets, uint64_t* out_bytes, void* streamPtr)
+try {
+	const char* who = "pire_hip_capture_lines_gather";
+	if (!t)
+		return GatherRefuse(who, "null table");
+	if (int rc = SplitArgsInvalid(who, raw, size, delim, out_line_count, "out_line_count"))
+		return rc;
+	// no gather output at all: spans only.  (The gather form keeps the span list to itself where the caller has no array for it.)
+	const bool gather = out_text || text_cap || out_offsets || out_bytes;
+	if (int rc = CaptureSelectOutputsInvalid(who, 0, need_final, true, out_hits || out_spans || gather, hit_cap, out_hit_count))
+		return rc;
+	if (gather) {
+		if (int rc = GatherOutputsInvalid(who, "hit_cap", hit_cap, tail, out_text, text_cap, out_offsets, out_bytes))
+			return rc;
+		if (int rc = GatherOverlaps(who, raw, size, out_text, text_cap))
+			return rc;
+	}
+	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
+	if (!onDevice && size == 0) {
+		*out_line_count = *out_hit_count = 0;
+		if (gather)
+			*out_bytes = 0;
+		if (out_offsets)
+			out_offsets[0] = 0;
+		return PIRE_HIP_OK;
+	}
+	BatchIO io(stream, onDevice);
+	const uint8_t* dRaw = nullptr;
+	if (int rc = io.In(static_cast<const uint8_t*>(raw), size_t(size), &dRaw))
+		return rc;
+	uint64_t n = 0, count = 0, bytes = 0;   // host pointers: the counts come back here first
+	uint64_t *dN = nullptr, *dCount = nullptr, *dHits = nullptr, *dSpans = nullptr, *dBytes = nullptr, *dOutOffsets = nullptr;
+	uint8_t* dOutText = nullptr;
+	if (int rc = io.Result(onDevice ? out_line_count : &n, 1, 1, &dN))
+		return rc;
+	if (int rc = io.Result(onDevice ? out_hit_count : &count, 1, 1, &dCount))
+		return rc;
+	if (gather)
+		if (int rc = io.Result(onDevice ? out_bytes : &bytes, 1, 1, &dBytes))
+			return rc;
+	if (int rc = io.Ready())
+		return rc;
+	// the split, into scratch that lives until the scan and the gather behind it are enqueued; n sizes the offsets
+	StreamScratch tiles(stream), text(stream), offsets(stream), ownSpans(stream);
+	SplitPlan plan;
+	if (int rc = LaunchSplitCount(dRaw, size, delim, dN, stream, tiles, &plan))
+		return rc;
+	if (int rc = ReadCount(dN, &n, stream))
+		return rc;
+	if (n >= (1ull << 32)) {
+		SetError(std::string(who) + ": 2^32 lines or more in one call");
+		return PIRE_HIP_EUNSUPPORTED;
+	}
+	if (int rc = text.Alloc(size_t(size) + 16, "hipMallocAsync(split text)"))
+		return rc;
+	if (int rc = offsets.Alloc((size_t(n) + 1) * 8, "hipMallocAsync(split offsets)"))
+		return rc;
+	if (int rc = LaunchSplitScatter(plan, text.get(), offsets.as<uint64_t>(), n, dN, stream))
+		return rc;
+	const uint64_t cap = std::min<uint64_t>(hit_cap, n);   // n lines have at most n hits
+	if (out_hits && cap)
+		if (int rc = io.Result(out_hits, size_t(cap), 0, &dHits))
+			return rc;
+	if (out_spans && cap)
+		if (int rc = io.Result(out_spans, size_t(cap) * 2, 0, &dSpans))
+			return rc;
+	uint64_t textRoom = 0;   // of out_text: the k captures and their tails are size + k bytes at most
+	if (gather && cap) {
+		if (!dSpans) {
+			if (int rc = ownSpans.Alloc(size_t(cap) * 16, "hipMallocAsync(capture spans)"))
+				return rc;
+			dSpans = ownSpans.as<uint64_t>();
+		}
+		textRoom = std::min(text_cap, size + cap);
+		if (textRoom)
+			if (int rc = io.Result(static_cast<uint8_t*>(out_text), size_t(textRoom), 0, &dOutText))
+				return rc;
+	}
+	if (gather && out_offsets)
+		if (int rc = io.Result(out_offsets, size_t(cap) + 1, 0, &dOutOffsets))
+			return rc;
+	{
+		const uint32_t runFlags = (flags & (PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END | PIRE_HIP_RUN_GENERIC)) | PIRE_HIP_RUN_ON_DEVICE;
+		const CaptureSelectOut sel = {need_final, 1, dHits, dSpans, cap, dCount};
+		if (int rc = CaptureRunImpl(t, text.get(), offsets.as<uint64_t>(), n, runFlags, nullptr, nullptr, nullptr, nullptr, &sel, stream))
+			return rc;
+	}
+	if (gather) {
+		// straight from raw, through the spans (cap == 0: *out_bytes = 0 and out_offsets[0] = 0, nothing is read)
+		const GatherSource src = {dRaw, nullptr, 0, nullptr, dSpans, size};
+		if (int rc = LaunchGather(src, dCount, cap, tail, dOutText, textRoom, dOutOffsets, dBytes, kGatherTotalUnknown, stream))
+			return rc;
+	}
+	if (int rc = io.Finish())
+		return rc;
+	if (onDevice)
+		return PIRE_HIP_OK;
+	*out_line_count = n;
+	*out_hit_count = count;
+	const uint64_t written = std::min<uint64_t>(count, cap);
+	hipError_t e = hipSuccess;
+	if (written && dHits)
+		e = hipMemcpy(out_hits, dHits, size_t(written) * 8, hipMemcpyDeviceToHost);
+	if (e == hipSuccess && written && out_spans)
+		e = hipMemcpy(out_spans, dSpans, size_t(written) * 16, hipMemcpyDeviceToHost);
+	if (gather) {
+		*out_bytes = bytes;
+		if (e == hipSuccess && dOutOffsets)
+			e = hipMemcpy(out_offsets, dOutOffsets, (size_t(written) + 1) * 8, hipMemcpyDeviceToHost);
+		if (e == hipSuccess && std::min(bytes, textRoom))
+			e = hipMemcpy(out_text, dOutText, size_t(std::min(bytes, textRoom)), hipMemcpyDeviceToHost);
+	}
+	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(captures)");
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
 // ---- first-use self-tests of the entry points with actions (selftest.h) -------------------------------------------------
 namespace {
 

@@ -1,0 +1,230 @@
+// From capture positions to captured substrings on the device (pire_hip_capture_select): which strings captured, and where.
+//
+// pire_hip_capture_run answers with two step counters per string.  What a caller of a capturing scanner wants is the
+// captured TEXT of the strings that captured at all -- a compacted, ascending list of byte ranges, the input form of
+// pire_hip_gather_spans.  This unit turns the one into the other without leaving the device, behind ANY of the capture
+// kernels (it reads positions, offsets and Final flags, nothing else of a scan; include/pire_hip.h has the formulas):
+//
+//   classify  one lane per string: begin, end and, where asked for, final -- 17 bytes, coalesced -> selected?  The selected
+//             bits of a wave are one ballot word, kept in scratch; one count per tile of 1 024 strings.
+//   scan      exclusive scan of the tile counts, one block; the total is the hit count (select.hip's kernel, LaunchTileScan).
+//   scatter   rank of a selected string = tile offset + the popcounts of the waves in front + mbcnt of its own wave's
+//             ballot word; the lane computes its span again from offsets and positions, clamped into the string.
+//
+// Three launches on the caller's stream, the shape of select.hip: no block waits for another block, no atomics (the same
+// input gives the same bits).  Plain HIP with compiler-placed waits: nothing here keeps data on its way in registers.
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "internal.h"
+
+namespace pirehip {
+
+namespace {
+
+constexpr uint32_t kCapThreads = 1024;   // one tile = 1 024 strings = 16 ballot words
+constexpr uint32_t kCapWaves = kCapThreads / 64;
+constexpr uint32_t kCapMaxBlocks = 8192;
+
+struct CaptureSelectParams {
+	const uint64_t* offsets;
+	const long long* begin;
+	const long long* end;
+	const uint8_t* fin;      // nullable: Final is not asked for
+	uint64_t n;
+	long long beginMark;     // B: 1 where the BeginMark step was counted
+	uint64_t shift;          // string i lies shift * i bytes further into the buffer of the spans
+	uint64_t* outHits;       // nullable
+	uint64_t* outSpans;      // nullable
+	uint64_t hitCap;
+	uint64_t* ballots;       // [tiles * 16] selected bits, one word per wave
+	uint32_t* tileCounts;    // [tiles] selected strings per tile; after the scan: selected strings in front of the tile
+	uint32_t tiles;
+};
+
+__global__ __launch_bounds__(kCapThreads) void CaptureClassifyKernel(CaptureSelectParams p)
+{
+	__shared__ uint32_t waveCount[kCapWaves];
+	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
+		const uint64_t i = uint64_t(tile) * kCapThreads + threadIdx.x;
+		bool sel = false;
+		if (i < p.n)
+			sel = p.begin[i] >= 0 && p.end[i] >= 0 && (!p.fin || p.fin[i] != 0);
+		const uint64_t ballot = __ballot(sel);
+		if (lane == 0) {
+			p.ballots[size_t(tile) * kCapWaves + wave] = ballot;
+			waveCount[wave] = uint32_t(__popcll(ballot));
+		}
+		__syncthreads();
+		if (threadIdx.x == 0) {
+			uint32_t sum = 0;
+			for (uint32_t w = 0; w < kCapWaves; ++w)
+				sum += waveCount[w];
+			p.tileCounts[tile] = sum;
+		}
+		__syncthreads();
+	}
+}
+
+__global__ __launch_bounds__(kCapThreads) void CaptureScatterKernel(CaptureSelectParams p)
+{
+	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
+		const uint64_t* words = p.ballots + size_t(tile) * kCapWaves;
+		// lanes 0..15 hold the tile's ballot words: the selected strings of the waves in front of this one ...
+		const uint64_t word = lane < kCapWaves ? words[lane] : 0;
+		uint32_t front = lane < wave ? uint32_t(__popcll(word)) : 0;
+		for (uint32_t d = 1; d < 64; d <<= 1)
+			front += uint32_t(__shfl_xor(int(front), int(d), 64));   // (over all 64 lanes: every lane ends with the sum)
+		// ... and this wave's own word
+		const uint32_t lo = uint32_t(__shfl(int(uint32_t(word)), int(wave), 64));
+		const uint32_t hi = uint32_t(__shfl(int(uint32_t(word >> 32)), int(wave), 64));
+		const uint64_t mine = (uint64_t(hi) << 32) | lo;
+		const uint64_t rank = uint64_t(p.tileCounts[tile]) + front + __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0));
+		if (((mine >> lane) & 1) && rank < p.hitCap) {   // (a selected bit: i < n, begin >= 0 and end >= 0)
+			const uint64_t i = uint64_t(tile) * kCapThreads + threadIdx.x;
+			if (p.outHits)
+				p.outHits[rank] = i;
+			if (p.outSpans) {
+				const uint64_t o0 = p.offsets[i], o1 = p.offsets[i + 1];
+				const uint64_t len = o1 >= o0 ? o1 - o0 : 0;   // (offsets that decrease: an empty string)
+				// begin >= 0 and B <= 1: the differences cannot wrap
+				const long long bb = p.begin[i] - p.beginMark, ee = p.end[i] - p.beginMark;
+				const uint64_t b = bb < 0 ? 0 : std::min<uint64_t>(uint64_t(bb), len);
+				const uint64_t e = ee < 0 ? b : std::min<uint64_t>(std::max<uint64_t>(uint64_t(ee), b), len);
+				const uint64_t base = o0 + p.shift * i;
+				p.outSpans[2 * rank] = base + b;
+				p.outSpans[2 * rank + 1] = base + e;
+			}
+		}
+	}
+}
+
+}  // namespace
+
+int LaunchCaptureSelect(const uint64_t* offsets, uint64_t n, bool beginMark, const long long* begin, const long long* end,
+                        const uint8_t* fin, uint64_t shift, uint64_t* outHits, uint64_t* outSpans, uint64_t hitCap,
+                        uint64_t* outHitCount, hipStream_t stream)
+{
+	if (n == 0) {
+		const hipError_t e = hipMemsetAsync(outHitCount, 0, 8, stream);
+		return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemsetAsync(hit count)");
+	}
+	if (n >= (1ull << 32)) {
+		SetError("pire_hip_capture_select: 2^32 strings or more in one call");   // tile offsets are 32 bits (as select.hip's)
+		return PIRE_HIP_EUNSUPPORTED;
+	}
+	CaptureSelectParams p;
+	p.offsets = offsets;
+	p.begin = begin;
+	p.end = end;
+	p.fin = fin;
+	p.n = n;
+	p.beginMark = beginMark ? 1 : 0;
+	p.shift = shift;
+	p.outHits = outHits;
+	p.outSpans = outSpans;
+	p.hitCap = outHits || outSpans ? hitCap : 0;
+	p.tiles = uint32_t((n + kCapThreads - 1) / kCapThreads);
+	// scratch: n / 8 bytes of ballot words + n / 256 bytes of tile counts, stream-ordered (the call only enqueues)
+	const size_t ballotBytes = size_t(p.tiles) * kCapWaves * 8;
+	StreamScratch scratch(stream);
+	if (int rc = scratch.Alloc(ballotBytes + size_t(p.tiles) * 4, "hipMallocAsync(capture select scratch)"))
+		return rc;
+	p.ballots = scratch.as<uint64_t>();
+	p.tileCounts = reinterpret_cast<uint32_t*>(scratch.as<uint8_t>() + ballotBytes);
+	const dim3 grid(std::min(p.tiles, kCapMaxBlocks));
+	hipLaunchKernelGGL(CaptureClassifyKernel, grid, dim3(kCapThreads), 0, stream, p);
+	LaunchTileScan(p.tileCounts, p.tiles, outHitCount, stream);
+	if (p.hitCap)
+		hipLaunchKernelGGL(CaptureScatterKernel, grid, dim3(kCapThreads), 0, stream, p);
+	const hipError_t e = hipGetLastError();
+	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "capture select launch");
+}
+
+int CaptureSelectOutputsInvalid(const char* who, uint64_t n, int needFinal, bool haveFinal, bool haveList, uint64_t hitCap,
+                                const void* outHitCount)
+{
+	const char* what = !outHitCount                          ? "null out_hit_count"
+	                   : needFinal && !haveFinal             ? "need_final with null final"
+	                   : hitCap && !haveList                 ? "hit_cap > 0 with null out_hits and null out_spans"
+	                   : n >= (1ull << 32)                   ? "2^32 strings or more in one call"
+	                                                         : nullptr;
+	if (!what)
+		return PIRE_HIP_OK;
+	SetError(std::string(who) + ": " + what);
+	return PIRE_HIP_EINVAL;
+}
+
+}  // namespace pirehip
+
+using namespace pirehip;
+
+extern "C" int pire_hip_capture_select(const uint64_t* offsets, uint64_t n, uint32_t flags, const int64_t* begin, const int64_t* end,
+                                       const uint8_t* fin, int need_final, uint64_t* out_hits, uint64_t* out_spans, uint64_t hit_cap,
+                                       uint64_t* out_hit_count, void* streamPtr)
+try {
+	const char* who = "pire_hip_capture_select";
+	if (int rc = CaptureSelectOutputsInvalid(who, n, need_final, fin != nullptr, out_hits || out_spans, hit_cap, out_hit_count))
+		return rc;
+	if (n && (!offsets || !begin || !end)) {
+		SetError(std::string(who) + ": n > 0 with null offsets, begin or end");
+		return PIRE_HIP_EINVAL;
+	}
+	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
+	const bool beginMark = (flags & PIRE_HIP_RUN_BEGIN) != 0;
+	if (!need_final)
+		fin = nullptr;
+	if (onDevice)
+		return LaunchCaptureSelect(offsets, n, beginMark, reinterpret_cast<const long long*>(begin), reinterpret_cast<const long long*>(end),
+		                           fin, 0, out_hits, out_spans, hit_cap, out_hit_count, stream);
+	if (n == 0) {
+		*out_hit_count = 0;
+		return PIRE_HIP_OK;
+	}
+	if (int rc = CheckOffsets(offsets, n))
+		return rc;
+	// host pointers: staged in, the three kernels, staged out -- the lists only as far as they were written
+	BatchIO io(stream, false);
+	const uint64_t* dOffsets = nullptr;
+	const int64_t *dBegin = nullptr, *dEnd = nullptr;
+	const uint8_t* dFin = nullptr;
+	int rc;
+	if ((rc = io.In(offsets, size_t(n) + 1, &dOffsets)) || (rc = io.In(begin, size_t(n), &dBegin)) || (rc = io.In(end, size_t(n), &dEnd)))
+		return rc;
+	if (fin)
+		if ((rc = io.In(fin, size_t(n), &dFin)))
+			return rc;
+	const uint64_t cap = std::min<uint64_t>(hit_cap, n);   // n strings have at most n hits: a host call stages no more
+	uint64_t count = 0;   // the count comes back here first
+	uint64_t *dCount = nullptr, *dHits = nullptr, *dSpans = nullptr;
+	if ((rc = io.Result(&count, 1, 1, &dCount)))
+		return rc;
+	if (out_hits && cap)
+		if ((rc = io.Result(out_hits, size_t(cap), 0, &dHits)))
+			return rc;
+	if (out_spans && cap)
+		if ((rc = io.Result(out_spans, size_t(cap) * 2, 0, &dSpans)))
+			return rc;
+	if ((rc = io.Ready()))
+		return rc;
+	if ((rc = LaunchCaptureSelect(dOffsets, n, beginMark, reinterpret_cast<const long long*>(dBegin), reinterpret_cast<const long long*>(dEnd),
+	                              dFin, 0, dHits, dSpans, cap, dCount, stream)))
+		return rc;
+	if ((rc = io.Finish()))
+		return rc;
+	*out_hit_count = count;
+	const uint64_t written = std::min<uint64_t>(count, cap);
+	hipError_t e = hipSuccess;
+	if (written && dHits)
+		e = hipMemcpy(out_hits, dHits, size_t(written) * 8, hipMemcpyDeviceToHost);
+	if (e == hipSuccess && written && dSpans)
+		e = hipMemcpy(out_spans, dSpans, size_t(written) * 16, hipMemcpyDeviceToHost);
+	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(hits)");
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}

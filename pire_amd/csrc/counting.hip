@@ -2189,12 +2189,15 @@ int EnsureCaptureTable(pire_hip_counting_table* t, pire_hip_table** table, const
 }  // namespace
 }  // namespace pirehip
 
-extern "C" {
+namespace pirehip {
 
-int pire_hip_capture_run(pire_hip_counting_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
-                         uint32_t* out_state_idx, uint8_t* out_final, int64_t* out_begin, int64_t* out_end, void* streamPtr)
-try {
-	if (!t || (n && (!offsets || !out_begin || !out_end))) {
+// sel == nullptr: pire_hip_capture_run.  Else out_begin and out_end may be null, and the pass of capture_select.hip follows
+// the scan on the same stream (pire_hip_capture_run_select; sel->shift = 1: the lines of pire_hip_capture_lines_gather).
+int CaptureRunImpl(pire_hip_counting_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
+                   uint32_t* out_state_idx, uint8_t* out_final, int64_t* out_begin, int64_t* out_end, const CaptureSelectOut* sel,
+                   hipStream_t stream)
+{
+	if (!t || (n && (!offsets || (!sel && (!out_begin || !out_end))))) {
 		SetError("bad argument");
 		return PIRE_HIP_EINVAL;
 	}
@@ -2202,9 +2205,14 @@ try {
 		SetError("a CapturingScanner serialises as a LoadedScanner (type 4) table");
 		return PIRE_HIP_EINVAL;
 	}
-	if (n == 0)
+	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
+	if (n == 0) {
+		if (sel && !onDevice)
+			*sel->outHitCount = 0;
+		else if (sel)
+			return LaunchCaptureSelect(nullptr, 0, false, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, sel->outHitCount, stream);
 		return PIRE_HIP_OK;
-	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+	}
 	if (int rc = SelfTestCapture(t, flags, stream))   // first use on this device (selftest.h)
 		return rc;
 	CountingDevice image;
@@ -2282,18 +2290,87 @@ try {
 		*done = true;
 		return LaunchRaggedCapture(sp, TakeWorkSlot(ct, sp), infoDev, dB, dE, stream);
 	};
-	BatchIO io(stream, (flags & PIRE_HIP_RUN_ON_DEVICE) != 0);
+	BatchIO io(stream, onDevice);
 	int rc;
 	if ((rc = io.Text(text, offsets, n, 0, 0, &p.text, &p.offsets)) || (rc = io.Result(out_state_idx, n, n, &p.outIdx)) ||
 	    (rc = io.Result(out_final, n, n, &p.outFinal)) || (rc = io.Result(reinterpret_cast<long long*>(out_begin), n, n, &p.outBegin)) ||
-	    (rc = io.Result(reinterpret_cast<long long*>(out_end), n, n, &p.outEnd)) || (rc = io.Ready()))
+	    (rc = io.Result(reinterpret_cast<long long*>(out_end), n, n, &p.outEnd)))
+		return rc;
+	// the pass behind the scan: what it reads and the caller has no array for lives in scratch (a host-pointer call's
+	// Result() has allocated it already), its lists are staged as far as n strings can fill them
+	StreamScratch ownPositions(stream), ownFinal(stream);
+	const uint64_t cap = sel ? std::min<uint64_t>(sel->hitCap, n) : 0;
+	uint64_t count = 0;   // host pointers: the count comes back here first
+	uint64_t *dCount = nullptr, *dHits = nullptr, *dSpans = nullptr;
+	if (sel) {
+		if (onDevice && (!p.outBegin || !p.outEnd)) {
+			if ((rc = ownPositions.Alloc(size_t(n) * 16, "hipMallocAsync(capture positions)")))
+				return rc;
+			if (!p.outBegin)
+				p.outBegin = ownPositions.as<long long>();
+			if (!p.outEnd)
+				p.outEnd = ownPositions.as<long long>() + n;
+		}
+		if (onDevice && sel->needFinal && !p.outFinal) {
+			if ((rc = ownFinal.Alloc(size_t(n), "hipMallocAsync(capture final)")))
+				return rc;
+			p.outFinal = ownFinal.as<uint8_t>();
+		}
+		if ((rc = io.Result(onDevice ? sel->outHitCount : &count, 1, 1, &dCount)))
+			return rc;
+		if (sel->outHits && cap)
+			if ((rc = io.Result(sel->outHits, size_t(cap), 0, &dHits)))
+				return rc;
+		if (sel->outSpans && cap)
+			if ((rc = io.Result(sel->outSpans, size_t(cap) * 2, 0, &dSpans)))
+				return rc;
+	}
+	if ((rc = io.Ready()))
 		return rc;
 	bool done = false;
 	if ((rc = ragged(p.text, p.offsets, p.outIdx, p.outFinal, p.outBegin, p.outEnd, &done)))
 		return rc;
 	if (!done && (rc = launchPerLane()))
 		return rc;
-	return io.Finish();
+	if (sel)
+		if ((rc = LaunchCaptureSelect(p.offsets, n, (flags & PIRE_HIP_RUN_BEGIN) != 0, p.outBegin, p.outEnd,
+		                              sel->needFinal ? p.outFinal : nullptr, sel->shift, dHits, dSpans, cap, dCount, stream)))
+			return rc;
+	if ((rc = io.Finish()))
+		return rc;
+	if (!sel || onDevice)
+		return PIRE_HIP_OK;
+	*sel->outHitCount = count;
+	const uint64_t written = std::min<uint64_t>(count, cap);
+	hipError_t e = hipSuccess;
+	if (written && dHits)
+		e = hipMemcpy(sel->outHits, dHits, size_t(written) * 8, hipMemcpyDeviceToHost);
+	if (e == hipSuccess && written && dSpans)
+		e = hipMemcpy(sel->outSpans, dSpans, size_t(written) * 16, hipMemcpyDeviceToHost);
+	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(hits)");
+}
+
+}  // namespace pirehip
+
+extern "C" {
+
+int pire_hip_capture_run(pire_hip_counting_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
+                         uint32_t* out_state_idx, uint8_t* out_final, int64_t* out_begin, int64_t* out_end, void* stream)
+try {
+	return CaptureRunImpl(t, text, offsets, n, flags, out_state_idx, out_final, out_begin, out_end, nullptr, static_cast<hipStream_t>(stream));
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_capture_run_select(pire_hip_counting_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
+                                int need_final, uint32_t* out_state_idx, uint8_t* out_final, int64_t* out_begin, int64_t* out_end,
+                                uint64_t* out_hits, uint64_t* out_spans, uint64_t hit_cap, uint64_t* out_hit_count, void* stream)
+try {
+	// (Final comes from the scan itself: the pass never lacks it)
+	if (int rc = CaptureSelectOutputsInvalid("pire_hip_capture_run_select", n, need_final, true, out_hits || out_spans, hit_cap, out_hit_count))
+		return rc;
+	const CaptureSelectOut sel = {need_final, 0, out_hits, out_spans, hit_cap, out_hit_count};
+	return CaptureRunImpl(t, text, offsets, n, flags, out_state_idx, out_final, out_begin, out_end, &sel, static_cast<hipStream_t>(stream));
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }

@@ -1066,6 +1066,33 @@ void FreeSelect(pire_hip_table* t);
 int LaunchSelect(const SelectDevice& image, uint32_t states, uint32_t words, const uint32_t* stateIdx, uint64_t n,
                  const uint64_t* want, uint64_t* outMasks, uint64_t* outHits, uint64_t* outHitMasks, uint64_t hitCap,
                  uint64_t* outHitCount, hipStream_t stream);
+// The scan of both compactions (select.hip, capture_select.hip): exclusive scan of counts[entries] -- selected strings per
+// tile of 1 024 -- in place, one block; *outCount = the total.  Enqueues; the caller asks hipGetLastError() behind its launches.
+void LaunchTileScan(uint32_t* counts, uint32_t entries, uint64_t* outCount, hipStream_t stream);
+// capture_select.hip: from capture positions to a compacted, ascending list of byte ranges (pire_hip_capture_select).
+// Device pointers only, three kernels enqueued on `stream`, scratch from the stream-ordered allocator.  fin == nullptr:
+// Final is not asked for.  shift: string i lies shift * i bytes further into the buffer the spans are counted in (1: the
+// offsets are pire_hip_split's and the spans are ranges of the raw buffer).
+int LaunchCaptureSelect(const uint64_t* offsets, uint64_t n, bool beginMark, const long long* begin, const long long* end,
+                        const uint8_t* fin, uint64_t shift, uint64_t* outHits, uint64_t* outSpans, uint64_t hitCap,
+                        uint64_t* outHitCount, hipStream_t stream);
+// What pire_hip_capture_select refuses of its outputs before any device is touched (haveList: the hits have somewhere to go)
+int CaptureSelectOutputsInvalid(const char* who, uint64_t n, int needFinal, bool haveFinal, bool haveList, uint64_t hitCap,
+                                const void* outHitCount);
+// counting.hip: pire_hip_capture_run, and behind it -- where sel is not null -- the pass above on the same stream, on the
+// staged copy of a host-pointer call.  The position and Final arrays the pass needs and the caller has no room for live in
+// stream-ordered scratch.
+struct CaptureSelectOut {
+	int needFinal;
+	uint64_t shift;
+	uint64_t* outHits;
+	uint64_t* outSpans;
+	uint64_t hitCap;
+	uint64_t* outHitCount;
+};
+int CaptureRunImpl(pire_hip_counting_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
+                   uint32_t* outIdx, uint8_t* outFinal, int64_t* outBegin, int64_t* outEnd, const CaptureSelectOut* sel,
+                   hipStream_t stream);
 // split.hip: raw text into strings (pire_hip_split).  Device pointers only, everything enqueued on `stream`.  The pass
 // comes in two halves because a caller may want the number of strings before it has room for their offsets:
 // LaunchSplitCount counts and scans (*outN = n; the tile prefixes stay in `scratch`, the caller's owner, which has to live

@@ -264,6 +264,11 @@ int UploadSelect(pire_hip_table* t, SelectDevice* image)
 	return PIRE_HIP_OK;
 }
 
+void LaunchTileScan(uint32_t* counts, uint32_t entries, uint64_t* outCount, hipStream_t stream)
+{
+	hipLaunchKernelGGL(SelectScanKernel, dim3(1), dim3(kSelThreads), 0, stream, counts, entries, outCount);
+}
+
 int LaunchSelect(const SelectDevice& image, uint32_t states, uint32_t words, const uint32_t* stateIdx, uint64_t n,
                  const uint64_t* want, uint64_t* outMasks, uint64_t* outHits, uint64_t* outHitMasks, uint64_t hitCap,
                  uint64_t* outHitCount, hipStream_t stream)
@@ -310,7 +315,7 @@ int LaunchSelect(const SelectDevice& image, uint32_t states, uint32_t words, con
 	} else {
 		hipLaunchKernelGGL(SelectClassifyKernel<false>, dim3(std::min(p.tiles, kSelMaxBlocks)), dim3(kSelThreads), 0, stream, p);
 	}
-	hipLaunchKernelGGL(SelectScanKernel, dim3(1), dim3(kSelThreads), 0, stream, p.tileCounts, p.tiles, outHitCount);
+	LaunchTileScan(p.tileCounts, p.tiles, outHitCount, stream);
 	if (p.hitCap)
 		hipLaunchKernelGGL(SelectScatterKernel, dim3(std::min(p.tiles, kSelMaxBlocks)), dim3(kSelThreads), 0, stream, p);
 	const hipError_t e = hipGetLastError();
