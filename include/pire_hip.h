@@ -472,6 +472,54 @@ int pire_hip_run_select_strided(pire_hip_table* t, const void* text, uint64_t n,
                                 uint64_t* out_counts, const uint64_t* want, uint64_t* out_masks, uint64_t* out_hits,
                                 uint64_t* out_hit_masks, uint64_t hit_cap, uint64_t* out_hit_count, void* stream);
 
+/* ---- one hit list per regexp, on the device --------------------------------------------------------------- */
+
+/*
+ * From end states to the question a multi-rule caller asks: for EVERY regexp r of a glued scanner, the ascending list of
+ * the strings that matched r, in one pass.  R = RegexpsCount(); state_idx[i] as for pire_hip_select.
+ *   member(i, r)  <=>  r is in AcceptedRegexps(state_idx[i]) (multi.h:149-158) and r < R   (the mask image of
+ *                      pire_hip_select: reference state numbering, untouched by re-rankings)
+ * out_hit_counts (required when R > 0) [R]  out_hit_counts[r] = the number of i with member(i, r), the full count also
+ *                where it exceeds hit_cap; every one of the R entries is written, zeros included
+ * out_hits       (nullable when hit_cap == 0) [R][hit_cap]  row r = the indices i with member(i, r), ASCENDING; only the
+ *                first min(out_hit_counts[r], hit_cap) entries of a row are written, nothing behind them, in that row or
+ *                any other.  A string that matches k regexps appears in k rows.
+ * The pitch is fixed so that the rows chain into R gathers with device pointers and no read-back: row r is
+ * pire_hip_gather(.., idx = out_hits + r * hit_cap, idx_count = out_hit_counts + r, idx_cap = hit_cap, ..).
+ * n == 0 writes R zero counts.  R == 0 returns PIRE_HIP_OK and writes nothing.  n >= 2^32: PIRE_HIP_EUNSUPPORTED.
+ * flags: PIRE_HIP_RUN_ON_DEVICE -> every pointer is a device pointer and the call only enqueues on `stream`: three
+ *        kernels (count per tile and regexp, R scans, scatter), no atomics -- the same input gives the same bits.  The
+ *        per-call scratch (4 * R * ceil(n / 1024) bytes) comes from the stream-ordered allocator (hipMallocAsync /
+ *        hipFreeAsync on `stream`), as pire_hip_select's does: enqueue-only, and legal inside a stream capture under the
+ *        same condition as that call -- not something every capture mode accepts.  The first call on a device uploads the
+ *        table's mask image synchronously (pire_hip_select's; pire_hip_table_upload() beforehand does that too).  A
+ *        state_idx[i] >= Size() is undefined in this mode for the caller; it reads nothing and is a member of no row.
+ *        Otherwise host pointers: staged, synchronises; a state_idx[i] >= Size() is PIRE_HIP_EINVAL.  The rows are staged
+ *        at a pitch of min(hit_cap, n) and come back one by one, only their written entries; the caller's pitch stays
+ *        hit_cap.
+ * PIRE_HIP_EINVAL before any device is touched: null table, n with a null state_idx, null out_hit_counts (R > 0),
+ * hit_cap > 0 with null out_hits.
+ * pire_hip_last_kernel() is not changed by the pass: it keeps naming the scan kernel.  No first-use self-test (as
+ * pire_hip_select).
+ */
+int pire_hip_route(pire_hip_table* t, const uint32_t* state_idx, uint64_t n, uint32_t flags, uint64_t* out_hits,
+                   uint64_t hit_cap, uint64_t* out_hit_counts, void* stream);
+
+/*
+ * pire_hip_run / pire_hip_run_strided followed by pire_hip_route behind one call, on the same stream.  The first
+ * arguments, the flags and out_state_idx / out_final / out_counts (each nullable) are the run calls'; the rest
+ * pire_hip_route's.  With out_state_idx == NULL the state indices live in scratch of the library's own (stream-ordered in
+ * ON_DEVICE mode).  In host-pointer mode the indices of the whole batch arrive in one array before the pass: hit indices
+ * are relative to the whole batch, whatever chunks the staging cut it into.  R == 0: the scan runs, the pass writes nothing.
+ */
+int pire_hip_run_route(pire_hip_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
+                       const uint32_t* init_state_idx, uint32_t* out_state_idx, uint8_t* out_final, uint64_t* out_counts,
+                       uint64_t* out_hits, uint64_t hit_cap, uint64_t* out_hit_counts, void* stream);
+int pire_hip_run_route_strided(pire_hip_table* t, const void* text, uint64_t n, uint64_t len, uint64_t stride, uint32_t flags,
+                               const uint32_t* init_state_idx, uint32_t* out_state_idx, uint8_t* out_final,
+                               uint64_t* out_counts, uint64_t* out_hits, uint64_t hit_cap, uint64_t* out_hit_counts,
+                               void* stream);
+
 /* ---- raw text into strings, on the device ------------------------------------------------------------------- */
 
 /* The split pass cuts raw into tiles of this many bytes, on the 16-byte grid of raw's address (tests aim at its edges). */
@@ -520,6 +568,25 @@ int pire_hip_split(const void* raw, uint64_t size, uint32_t delim, uint32_t flag
 int pire_hip_run_lines_select(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
                               const uint64_t* want, uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_hit_spans,
                               uint64_t* out_hit_masks, uint64_t hit_cap, uint64_t* out_hit_count, void* stream);
+
+/*
+ * Raw bytes in, the matching lines of every regexp out: the split and the scan of pire_hip_run_lines_select, then
+ * pire_hip_route on the lines and one small kernel that turns all rows into byte ranges of the raw buffer.
+ * out_line_count (required)  n, the number of lines
+ * out_hits, hit_cap, out_hit_counts: exactly pire_hip_route's, the indices being line numbers (from 0)
+ * out_hit_spans  (nullable, needs out_hits) [R][hit_cap][2]  begin, end: hit k of row r is raw[begin, end), its delimiter
+ *                not included, exactly as in pire_hip_run_lines_select; written as far as the row's hits are.  The layout
+ *                makes pire_hip_gather_spans(raw, size, out_hit_spans + 2 * r * hit_cap, out_hit_counts + r, hit_cap, ..)
+ *                legal with device pointers and no read-back.
+ * flags as pire_hip_run_lines_select.  The call reads n back to size the offsets: it synchronises `stream` once EVEN WITH
+ * PIRE_HIP_RUN_ON_DEVICE, at the same place and for the same reason as pire_hip_run_lines_select, and adds no second
+ * wait.  size == 0: n = 0 and R zero counts.  R == 0: n is written, nothing else.
+ * PIRE_HIP_EINVAL before any device is touched: what pire_hip_route refuses, out_hit_spans without out_hits, delim > 255,
+ * null out_line_count, size > 0 with null raw.  pire_hip_last_kernel() names the scan kernel.  Fewer than 2^32 lines.
+ */
+int pire_hip_run_lines_route(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
+                             uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_hit_spans, uint64_t hit_cap,
+                             uint64_t* out_hit_counts, void* stream);
 
 /* ---- the selected strings gathered into a batch, on the device ------------------------------------------------ */
 

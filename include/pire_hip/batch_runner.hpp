@@ -184,7 +184,7 @@ public:
 		m_offsets = offsets;
 		m_n = n;
 		m_onDevice = false;
-		m_ran = m_lines = false;
+		m_ran = m_lines = m_routed = m_routeFetched = false;
 		return *this;
 	}
 
@@ -197,7 +197,7 @@ public:
 		m_len = m_stride = 0;
 		m_stream = stream;
 		m_onDevice = true;
-		m_ran = m_lines = false;
+		m_ran = m_lines = m_routed = m_routeFetched = false;
 		return *this;
 	}
 
@@ -211,7 +211,7 @@ public:
 		m_stride = stride;
 		m_stream = stream;
 		m_onDevice = true;
-		m_ran = m_lines = false;
+		m_ran = m_lines = m_routed = m_routeFetched = false;
 		return *this;
 	}
 
@@ -245,7 +245,7 @@ public:
 		m_n = 0;
 		m_len = size;
 		m_delim = uint8_t(delim);
-		m_onDevice = m_ran = m_selected = m_hitsFetched = m_textFetched = false;
+		m_onDevice = m_ran = m_selected = m_hitsFetched = m_textFetched = m_routed = m_routeFetched = false;
 		m_lines = true;
 		return *this;
 	}
@@ -321,12 +321,43 @@ public:
 	const uint64_t* DeviceHitMasks() { ExecuteSelect(); return static_cast<const uint64_t*>(m_devHitMasks.Get()); }
 	const uint64_t* DeviceHitCount() { ExecuteSelect(); return static_cast<const uint64_t*>(m_devHitCount.Get()); }
 
+	/*
+	 * One hit list PER REGEXP, answered on the device (pire_hip_route) -- after a Run*().End(), and after RunLines():
+	 *     run.Begin().Run(text, offsets, n).End().Route();
+	 *     run.RouteCount(r)   how many strings matched regexp r       run.RouteHits(r)  their indices, ascending
+	 *     run.Begin().RunLines(raw, size).End().Route();              the same per line of raw, and
+	 *     run.RouteSpans(r)   [2 * k], [2 * k + 1]: hit k of regexp r is raw[begin, end)
+	 * The host loop over States() with one AcceptedRegexps lookup per string, bucketed by regexp, gives the same answer.
+	 * After RunDevice*: DeviceRouteHits() ([RegexpsCount()][RoutePitch()], row r at r * RoutePitch()) and DeviceRouteCounts()
+	 * ([RegexpsCount()]) leave them where a consumer on the GPU wants them -- pire_hip_gather takes row r and its count as
+	 * they lie (ordered on RunDevice's stream).
+	 */
+	BatchRunner& Route()
+	{
+		m_routed = m_routeFetched = false;
+		return *this;
+	}
+	uint64_t RouteCount(size_t r) { FetchRoute(); return m_routeCounts.at(r); }
+	const std::vector<uint64_t>& RouteHits(size_t r) { FetchRoute(); return m_routeHits.at(r); }
+	const std::vector<uint64_t>& RouteSpans(size_t r)
+	{
+		if (!m_lines)
+			throw Pire::Error("pire_hip: RouteSpans() follows RunLines()");
+		FetchRoute();
+		return m_routeSpans.at(r);
+	}
+	const uint64_t* DeviceRouteHits() { ExecuteRoute(); return static_cast<const uint64_t*>(m_devRouteHits.Get()); }
+	const uint64_t* DeviceRouteCounts() { ExecuteRoute(); return static_cast<const uint64_t*>(m_devRouteCounts.Get()); }
+	size_t RoutePitch() { ExecuteRoute(); return m_routePitch; }
+
 	const Table<Scanner>& GetTable() const { return *m_table; }
 	uint32_t Flags() const { return m_flags; }
 
 private:
 	void Reset()
 	{
+		m_routed = m_routeFetched = false;
+		m_routePitch = 0;
 		m_selected = m_hitsFetched = m_haveWant = m_lines = m_textFetched = false;
 		m_hitCount = m_lineCount = 0;
 		m_delim = 0;
@@ -488,6 +519,88 @@ private:
 		m_hitsFetched = true;
 	}
 
+	size_t Regexps() const
+	{
+		pire_hip_table_info info;
+		Check(pire_hip_table_get_info(m_table->Handle(), &info));
+		return size_t(info.regexps);
+	}
+
+	/* Rows of a pitch of `pitch` entries (x `width` words) cut to their counts */
+	static void CutRows(const std::vector<uint64_t>& flat, const std::vector<uint64_t>& counts, size_t pitch, size_t width,
+	                    std::vector<std::vector<uint64_t> >& rows)
+	{
+		rows.assign(counts.size(), std::vector<uint64_t>());
+		for (size_t r = 0; r < counts.size(); ++r)
+			rows[r].assign(flat.begin() + r * pitch * width, flat.begin() + (r * pitch + size_t(counts[r])) * width);
+	}
+
+	void ExecuteRoute()
+	{
+		if (m_routed && m_ran)
+			return;
+		const size_t regexps = Regexps();
+		m_routeCounts.assign(regexps, 0);
+		if (m_lines) {
+			/* one call; the grow-and-retry of ExecuteLines() on the longest row */
+			std::vector<uint64_t> hits, spans;
+			for (size_t cap = m_len / 64 + 1024;; ) {
+				hits.resize(regexps * cap);
+				spans.resize(regexps * cap * 2);
+				Check(pire_hip_run_lines_route(m_table->Handle(), m_text, m_len, m_delim, m_flags, &m_lineCount, hits.data(), spans.data(),
+				                               cap, m_routeCounts.data(), nullptr));
+				uint64_t longest = 0;
+				for (size_t r = 0; r < regexps; ++r)
+					longest = m_routeCounts[r] > longest ? m_routeCounts[r] : longest;
+				if (longest <= cap) {
+					m_routePitch = cap;
+					break;
+				}
+				cap = size_t(longest);
+			}
+			CutRows(hits, m_routeCounts, m_routePitch, 1, m_routeHits);
+			CutRows(spans, m_routeCounts, m_routePitch, 2, m_routeSpans);
+			m_ran = m_routed = m_routeFetched = true;
+			return;
+		}
+		Execute();
+		m_routePitch = m_n;
+		if (m_onDevice) {
+			uint64_t* hits = static_cast<uint64_t*>(m_devRouteHits.Reserve((regexps * m_n + 1) * 8));
+			uint64_t* counts = static_cast<uint64_t*>(m_devRouteCounts.Reserve((regexps + 1) * 8));
+			Check(pire_hip_route(m_table->Handle(), static_cast<const uint32_t*>(m_devIdx.Get()), m_n, PIRE_HIP_RUN_ON_DEVICE,
+			                     m_n ? hits : nullptr, m_n, counts, m_stream));
+			m_routeFetched = false;
+		} else {
+			std::vector<uint64_t> hits(regexps * m_n);
+			Check(pire_hip_route(m_table->Handle(), m_idx.data(), m_n, 0, m_n ? hits.data() : nullptr, m_n, m_routeCounts.data(), nullptr));
+			CutRows(hits, m_routeCounts, m_routePitch, 1, m_routeHits);
+			m_routeFetched = true;
+		}
+		m_routed = true;
+	}
+
+	void FetchRoute()
+	{
+		ExecuteRoute();
+		if (m_routeFetched)
+			return;
+		const size_t regexps = m_routeCounts.size();
+		if (regexps) {
+			Check(pire_hip_copy_to_host(m_routeCounts.data(), m_devRouteCounts.Get(), regexps * 8, m_stream));
+			Check(pire_hip_stream_synchronize(m_stream));
+		}
+		m_routeHits.assign(regexps, std::vector<uint64_t>());
+		for (size_t r = 0; r < regexps; ++r) {
+			m_routeHits[r].resize(size_t(m_routeCounts[r]));
+			if (m_routeCounts[r])
+				Check(pire_hip_copy_to_host(m_routeHits[r].data(), static_cast<const uint64_t*>(m_devRouteHits.Get()) + r * m_routePitch,
+				                            size_t(m_routeCounts[r]) * 8, m_stream));
+		}
+		Check(pire_hip_stream_synchronize(m_stream));
+		m_routeFetched = true;
+	}
+
 	/* Per-string results on the host, as Scanner::State values. */
 	void Fetch()
 	{
@@ -535,6 +648,11 @@ private:
 	uint64_t m_hitCount, m_lineCount;
 	std::vector<uint64_t> m_want, m_hits, m_hitMasks, m_hitSpans;
 	DeviceBuffer m_devHits, m_devHitMasks, m_devHitCount, m_devWant;
+	bool m_routed, m_routeFetched;
+	size_t m_routePitch;
+	std::vector<uint64_t> m_routeCounts;
+	std::vector<std::vector<uint64_t> > m_routeHits, m_routeSpans;
+	DeviceBuffer m_devRouteHits, m_devRouteCounts;
 	ystring m_ownText;
 	std::vector<uint64_t> m_ownOffsets;
 };

@@ -179,6 +179,14 @@ ABI = [
     ("pire_hip_run_select_strided", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_route", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_run_route", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_run_route_strided", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                             C.c_void_p, C.c_void_p]),
+    ("pire_hip_run_lines_route", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_split", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                  C.c_void_p]),
     ("pire_hip_run_lines_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
@@ -759,6 +767,166 @@ class Table:
         _check(lib().pire_hip_run_lines_select(self._h, raw_ptr or None, size, delim, flags | FLAG_ON_DEVICE, want_ptr or None,
                                                out_line_count_ptr or None, out_hits_ptr or None, out_hit_spans_ptr or None,
                                                out_hit_masks_ptr or None, hit_cap, out_hit_count_ptr or None, stream or None))
+
+    # --- one ascending hit list per regexp (pire_hip_route): counts uint64[R], hits a list of R arrays (row r: the strings
+    # that matched regexp r).  device=True: the same call with PIRE_HIP_RUN_ON_DEVICE on torch buffers (the inputs are copied
+    # to the current device first, the rows fetched afterwards; "device_hits" int64[R, cap] and "device_counts" int64[R] stay
+    # there for chaining); the *_device methods below take raw addresses and only enqueue.
+    @staticmethod
+    def _route_rows(counts, flat, cap, width=1):
+        r = len(counts)
+        rows = flat.reshape(r, cap, width) if width > 1 else flat.reshape(r, cap)
+        return [rows[k, :min(int(counts[k]), cap)].copy() for k in range(r)]
+
+    def _route_call(self, n, cap, device, call, spans=False):
+        """call(hits_ptr, spans_ptr, counts_ptr, flag, stream) makes the C call; -> the result dict"""
+        r = self.RegexpsCount
+        if not device:
+            counts = np.zeros(r, dtype=np.uint64)
+            hits = np.zeros(max(r * cap, 1), dtype=np.uint64)
+            sp = np.zeros(max(r * cap, 1) * 2, dtype=np.uint64) if spans else None
+            call(hits.ctypes.data if cap else None, sp.ctypes.data if spans and cap else None, counts.ctypes.data if r else None,
+                 0, None)
+            out = {"counts": counts, "hits": self._route_rows(counts, hits[:r * cap], cap)}
+            if spans:
+                out["spans"] = self._route_rows(counts, sp[:r * cap * 2], cap, 2)
+            return out
+        import torch
+
+        dc = torch.zeros(max(r, 1), dtype=torch.int64, device="cuda")
+        dh = torch.zeros((max(r, 1), max(cap, 1)), dtype=torch.int64, device="cuda")
+        ds = torch.zeros((max(r, 1), max(cap, 1), 2), dtype=torch.int64, device="cuda") if spans else None
+        call(dh.data_ptr() if cap else None, ds.data_ptr() if spans and cap else None, dc.data_ptr() if r else None,
+             FLAG_ON_DEVICE, torch.cuda.current_stream().cuda_stream or None)
+        torch.cuda.synchronize()
+        counts = dc.cpu().numpy().view(np.uint64)[:r].copy()
+        out = {"counts": counts, "hits": self._route_rows(counts, dh.cpu().numpy().view(np.uint64)[:r, :cap].reshape(-1), cap),
+               "device_hits": dh, "device_counts": dc}
+        if spans:
+            out["spans"] = self._route_rows(counts, ds.cpu().numpy().view(np.uint64)[:r, :cap].reshape(-1), cap, 2)
+            out["device_spans"] = ds
+        return out
+
+    @staticmethod
+    def _to_device(a):
+        import torch
+
+        a = np.ascontiguousarray(a)
+        signed = {np.dtype(np.uint32): np.int32, np.dtype(np.uint64): np.int64}.get(a.dtype)
+        if a.size == 0:
+            return torch.zeros(256, dtype=torch.uint8, device="cuda")
+        return torch.as_tensor(a.view(signed) if signed else a, device="cuda")
+
+    def route(self, state_idx, cap=None, device=False):
+        """pire_hip_route: {"counts": u64[R], "hits": [R arrays]}; cap None = room for every string in every row."""
+        idx = np.ascontiguousarray(state_idx, dtype=np.uint32)
+        n = len(idx)
+        cap = n if cap is None else int(cap)
+        src = self._to_device(idx) if device else idx
+        ptr = (src.data_ptr() if device else idx.ctypes.data) if n else None
+
+        def call(hits, _spans, counts, flag, stream):
+            _check(lib().pire_hip_route(self._h, ptr, n, flag, hits, cap, counts, stream))
+        return self._route_call(n, cap, device, call)
+
+    def run_route(self, text, offsets, flags=FLAG_BEGIN | FLAG_END, cap=None, init_idx=None, states=True, device=False):
+        """pire_hip_run_route: route()'s dict plus "idx" / "final" of the scan (states=False: the library keeps the state
+        indices to itself)."""
+        text = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray))
+                                    else text, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        return self._run_route(n, cap, init_idx, states, device, flags, (text, offsets), None)
+
+    def run_route_strided(self, text2d, flags=FLAG_BEGIN | FLAG_END, cap=None, init_idx=None, states=True, device=False):
+        """pire_hip_run_route_strided on fixed-length records uint8[n, len]: run_route()'s dict."""
+        text2d = np.ascontiguousarray(text2d, dtype=np.uint8)
+        return self._run_route(text2d.shape[0], cap, init_idx, states, device, flags, None, text2d)
+
+    def _run_route(self, n, cap, init_idx, states, device, flags, batch, records):
+        cap = n if cap is None else int(cap)
+        init = None if init_idx is None else np.ascontiguousarray(init_idx, dtype=np.uint32)
+        flags &= ~FLAG_ON_DEVICE
+        if device:
+            import torch
+
+            hold = [self._to_device(a) for a in (batch if records is None else (records,))]
+            dinit = None if init is None else self._to_device(init)
+            idx = torch.zeros(max(n, 1), dtype=torch.int32, device="cuda") if states else None
+            fin = torch.zeros(max(n, 1), dtype=torch.uint8, device="cuda") if states else None
+            ptrs = [h.data_ptr() for h in hold]
+            pinit, pidx, pfin = (None if x is None else x.data_ptr() for x in (dinit, idx, fin))
+        else:
+            idx = np.empty(n, dtype=np.uint32) if states else None
+            fin = np.empty(n, dtype=np.uint8) if states else None
+            if records is None:
+                ptrs = [batch[0].ctypes.data if batch[0].size else None, batch[1].ctypes.data]
+            else:
+                ptrs = [records.ctypes.data if records.size else None]
+            pinit, pidx, pfin = _np_ptr(init), _np_ptr(idx), _np_ptr(fin)
+
+        def call(hits, _spans, counts, flag, stream):
+            if records is None:
+                _check(lib().pire_hip_run_route(self._h, ptrs[0], ptrs[1], n, flags | flag, pinit, pidx, pfin, None, hits, cap, counts,
+                                                stream))
+            else:
+                _check(lib().pire_hip_run_route_strided(self._h, ptrs[0], n, records.shape[1], records.shape[1], flags | flag, pinit,
+                                                        pidx, pfin, None, hits, cap, counts, stream))
+        out = self._route_call(n, cap, device, call)
+        if states and device:
+            idx, fin = idx.cpu().numpy().view(np.uint32)[:n], fin.cpu().numpy()[:n]
+        out["idx"], out["final"] = idx, fin
+        return out
+
+    def run_lines_route(self, raw, delim: int = 10, flags=FLAG_BEGIN | FLAG_END, cap=None, device=False):
+        """pire_hip_run_lines_route: {"lines", "counts": u64[R], "hits": [R arrays of line numbers], "spans": [R arrays u64[k, 2]]};
+        cap None = room for a hit on every line (no more lines than bytes) in every row."""
+        raw = _raw_bytes(raw)
+        cap = raw.size if cap is None else int(cap)
+        flags &= ~FLAG_ON_DEVICE
+        if device:
+            import torch
+
+            src = self._to_device(raw)
+            dn = torch.zeros(1, dtype=torch.int64, device="cuda")
+            praw, pn = src.data_ptr() if raw.size else None, dn.data_ptr()
+        else:
+            lines = C.c_uint64(0)
+            praw, pn = raw.ctypes.data if raw.size else None, C.addressof(lines)
+
+        def call(hits, spans, counts, flag, stream):
+            _check(lib().pire_hip_run_lines_route(self._h, praw, raw.size, delim, flags | flag, pn, hits, spans, cap, counts, stream))
+        out = self._route_call(raw.size, cap, device, call, spans=True)
+        out["lines"] = int(dn.cpu().numpy()[0]) if device else int(lines.value)
+        return out
+
+    def route_device(self, state_idx_ptr: int, n: int, out_hit_counts_ptr: int, out_hits_ptr=0, hit_cap=0, stream: int = 0):
+        """pire_hip_route with PIRE_HIP_RUN_ON_DEVICE: raw device addresses, only enqueues on `stream`."""
+        _check(lib().pire_hip_route(self._h, state_idx_ptr or None, n, FLAG_ON_DEVICE, out_hits_ptr or None, hit_cap,
+                                    out_hit_counts_ptr or None, stream or None))
+
+    def run_route_device(self, text_ptr: int, offsets_ptr: int, n: int, flags, out_hit_counts_ptr: int, out_hits_ptr=0, hit_cap=0,
+                         out_idx_ptr=0, out_final_ptr=0, out_counts_ptr=0, init_ptr=0, stream: int = 0):
+        """pire_hip_run_route on device pointers (FLAG_HOST_OFFSETS in `flags`: offsets_ptr is a host address)."""
+        _check(lib().pire_hip_run_route(self._h, text_ptr or None, offsets_ptr or None, n, flags | FLAG_ON_DEVICE, init_ptr or None,
+                                        out_idx_ptr or None, out_final_ptr or None, out_counts_ptr or None, out_hits_ptr or None,
+                                        hit_cap, out_hit_counts_ptr or None, stream or None))
+
+    def run_route_strided_device(self, text_ptr: int, n: int, length: int, stride: int, flags, out_hit_counts_ptr: int,
+                                 out_hits_ptr=0, hit_cap=0, out_idx_ptr=0, out_final_ptr=0, out_counts_ptr=0, init_ptr=0,
+                                 stream: int = 0):
+        """pire_hip_run_route_strided on device pointers: fixed-length records, only enqueues on `stream`."""
+        _check(lib().pire_hip_run_route_strided(self._h, text_ptr or None, n, length, stride, flags | FLAG_ON_DEVICE,
+                                                init_ptr or None, out_idx_ptr or None, out_final_ptr or None,
+                                                out_counts_ptr or None, out_hits_ptr or None, hit_cap,
+                                                out_hit_counts_ptr or None, stream or None))
+
+    def run_lines_route_device(self, raw_ptr: int, size: int, flags, out_line_count_ptr: int, out_hit_counts_ptr: int,
+                               delim: int = 10, out_hits_ptr=0, out_hit_spans_ptr=0, hit_cap=0, stream: int = 0):
+        """pire_hip_run_lines_route on device pointers (synchronises `stream` once, as run_lines_select_device does)."""
+        _check(lib().pire_hip_run_lines_route(self._h, raw_ptr or None, size, delim, flags | FLAG_ON_DEVICE,
+                                              out_line_count_ptr or None, out_hits_ptr or None, out_hit_spans_ptr or None, hit_cap,
+                                              out_hit_counts_ptr or None, stream or None))
 
     # --- raw bytes in, the matching lines out as bytes (pire_hip_run_lines_gather)
     def run_lines_gather_host(self, raw, delim: int = 10, flags=FLAG_BEGIN | FLAG_END, want=None, tail=-1, hit_cap=None,

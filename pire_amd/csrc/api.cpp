@@ -1730,6 +1730,171 @@ try {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
 
+// ---- one hit list per regexp (route.hip) --------------------------------------------------------------------------------
+namespace {
+
+uint32_t HostRegexps(const pire_hip_table* t)
+{
+	const auto stable = HostLock(t);
+	return t->host.regexps;
+}
+
+// What the route entry points refuse before any device is touched
+int RouteArgsInvalid(const char* who, const pire_hip_table* t, const uint32_t* stateIdx, bool needIdx, uint64_t n,
+                     const uint64_t* outHits, const uint64_t* outHitSpans, uint64_t hitCap, const uint64_t* outHitCounts)
+{
+	const char* what = !t                                             ? "null table"
+	                   : needIdx && n && !stateIdx                    ? "null state_idx"
+	                   : !outHitCounts && HostRegexps(t)              ? "null out_hit_counts"
+	                   : hitCap && !outHits                           ? "hit_cap > 0 with null out_hits"
+	                   : outHitSpans && !outHits                      ? "out_hit_spans without out_hits"
+	                                                                  : nullptr;
+	if (!what)
+		return PIRE_HIP_OK;
+	SetError(std::string(who) + ": " + what);
+	return PIRE_HIP_EINVAL;
+}
+
+// Host pointers: the rows come back one by one and only as far as they were written; the caller's pitch stays hitCap
+int RouteRowsBack(uint32_t regexps, const uint64_t* counts, uint64_t staged, uint64_t hitCap, const uint64_t* dHits, uint64_t* outHits,
+                  const uint64_t* dSpans, uint64_t* outSpans)
+{
+	for (uint32_t r = 0; r < regexps && dHits; ++r) {
+		const uint64_t written = std::min(counts[r], staged);
+		if (!written)
+			continue;
+		hipError_t e = hipMemcpy(outHits + uint64_t(r) * hitCap, dHits + uint64_t(r) * staged, size_t(written) * 8, hipMemcpyDeviceToHost);
+		if (e == hipSuccess && dSpans)
+			e = hipMemcpy(outSpans + 2 * uint64_t(r) * hitCap, dSpans + 2 * uint64_t(r) * staged, size_t(written) * 16,
+			              hipMemcpyDeviceToHost);
+		if (e != hipSuccess)
+			return HipFail(e, "hipMemcpy(route hits)");
+	}
+	return PIRE_HIP_OK;
+}
+
+int RouteImpl(pire_hip_table* t, const uint32_t* stateIdx, uint64_t n, uint32_t flags, uint64_t* outHits, uint64_t hitCap,
+              uint64_t* outHitCounts, hipStream_t stream)
+{
+	uint32_t states, words, regexps;
+	{
+		const std::shared_lock<std::shared_mutex> stable(t->adaptMutex);
+		states = t->host.states;
+		regexps = t->host.regexps;
+		words = SelectMaskWords(regexps);
+	}
+	if (n >= (1ull << 32)) {
+		SetError("pire_hip_route: 2^32 strings or more in one call");
+		return PIRE_HIP_EUNSUPPORTED;
+	}
+	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
+	if (!onDevice)
+		for (uint64_t i = 0; i < n; ++i)
+			if (stateIdx[i] >= states) {
+				SetError("pire_hip_route: state_idx out of range");
+				return PIRE_HIP_EINVAL;
+			}
+	if (regexps == 0)
+		return PIRE_HIP_OK;   // no rows: nothing to write
+	if (!onDevice && n == 0) {
+		std::fill(outHitCounts, outHitCounts + regexps, uint64_t(0));
+		return PIRE_HIP_OK;
+	}
+	SelectDevice image;
+	{
+		// (the image is in reference numbering: built once, whatever re-rankings come; the lock is for reading t->host)
+		const std::shared_lock<std::shared_mutex> stable(t->adaptMutex);
+		if (int rc = UploadSelect(t, &image))
+			return rc;
+	}
+	// host pointers: staged in, the three kernels, staged out -- the rows at a pitch of their own, min(hit_cap, n)
+	BatchIO io(stream, onDevice);
+	const uint32_t* dIdx = nullptr;
+	if (int rc = io.In(stateIdx, size_t(n), &dIdx))
+		return rc;
+	const uint64_t cap = onDevice ? hitCap : std::min<uint64_t>(hitCap, n);
+	uint64_t *dCounts = nullptr, *dHits = nullptr;
+	if (int rc = io.Result(outHitCounts, regexps, regexps, &dCounts))
+		return rc;
+	if (outHits && cap)
+		if (int rc = io.Result(outHits, size_t(regexps) * size_t(cap), 0, &dHits))
+			return rc;
+	if (int rc = io.Ready())
+		return rc;
+	if (int rc = LaunchRoute(image, states, words, regexps, dIdx, n, dHits, dHits ? cap : 0, dCounts, stream))
+		return rc;
+	if (int rc = io.Finish())
+		return rc;
+	return onDevice ? PIRE_HIP_OK : RouteRowsBack(regexps, outHitCounts, cap, hitCap, dHits, outHits, nullptr, nullptr);
+}
+
+// pire_hip_run[_strided] followed by pire_hip_route on the same stream; `run` makes the scan call with the state-index
+// array it is given (the shape of RunSelectImpl)
+int RunRouteImpl(const char* who, pire_hip_table* t, uint64_t n, uint32_t flags, uint32_t* outIdx, uint64_t* outHits, uint64_t hitCap,
+                 uint64_t* outHitCounts, void* streamPtr, const std::function<int(uint32_t*)>& run)
+{
+	if (int rc = RouteArgsInvalid(who, t, nullptr, false, n, outHits, nullptr, hitCap, outHitCounts))
+		return rc;
+	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+	if (!(flags & PIRE_HIP_RUN_ON_DEVICE)) {
+		// (whatever staging path the scan takes, its state indices arrive in ONE host array before the route pass sees
+		// them: hit indices are relative to the whole batch)
+		std::vector<uint32_t> own;
+		if (!outIdx) {
+			own.resize(size_t(n));
+			outIdx = own.data();
+		}
+		if (int rc = run(outIdx))
+			return rc;
+		return RouteImpl(t, outIdx, n, 0, outHits, hitCap, outHitCounts, stream);
+	}
+	StreamScratch scratch(stream);
+	if (!outIdx && n) {
+		if (int rc = scratch.Alloc(size_t(n) * 4, "hipMallocAsync(state indices)"))
+			return rc;
+		outIdx = scratch.as<uint32_t>();
+	}
+	if (int rc = run(outIdx))
+		return rc;
+	return RouteImpl(t, outIdx, n, PIRE_HIP_RUN_ON_DEVICE, outHits, hitCap, outHitCounts, stream);
+}
+
+}  // namespace
+
+int pire_hip_route(pire_hip_table* t, const uint32_t* state_idx, uint64_t n, uint32_t flags, uint64_t* out_hits, uint64_t hit_cap,
+                   uint64_t* out_hit_counts, void* stream)
+try {
+	if (int rc = RouteArgsInvalid("pire_hip_route", t, state_idx, true, n, out_hits, nullptr, hit_cap, out_hit_counts))
+		return rc;
+	return RouteImpl(t, state_idx, n, flags, out_hits, hit_cap, out_hit_counts, static_cast<hipStream_t>(stream));
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_run_route(pire_hip_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
+                       const uint32_t* init_state_idx, uint32_t* out_state_idx, uint8_t* out_final, uint64_t* out_counts,
+                       uint64_t* out_hits, uint64_t hit_cap, uint64_t* out_hit_counts, void* stream)
+try {
+	return RunRouteImpl("pire_hip_run_route", t, n, flags, out_state_idx, out_hits, hit_cap, out_hit_counts, stream, [&](uint32_t* idx) {
+		return pire_hip_run(t, text, offsets, n, flags, init_state_idx, idx, out_final, out_counts, stream);
+	});
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_run_route_strided(pire_hip_table* t, const void* text, uint64_t n, uint64_t len, uint64_t stride, uint32_t flags,
+                               const uint32_t* init_state_idx, uint32_t* out_state_idx, uint8_t* out_final, uint64_t* out_counts,
+                               uint64_t* out_hits, uint64_t hit_cap, uint64_t* out_hit_counts, void* stream)
+try {
+	return RunRouteImpl("pire_hip_run_route_strided", t, n, flags, out_state_idx, out_hits, hit_cap, out_hit_counts, stream,
+	                    [&](uint32_t* idx) {
+		                    return pire_hip_run_strided(t, text, n, len, stride, flags, init_state_idx, idx, out_final, out_counts,
+		                                                stream);
+	                    });
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
 // ---- raw text into strings (split.hip) -----------------------------------------------------------------------------------
 namespace {
 
@@ -1861,6 +2026,31 @@ int GatherOverlaps(const char* who, const void* source, uint64_t size, const voi
 	return PIRE_HIP_EINVAL;
 }
 
+// The lines of a raw buffer as text + offsets in scratch of the library's own, for the scan of a lines form: the split's
+// count and scan, n read back (*dN and *n: the one wait of such a call, it sizes the offsets), the split's scatter
+struct LinesScratch {
+	StreamScratch tiles, text, offsets;
+	explicit LinesScratch(hipStream_t s) : tiles(s), text(s), offsets(s) {}
+};
+int SplitLines(const char* who, const uint8_t* dRaw, uint64_t size, uint32_t delim, uint64_t* dN, uint64_t* n, hipStream_t stream,
+               LinesScratch& out)
+{
+	SplitPlan plan;
+	if (int rc = LaunchSplitCount(dRaw, size, delim, dN, stream, out.tiles, &plan))
+		return rc;
+	if (int rc = ReadCount(dN, n, stream))
+		return rc;
+	if (*n >= (1ull << 32)) {
+		SetError(std::string(who) + ": 2^32 lines or more in one call");
+		return PIRE_HIP_EUNSUPPORTED;
+	}
+	if (int rc = out.text.Alloc(size_t(size) + 16, "hipMallocAsync(split text)"))
+		return rc;
+	if (int rc = out.offsets.Alloc((size_t(*n) + 1) * 8, "hipMallocAsync(split offsets)"))
+		return rc;
+	return LaunchSplitScatter(plan, out.text.get(), out.offsets.as<uint64_t>(), *n, dN, stream);
+}
+
 int RunLinesImpl(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags, const uint64_t* want,
                  uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_hit_spans, uint64_t* out_hit_masks, uint64_t hit_cap,
                  uint64_t* out_hit_count, void* streamPtr, const LinesGather* gather)
@@ -1916,21 +2106,10 @@ int RunLinesImpl(pire_hip_table* t, const void* raw, uint64_t size, uint32_t del
 	if (int rc = io.Ready())
 		return rc;
 	// the split, into scratch that lives until the scan and the gather behind it are enqueued; n sizes the offsets
-	StreamScratch tiles(stream), text(stream), offsets(stream), ownHits(stream), ownSpans(stream);
-	SplitPlan plan;
-	if (int rc = LaunchSplitCount(dRaw, size, delim, dN, stream, tiles, &plan))
-		return rc;
-	if (int rc = ReadCount(dN, &n, stream))
-		return rc;
-	if (n >= (1ull << 32)) {
-		SetError(std::string(who) + ": 2^32 lines or more in one call");
-		return PIRE_HIP_EUNSUPPORTED;
-	}
-	if (int rc = text.Alloc(size_t(size) + 16, "hipMallocAsync(split text)"))
-		return rc;
-	if (int rc = offsets.Alloc((size_t(n) + 1) * 8, "hipMallocAsync(split offsets)"))
-		return rc;
-	if (int rc = LaunchSplitScatter(plan, text.get(), offsets.as<uint64_t>(), n, dN, stream))
+	LinesScratch lines(stream);
+	StreamScratch ownHits(stream), ownSpans(stream);
+	StreamScratch &text = lines.text, &offsets = lines.offsets;
+	if (int rc = SplitLines(who, dRaw, size, delim, dN, &n, stream, lines))
 		return rc;
 	const uint64_t cap = std::min<uint64_t>(hit_cap, n);   // n lines have at most n hits
 	if (out_hits && cap) {
@@ -2083,6 +2262,74 @@ int pire_hip_run_lines_select(pire_hip_table* t, const void* raw, uint64_t size,
 try {
 	return RunLinesImpl(t, raw, size, delim, flags, want, out_line_count, out_hits, out_hit_spans, out_hit_masks, hit_cap,
 	                    out_hit_count, stream, nullptr);
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+// The frame of RunLinesImpl around the route pass: the same split (SplitLines: the call's one wait), the scan on the lines
+// with the state indices in scratch, one hit list per regexp, and the byte ranges of all rows in one launch
+int pire_hip_run_lines_route(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
+                             uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_hit_spans, uint64_t hit_cap,
+                             uint64_t* out_hit_counts, void* streamPtr)
+try {
+	const char* who = "pire_hip_run_lines_route";
+	if (int rc = RouteArgsInvalid(who, t, nullptr, false, 0, out_hits, out_hit_spans, hit_cap, out_hit_counts))
+		return rc;
+	if (int rc = SplitArgsInvalid(who, raw, size, delim, out_line_count, "out_line_count"))
+		return rc;
+	const uint32_t regexps = HostRegexps(t);
+	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
+	if (!onDevice && size == 0) {
+		*out_line_count = 0;
+		std::fill(out_hit_counts, out_hit_counts + regexps, uint64_t(0));
+		return PIRE_HIP_OK;
+	}
+	BatchIO io(stream, onDevice);
+	const uint8_t* dRaw = nullptr;
+	if (int rc = io.In(static_cast<const uint8_t*>(raw), size_t(size), &dRaw))
+		return rc;
+	uint64_t n = 0;   // host pointers: the line count comes back here first
+	uint64_t *dN = nullptr, *dCounts = nullptr, *dHits = nullptr, *dSpans = nullptr;
+	if (int rc = io.Result(onDevice ? out_line_count : &n, 1, 1, &dN))
+		return rc;
+	if (regexps)
+		if (int rc = io.Result(out_hit_counts, regexps, regexps, &dCounts))
+			return rc;
+	if (int rc = io.Ready())
+		return rc;
+	LinesScratch lines(stream);
+	if (int rc = SplitLines(who, dRaw, size, delim, dN, &n, stream, lines))
+		return rc;
+	const uint64_t cap = onDevice ? hit_cap : std::min<uint64_t>(hit_cap, n);   // host pointers: n lines have at most n hits a row
+	if (out_hits && cap && regexps) {
+		if (int rc = io.Result(out_hits, size_t(regexps) * size_t(cap), 0, &dHits))
+			return rc;
+		if (out_hit_spans)
+			if (int rc = io.Result(out_hit_spans, size_t(regexps) * size_t(cap) * 2, 0, &dSpans))
+				return rc;
+	}
+	if (n == 0) {
+		if (regexps) {
+			const hipError_t e = hipMemsetAsync(dCounts, 0, size_t(regexps) * 8, stream);
+			if (e != hipSuccess)
+				return HipFail(e, "hipMemsetAsync(hit counts)");
+		}
+	} else if (regexps) {
+		const uint32_t runFlags = (flags & (PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END | PIRE_HIP_RUN_GENERIC)) | PIRE_HIP_RUN_ON_DEVICE;
+		if (int rc = pire_hip_run_route(t, lines.text.get(), lines.offsets.as<uint64_t>(), n, runFlags, nullptr, nullptr, nullptr, nullptr,
+		                                dHits, dHits ? cap : 0, dCounts, stream))
+			return rc;
+		if (dSpans)
+			if (int rc = LaunchRouteSpans(dHits, dCounts, regexps, cap, n, lines.offsets.as<uint64_t>(), dSpans, stream))
+				return rc;
+	}
+	if (int rc = io.Finish())
+		return rc;
+	if (onDevice)
+		return PIRE_HIP_OK;
+	*out_line_count = n;
+	return RouteRowsBack(regexps, out_hit_counts, cap, hit_cap, dHits, out_hits, dSpans, out_hit_spans);
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }

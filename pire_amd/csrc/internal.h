@@ -1113,6 +1113,14 @@ int LaunchSplitScatter(const SplitPlan& plan, void* outText, uint64_t* outOffset
                        hipStream_t stream);
 int LaunchSplitSpans(const uint64_t* hits, const uint64_t* hitCount, uint64_t cap, const uint64_t* offsets, uint64_t* spans,
                      hipStream_t stream);
+// route.hip: one ascending hit list per regexp (pire_hip_route).  Device pointers only, three kernels enqueued on `stream`,
+// regexps * ceil(n / 1024) * 4 bytes of scratch from the stream-ordered allocator.  outHits[regexps][hitCap] (nullable:
+// counts only), outHitCounts[regexps]; the image is the select pass's.  LaunchRouteSpans: [begin, end) in the raw buffer of
+// the first min(hitCounts[r], hitCap) hits of every row, spans[regexps][hitCap][2], one launch (offsets as LaunchSplitSpans').
+int LaunchRoute(const SelectDevice& image, uint32_t states, uint32_t words, uint32_t regexps, const uint32_t* stateIdx, uint64_t n,
+                uint64_t* outHits, uint64_t hitCap, uint64_t* outHitCounts, hipStream_t stream);
+int LaunchRouteSpans(const uint64_t* hits, const uint64_t* hitCounts, uint32_t regexps, uint64_t hitCap, uint64_t n,
+                     const uint64_t* offsets, uint64_t* spans, hipStream_t stream);
 // gather.hip: the listed strings of a batch back to back (pire_hip_gather).  Device pointers only, four kernels enqueued on
 // `stream`, no scratch and no allocation (outOffsets, cap + 1 entries, is required where cap > 0).  Where the source ranges come from:
 // spans != nullptr -> raw[spans[2j], spans[2j + 1]) with raw = text and `size` its length; else offsets + idx (nullable:
