@@ -1557,7 +1557,7 @@ try {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
 
-// ---- from end states to matches (select.hip) ---------------------------------------------------------------------------
+// ---- from end states to matches (select.hip, route.hip) ------------------------------------------------------------------
 namespace {
 
 // What pire_hip_select refuses before any device is touched
@@ -1576,35 +1576,65 @@ int SelectArgsInvalid(const pire_hip_table* t, const uint32_t* stateIdx, bool ne
 	return PIRE_HIP_EINVAL;
 }
 
+// The front of the select and the route pass: the table's sizes (a snapshot under the lock), the host form's look at its
+// state indices, the mask image of the current device.  *idle: a host call of no strings -- or, for a pass with a row per
+// regexp, a table of none -- leaves the device nothing to do: no image is uploaded, no device is touched.
+struct SelectImage {
+	uint32_t states, words, regexps;
+	SelectDevice device;
+};
+int SelectImageFor(const char* who, pire_hip_table* t, const uint32_t* stateIdx, uint64_t n, bool onDevice, bool rowPerRegexp,
+                   SelectImage* image, bool* idle)
+{
+	{
+		const std::shared_lock<std::shared_mutex> stable(t->adaptMutex);
+		image->states = t->host.states;
+		image->regexps = t->host.regexps;
+		image->words = SelectMaskWords(image->regexps);
+	}
+	if (!onDevice)
+		for (uint64_t i = 0; i < n; ++i)
+			if (stateIdx[i] >= image->states) {
+				SetError(std::string(who) + ": state_idx out of range");
+				return PIRE_HIP_EINVAL;
+			}
+	*idle = (!onDevice && n == 0) || (rowPerRegexp && image->regexps == 0);
+	if (*idle)
+		return PIRE_HIP_OK;
+	// (the image is in reference numbering: built once, whatever re-rankings come; the lock is for reading t->host)
+	const std::shared_lock<std::shared_mutex> stable(t->adaptMutex);
+	return UploadSelect(t, &image->device);
+}
+
+// Host pointers: the lists of a pass come back only as far as they were written -- row r of dev[rows][staged] (entries of
+// `width` words) into row r of out[rows][pitch], its first min(counts[r], staged) entries.  dev == nullptr: nothing.
+int HitsBack(uint32_t rows, const uint64_t* counts, uint64_t staged, uint64_t pitch, const uint64_t* dev, uint64_t* out, size_t width,
+             const char* what)
+{
+	for (uint32_t r = 0; r < rows && dev; ++r)
+		if (const uint64_t written = std::min(counts[r], staged)) {
+			const hipError_t e = hipMemcpy(out + uint64_t(r) * pitch * width, dev + uint64_t(r) * staged * width, size_t(written) * width * 8,
+			                               hipMemcpyDeviceToHost);
+			if (e != hipSuccess)
+				return HipFail(e, what);
+		}
+	return PIRE_HIP_OK;
+}
+
 int SelectImpl(pire_hip_table* t, const uint32_t* stateIdx, uint64_t n, const uint64_t* want, uint32_t flags,
                uint64_t* outMasks, uint64_t* outHits, uint64_t* outHitMasks, uint64_t hitCap, uint64_t* outHitCount,
                hipStream_t stream)
 {
-	uint32_t states, words;
-	{
-		const std::shared_lock<std::shared_mutex> stable(t->adaptMutex);
-		states = t->host.states;
-		words = SelectMaskWords(t->host.regexps);
-	}
 	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
-	if (!onDevice) {
-		for (uint64_t i = 0; i < n; ++i)
-			if (stateIdx[i] >= states) {
-				SetError("pire_hip_select: state_idx out of range");
-				return PIRE_HIP_EINVAL;
-			}
-		if (n == 0) {
-			*outHitCount = 0;
-			return PIRE_HIP_OK;
-		}
+	SelectImage image;
+	bool idle;
+	if (int rc = SelectImageFor("pire_hip_select", t, stateIdx, n, onDevice, false, &image, &idle))
+		return rc;
+	if (idle) {
+		*outHitCount = 0;
+		return PIRE_HIP_OK;
 	}
-	SelectDevice image;
-	{
-		// (the image is in reference numbering: built once, whatever re-rankings come; the lock is for reading t->host)
-		const std::shared_lock<std::shared_mutex> stable(t->adaptMutex);
-		if (int rc = UploadSelect(t, &image))
-			return rc;
-	}
+	const uint32_t words = image.words;
 	// host pointers: staged in, the three kernels, staged out -- the hits only as far as they were written
 	BatchIO io(stream, onDevice);
 	const uint32_t* dIdx = nullptr;
@@ -1615,9 +1645,8 @@ int SelectImpl(pire_hip_table* t, const uint32_t* stateIdx, uint64_t n, const ui
 		if (int rc = io.In(want, size_t(words), &dWant))
 			return rc;
 	const uint64_t cap = std::min<uint64_t>(hitCap, n);   // n strings have at most n hits: a host call stages no more
-	uint64_t count = 0;   // host pointers: the count comes back here first
 	uint64_t *dCount = nullptr, *dMasks = nullptr, *dHits = nullptr, *dHitMasks = nullptr;
-	if (int rc = io.Result(onDevice ? outHitCount : &count, 1, 1, &dCount))
+	if (int rc = io.Result(outHitCount, 1, 1, &dCount))   // (the count comes back first: it says how far the lists were written)
 		return rc;
 	if (outMasks)
 		if (int rc = io.Result(outMasks, size_t(n) * words, size_t(n) * words, &dMasks))
@@ -1630,26 +1659,41 @@ int SelectImpl(pire_hip_table* t, const uint32_t* stateIdx, uint64_t n, const ui
 			return rc;
 	if (int rc = io.Ready())
 		return rc;
-	if (int rc = LaunchSelect(image, states, words, dIdx, n, dWant, dMasks, dHits, dHitMasks, dHits ? cap : 0, dCount, stream))
+	if (int rc = LaunchSelect(image.device, image.states, words, dIdx, n, dWant, dMasks, dHits, dHitMasks, dHits ? cap : 0, dCount, stream))
 		return rc;
 	if (int rc = io.Finish())
 		return rc;
 	if (onDevice)
 		return PIRE_HIP_OK;
-	*outHitCount = count;
-	const uint64_t written = std::min<uint64_t>(count, dHits ? cap : 0);
-	if (written) {
-		hipError_t e = hipMemcpy(outHits, dHits, size_t(written) * 8, hipMemcpyDeviceToHost);
-		if (e == hipSuccess && dHitMasks)
-			e = hipMemcpy(outHitMasks, dHitMasks, size_t(written) * words * 8, hipMemcpyDeviceToHost);
-		if (e != hipSuccess)
-			return HipFail(e, "hipMemcpy(hits)");
-	}
-	return PIRE_HIP_OK;
+	if (int rc = HitsBack(1, outHitCount, cap, cap, dHits, outHits, 1, "hipMemcpy(hits)"))
+		return rc;
+	return HitsBack(1, outHitCount, cap, cap, dHits ? dHitMasks : nullptr, outHitMasks, words, "hipMemcpy(hits)");
 }
 
-// pire_hip_run[_strided] followed by pire_hip_select on the same stream; `run` makes the scan call with the state-index
-// array it is given
+// pire_hip_run[_strided] followed by a pass over its state indices on the same stream: the one owner of the state-index
+// array where the caller has none -- a vector with host pointers, stream-ordered scratch on the device.  `run` makes the scan
+// call with the array it is given, `pass` the select or the route call (its flags: ON_DEVICE or nothing).
+// (Whatever staging path the scan takes -- chunked, one piece, segmented --, its state indices arrive in ONE host array
+// before the pass sees them: hit indices are relative to the whole batch.)
+int RunThenPass(uint64_t n, uint32_t flags, uint32_t* outIdx, hipStream_t stream, const std::function<int(uint32_t*)>& run,
+                const std::function<int(const uint32_t*, uint32_t)>& pass)
+{
+	const uint32_t onDevice = flags & PIRE_HIP_RUN_ON_DEVICE;
+	std::vector<uint32_t> own;
+	StreamScratch scratch(stream);
+	if (!outIdx && !onDevice) {
+		own.resize(size_t(n));
+		outIdx = own.data();
+	} else if (!outIdx && n) {
+		if (int rc = scratch.Alloc(size_t(n) * 4, "hipMallocAsync(state indices)"))
+			return rc;
+		outIdx = scratch.as<uint32_t>();
+	}
+	if (int rc = run(outIdx))
+		return rc;
+	return pass(outIdx, onDevice);
+}
+
 int RunSelectImpl(pire_hip_table* t, uint64_t n, const uint64_t* want, uint32_t flags, uint32_t* outIdx, uint64_t* outMasks,
                   uint64_t* outHits, uint64_t* outHitMasks, uint64_t hitCap, uint64_t* outHitCount, void* streamPtr,
                   const std::function<int(uint32_t*)>& run)
@@ -1657,27 +1701,82 @@ int RunSelectImpl(pire_hip_table* t, uint64_t n, const uint64_t* want, uint32_t 
 	if (int rc = SelectArgsInvalid(t, nullptr, false, n, outHits, outHitMasks, hitCap, outHitCount))
 		return rc;
 	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
-	if (!(flags & PIRE_HIP_RUN_ON_DEVICE)) {
-		// (whatever staging path the scan takes -- chunked, one piece, segmented --, its state indices arrive in ONE host
-		// array before the select pass sees them: hit indices are relative to the whole batch)
-		std::vector<uint32_t> own;
-		if (!outIdx) {
-			own.resize(size_t(n));
-			outIdx = own.data();
-		}
-		if (int rc = run(outIdx))
-			return rc;
-		return SelectImpl(t, outIdx, n, want, 0, outMasks, outHits, outHitMasks, hitCap, outHitCount, stream);
+	return RunThenPass(n, flags, outIdx, stream, run, [&](const uint32_t* idx, uint32_t passFlags) {
+		return SelectImpl(t, idx, n, want, passFlags, outMasks, outHits, outHitMasks, hitCap, outHitCount, stream);
+	});
+}
+
+uint32_t HostRegexps(const pire_hip_table* t)
+{
+	const auto stable = HostLock(t);
+	return t->host.regexps;
+}
+
+// What the route entry points refuse before any device is touched
+int RouteArgsInvalid(const char* who, const pire_hip_table* t, const uint32_t* stateIdx, bool needIdx, uint64_t n,
+                     const uint64_t* outHits, const uint64_t* outHitSpans, uint64_t hitCap, const uint64_t* outHitCounts)
+{
+	const char* what = !t                                             ? "null table"
+	                   : needIdx && n && !stateIdx                    ? "null state_idx"
+	                   : !outHitCounts && HostRegexps(t)              ? "null out_hit_counts"
+	                   : hitCap && !outHits                           ? "hit_cap > 0 with null out_hits"
+	                   : outHitSpans && !outHits                      ? "out_hit_spans without out_hits"
+	                                                                  : nullptr;
+	if (!what)
+		return PIRE_HIP_OK;
+	SetError(std::string(who) + ": " + what);
+	return PIRE_HIP_EINVAL;
+}
+
+int RouteImpl(pire_hip_table* t, const uint32_t* stateIdx, uint64_t n, uint32_t flags, uint64_t* outHits, uint64_t hitCap,
+              uint64_t* outHitCounts, hipStream_t stream)
+{
+	if (n >= (1ull << 32)) {
+		SetError("pire_hip_route: 2^32 strings or more in one call");
+		return PIRE_HIP_EUNSUPPORTED;
 	}
-	StreamScratch scratch(stream);
-	if (!outIdx && n) {
-		if (int rc = scratch.Alloc(size_t(n) * 4, "hipMallocAsync(state indices)"))
-			return rc;
-		outIdx = scratch.as<uint32_t>();
-	}
-	if (int rc = run(outIdx))
+	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
+	SelectImage image;
+	bool idle;
+	if (int rc = SelectImageFor("pire_hip_route", t, stateIdx, n, onDevice, true, &image, &idle))
 		return rc;
-	return SelectImpl(t, outIdx, n, want, PIRE_HIP_RUN_ON_DEVICE, outMasks, outHits, outHitMasks, hitCap, outHitCount, stream);
+	const uint32_t regexps = image.regexps;
+	if (idle) {
+		if (regexps)   // (no rows: nothing to write)
+			std::fill(outHitCounts, outHitCounts + regexps, uint64_t(0));
+		return PIRE_HIP_OK;
+	}
+	// host pointers: staged in, the three kernels, staged out -- the rows at a pitch of their own, min(hit_cap, n)
+	BatchIO io(stream, onDevice);
+	const uint32_t* dIdx = nullptr;
+	if (int rc = io.In(stateIdx, size_t(n), &dIdx))
+		return rc;
+	const uint64_t cap = onDevice ? hitCap : std::min<uint64_t>(hitCap, n);
+	uint64_t *dCounts = nullptr, *dHits = nullptr;
+	if (int rc = io.Result(outHitCounts, regexps, regexps, &dCounts))
+		return rc;
+	if (outHits && cap)
+		if (int rc = io.Result(outHits, size_t(regexps) * size_t(cap), 0, &dHits))
+			return rc;
+	if (int rc = io.Ready())
+		return rc;
+	if (int rc = LaunchRoute(image.device, image.states, image.words, regexps, dIdx, n, dHits, dHits ? cap : 0, dCounts, stream))
+		return rc;
+	if (int rc = io.Finish())
+		return rc;
+	// (the caller's pitch stays hitCap)
+	return onDevice ? PIRE_HIP_OK : HitsBack(regexps, outHitCounts, cap, hitCap, dHits, outHits, 1, "hipMemcpy(route hits)");
+}
+
+int RunRouteImpl(const char* who, pire_hip_table* t, uint64_t n, uint32_t flags, uint32_t* outIdx, uint64_t* outHits, uint64_t hitCap,
+                 uint64_t* outHitCounts, void* streamPtr, const std::function<int(uint32_t*)>& run)
+{
+	if (int rc = RouteArgsInvalid(who, t, nullptr, false, n, outHits, nullptr, hitCap, outHitCounts))
+		return rc;
+	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+	return RunThenPass(n, flags, outIdx, stream, run, [&](const uint32_t* idx, uint32_t passFlags) {
+		return RouteImpl(t, idx, n, passFlags, outHits, hitCap, outHitCounts, stream);
+	});
 }
 
 }  // namespace
@@ -1729,137 +1828,6 @@ try {
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
-
-// ---- one hit list per regexp (route.hip) --------------------------------------------------------------------------------
-namespace {
-
-uint32_t HostRegexps(const pire_hip_table* t)
-{
-	const auto stable = HostLock(t);
-	return t->host.regexps;
-}
-
-// What the route entry points refuse before any device is touched
-int RouteArgsInvalid(const char* who, const pire_hip_table* t, const uint32_t* stateIdx, bool needIdx, uint64_t n,
-                     const uint64_t* outHits, const uint64_t* outHitSpans, uint64_t hitCap, const uint64_t* outHitCounts)
-{
-	const char* what = !t                                             ? "null table"
-	                   : needIdx && n && !stateIdx                    ? "null state_idx"
-	                   : !outHitCounts && HostRegexps(t)              ? "null out_hit_counts"
-	                   : hitCap && !outHits                           ? "hit_cap > 0 with null out_hits"
-	                   : outHitSpans && !outHits                      ? "out_hit_spans without out_hits"
-	                                                                  : nullptr;
-	if (!what)
-		return PIRE_HIP_OK;
-	SetError(std::string(who) + ": " + what);
-	return PIRE_HIP_EINVAL;
-}
-
-// Host pointers: the rows come back one by one and only as far as they were written; the caller's pitch stays hitCap
-int RouteRowsBack(uint32_t regexps, const uint64_t* counts, uint64_t staged, uint64_t hitCap, const uint64_t* dHits, uint64_t* outHits,
-                  const uint64_t* dSpans, uint64_t* outSpans)
-{
-	for (uint32_t r = 0; r < regexps && dHits; ++r) {
-		const uint64_t written = std::min(counts[r], staged);
-		if (!written)
-			continue;
-		hipError_t e = hipMemcpy(outHits + uint64_t(r) * hitCap, dHits + uint64_t(r) * staged, size_t(written) * 8, hipMemcpyDeviceToHost);
-		if (e == hipSuccess && dSpans)
-			e = hipMemcpy(outSpans + 2 * uint64_t(r) * hitCap, dSpans + 2 * uint64_t(r) * staged, size_t(written) * 16,
-			              hipMemcpyDeviceToHost);
-		if (e != hipSuccess)
-			return HipFail(e, "hipMemcpy(route hits)");
-	}
-	return PIRE_HIP_OK;
-}
-
-int RouteImpl(pire_hip_table* t, const uint32_t* stateIdx, uint64_t n, uint32_t flags, uint64_t* outHits, uint64_t hitCap,
-              uint64_t* outHitCounts, hipStream_t stream)
-{
-	uint32_t states, words, regexps;
-	{
-		const std::shared_lock<std::shared_mutex> stable(t->adaptMutex);
-		states = t->host.states;
-		regexps = t->host.regexps;
-		words = SelectMaskWords(regexps);
-	}
-	if (n >= (1ull << 32)) {
-		SetError("pire_hip_route: 2^32 strings or more in one call");
-		return PIRE_HIP_EUNSUPPORTED;
-	}
-	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
-	if (!onDevice)
-		for (uint64_t i = 0; i < n; ++i)
-			if (stateIdx[i] >= states) {
-				SetError("pire_hip_route: state_idx out of range");
-				return PIRE_HIP_EINVAL;
-			}
-	if (regexps == 0)
-		return PIRE_HIP_OK;   // no rows: nothing to write
-	if (!onDevice && n == 0) {
-		std::fill(outHitCounts, outHitCounts + regexps, uint64_t(0));
-		return PIRE_HIP_OK;
-	}
-	SelectDevice image;
-	{
-		// (the image is in reference numbering: built once, whatever re-rankings come; the lock is for reading t->host)
-		const std::shared_lock<std::shared_mutex> stable(t->adaptMutex);
-		if (int rc = UploadSelect(t, &image))
-			return rc;
-	}
-	// host pointers: staged in, the three kernels, staged out -- the rows at a pitch of their own, min(hit_cap, n)
-	BatchIO io(stream, onDevice);
-	const uint32_t* dIdx = nullptr;
-	if (int rc = io.In(stateIdx, size_t(n), &dIdx))
-		return rc;
-	const uint64_t cap = onDevice ? hitCap : std::min<uint64_t>(hitCap, n);
-	uint64_t *dCounts = nullptr, *dHits = nullptr;
-	if (int rc = io.Result(outHitCounts, regexps, regexps, &dCounts))
-		return rc;
-	if (outHits && cap)
-		if (int rc = io.Result(outHits, size_t(regexps) * size_t(cap), 0, &dHits))
-			return rc;
-	if (int rc = io.Ready())
-		return rc;
-	if (int rc = LaunchRoute(image, states, words, regexps, dIdx, n, dHits, dHits ? cap : 0, dCounts, stream))
-		return rc;
-	if (int rc = io.Finish())
-		return rc;
-	return onDevice ? PIRE_HIP_OK : RouteRowsBack(regexps, outHitCounts, cap, hitCap, dHits, outHits, nullptr, nullptr);
-}
-
-// pire_hip_run[_strided] followed by pire_hip_route on the same stream; `run` makes the scan call with the state-index
-// array it is given (the shape of RunSelectImpl)
-int RunRouteImpl(const char* who, pire_hip_table* t, uint64_t n, uint32_t flags, uint32_t* outIdx, uint64_t* outHits, uint64_t hitCap,
-                 uint64_t* outHitCounts, void* streamPtr, const std::function<int(uint32_t*)>& run)
-{
-	if (int rc = RouteArgsInvalid(who, t, nullptr, false, n, outHits, nullptr, hitCap, outHitCounts))
-		return rc;
-	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
-	if (!(flags & PIRE_HIP_RUN_ON_DEVICE)) {
-		// (whatever staging path the scan takes, its state indices arrive in ONE host array before the route pass sees
-		// them: hit indices are relative to the whole batch)
-		std::vector<uint32_t> own;
-		if (!outIdx) {
-			own.resize(size_t(n));
-			outIdx = own.data();
-		}
-		if (int rc = run(outIdx))
-			return rc;
-		return RouteImpl(t, outIdx, n, 0, outHits, hitCap, outHitCounts, stream);
-	}
-	StreamScratch scratch(stream);
-	if (!outIdx && n) {
-		if (int rc = scratch.Alloc(size_t(n) * 4, "hipMallocAsync(state indices)"))
-			return rc;
-		outIdx = scratch.as<uint32_t>();
-	}
-	if (int rc = run(outIdx))
-		return rc;
-	return RouteImpl(t, outIdx, n, PIRE_HIP_RUN_ON_DEVICE, outHits, hitCap, outHitCounts, stream);
-}
-
-}  // namespace
 
 int pire_hip_route(pire_hip_table* t, const uint32_t* state_idx, uint64_t n, uint32_t flags, uint64_t* out_hits, uint64_t hit_cap,
                    uint64_t* out_hit_counts, void* stream)
@@ -1920,6 +1888,17 @@ int ReadCount(const uint64_t* dev, uint64_t* host, hipStream_t stream)
 	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "reading the number of strings back");
 }
 
+// What the passes that are not in-place refuse: outText[0, textCap) over source[0, size)
+int GatherOverlaps(const char* who, const void* source, uint64_t size, const void* outText, uint64_t textCap,
+                   const char* what = "out_text overlaps the source (the pass is not in-place)")
+{
+	const uintptr_t r = reinterpret_cast<uintptr_t>(source), o = reinterpret_cast<uintptr_t>(outText);
+	if (!(outText && size && textCap && o < r + size && r < o + textCap))
+		return PIRE_HIP_OK;
+	SetError(std::string(who) + ": " + what);
+	return PIRE_HIP_EINVAL;
+}
+
 }  // namespace
 
 int pire_hip_split(const void* raw, uint64_t size, uint32_t delim, uint32_t flags, void* out_text, uint64_t* out_offsets,
@@ -1931,11 +1910,8 @@ try {
 		SetError("pire_hip_split: offsets_cap > 0 with null out_offsets");
 		return PIRE_HIP_EINVAL;
 	}
-	const uintptr_t r = reinterpret_cast<uintptr_t>(raw), o = reinterpret_cast<uintptr_t>(out_text);
-	if (out_text && size && o < r + size && r < o + size) {
-		SetError("pire_hip_split: out_text overlaps raw (the pass is not in-place)");
-		return PIRE_HIP_EINVAL;
-	}
+	if (int rc = GatherOverlaps("pire_hip_split", raw, size, out_text, size, "out_text overlaps raw (the pass is not in-place)"))
+		return rc;
 	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
 	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
 	if (!onDevice && size == 0) {
@@ -1985,13 +1961,17 @@ try {
 
 namespace {
 
-// What pire_hip_run_lines_gather adds to pire_hip_run_lines_select: where the bytes of the selected lines go
+// What the gather forms of the lines entry points add: where the bytes of the selected lines go, and which lists the frame
+// keeps in scratch of its own where the caller has no array for them (the spans always; the hits where the pass writes
+// its spans from them)
 struct LinesGather {
 	uint32_t tail;
 	void* outText;
 	uint64_t textCap;
 	uint64_t* outOffsets;
 	uint64_t* outBytes;
+	bool needHits;
+	const char* spansLabel;
 };
 
 // What the gather entry points refuse of their outputs before any device is touched.  capAlias: what this entry point
@@ -2014,15 +1994,6 @@ int GatherOutputsInvalid(const char* who, const char* capAlias, uint64_t cap, ui
 int GatherRefuse(const char* who, const char* what)
 {
 	SetError(std::string(who) + ": " + what);
-	return PIRE_HIP_EINVAL;
-}
-
-int GatherOverlaps(const char* who, const void* source, uint64_t size, const void* outText, uint64_t textCap)
-{
-	const uintptr_t r = reinterpret_cast<uintptr_t>(source), o = reinterpret_cast<uintptr_t>(outText);
-	if (!(outText && size && textCap && o < r + size && r < o + textCap))
-		return PIRE_HIP_OK;
-	SetError(std::string(who) + ": out_text overlaps the source (the pass is not in-place)");
 	return PIRE_HIP_EINVAL;
 }
 
@@ -2051,6 +2022,145 @@ int SplitLines(const char* who, const uint8_t* dRaw, uint64_t size, uint32_t del
 	return LaunchSplitScatter(plan, out.text.get(), out.offsets.as<uint64_t>(), *n, dN, stream);
 }
 
+// The frame of the three lines entry points (pire_hip_run_lines_select / _gather, pire_hip_run_lines_route,
+// pire_hip_capture_lines_gather) around their scan + pass: raw bytes in, hit lists (and, in the gather forms, the bytes of the
+// hits) out.  An entry point checks its arguments, then walks the frame's steps in this order:
+//   HostEdge   an empty buffer with host pointers: the line count and the gather's outputs are zeroed, no device is touched
+//   Open       raw staged in (inputs of the entry point's own go in behind it: the select form's `want`)
+//   Split      the line count, `rows` hit counts and the byte count staged to come back first; SplitLines -- the call's one
+//              wait --; cap: no list is longer than the lines are many
+//   Lists      hits[rows][cap] and spans[rows][cap][2] staged at size 0 where the caller has arrays for them; a gather form:
+//              scratch for the lists it chains on and the caller did not ask for, out_text and out_offsets
+//   -- the entry point enqueues its scan + pass on the lines (Text(), Offsets(), n, cap, RunFlags()) into dCounts / dHits / dSpans --
+//   Close      a gather form: the gather straight from raw through the spans; Finish(); host pointers: the line count, and
+//              the lists, offsets and text back only as far as they were written (HitsBack)
+struct LinesFrame {
+	const char* who;
+	const uint8_t* raw;
+	uint64_t size;
+	uint32_t delim, flags;
+	const LinesGather* gather;   // nullable
+	hipStream_t stream;
+	bool onDevice;
+	BatchIO io;
+	LinesScratch lines;
+	StreamScratch ownHits, ownSpans;
+	uint64_t n = 0, cap = 0, hitCap = 0, textRoom = 0;   // textRoom of out_text: k lines and their tails are size + k bytes at most
+	uint32_t rows = 0;
+	uint64_t *outLineCount = nullptr, *outCounts = nullptr, *outHits = nullptr, *outSpans = nullptr;
+	const uint8_t* dRaw = nullptr;
+	uint64_t *dN = nullptr, *dCounts = nullptr, *dHits = nullptr, *dSpans = nullptr, *dBytes = nullptr, *dOutOffsets = nullptr;
+	uint8_t* dOutText = nullptr;
+
+	LinesFrame(const char* who_, const void* raw_, uint64_t size_, uint32_t delim_, uint32_t flags_, const LinesGather* gather_, void* stream_)
+		: who(who_), raw(static_cast<const uint8_t*>(raw_)), size(size_), delim(delim_), flags(flags_), gather(gather_),
+		  stream(static_cast<hipStream_t>(stream_)), onDevice((flags_ & PIRE_HIP_RUN_ON_DEVICE) != 0), io(stream, onDevice), lines(stream),
+		  ownHits(stream), ownSpans(stream)
+	{
+	}
+	const void* Text() const { return lines.text.get(); }
+	const uint64_t* Offsets() const { return lines.offsets.as<uint64_t>(); }
+	uint32_t RunFlags() const { return (flags & (PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END | PIRE_HIP_RUN_GENERIC)) | PIRE_HIP_RUN_ON_DEVICE; }
+
+	bool HostEdge(uint64_t* lineCount)
+	{
+		if (onDevice || size)
+			return false;
+		*lineCount = 0;
+		if (gather) {
+			*gather->outBytes = 0;
+			if (gather->outOffsets)
+				gather->outOffsets[0] = 0;
+		}
+		return true;
+	}
+	int Open() { return io.In(raw, size_t(size), &dRaw); }
+	// capByLines: false where a device caller's pitch has to stay hit_cap itself (the route form's rows)
+	int Split(uint64_t* lineCount, uint64_t* counts, uint32_t rows_, uint64_t hitCap_, bool capByLines)
+	{
+		outLineCount = lineCount, outCounts = counts, rows = rows_, hitCap = hitCap_;
+		if (int rc = io.Result(onDevice ? lineCount : &n, 1, 1, &dN))   // (host pointers: n comes back here first)
+			return rc;
+		if (rows)
+			if (int rc = io.Result(counts, rows, rows, &dCounts))
+				return rc;
+		if (gather)
+			if (int rc = io.Result(gather->outBytes, 1, 1, &dBytes))
+				return rc;
+		if (int rc = io.Ready())
+			return rc;
+		// the split, into scratch that lives until the scan and the gather behind it are enqueued; n sizes the offsets
+		if (int rc = SplitLines(who, dRaw, size, delim, dN, &n, stream, lines))
+			return rc;
+		cap = capByLines ? std::min<uint64_t>(hitCap, n) : hitCap;   // n lines have at most n hits
+		return PIRE_HIP_OK;
+	}
+	int Lists(uint64_t* hits, uint64_t* spans)
+	{
+		outHits = hits, outSpans = spans;
+		const size_t entries = size_t(rows) * size_t(cap);
+		if (hits && entries)
+			if (int rc = io.Result(hits, entries, 0, &dHits))
+				return rc;
+		if (spans && entries)
+			if (int rc = io.Result(spans, entries * 2, 0, &dSpans))
+				return rc;
+		if (!gather)
+			return PIRE_HIP_OK;
+		if (cap) {
+			if (!dHits && gather->needHits) {
+				if (int rc = ownHits.Alloc(size_t(cap) * 8, "hipMallocAsync(hits)"))
+					return rc;
+				dHits = ownHits.as<uint64_t>();
+			}
+			if (!dSpans) {
+				if (int rc = ownSpans.Alloc(size_t(cap) * 16, gather->spansLabel))
+					return rc;
+				dSpans = ownSpans.as<uint64_t>();
+			}
+			textRoom = std::min(gather->textCap, size + cap);
+			if (textRoom)
+				if (int rc = io.Result(static_cast<uint8_t*>(gather->outText), size_t(textRoom), 0, &dOutText))
+					return rc;
+		}
+		return gather->outOffsets ? io.Result(gather->outOffsets, size_t(cap) + 1, 0, &dOutOffsets) : PIRE_HIP_OK;
+	}
+	// n == 0: the hit counts are zeroed where the entry point has no pass to do it
+	int ZeroCounts(const char* what)
+	{
+		const hipError_t e = rows ? hipMemsetAsync(dCounts, 0, size_t(rows) * 8, stream) : hipSuccess;
+		return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, what);
+	}
+	int Close(const char* backLabel)
+	{
+		if (gather) {
+			// straight from raw, through the spans (cap == 0: *out_bytes = 0 and out_offsets[0] = 0, nothing is read)
+			const GatherSource src = {dRaw, nullptr, 0, nullptr, dSpans, size};
+			if (int rc = LaunchGather(src, dCounts, cap, gather->tail, dOutText, textRoom, dOutOffsets, dBytes, kGatherTotalUnknown, stream))
+				return rc;
+		}
+		if (int rc = io.Finish())
+			return rc;
+		if (onDevice)
+			return PIRE_HIP_OK;
+		*outLineCount = n;
+		// (the caller's pitch stays hit_cap where the staged rows are cap long)
+		if (int rc = HitsBack(rows, outCounts, cap, hitCap, outHits ? dHits : nullptr, outHits, 1, backLabel))
+			return rc;
+		if (int rc = HitsBack(rows, outCounts, cap, hitCap, outSpans ? dSpans : nullptr, outSpans, 2, backLabel))
+			return rc;
+		if (!gather)
+			return PIRE_HIP_OK;
+		const uint64_t written = std::min(outCounts[0], cap), bytes = std::min(*gather->outBytes, textRoom);
+		hipError_t e = hipSuccess;
+		if (dOutOffsets)
+			e = hipMemcpy(gather->outOffsets, dOutOffsets, (size_t(written) + 1) * 8, hipMemcpyDeviceToHost);
+		if (e == hipSuccess && bytes)
+			e = hipMemcpy(gather->outText, dOutText, size_t(bytes), hipMemcpyDeviceToHost);
+		return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, backLabel);
+	}
+};
+
 int RunLinesImpl(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags, const uint64_t* want,
                  uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_hit_spans, uint64_t* out_hit_masks, uint64_t hit_cap,
                  uint64_t* out_hit_count, void* streamPtr, const LinesGather* gather)
@@ -2072,118 +2182,40 @@ int RunLinesImpl(pire_hip_table* t, const void* raw, uint64_t size, uint32_t del
 		if (int rc = GatherOverlaps(who, raw, size, gather->outText, gather->textCap))
 			return rc;
 	}
-	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
-	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
-	if (!onDevice && size == 0) {
-		*out_line_count = *out_hit_count = 0;
-		if (gather) {
-			*gather->outBytes = 0;
-			if (gather->outOffsets)
-				gather->outOffsets[0] = 0;
-		}
+	LinesFrame f(who, raw, size, delim, flags, gather, streamPtr);
+	if (f.HostEdge(out_line_count)) {
+		*out_hit_count = 0;
 		return PIRE_HIP_OK;
 	}
 	const uint32_t words = pire_hip_table_mask_words(t);
-	BatchIO io(stream, onDevice);
-	const uint8_t* dRaw = nullptr;
 	const uint64_t* dWant = nullptr;
-	if (int rc = io.In(static_cast<const uint8_t*>(raw), size_t(size), &dRaw))
+	uint64_t* dHitMasks = nullptr;
+	if (int rc = f.Open())
 		return rc;
 	if (want)
-		if (int rc = io.In(want, size_t(words), &dWant))
+		if (int rc = f.io.In(want, size_t(words), &dWant))
 			return rc;
-	uint64_t n = 0, count = 0, bytes = 0;   // host pointers: the counts come back here first
-	uint64_t *dN = nullptr, *dCount = nullptr, *dHits = nullptr, *dSpans = nullptr, *dHitMasks = nullptr;
-	uint64_t *dBytes = nullptr, *dOutOffsets = nullptr;
-	uint8_t* dOutText = nullptr;
-	if (int rc = io.Result(onDevice ? out_line_count : &n, 1, 1, &dN))
+	if (int rc = f.Split(out_line_count, out_hit_count, 1, hit_cap, true))
 		return rc;
-	if (int rc = io.Result(onDevice ? out_hit_count : &count, 1, 1, &dCount))
+	if (int rc = f.Lists(out_hits, out_hit_spans))
 		return rc;
-	if (gather)
-		if (int rc = io.Result(onDevice ? gather->outBytes : &bytes, 1, 1, &dBytes))
+	if (out_hits && out_hit_masks && f.cap)
+		if (int rc = f.io.Result(out_hit_masks, size_t(f.cap) * words, 0, &dHitMasks))
 			return rc;
-	if (int rc = io.Ready())
-		return rc;
-	// the split, into scratch that lives until the scan and the gather behind it are enqueued; n sizes the offsets
-	LinesScratch lines(stream);
-	StreamScratch ownHits(stream), ownSpans(stream);
-	StreamScratch &text = lines.text, &offsets = lines.offsets;
-	if (int rc = SplitLines(who, dRaw, size, delim, dN, &n, stream, lines))
-		return rc;
-	const uint64_t cap = std::min<uint64_t>(hit_cap, n);   // n lines have at most n hits
-	if (out_hits && cap) {
-		if (int rc = io.Result(out_hits, size_t(cap), 0, &dHits))
+	if (f.n == 0) {
+		if (int rc = f.ZeroCounts("hipMemsetAsync(hit count)"))
 			return rc;
-		if (out_hit_spans)
-			if (int rc = io.Result(out_hit_spans, size_t(cap) * 2, 0, &dSpans))
-				return rc;
-		if (out_hit_masks)
-			if (int rc = io.Result(out_hit_masks, size_t(cap) * words, 0, &dHitMasks))
-				return rc;
-	}
-	uint64_t textRoom = 0;   // of out_text: the k lines and their tails are size + k bytes at most
-	if (gather && cap) {
-		if (!dHits) {
-			if (int rc = ownHits.Alloc(size_t(cap) * 8, "hipMallocAsync(hits)"))
-				return rc;
-			dHits = ownHits.as<uint64_t>();
-		}
-		if (!dSpans) {
-			if (int rc = ownSpans.Alloc(size_t(cap) * 16, "hipMallocAsync(hit spans)"))
-				return rc;
-			dSpans = ownSpans.as<uint64_t>();
-		}
-		textRoom = std::min(gather->textCap, size + cap);
-		if (textRoom)
-			if (int rc = io.Result(static_cast<uint8_t*>(gather->outText), size_t(textRoom), 0, &dOutText))
-				return rc;
-	}
-	if (gather && gather->outOffsets)
-		if (int rc = io.Result(gather->outOffsets, size_t(cap) + 1, 0, &dOutOffsets))
-			return rc;
-	if (n == 0) {
-		const hipError_t e = hipMemsetAsync(dCount, 0, 8, stream);
-		if (e != hipSuccess)
-			return HipFail(e, "hipMemsetAsync(hit count)");
 	} else {
-		const uint32_t runFlags = (flags & (PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END | PIRE_HIP_RUN_GENERIC)) | PIRE_HIP_RUN_ON_DEVICE;
-		if (int rc = pire_hip_run_select(t, text.get(), offsets.as<uint64_t>(), n, runFlags, nullptr, nullptr, nullptr, nullptr, dWant,
-		                                 nullptr, dHits, dHitMasks, dHits ? cap : 0, dCount, stream))
+		if (int rc = pire_hip_run_select(t, f.Text(), f.Offsets(), f.n, f.RunFlags(), nullptr, nullptr, nullptr, nullptr, dWant, nullptr,
+		                                 f.dHits, dHitMasks, f.dHits ? f.cap : 0, f.dCounts, f.stream))
 			return rc;
-		if (dSpans)
-			if (int rc = LaunchSplitSpans(dHits, dCount, cap, offsets.as<uint64_t>(), dSpans, stream))
+		if (f.dSpans)
+			if (int rc = LaunchHitSpans(f.dHits, f.dCounts, 1, f.cap, f.cap, f.Offsets(), f.dSpans, f.stream, "split spans launch"))
 				return rc;
 	}
-	if (gather) {
-		// straight from raw, through the spans (cap == 0: *out_bytes = 0 and out_offsets[0] = 0, nothing is read)
-		const GatherSource src = {dRaw, nullptr, 0, nullptr, dSpans, size};
-		if (int rc = LaunchGather(src, dCount, cap, gather->tail, dOutText, textRoom, dOutOffsets, dBytes, kGatherTotalUnknown, stream))
-			return rc;
-	}
-	if (int rc = io.Finish())
+	if (int rc = f.Close("hipMemcpy(hits)"))
 		return rc;
-	if (onDevice)
-		return PIRE_HIP_OK;
-	*out_line_count = n;
-	*out_hit_count = count;
-	const uint64_t written = std::min<uint64_t>(count, dHits ? cap : 0);
-	hipError_t e = hipSuccess;
-	if (written && out_hits) {
-		e = hipMemcpy(out_hits, dHits, size_t(written) * 8, hipMemcpyDeviceToHost);
-		if (e == hipSuccess && out_hit_spans)
-			e = hipMemcpy(out_hit_spans, dSpans, size_t(written) * 16, hipMemcpyDeviceToHost);
-		if (e == hipSuccess && dHitMasks)
-			e = hipMemcpy(out_hit_masks, dHitMasks, size_t(written) * words * 8, hipMemcpyDeviceToHost);
-	}
-	if (gather) {
-		*gather->outBytes = bytes;
-		if (e == hipSuccess && dOutOffsets)
-			e = hipMemcpy(gather->outOffsets, dOutOffsets, (size_t(written) + 1) * 8, hipMemcpyDeviceToHost);
-		if (e == hipSuccess && std::min(bytes, textRoom))
-			e = hipMemcpy(gather->outText, dOutText, size_t(std::min(bytes, textRoom)), hipMemcpyDeviceToHost);
-	}
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(hits)");
+	return f.onDevice ? PIRE_HIP_OK : HitsBack(1, out_hit_count, f.cap, f.cap, dHitMasks, out_hit_masks, words, "hipMemcpy(hits)");
 }
 
 // Both gather entry points behind their checks.  spans == nullptr: text + offsets[n + 1] + idx; else raw = text, `size` bytes.
@@ -2266,8 +2298,8 @@ try {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
 
-// The frame of RunLinesImpl around the route pass: the same split (SplitLines: the call's one wait), the scan on the lines
-// with the state indices in scratch, one hit list per regexp, and the byte ranges of all rows in one launch
+// The frame around the route pass: the scan on the lines with the state indices in scratch, one hit list per regexp, and the
+// byte ranges of all rows in one launch
 int pire_hip_run_lines_route(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
                              uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_hit_spans, uint64_t hit_cap,
                              uint64_t* out_hit_counts, void* streamPtr)
@@ -2278,58 +2310,31 @@ try {
 	if (int rc = SplitArgsInvalid(who, raw, size, delim, out_line_count, "out_line_count"))
 		return rc;
 	const uint32_t regexps = HostRegexps(t);
-	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
-	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
-	if (!onDevice && size == 0) {
-		*out_line_count = 0;
+	LinesFrame f(who, raw, size, delim, flags, nullptr, streamPtr);
+	if (f.HostEdge(out_line_count)) {
 		std::fill(out_hit_counts, out_hit_counts + regexps, uint64_t(0));
 		return PIRE_HIP_OK;
 	}
-	BatchIO io(stream, onDevice);
-	const uint8_t* dRaw = nullptr;
-	if (int rc = io.In(static_cast<const uint8_t*>(raw), size_t(size), &dRaw))
+	if (int rc = f.Open())
 		return rc;
-	uint64_t n = 0;   // host pointers: the line count comes back here first
-	uint64_t *dN = nullptr, *dCounts = nullptr, *dHits = nullptr, *dSpans = nullptr;
-	if (int rc = io.Result(onDevice ? out_line_count : &n, 1, 1, &dN))
+	// (host pointers: n lines have at most n hits a row; a device caller's pitch is hit_cap itself)
+	if (int rc = f.Split(out_line_count, out_hit_counts, regexps, hit_cap, !f.onDevice))
 		return rc;
-	if (regexps)
-		if (int rc = io.Result(out_hit_counts, regexps, regexps, &dCounts))
+	if (int rc = f.Lists(out_hits, out_hit_spans))
+		return rc;
+	if (f.n == 0) {
+		if (int rc = f.ZeroCounts("hipMemsetAsync(hit counts)"))
 			return rc;
-	if (int rc = io.Ready())
-		return rc;
-	LinesScratch lines(stream);
-	if (int rc = SplitLines(who, dRaw, size, delim, dN, &n, stream, lines))
-		return rc;
-	const uint64_t cap = onDevice ? hit_cap : std::min<uint64_t>(hit_cap, n);   // host pointers: n lines have at most n hits a row
-	if (out_hits && cap && regexps) {
-		if (int rc = io.Result(out_hits, size_t(regexps) * size_t(cap), 0, &dHits))
-			return rc;
-		if (out_hit_spans)
-			if (int rc = io.Result(out_hit_spans, size_t(regexps) * size_t(cap) * 2, 0, &dSpans))
-				return rc;
-	}
-	if (n == 0) {
-		if (regexps) {
-			const hipError_t e = hipMemsetAsync(dCounts, 0, size_t(regexps) * 8, stream);
-			if (e != hipSuccess)
-				return HipFail(e, "hipMemsetAsync(hit counts)");
-		}
 	} else if (regexps) {
-		const uint32_t runFlags = (flags & (PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END | PIRE_HIP_RUN_GENERIC)) | PIRE_HIP_RUN_ON_DEVICE;
-		if (int rc = pire_hip_run_route(t, lines.text.get(), lines.offsets.as<uint64_t>(), n, runFlags, nullptr, nullptr, nullptr, nullptr,
-		                                dHits, dHits ? cap : 0, dCounts, stream))
+		if (int rc = pire_hip_run_route(t, f.Text(), f.Offsets(), f.n, f.RunFlags(), nullptr, nullptr, nullptr, nullptr, f.dHits,
+		                                f.dHits ? f.cap : 0, f.dCounts, f.stream))
 			return rc;
-		if (dSpans)
-			if (int rc = LaunchRouteSpans(dHits, dCounts, regexps, cap, n, lines.offsets.as<uint64_t>(), dSpans, stream))
+		if (f.dSpans)   // (n lines: no row has more hits)
+			if (int rc = LaunchHitSpans(f.dHits, f.dCounts, regexps, f.cap, std::min(f.cap, f.n), f.Offsets(), f.dSpans, f.stream,
+			                            "route spans launch"))
 				return rc;
 	}
-	if (int rc = io.Finish())
-		return rc;
-	if (onDevice)
-		return PIRE_HIP_OK;
-	*out_line_count = n;
-	return RouteRowsBack(regexps, out_hit_counts, cap, hit_cap, dHits, out_hits, dSpans, out_hit_spans);
+	return f.Close("hipMemcpy(route hits)");
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
@@ -2378,7 +2383,7 @@ int pire_hip_run_lines_gather(pire_hip_table* t, const void* raw, uint64_t size,
                               uint64_t* out_hit_count, void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes,
                               void* stream)
 try {
-	const LinesGather gather = {tail, out_text, text_cap, out_offsets, out_bytes};
+	const LinesGather gather = {tail, out_text, text_cap, out_offsets, out_bytes, true, "hipMallocAsync(hit spans)"};
 	return RunLinesImpl(t, raw, size, delim, flags, want, out_line_count, out_hits, nullptr, nullptr, hit_cap, out_hit_count, stream,
 	                    &gather);
 } catch (...) {
@@ -2386,8 +2391,8 @@ try {
 }
 
 // ---- raw bytes in, the captured field of every line out (split.hip, counting.hip, capture_select.hip, gather.hip) ---------
-// The frame of RunLinesImpl around a capturing scanner: the split into scratch, the capture scan on the lines, the pass
-// with shift = 1 (string i of the split buffer lies i bytes further into raw), the gather from raw through its spans.
+// The frame around a capturing scanner: the capture scan on the lines, the pass with shift = 1 (string i of the split buffer
+// lies i bytes further into raw), the gather from raw through its spans.
 int pire_hip_capture_lines_gather(pire_hip_counting_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
                                   int need_final, uint32_t tail, uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_spans,
                                   uint64_t hit_cap, uint64_t* out_hit_count, void* out_text, uint64_t text_cap,
@@ -2399,112 +2404,32 @@ try {
 	if (int rc = SplitArgsInvalid(who, raw, size, delim, out_line_count, "out_line_count"))
 		return rc;
 	// no gather output at all: spans only.  (The gather form keeps the span list to itself where the caller has no array for it.)
-	const bool gather = out_text || text_cap || out_offsets || out_bytes;
-	if (int rc = CaptureSelectOutputsInvalid(who, 0, need_final, true, out_hits || out_spans || gather, hit_cap, out_hit_count))
+	const bool gathers = out_text || text_cap || out_offsets || out_bytes;
+	if (int rc = CaptureSelectOutputsInvalid(who, 0, need_final, true, out_hits || out_spans || gathers, hit_cap, out_hit_count))
 		return rc;
-	if (gather) {
+	if (gathers) {
 		if (int rc = GatherOutputsInvalid(who, "hit_cap", hit_cap, tail, out_text, text_cap, out_offsets, out_bytes))
 			return rc;
 		if (int rc = GatherOverlaps(who, raw, size, out_text, text_cap))
 			return rc;
 	}
-	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
-	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
-	if (!onDevice && size == 0) {
-		*out_line_count = *out_hit_count = 0;
-		if (gather)
-			*out_bytes = 0;
-		if (out_offsets)
-			out_offsets[0] = 0;
+	const LinesGather gather = {tail, out_text, text_cap, out_offsets, out_bytes, false, "hipMallocAsync(capture spans)"};
+	LinesFrame f(who, raw, size, delim, flags, gathers ? &gather : nullptr, streamPtr);
+	if (f.HostEdge(out_line_count)) {
+		*out_hit_count = 0;
 		return PIRE_HIP_OK;
 	}
-	BatchIO io(stream, onDevice);
-	const uint8_t* dRaw = nullptr;
-	if (int rc = io.In(static_cast<const uint8_t*>(raw), size_t(size), &dRaw))
+	if (int rc = f.Open())
 		return rc;
-	uint64_t n = 0, count = 0, bytes = 0;   // host pointers: the counts come back here first
-	uint64_t *dN = nullptr, *dCount = nullptr, *dHits = nullptr, *dSpans = nullptr, *dBytes = nullptr, *dOutOffsets = nullptr;
-	uint8_t* dOutText = nullptr;
-	if (int rc = io.Result(onDevice ? out_line_count : &n, 1, 1, &dN))
+	if (int rc = f.Split(out_line_count, out_hit_count, 1, hit_cap, true))
 		return rc;
-	if (int rc = io.Result(onDevice ? out_hit_count : &count, 1, 1, &dCount))
+	if (int rc = f.Lists(out_hits, out_spans))
 		return rc;
-	if (gather)
-		if (int rc = io.Result(onDevice ? out_bytes : &bytes, 1, 1, &dBytes))
-			return rc;
-	if (int rc = io.Ready())
+	// (no lines: the pass itself zeroes the count)
+	const CaptureSelectOut sel = {need_final, 1, f.dHits, f.dSpans, f.cap, f.dCounts};
+	if (int rc = CaptureRunImpl(t, f.Text(), f.Offsets(), f.n, f.RunFlags(), nullptr, nullptr, nullptr, nullptr, &sel, f.stream))
 		return rc;
-	// the split, into scratch that lives until the scan and the gather behind it are enqueued; n sizes the offsets
-	StreamScratch tiles(stream), text(stream), offsets(stream), ownSpans(stream);
-	SplitPlan plan;
-	if (int rc = LaunchSplitCount(dRaw, size, delim, dN, stream, tiles, &plan))
-		return rc;
-	if (int rc = ReadCount(dN, &n, stream))
-		return rc;
-	if (n >= (1ull << 32)) {
-		SetError(std::string(who) + ": 2^32 lines or more in one call");
-		return PIRE_HIP_EUNSUPPORTED;
-	}
-	if (int rc = text.Alloc(size_t(size) + 16, "hipMallocAsync(split text)"))
-		return rc;
-	if (int rc = offsets.Alloc((size_t(n) + 1) * 8, "hipMallocAsync(split offsets)"))
-		return rc;
-	if (int rc = LaunchSplitScatter(plan, text.get(), offsets.as<uint64_t>(), n, dN, stream))
-		return rc;
-	const uint64_t cap = std::min<uint64_t>(hit_cap, n);   // n lines have at most n hits
-	if (out_hits && cap)
-		if (int rc = io.Result(out_hits, size_t(cap), 0, &dHits))
-			return rc;
-	if (out_spans && cap)
-		if (int rc = io.Result(out_spans, size_t(cap) * 2, 0, &dSpans))
-			return rc;
-	uint64_t textRoom = 0;   // of out_text: the k captures and their tails are size + k bytes at most
-	if (gather && cap) {
-		if (!dSpans) {
-			if (int rc = ownSpans.Alloc(size_t(cap) * 16, "hipMallocAsync(capture spans)"))
-				return rc;
-			dSpans = ownSpans.as<uint64_t>();
-		}
-		textRoom = std::min(text_cap, size + cap);
-		if (textRoom)
-			if (int rc = io.Result(static_cast<uint8_t*>(out_text), size_t(textRoom), 0, &dOutText))
-				return rc;
-	}
-	if (gather && out_offsets)
-		if (int rc = io.Result(out_offsets, size_t(cap) + 1, 0, &dOutOffsets))
-			return rc;
-	{
-		const uint32_t runFlags = (flags & (PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END | PIRE_HIP_RUN_GENERIC)) | PIRE_HIP_RUN_ON_DEVICE;
-		const CaptureSelectOut sel = {need_final, 1, dHits, dSpans, cap, dCount};
-		if (int rc = CaptureRunImpl(t, text.get(), offsets.as<uint64_t>(), n, runFlags, nullptr, nullptr, nullptr, nullptr, &sel, stream))
-			return rc;
-	}
-	if (gather) {
-		// straight from raw, through the spans (cap == 0: *out_bytes = 0 and out_offsets[0] = 0, nothing is read)
-		const GatherSource src = {dRaw, nullptr, 0, nullptr, dSpans, size};
-		if (int rc = LaunchGather(src, dCount, cap, tail, dOutText, textRoom, dOutOffsets, dBytes, kGatherTotalUnknown, stream))
-			return rc;
-	}
-	if (int rc = io.Finish())
-		return rc;
-	if (onDevice)
-		return PIRE_HIP_OK;
-	*out_line_count = n;
-	*out_hit_count = count;
-	const uint64_t written = std::min<uint64_t>(count, cap);
-	hipError_t e = hipSuccess;
-	if (written && dHits)
-		e = hipMemcpy(out_hits, dHits, size_t(written) * 8, hipMemcpyDeviceToHost);
-	if (e == hipSuccess && written && out_spans)
-		e = hipMemcpy(out_spans, dSpans, size_t(written) * 16, hipMemcpyDeviceToHost);
-	if (gather) {
-		*out_bytes = bytes;
-		if (e == hipSuccess && dOutOffsets)
-			e = hipMemcpy(out_offsets, dOutOffsets, (size_t(written) + 1) * 8, hipMemcpyDeviceToHost);
-		if (e == hipSuccess && std::min(bytes, textRoom))
-			e = hipMemcpy(out_text, dOutText, size_t(std::min(bytes, textRoom)), hipMemcpyDeviceToHost);
-	}
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(captures)");
+	return f.Close("hipMemcpy(captures)");
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }

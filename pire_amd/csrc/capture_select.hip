@@ -11,21 +11,24 @@
 //   scatter   rank of a selected string = tile offset + the popcounts of the waves in front + mbcnt of its own wave's
 //             ballot word; the lane computes its span again from offsets and positions, clamped into the string.
 //
-// Three launches on the caller's stream, the shape of select.hip: no block waits for another block, no atomics (the same
-// input gives the same bits).  Plain HIP with compiler-placed waits: nothing here keeps data on its way in registers.
+// The classify tail, the scatter head and the launcher's front are the select pass's too (compact.h TileBallot / TileRank,
+// select.hip TileCompaction).  Three launches on the caller's stream, the shape of select.hip: no block waits for another
+// block, no atomics (the same input gives the same bits).  Plain HIP with compiler-placed waits: nothing here keeps data on
+// its way in registers.
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
+#include "compact.h"
 #include "internal.h"
 
 namespace pirehip {
 
 namespace {
 
-constexpr uint32_t kCapThreads = 1024;   // one tile = 1 024 strings = 16 ballot words
-constexpr uint32_t kCapWaves = kCapThreads / 64;
+constexpr uint32_t kCapThreads = kBlockThreads;   // one tile = 1 024 strings = 16 ballot words
+constexpr uint32_t kCapWaves = kBlockWaves;
 constexpr uint32_t kCapMaxBlocks = 8192;
 
 struct CaptureSelectParams {
@@ -47,44 +50,21 @@ struct CaptureSelectParams {
 __global__ __launch_bounds__(kCapThreads) void CaptureClassifyKernel(CaptureSelectParams p)
 {
 	__shared__ uint32_t waveCount[kCapWaves];
-	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
 		const uint64_t i = uint64_t(tile) * kCapThreads + threadIdx.x;
 		bool sel = false;
 		if (i < p.n)
 			sel = p.begin[i] >= 0 && p.end[i] >= 0 && (!p.fin || p.fin[i] != 0);
-		const uint64_t ballot = __ballot(sel);
-		if (lane == 0) {
-			p.ballots[size_t(tile) * kCapWaves + wave] = ballot;
-			waveCount[wave] = uint32_t(__popcll(ballot));
-		}
-		__syncthreads();
-		if (threadIdx.x == 0) {
-			uint32_t sum = 0;
-			for (uint32_t w = 0; w < kCapWaves; ++w)
-				sum += waveCount[w];
-			p.tileCounts[tile] = sum;
-		}
-		__syncthreads();
+		TileBallot(sel, tile, p.ballots, p.tileCounts, waveCount);
 	}
 }
 
 __global__ __launch_bounds__(kCapThreads) void CaptureScatterKernel(CaptureSelectParams p)
 {
-	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
-		const uint64_t* words = p.ballots + size_t(tile) * kCapWaves;
-		// lanes 0..15 hold the tile's ballot words: the selected strings of the waves in front of this one ...
-		const uint64_t word = lane < kCapWaves ? words[lane] : 0;
-		uint32_t front = lane < wave ? uint32_t(__popcll(word)) : 0;
-		for (uint32_t d = 1; d < 64; d <<= 1)
-			front += uint32_t(__shfl_xor(int(front), int(d), 64));   // (over all 64 lanes: every lane ends with the sum)
-		// ... and this wave's own word
-		const uint32_t lo = uint32_t(__shfl(int(uint32_t(word)), int(wave), 64));
-		const uint32_t hi = uint32_t(__shfl(int(uint32_t(word >> 32)), int(wave), 64));
-		const uint64_t mine = (uint64_t(hi) << 32) | lo;
-		const uint64_t rank = uint64_t(p.tileCounts[tile]) + front + __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0));
-		if (((mine >> lane) & 1) && rank < p.hitCap) {   // (a selected bit: i < n, begin >= 0 and end >= 0)
+		bool selected;
+		const uint64_t rank = TileRank(tile, p.ballots, p.tileCounts, &selected);
+		if (selected && rank < p.hitCap) {   // (a selected bit: i < n, begin >= 0 and end >= 0)
 			const uint64_t i = uint64_t(tile) * kCapThreads + threadIdx.x;
 			if (p.outHits)
 				p.outHits[rank] = i;
@@ -109,15 +89,12 @@ int LaunchCaptureSelect(const uint64_t* offsets, uint64_t n, bool beginMark, con
                         const uint8_t* fin, uint64_t shift, uint64_t* outHits, uint64_t* outSpans, uint64_t hitCap,
                         uint64_t* outHitCount, hipStream_t stream)
 {
-	if (n == 0) {
-		const hipError_t e = hipMemsetAsync(outHitCount, 0, 8, stream);
-		return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemsetAsync(hit count)");
-	}
-	if (n >= (1ull << 32)) {
-		SetError("pire_hip_capture_select: 2^32 strings or more in one call");   // tile offsets are 32 bits (as select.hip's)
-		return PIRE_HIP_EUNSUPPORTED;
-	}
 	CaptureSelectParams p;
+	StreamScratch scratch(stream);
+	const int rc = TileCompaction("pire_hip_capture_select", "hipMallocAsync(capture select scratch)", n, outHitCount, stream, scratch,
+	                              &p.tiles, &p.ballots, &p.tileCounts);
+	if (rc || !p.tiles)
+		return rc;
 	p.offsets = offsets;
 	p.begin = begin;
 	p.end = end;
@@ -128,17 +105,9 @@ int LaunchCaptureSelect(const uint64_t* offsets, uint64_t n, bool beginMark, con
 	p.outHits = outHits;
 	p.outSpans = outSpans;
 	p.hitCap = outHits || outSpans ? hitCap : 0;
-	p.tiles = uint32_t((n + kCapThreads - 1) / kCapThreads);
-	// scratch: n / 8 bytes of ballot words + n / 256 bytes of tile counts, stream-ordered (the call only enqueues)
-	const size_t ballotBytes = size_t(p.tiles) * kCapWaves * 8;
-	StreamScratch scratch(stream);
-	if (int rc = scratch.Alloc(ballotBytes + size_t(p.tiles) * 4, "hipMallocAsync(capture select scratch)"))
-		return rc;
-	p.ballots = scratch.as<uint64_t>();
-	p.tileCounts = reinterpret_cast<uint32_t*>(scratch.as<uint8_t>() + ballotBytes);
 	const dim3 grid(std::min(p.tiles, kCapMaxBlocks));
 	hipLaunchKernelGGL(CaptureClassifyKernel, grid, dim3(kCapThreads), 0, stream, p);
-	LaunchTileScan(p.tileCounts, p.tiles, outHitCount, stream);
+	LaunchTileScan(p.tileCounts, 1, p.tiles, outHitCount, stream);
 	if (p.hitCap)
 		hipLaunchKernelGGL(CaptureScatterKernel, grid, dim3(kCapThreads), 0, stream, p);
 	const hipError_t e = hipGetLastError();

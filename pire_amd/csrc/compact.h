@@ -1,0 +1,83 @@
+// The pieces the hit passes share on the device (select.hip, capture_select.hip, route.hip, split.hip, gather.hip): the
+// prefix sum over a block of 1 024 threads and the ballot compaction of a tile of 1 024 strings.  Device only, force-inlined
+// into the kernels that use them; DESIGN.md section 4.15 says who owns what.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace pirehip {
+
+constexpr uint32_t kBlockThreads = 1024;   // every kernel that uses these pieces is launched with this many threads ...
+constexpr uint32_t kBlockWaves = kBlockThreads / 64;   // ... one tile of the compaction = 1 024 strings = 16 ballot words
+
+__device__ __forceinline__ uint32_t ShuffleUp(uint32_t v, uint32_t d) { return uint32_t(__shfl_up(int(v), int(d), 64)); }
+__device__ __forceinline__ uint64_t ShuffleUp(uint64_t v, uint32_t d) { return __shfl_up(static_cast<unsigned long long>(v), d, 64); }
+
+// The sum of v over the lanes in front of this one in the block, and over all of them (waveSum: 16 words of LDS).  Two
+// barriers: the call may be repeated at once.
+template <class T>
+__device__ __forceinline__ T BlockExclusive(T v, T* waveSum, T* total)
+{
+	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	T incl = v;
+	for (uint32_t d = 1; d < 64; d <<= 1) {
+		const T up = ShuffleUp(incl, d);
+		if (lane >= d)
+			incl += up;
+	}
+	if (lane == 63)
+		waveSum[wave] = incl;
+	__syncthreads();
+	T before = 0, all = 0;
+	for (uint32_t w = 0; w < kBlockWaves; ++w) {
+		const T ws = waveSum[w];
+		before += w < wave ? ws : 0;
+		all += ws;
+	}
+	__syncthreads();   // (the next call writes waveSum again)
+	*total = all;
+	return before + incl - v;
+}
+
+// The classify tail of a ballot compaction: the selected bits of the wave are one ballot word, kept in
+// ballots[tile * 16 + wave]; tileCounts[tile] = the selected strings of the tile (waveCount: 16 words of LDS).
+__device__ __forceinline__ void TileBallot(bool sel, uint32_t tile, uint64_t* ballots, uint32_t* tileCounts, uint32_t* waveCount)
+{
+	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const uint64_t ballot = __ballot(sel);
+	if (lane == 0) {
+		ballots[size_t(tile) * kBlockWaves + wave] = ballot;
+		waveCount[wave] = uint32_t(__popcll(ballot));
+	}
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		uint32_t sum = 0;
+		for (uint32_t w = 0; w < kBlockWaves; ++w)
+			sum += waveCount[w];
+		tileCounts[tile] = sum;
+	}
+	__syncthreads();
+}
+
+// The scatter head: *selected = this lane's string was selected; its rank among the selected strings of the batch = the
+// scanned tile count + the popcounts of the waves in front + mbcnt of its own wave's ballot word: ascending, no atomics.
+__device__ __forceinline__ uint64_t TileRank(uint32_t tile, const uint64_t* ballots, const uint32_t* tileCounts, bool* selected)
+{
+	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const uint64_t* words = ballots + size_t(tile) * kBlockWaves;
+	// lanes 0..15 hold the tile's ballot words: the selected strings of the waves in front of this one ...
+	const uint64_t word = lane < kBlockWaves ? words[lane] : 0;
+	uint32_t front = lane < wave ? uint32_t(__popcll(word)) : 0;
+	for (uint32_t d = 1; d < 64; d <<= 1)
+		front += uint32_t(__shfl_xor(int(front), int(d), 64));   // (over all 64 lanes: every lane ends with the sum)
+	// ... and this wave's own word
+	const uint32_t lo = uint32_t(__shfl(int(uint32_t(word)), int(wave), 64));
+	const uint32_t hi = uint32_t(__shfl(int(uint32_t(word >> 32)), int(wave), 64));
+	const uint64_t mine = (uint64_t(hi) << 32) | lo;
+	*selected = (mine >> lane) & 1;
+	return uint64_t(tileCounts[tile]) + front + __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0));
+}
+
+}  // namespace pirehip

@@ -29,6 +29,7 @@
 //             3 MiB spreads over about 190 blocks, 300 empty strings cost nothing.  A tile of more strings than the stage
 //             holds (2 048: strings of under 8 bytes on average) reads boundaries and sources from global memory instead.
 //
+// The block-wide prefix sum of the first three kernels is compact.h's BlockExclusive, over 64-bit sums.
 // Four launches on the caller's stream, the shape of select.hip and split.hip: no block waits for another block, no
 // atomics (the output is the same bits every time), no scratch.  Plain HIP with compiler-placed waits: nothing here keeps data on its way in registers.
 
@@ -36,14 +37,15 @@
 
 #include <algorithm>
 
+#include "compact.h"
 #include "internal.h"
 
 namespace pirehip {
 
 namespace {
 
-constexpr uint32_t kGatThreads = 1024;
-constexpr uint32_t kGatWaves = kGatThreads / 64;
+constexpr uint32_t kGatThreads = kBlockThreads;
+constexpr uint32_t kGatWaves = kBlockWaves;
 constexpr uint32_t kGatTile = PIRE_HIP_GATHER_TILE_BYTES;   // 16 output bytes a lane
 constexpr uint32_t kGatStage = 2048;                        // string boundaries of a tile kept in LDS: 4 + 8 bytes each
 constexpr uint32_t kGatMaxBlocks = 2048;                    // 2 blocks on each of 256 CUs, four rounds; tiles in a grid-stride loop
@@ -101,37 +103,13 @@ __device__ __forceinline__ uint64_t Length(const GatherParams& p, uint64_t j, ui
 	return len + p.a;
 }
 
-// The sum of v over the lanes up to and including this one in the block, and over all of them (waveSum: 16 words of LDS)
-__device__ __forceinline__ uint64_t BlockInclusive(uint64_t v, uint64_t* waveSum, uint64_t* total)
-{
-	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	uint64_t incl = v;
-	for (uint32_t d = 1; d < 64; d <<= 1) {
-		const uint64_t up = __shfl_up(static_cast<unsigned long long>(incl), d, 64);
-		if (lane >= d)
-			incl += up;
-	}
-	if (lane == 63)
-		waveSum[wave] = incl;
-	__syncthreads();
-	uint64_t before = 0, all = 0;
-	for (uint32_t w = 0; w < kGatWaves; ++w) {
-		const uint64_t ws = waveSum[w];
-		before += w < wave ? ws : 0;
-		all += ws;
-	}
-	__syncthreads();   // (the next call writes waveSum again)
-	*total = all;
-	return before + incl;
-}
-
 __global__ __launch_bounds__(kGatThreads) void GatherLengthsKernel(GatherParams p)
 {
 	__shared__ uint64_t waveSum[kGatWaves];
 	const uint64_t k = Strings(p);
 	for (uint64_t base = uint64_t(blockIdx.x) * kGatThreads; base < k; base += uint64_t(gridDim.x) * kGatThreads) {
 		uint64_t total;
-		(void)BlockInclusive(Length(p, base + threadIdx.x, k), waveSum, &total);
+		(void)BlockExclusive(Length(p, base + threadIdx.x, k), waveSum, &total);
 		if (threadIdx.x == 0)
 			*TileSum(p, base / kGatThreads) = total;
 	}
@@ -148,9 +126,9 @@ __global__ __launch_bounds__(kGatThreads) void GatherScanKernel(GatherParams p)
 		const uint64_t i = base + threadIdx.x;
 		const uint64_t v = i < tiles ? *TileSum(p, i) : 0;
 		uint64_t total;
-		const uint64_t incl = BlockInclusive(v, waveSum, &total);
+		const uint64_t front = BlockExclusive(v, waveSum, &total);
 		if (i < tiles)
-			*TileSum(p, i) = carry + incl - v;
+			*TileSum(p, i) = carry + front;
 		carry += total;
 	}
 	if (threadIdx.x == 0) {
@@ -168,7 +146,8 @@ __global__ __launch_bounds__(kGatThreads) void GatherOffsetsKernel(GatherParams 
 		const uint64_t j = base + threadIdx.x;
 		const uint64_t front = *TileSum(p, base / kGatThreads);   // (read by every lane before the barriers of the scan, written behind them)
 		uint64_t total;
-		const uint64_t incl = BlockInclusive(Length(p, j, k), waveSum, &total);
+		const uint64_t len = Length(p, j, k);
+		const uint64_t incl = BlockExclusive(len, waveSum, &total) + len;   // (inclusive: the entry BEHIND string j)
 		if (j < k)
 			p.outOffsets[j + 1] = front + incl;
 	}

@@ -1066,9 +1066,15 @@ void FreeSelect(pire_hip_table* t);
 int LaunchSelect(const SelectDevice& image, uint32_t states, uint32_t words, const uint32_t* stateIdx, uint64_t n,
                  const uint64_t* want, uint64_t* outMasks, uint64_t* outHits, uint64_t* outHitMasks, uint64_t hitCap,
                  uint64_t* outHitCount, hipStream_t stream);
-// The scan of both compactions (select.hip, capture_select.hip): exclusive scan of counts[entries] -- selected strings per
-// tile of 1 024 -- in place, one block; *outCount = the total.  Enqueues; the caller asks hipGetLastError() behind its launches.
-void LaunchTileScan(uint32_t* counts, uint32_t entries, uint64_t* outCount, hipStream_t stream);
+// The scan of every hit pass (select.hip, capture_select.hip, route.hip): exclusive scan of every row of
+// counts[rows][entries] -- selected strings per tile of 1 024 -- in place, a block per row; outCounts[r] = the total of row r.
+// Enqueues; the caller asks hipGetLastError() behind its launches.
+void LaunchTileScan(uint32_t* counts, uint32_t rows, uint32_t entries, uint64_t* outCounts, hipStream_t stream);
+// The front of both ballot compactions' launchers (select.hip, capture_select.hip).  n == 0: *outHitCount is zeroed on the
+// stream and *tiles = 0 (nothing to launch); 2^32 strings or more: refused in `who`'s name; else *tiles = ceil(n / 1024) and
+// the one allocation of `scratch`, carved into ballots[tiles * 16] and tileCounts[tiles].
+int TileCompaction(const char* who, const char* scratchLabel, uint64_t n, uint64_t* outHitCount, hipStream_t stream, StreamScratch& scratch,
+                   uint32_t* tiles, uint64_t** ballots, uint32_t** tileCounts);
 // capture_select.hip: from capture positions to a compacted, ascending list of byte ranges (pire_hip_capture_select).
 // Device pointers only, three kernels enqueued on `stream`, scratch from the stream-ordered allocator.  fin == nullptr:
 // Final is not asked for.  shift: string i lies shift * i bytes further into the buffer the spans are counted in (1: the
@@ -1097,7 +1103,9 @@ int CaptureRunImpl(pire_hip_counting_table* t, const void* text, const uint64_t*
 // comes in two halves because a caller may want the number of strings before it has room for their offsets:
 // LaunchSplitCount counts and scans (*outN = n; the tile prefixes stay in `scratch`, the caller's owner, which has to live
 // until the scatter is enqueued), LaunchSplitScatter writes offsets[0..min(n, cap)] and, where outText is not null, the text
-// without its delimiters.  LaunchSplitSpans: [begin, end) in the raw buffer of the first min(*hitCount, cap) hits.
+// without its delimiters.  LaunchHitSpans: [begin, end) in the raw buffer of the first min(counts[r], kMax) hits of every row
+// of hits[rows][pitch], spans[rows][pitch][2], one launch (one list: rows = 1, pitch = kMax = its capacity); `what` names
+// the launch where it fails.
 struct SplitPlan {
 	const uint8_t* raw;
 	uint32_t head;       // raw's address modulo 16: tiles and lanes are cut on the 16-byte grid, raw[0] is byte `head` of the first lane
@@ -1111,16 +1119,13 @@ int LaunchSplitCount(const void* raw, uint64_t size, uint32_t delim, uint64_t* o
                      SplitPlan* plan);
 int LaunchSplitScatter(const SplitPlan& plan, void* outText, uint64_t* outOffsets, uint64_t offsetsCap, const uint64_t* outN,
                        hipStream_t stream);
-int LaunchSplitSpans(const uint64_t* hits, const uint64_t* hitCount, uint64_t cap, const uint64_t* offsets, uint64_t* spans,
-                     hipStream_t stream);
+int LaunchHitSpans(const uint64_t* hits, const uint64_t* counts, uint32_t rows, uint64_t pitch, uint64_t kMax, const uint64_t* offsets,
+                   uint64_t* spans, hipStream_t stream, const char* what);
 // route.hip: one ascending hit list per regexp (pire_hip_route).  Device pointers only, three kernels enqueued on `stream`,
 // regexps * ceil(n / 1024) * 4 bytes of scratch from the stream-ordered allocator.  outHits[regexps][hitCap] (nullable:
-// counts only), outHitCounts[regexps]; the image is the select pass's.  LaunchRouteSpans: [begin, end) in the raw buffer of
-// the first min(hitCounts[r], hitCap) hits of every row, spans[regexps][hitCap][2], one launch (offsets as LaunchSplitSpans').
+// counts only), outHitCounts[regexps]; the image and the scan kernel are the select pass's.
 int LaunchRoute(const SelectDevice& image, uint32_t states, uint32_t words, uint32_t regexps, const uint32_t* stateIdx, uint64_t n,
                 uint64_t* outHits, uint64_t hitCap, uint64_t* outHitCounts, hipStream_t stream);
-int LaunchRouteSpans(const uint64_t* hits, const uint64_t* hitCounts, uint32_t regexps, uint64_t hitCap, uint64_t n,
-                     const uint64_t* offsets, uint64_t* spans, hipStream_t stream);
 // gather.hip: the listed strings of a batch back to back (pire_hip_gather).  Device pointers only, four kernels enqueued on
 // `stream`, no scratch and no allocation (outOffsets, cap + 1 entries, is required where cap > 0).  Where the source ranges come from:
 // spans != nullptr -> raw[spans[2j], spans[2j + 1]) with raw = text and `size` its length; else offsets + idx (nullable:

@@ -13,14 +13,14 @@
 //             one ballot + popcount each.  The per-wave counts meet in LDS, 64 regexps (one mask word) a round, so no
 //             number of regexps outgrows the LDS; tileCounts[r][tile] is written for every r, zeros included.
 //   scan      R independent exclusive scans of `tiles` entries, a block per regexp (grid-stride), 1 024 entries a step
-//             with a carry; the total of row r is out_hit_counts[r].
+//             with a carry; the total of row r is out_hit_counts[r] (select.hip's kernel, LaunchTileScan with R rows).
 //   scatter   re-reads the state indices and the mask records (no ballot scratch): rank = scanned tile offset + the same
 //             regexp's popcounts of the waves in front (an LDS phase) + mbcnt of the wave's own ballot.
 //
 // Three launches on the caller's stream; no block ever waits for another block, no atomics: the order inside a row is the
 // order of the strings, whatever the timing.  The image is the select pass's (internal.h SelectHost: reference numbering,
-// no re-ranking touches it).  Plain HIP with compiler-placed waits.  The lines form adds RouteSpansKernel: the byte
-// ranges of all rows in one launch over (r, k).
+// no re-ranking touches it).  Plain HIP with compiler-placed waits.  The lines form adds the byte ranges of all rows in one
+// launch over (r, k): split.hip's SplitSpansKernel, LaunchHitSpans.
 
 #include <hip/hip_runtime.h>
 
@@ -35,7 +35,6 @@ namespace {
 constexpr uint32_t kRouteThreads = 1024;           // one tile = 1 024 strings = 16 waves
 constexpr uint32_t kRouteWaves = kRouteThreads / 64;
 constexpr uint32_t kRouteMaxBlocks = 8192;
-constexpr uint32_t kRouteScanBlocks = 1024;
 
 struct RouteParams {
 	const uint64_t* masks;   // [states * words], reference numbering
@@ -110,43 +109,6 @@ __global__ __launch_bounds__(kRouteThreads) void RouteCountKernel(RouteParams p)
 	}
 }
 
-// Exclusive scan of every row of counts[regexps][entries] in place, a block per row: 1 024 entries (2^20 strings) a step,
-// a carry between the steps.  outCounts[r] = the total of row r.
-__global__ __launch_bounds__(kRouteThreads) void RouteScanKernel(uint32_t* counts, uint32_t regexps, uint32_t entries, uint64_t* outCounts)
-{
-	__shared__ uint32_t waveSum[kRouteWaves];
-	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	for (uint32_t r = blockIdx.x; r < regexps; r += gridDim.x) {
-		uint32_t* row = counts + size_t(r) * entries;
-		uint32_t carry = 0;
-		for (uint32_t base = 0; base < entries; base += kRouteThreads) {
-			const uint32_t i = base + threadIdx.x;
-			const uint32_t v = i < entries ? row[i] : 0;
-			uint32_t incl = v;
-			for (uint32_t d = 1; d < 64; d <<= 1) {
-				const uint32_t up = uint32_t(__shfl_up(int(incl), int(d), 64));
-				if (lane >= d)
-					incl += up;
-			}
-			if (lane == 63)
-				waveSum[wave] = incl;
-			__syncthreads();
-			uint32_t before = 0, total = 0;
-			for (uint32_t w = 0; w < kRouteWaves; ++w) {
-				const uint32_t ws = waveSum[w];
-				before += w < wave ? ws : 0;
-				total += ws;
-			}
-			if (i < entries)
-				row[i] = carry + before + incl - v;
-			carry += total;
-			__syncthreads();
-		}
-		if (threadIdx.x == 0)
-			outCounts[r] = carry;
-	}
-}
-
 __global__ __launch_bounds__(kRouteThreads) void RouteScatterKernel(RouteParams p)
 {
 	__shared__ uint32_t waveBase[kRouteWaves][64];
@@ -184,21 +146,6 @@ __global__ __launch_bounds__(kRouteThreads) void RouteScatterKernel(RouteParams 
 	}
 }
 
-// The lines form: hit k of row r is line hits[r][k] = raw[offsets[i] + i, offsets[i + 1] + i) (the offsets are those of the
-// text without its delimiters, as SplitSpansKernel reads them), for k < min(counts[r], kMax, pitch)
-__global__ void RouteSpansKernel(const uint64_t* hits, const uint64_t* counts, uint32_t regexps, uint64_t pitch, uint64_t kMax,
-                                 const uint64_t* offsets, uint64_t* spans)
-{
-	const uint64_t k = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-	for (uint32_t r = blockIdx.y; r < regexps; r += gridDim.y)
-		if (k < kMax && k < counts[r]) {
-			const uint64_t at = uint64_t(r) * pitch + k;
-			const uint64_t i = hits[at];
-			spans[2 * at] = offsets[i] + i;
-			spans[2 * at + 1] = offsets[i + 1] + i;
-		}
-}
-
 }  // namespace
 
 int LaunchRoute(const SelectDevice& image, uint32_t states, uint32_t words, uint32_t regexps, const uint32_t* stateIdx, uint64_t n,
@@ -231,24 +178,11 @@ int LaunchRoute(const SelectDevice& image, uint32_t states, uint32_t words, uint
 	p.tileCounts = scratch.as<uint32_t>();
 	const dim3 grid(std::min(p.tiles, kRouteMaxBlocks));
 	hipLaunchKernelGGL(RouteCountKernel, grid, dim3(kRouteThreads), 0, stream, p);
-	hipLaunchKernelGGL(RouteScanKernel, dim3(std::min(regexps, kRouteScanBlocks)), dim3(kRouteThreads), 0, stream, p.tileCounts, regexps,
-	                   p.tiles, outHitCounts);
+	LaunchTileScan(p.tileCounts, regexps, p.tiles, outHitCounts, stream);
 	if (p.hitCap)
 		hipLaunchKernelGGL(RouteScatterKernel, grid, dim3(kRouteThreads), 0, stream, p);
 	const hipError_t e = hipGetLastError();
 	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "route launch");
-}
-
-int LaunchRouteSpans(const uint64_t* hits, const uint64_t* hitCounts, uint32_t regexps, uint64_t hitCap, uint64_t n,
-                     const uint64_t* offsets, uint64_t* spans, hipStream_t stream)
-{
-	const uint64_t kMax = std::min(hitCap, n);   // n lines: no row has more hits
-	if (!kMax || !regexps)
-		return PIRE_HIP_OK;
-	const dim3 grid(uint32_t((kMax + 255) / 256), std::min(regexps, 65535u));
-	hipLaunchKernelGGL(RouteSpansKernel, grid, dim3(256), 0, stream, hits, hitCounts, regexps, hitCap, kMax, offsets, spans);
-	const hipError_t e = hipGetLastError();
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "route spans launch");
 }
 
 }  // namespace pirehip

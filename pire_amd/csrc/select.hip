@@ -9,10 +9,12 @@
 //             (internal.h SelectHost).  Reference numbering, so no re-ranking ever touches it.
 //   classify  one lane per string: state index -> mask record -> selected?  The masks go out if asked for; the selected
 //             bits of a wave are one ballot word, kept in scratch; one count per tile of 1 024 strings.
-//   scan      exclusive scan of the tile counts, one block; the total is the hit count.
+//   scan      exclusive scan of the tile counts, one block a row of them (one row here; capture_select.hip's one and
+//             route.hip's R rows go through the same kernel, LaunchTileScan); the total is the hit count.
 //   scatter   rank of a selected string = tile offset + the popcounts of the waves in front + mbcnt of its own wave's
 //             ballot word: the hits come out in ascending order, deterministically, with no atomics.
 //
+// The block scan, the classify tail and the scatter head are compact.h's (BlockExclusive, TileBallot, TileRank).
 // Three launches on the caller's stream, the shape of order.hip.  No block ever waits for another block (no look-back,
 // no flags between blocks): the order of the three kernels on the stream is the only synchronisation.
 //
@@ -24,14 +26,16 @@
 
 #include <algorithm>
 
+#include "compact.h"
 #include "internal.h"
 
 namespace pirehip {
 
 namespace {
 
-constexpr uint32_t kSelThreads = 1024;             // one tile = 1 024 strings = 16 ballot words
-constexpr uint32_t kSelWaves = kSelThreads / 64;
+constexpr uint32_t kSelThreads = kBlockThreads;    // one tile = 1 024 strings = 16 ballot words
+constexpr uint32_t kSelWaves = kBlockWaves;
+constexpr uint32_t kSelScanBlocks = 1024;          // the tile scan's grid: a block per row, rows in a grid-stride loop
 constexpr uint32_t kSelLdsStates = 8192;           // x 8 bytes = 64 KiB: two blocks a CU
 constexpr uint32_t kSelLdsBlocks = 512;            // the LDS form's grid: 2 blocks on each of 256 CUs, tiles in a grid-stride loop
 constexpr uint32_t kSelMaxBlocks = 8192;
@@ -65,7 +69,6 @@ __global__ __launch_bounds__(kSelThreads) void SelectClassifyKernel(SelectParams
 			ldsMasks[s] = p.masks[s];
 		__syncthreads();
 	}
-	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	const bool needMask = p.want || p.outMasks;
 	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
 		const uint64_t i = uint64_t(tile) * kSelThreads + threadIdx.x;
@@ -108,72 +111,38 @@ __global__ __launch_bounds__(kSelThreads) void SelectClassifyKernel(SelectParams
 				}
 			}
 		}
-		const uint64_t ballot = __ballot(sel);
-		if (lane == 0) {
-			p.ballots[size_t(tile) * kSelWaves + wave] = ballot;
-			waveCount[wave] = uint32_t(__popcll(ballot));
-		}
-		__syncthreads();
-		if (threadIdx.x == 0) {
-			uint32_t sum = 0;
-			for (uint32_t w = 0; w < kSelWaves; ++w)
-				sum += waveCount[w];
-			p.tileCounts[tile] = sum;
-		}
-		__syncthreads();
+		TileBallot(sel, tile, p.ballots, p.tileCounts, waveCount);
 	}
 }
 
-// Exclusive scan of counts[entries] in place, one block: 1 024 entries (2^20 strings) a step, a carry between the steps.
-// A batch of 2^20 strings is one step; 2^24 strings, sixteen.  *outCount = the total.
-__global__ __launch_bounds__(kSelThreads) void SelectScanKernel(uint32_t* counts, uint32_t entries, uint64_t* outCount)
+// The tile scan of every hit pass (this unit, capture_select.hip, route.hip): exclusive scan of every row of
+// counts[rows][entries] in place, a block per row (grid-stride): 1 024 entries (2^20 strings) a step, a carry between the
+// steps.  A batch of 2^20 strings is one step; 2^24 strings, sixteen.  outCounts[r] = the total of row r.
+__global__ __launch_bounds__(kSelThreads) void SelectScanKernel(uint32_t* counts, uint32_t rows, uint32_t entries, uint64_t* outCounts)
 {
 	__shared__ uint32_t waveSum[kSelWaves];
-	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	uint32_t carry = 0;
-	for (uint32_t base = 0; base < entries; base += kSelThreads) {
-		const uint32_t i = base + threadIdx.x;
-		const uint32_t v = i < entries ? counts[i] : 0;
-		uint32_t incl = v;
-		for (uint32_t d = 1; d < 64; d <<= 1) {
-			const uint32_t up = uint32_t(__shfl_up(int(incl), int(d), 64));
-			if (lane >= d)
-				incl += up;
+	for (uint32_t r = blockIdx.x; r < rows; r += gridDim.x) {
+		uint32_t* row = counts + size_t(r) * entries;
+		uint32_t carry = 0;
+		for (uint32_t base = 0; base < entries; base += kSelThreads) {
+			const uint32_t i = base + threadIdx.x;
+			uint32_t total;
+			const uint32_t front = BlockExclusive(i < entries ? row[i] : 0, waveSum, &total);
+			if (i < entries)
+				row[i] = carry + front;
+			carry += total;
 		}
-		if (lane == 63)
-			waveSum[wave] = incl;
-		__syncthreads();
-		uint32_t before = 0, total = 0;
-		for (uint32_t w = 0; w < kSelWaves; ++w) {
-			const uint32_t ws = waveSum[w];
-			before += w < wave ? ws : 0;
-			total += ws;
-		}
-		if (i < entries)
-			counts[i] = carry + before + incl - v;
-		carry += total;
-		__syncthreads();
+		if (threadIdx.x == 0)
+			outCounts[r] = carry;
 	}
-	if (threadIdx.x == 0)
-		*outCount = carry;
 }
 
 __global__ __launch_bounds__(kSelThreads) void SelectScatterKernel(SelectParams p)
 {
-	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
-		const uint64_t* words = p.ballots + size_t(tile) * kSelWaves;
-		// lanes 0..15 hold the tile's ballot words: the selected strings of the waves in front of this one ...
-		const uint64_t word = lane < kSelWaves ? words[lane] : 0;
-		uint32_t front = lane < wave ? uint32_t(__popcll(word)) : 0;
-		for (uint32_t d = 1; d < 64; d <<= 1)
-			front += uint32_t(__shfl_xor(int(front), int(d), 64));   // (over all 64 lanes: every lane ends with the sum)
-		// ... and this wave's own word
-		const uint32_t lo = uint32_t(__shfl(int(uint32_t(word)), int(wave), 64));
-		const uint32_t hi = uint32_t(__shfl(int(uint32_t(word >> 32)), int(wave), 64));
-		const uint64_t mine = (uint64_t(hi) << 32) | lo;
-		const uint64_t rank = uint64_t(p.tileCounts[tile]) + front + __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0));
-		if (((mine >> lane) & 1) && rank < p.hitCap) {
+		bool selected;
+		const uint64_t rank = TileRank(tile, p.ballots, p.tileCounts, &selected);
+		if (selected && rank < p.hitCap) {
 			const uint64_t i = uint64_t(tile) * kSelThreads + threadIdx.x;
 			p.outHits[rank] = i;
 			if (p.outHitMasks) {
@@ -264,24 +233,44 @@ int UploadSelect(pire_hip_table* t, SelectDevice* image)
 	return PIRE_HIP_OK;
 }
 
-void LaunchTileScan(uint32_t* counts, uint32_t entries, uint64_t* outCount, hipStream_t stream)
+void LaunchTileScan(uint32_t* counts, uint32_t rows, uint32_t entries, uint64_t* outCounts, hipStream_t stream)
 {
-	hipLaunchKernelGGL(SelectScanKernel, dim3(1), dim3(kSelThreads), 0, stream, counts, entries, outCount);
+	hipLaunchKernelGGL(SelectScanKernel, dim3(std::min(rows, kSelScanBlocks)), dim3(kSelThreads), 0, stream, counts, rows, entries, outCounts);
+}
+
+int TileCompaction(const char* who, const char* scratchLabel, uint64_t n, uint64_t* outHitCount, hipStream_t stream, StreamScratch& scratch,
+                   uint32_t* tiles, uint64_t** ballots, uint32_t** tileCounts)
+{
+	*tiles = 0;
+	if (n == 0) {
+		const hipError_t e = hipMemsetAsync(outHitCount, 0, 8, stream);
+		return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemsetAsync(hit count)");
+	}
+	if (n >= (1ull << 32)) {
+		SetError(std::string(who) + ": 2^32 strings or more in one call");   // tile offsets are 32 bits (as order.hip's indices)
+		return PIRE_HIP_EUNSUPPORTED;
+	}
+	const uint32_t t = uint32_t((n + kSelThreads - 1) / kSelThreads);
+	// scratch: n / 8 bytes of ballot words + n / 256 bytes of tile counts, stream-ordered (the call only enqueues)
+	const size_t ballotBytes = size_t(t) * kSelWaves * 8;
+	if (int rc = scratch.Alloc(ballotBytes + size_t(t) * 4, scratchLabel))
+		return rc;
+	*ballots = scratch.as<uint64_t>();
+	*tileCounts = reinterpret_cast<uint32_t*>(scratch.as<uint8_t>() + ballotBytes);
+	*tiles = t;
+	return PIRE_HIP_OK;
 }
 
 int LaunchSelect(const SelectDevice& image, uint32_t states, uint32_t words, const uint32_t* stateIdx, uint64_t n,
                  const uint64_t* want, uint64_t* outMasks, uint64_t* outHits, uint64_t* outHitMasks, uint64_t hitCap,
                  uint64_t* outHitCount, hipStream_t stream)
 {
-	if (n == 0) {
-		const hipError_t e = hipMemsetAsync(outHitCount, 0, 8, stream);
-		return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemsetAsync(hit count)");
-	}
-	if (n >= (1ull << 32)) {
-		SetError("pire_hip_select: 2^32 strings or more in one call");   // tile offsets are 32 bits (as order.hip's indices)
-		return PIRE_HIP_EUNSUPPORTED;
-	}
 	SelectParams p;
+	StreamScratch scratch(stream);
+	const int rc = TileCompaction("pire_hip_select", "hipMallocAsync(select scratch)", n, outHitCount, stream, scratch, &p.tiles, &p.ballots,
+	                              &p.tileCounts);
+	if (rc || !p.tiles)
+		return rc;
 	p.masks = image.masks;
 	p.fin = image.fin;
 	p.states = states;
@@ -294,14 +283,6 @@ int LaunchSelect(const SelectDevice& image, uint32_t states, uint32_t words, con
 	p.outHits = outHits;
 	p.outHitMasks = outHitMasks;
 	p.hitCap = outHits ? hitCap : 0;
-	p.tiles = uint32_t((n + kSelThreads - 1) / kSelThreads);
-	// scratch: n / 8 bytes of ballot words + n / 256 bytes of tile counts, stream-ordered (the call only enqueues)
-	const size_t ballotBytes = size_t(p.tiles) * kSelWaves * 8;
-	StreamScratch scratch(stream);
-	if (int rc = scratch.Alloc(ballotBytes + size_t(p.tiles) * 4, "hipMallocAsync(select scratch)"))
-		return rc;
-	p.ballots = scratch.as<uint64_t>();
-	p.tileCounts = reinterpret_cast<uint32_t*>(scratch.as<uint8_t>() + ballotBytes);
 	// The LDS form reads states * 8 bytes per BLOCK to save 8 bytes per STRING: only where a block of the small grid
 	// walks at least twice as many strings as the table has states
 	const uint32_t ldsGrid = std::min(p.tiles, kSelLdsBlocks);
@@ -315,7 +296,7 @@ int LaunchSelect(const SelectDevice& image, uint32_t states, uint32_t words, con
 	} else {
 		hipLaunchKernelGGL(SelectClassifyKernel<false>, dim3(std::min(p.tiles, kSelMaxBlocks)), dim3(kSelThreads), 0, stream, p);
 	}
-	LaunchTileScan(p.tileCounts, p.tiles, outHitCount, stream);
+	LaunchTileScan(p.tileCounts, 1, p.tiles, outHitCount, stream);
 	if (p.hitCap)
 		hipLaunchKernelGGL(SelectScatterKernel, dim3(std::min(p.tiles, kSelMaxBlocks)), dim3(kSelThreads), 0, stream, p);
 	const hipError_t e = hipGetLastError();

@@ -29,20 +29,22 @@
 // Plain HIP with compiler-placed waits: nothing here keeps data on its way in registers.
 //
 // pire_hip_run_lines_select (api.cpp) splits into scratch, scans, selects, and SplitSpansKernel turns the hit list into
-// byte ranges of the raw buffer.
+// byte ranges of the raw buffer -- and the R hit lists of pire_hip_run_lines_route, in one launch (LaunchHitSpans).  The
+// block-wide prefix sum of the three kernels is compact.h's BlockExclusive.
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
+#include "compact.h"
 #include "internal.h"
 
 namespace pirehip {
 
 namespace {
 
-constexpr uint32_t kSplitThreads = 1024;
-constexpr uint32_t kSplitWaves = kSplitThreads / 64;
+constexpr uint32_t kSplitThreads = kBlockThreads;
+constexpr uint32_t kSplitWaves = kBlockWaves;
 constexpr uint32_t kSplitTile = PIRE_HIP_SPLIT_TILE_BYTES;   // 16 bytes a lane
 constexpr uint32_t kSplitMaxBlocks = 2048;                   // 2 blocks on each of 256 CUs, four rounds; tiles in a grid-stride loop
 static_assert(kSplitTile == kSplitThreads * 16, "one dwordx4 per lane and tile");
@@ -76,30 +78,6 @@ __device__ __forceinline__ uint32_t LoadLane(const SplitPlan& p, uint64_t v, uin
 		dm |= (((t >> 7) | (t >> 14) | (t >> 21) | (t >> 28)) & 0xFu) << (4 * k);
 	}
 	return dm & *valid;
-}
-
-// The sum of c over the lanes in front of this one in the block, and over all of them (waveSum: 16 words of LDS)
-__device__ __forceinline__ uint32_t BlockExclusive(uint32_t c, uint32_t* waveSum, uint32_t* total)
-{
-	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	uint32_t incl = c;
-	for (uint32_t d = 1; d < 64; d <<= 1) {
-		const uint32_t up = uint32_t(__shfl_up(int(incl), int(d), 64));
-		if (lane >= d)
-			incl += up;
-	}
-	if (lane == 63)
-		waveSum[wave] = incl;
-	__syncthreads();
-	uint32_t before = 0, all = 0;
-	for (uint32_t w = 0; w < kSplitWaves; ++w) {
-		const uint32_t ws = waveSum[w];
-		before += w < wave ? ws : 0;
-		all += ws;
-	}
-	__syncthreads();   // (the next call writes waveSum again)
-	*total = all;
-	return before + incl - c;
 }
 
 __global__ __launch_bounds__(kSplitThreads) void SplitCountKernel(SplitPlan p)
@@ -218,15 +196,20 @@ __global__ __launch_bounds__(kSplitThreads) void SplitScatterKernel(SplitPlan p,
 	}
 }
 
-// spans[k] = the bytes of hit k in the raw buffer: line i is raw[offsets[i] + i, offsets[i + 1] + i)
-__global__ void SplitSpansKernel(const uint64_t* hits, const uint64_t* hitCount, uint64_t cap, const uint64_t* offsets, uint64_t* spans)
+// The spans of the hit lists hits[rows][pitch]: hit k of row r is line i = hits[r][k], the bytes raw[offsets[i] + i,
+// offsets[i + 1] + i) of the raw buffer (offsets: of the text without its delimiters), for k < min(counts[r], kMax).  One
+// list (the select pass's): rows = 1, pitch = kMax = its capacity; the route pass's R rows in the same launch, over (r, k).
+__global__ void SplitSpansKernel(const uint64_t* hits, const uint64_t* counts, uint32_t rows, uint64_t pitch, uint64_t kMax,
+                                 const uint64_t* offsets, uint64_t* spans)
 {
 	const uint64_t k = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-	if (k < cap && k < *hitCount) {
-		const uint64_t i = hits[k];
-		spans[2 * k] = offsets[i] + i;
-		spans[2 * k + 1] = offsets[i + 1] + i;
-	}
+	for (uint32_t r = blockIdx.y; r < rows; r += gridDim.y)
+		if (k < kMax && k < counts[r]) {
+			const uint64_t at = uint64_t(r) * pitch + k;
+			const uint64_t i = hits[at];
+			spans[2 * at] = offsets[i] + i;
+			spans[2 * at + 1] = offsets[i + 1] + i;
+		}
 }
 
 }  // namespace
@@ -272,14 +255,15 @@ int LaunchSplitScatter(const SplitPlan& p, void* outText, uint64_t* outOffsets, 
 	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "split launch");
 }
 
-int LaunchSplitSpans(const uint64_t* hits, const uint64_t* hitCount, uint64_t cap, const uint64_t* offsets, uint64_t* spans,
-                     hipStream_t stream)
+int LaunchHitSpans(const uint64_t* hits, const uint64_t* counts, uint32_t rows, uint64_t pitch, uint64_t kMax, const uint64_t* offsets,
+                   uint64_t* spans, hipStream_t stream, const char* what)
 {
-	if (!cap)
+	if (!kMax || !rows)
 		return PIRE_HIP_OK;
-	hipLaunchKernelGGL(SplitSpansKernel, dim3(uint32_t((cap + 255) / 256)), dim3(256), 0, stream, hits, hitCount, cap, offsets, spans);
+	const dim3 grid(uint32_t((kMax + 255) / 256), std::min(rows, 65535u));
+	hipLaunchKernelGGL(SplitSpansKernel, grid, dim3(256), 0, stream, hits, counts, rows, pitch, kMax, offsets, spans);
 	const hipError_t e = hipGetLastError();
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "split spans launch");
+	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, what);
 }
 
 }  // namespace pirehip

@@ -512,6 +512,39 @@ def test_an_index_or_span_out_of_range(torch_cuda):
 
 # ---- GPU: the spans form, the inverse of the split ---------------------------------------------------------------------------
 
+@gpu
+def test_the_64_bit_carry_of_the_scan_over_more_than_1024_tiles_of_strings(torch_cuda):
+    """(1 << 20) + 1025 strings of 0-3 bytes are 1 026 tiles of strings: the scan of the tile sums takes a second step and
+    carries the 64-bit total of the first into it.  Device pointers, the identity for idx, a tail byte; numpy says what
+    out_offsets and out_text have to be."""
+    torch = torch_cuda
+    rng = np.random.RandomState(41)
+    k, tail = (1 << 20) + 1025, 10
+    lens = rng.randint(0, 4, size=k).astype(np.uint64)
+    offs = np.zeros(k + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum(lens)
+    size = int(offs[-1])
+    text = rng.randint(97, 123, size=size).astype(np.uint8)
+    exp_offs = np.zeros(k + 1, dtype=np.uint64)
+    exp_offs[1:] = np.cumsum(lens + np.uint64(1))
+    total = int(exp_offs[-1])
+    exp_text = np.full(total, tail, dtype=np.uint8)
+    exp_text[np.arange(size) + np.repeat(np.arange(k), lens.astype(np.int64))] = text   # byte p of string j moves j tails further
+    d_text = torch.as_tensor(text, device="cuda")
+    d_offs = torch.as_tensor(offs.view(np.int64), device="cuda")
+    out_text = torch.full((total + 64,), 0xEE, dtype=torch.uint8, device="cuda")
+    out_offs = torch.full((k + 1 + 8,), -1, dtype=torch.int64, device="cuda")
+    out_bytes = torch.full((1,), -1, dtype=torch.int64, device="cuda")
+    pb.gather_device(d_text.data_ptr(), d_offs.data_ptr(), k, out_bytes.data_ptr(), idx_cap=k, tail=tail, out_text_ptr=out_text.data_ptr(),
+                     text_cap=total, out_offsets_ptr=out_offs.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert int(out_bytes.cpu()[0]) == total
+    got_offs = out_offs.cpu().numpy().view(np.uint64)
+    assert (got_offs[:k + 1] == exp_offs).all() and (got_offs[k + 1:] == np.uint64(0xFFFFFFFFFFFFFFFF)).all()
+    got_text = out_text.cpu().numpy()
+    assert (got_text[:total] == exp_text).all() and (got_text[total:] == 0xEE).all()
+
+
 def log_like_raw(rng, lines, last_terminated=True):
     words = [b"GET", b"POST", b"/index.html", b"/api/v1/items", b"200", b"404", b"hello  world", b"hello world", b"-", b"\"Mozilla/5.0\""]
     out = []

@@ -195,7 +195,9 @@ def test_the_route_unit_passes_the_build_audit():
     assert names.count("route.hip") == 1 and units.count("route.hip") == 1
     fails, seen = ba.audit("route.hip")
     assert not fails, fails
-    assert len(seen) == 4 and all("Route" in k for k in seen), seen
+    # (count and scatter; the scan is select.hip's SelectScanKernel, the lines form's spans split.hip's SplitSpansKernel: each
+    # is audited with the unit it lives in)
+    assert len(seen) == 2 and all("Route" in k for k in seen), seen
 
 
 def test_the_route_pass_names_no_kernel_of_its_own():
@@ -357,6 +359,31 @@ def test_capacity(torch_cuda):
     for r in range(t.RegexpsCount):
         k = int(e40["counts"][r])
         assert (rows[r, :k] == e40["hits"][r]).all() and (rows[r, k:] == np.uint64(POISON)).all()
+
+
+# ---- GPU: the scan's carry -------------------------------------------------------------------------------------------------
+
+@gpu
+def test_every_rows_scan_carries_over_more_than_1024_tiles(torch_cuda):
+    """(1 << 20) + 1025 strings are 1 026 tiles: the scan of every row takes a second step of 1 024 entries and carries the
+    total of the first into it.  Synthetic state indices (no scan), three regexps with members behind tile 1 024; hit_cap = n:
+    every row complete and ascending, counts exact; hit_cap = 1 000: counts still full, rows cut, the guard words untouched."""
+    torch = torch_cuda
+    case, t, o = table_of("set_a")
+    pool = state_pool(t, o, case)
+    single = {r: s for k, s in pool.items() for r in k if len(k) == 1}
+    rs = sorted(single)
+    assert t.RegexpsCount >= 2 and len(rs) >= 3
+    n = (1 << 20) + 1025
+    rng = np.random.RandomState(31)
+    choice = np.array([pool[frozenset()], pool[max(pool, key=len)]] + [single[r] for r in rs[:3]], dtype=np.uint32)
+    idx = choice[rng.randint(len(choice), size=n)]
+    idx[n - 1], idx[n - 2], idx[1024 * 1024 + 3] = single[rs[0]], single[rs[1]], single[rs[2]]
+    exp = expected_route(t, idx)
+    for r in rs[:3]:
+        assert int(exp["hits"][r][-1]) >= 1024 * 1024 and int(exp["counts"][r]) > 1024
+    check(dev_route(torch, t, idx), exp)
+    check(dev_route(torch, t, idx, 1000), exp, 1000)
 
 
 # ---- GPU: tile and wave edges ----------------------------------------------------------------------------------------------
