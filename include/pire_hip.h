@@ -656,6 +656,69 @@ int pire_hip_run_lines_gather(pire_hip_table* t, const void* raw, uint64_t size,
                               uint64_t* out_hits, uint64_t hit_cap, uint64_t* out_hit_count,
                               void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes, void* stream);
 
+/* ---- one column of every string, on the device ------------------------------------------------------------------- */
+
+/* The fields pass cuts text into tiles of this many bytes, on the 16-byte grid of text's address (tests aim at its edges). */
+#define PIRE_HIP_FIELDS_TILE_BYTES 16384u
+#define PIRE_HIP_FIELDS_REST 0x1u        /* in `mode` */
+
+/*
+ * Where field `field` (from 0) of every string is: `awk -F sep '{print $(field + 1)}'` as byte ranges, the step between a
+ * batch of records (access logs, TSV exports: what pire_hip_split hands back) and a scan of ONE column of them.
+ * String i is text[offsets[i], offsets[i + 1]); offsets do not decrease.  It holds m bytes equal to `sep`, at positions
+ * q_1 < ... < q_m (absolute in text); its m + 1 fields are the runs between them, so empty fields exist.  With
+ * q_0 = offsets[i] - 1, q_{m+1} = offsets[i + 1] and k = field:
+ *   k <= m:  out_spans[2i] = q_k + 1,  out_spans[2i + 1] = q_{k+1}
+ *            mode & PIRE_HIP_FIELDS_REST:  out_spans[2i + 1] = offsets[i + 1] instead (`cut -f k-`: the last column of a
+ *            log line may hold the separator)
+ *   k >  m:  out_spans[2i] = out_spans[2i + 1] = offsets[i + 1]            (an empty span at the end of the string)
+ * so an empty string gives an empty span at its offset.  Exactly 2n entries are written, nothing behind them; n == 0
+ * writes nothing.  The spans are ranges of text:
+ *   pire_hip_gather_spans(text, offsets[n], out_spans, NULL, n, PIRE_HIP_GATHER_NO_TAIL, ...)
+ * is legal on them with device pointers (any size >= offsets[n] does: no read-back), and its output string i is the field
+ * of input string i -- indices survive.  sep is a byte value.
+ * flags: PIRE_HIP_RUN_ON_DEVICE -> every pointer is a device pointer and the call only enqueues on `stream`: four kernels
+ *        (defaults per string, count per tile, one-block carry, resolve).  The work is divided by BYTES -- tiles of
+ *        PIRE_HIP_FIELDS_TILE_BYTES --: one line of megabytes, or a million empty ones, cost what their bytes cost.  The
+ *        text is read twice.  No atomics -- the same input gives the same bits --, 16 bytes of scratch per block of the
+ *        grid (at most 2 048 blocks, whatever the text holds) from the stream-ordered allocator.  text may have any
+ *        alignment.
+ *        Otherwise host pointers: staged, synchronises.
+ * PIRE_HIP_EINVAL before any device is touched: sep > 255, unknown bits in mode, n > 0 with null offsets or null out_spans,
+ * and with host pointers offsets that decrease and offsets[n] > 0 with null text.  PIRE_HIP_EUNSUPPORTED: n >= 2^32.
+ * pire_hip_last_kernel() is not changed by the pass.  No first-use self-test (the pass takes no table, as pire_hip_split).
+ */
+int pire_hip_fields(const void* text, const uint64_t* offsets, uint64_t n, uint32_t sep, uint32_t field, uint32_t mode,
+                    uint32_t flags, uint64_t* out_spans, void* stream);
+
+/*
+ * Raw bytes in, the lines whose COLUMN matches out: `awk -F sep '$(field + 1) ~ /re/'`.  pire_hip_run_lines_select with one
+ * more step between its split and its scan: pire_hip_fields on the lines, pire_hip_gather_spans of the n fields into
+ * scratch of the library's own, and the scan on THAT batch -- so PIRE_HIP_RUN_BEGIN / PIRE_HIP_RUN_END step the marks
+ * around the field and an anchored pattern anchors to the column, and a match in another column selects nothing.  Hit k
+ * of the scan is line k of raw: out_hits are line numbers and out_hit_spans the WHOLE lines in raw, delimiter not included.
+ * A line with too few columns is scanned as the empty string.  sep, field, mode: as pire_hip_fields.
+ * Everything else -- want, hit_cap, out_hit_count (the whole count, also beyond hit_cap), out_hit_masks, nothing written
+ * behind the lists, the flags, the ONE synchronisation of `stream` (n read back between the split's scan and its scatter,
+ * EVEN WITH PIRE_HIP_RUN_ON_DEVICE) -- is pire_hip_run_lines_select's.
+ * PIRE_HIP_EINVAL before any device is touched: what pire_hip_run_lines_select refuses, sep > 255, sep == delim, unknown
+ * bits in mode.  pire_hip_last_kernel() names the scan kernel.  Fewer than 2^32 lines.
+ */
+int pire_hip_run_lines_field_select(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t sep,
+                                    uint32_t field, uint32_t mode, uint32_t flags, const uint64_t* want,
+                                    uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_hit_spans,
+                                    uint64_t* out_hit_masks, uint64_t hit_cap, uint64_t* out_hit_count, void* stream);
+
+/*
+ * pire_hip_run_lines_field_select followed by the gather of the selected WHOLE lines from raw: pire_hip_run_lines_gather
+ * with the scan on one column.  tail, out_hits (nullable), out_text, text_cap, out_offsets, out_bytes: as there.
+ */
+int pire_hip_run_lines_field_gather(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t sep,
+                                    uint32_t field, uint32_t mode, uint32_t flags, const uint64_t* want, uint32_t tail,
+                                    uint64_t* out_line_count, uint64_t* out_hits, uint64_t hit_cap, uint64_t* out_hit_count,
+                                    void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes,
+                                    void* stream);
+
 /*
  * Batched Runner over the table walked as a Pire::HalfFinalScanner (scanners/half_final.h:32-227).  A
  * HalfFinalScanner IS a Scanner (same Save() bytes, ingest it with pire_hip_table_create), but its Initialize and

@@ -245,8 +245,24 @@ public:
 		m_n = 0;
 		m_len = size;
 		m_delim = uint8_t(delim);
-		m_onDevice = m_ran = m_selected = m_hitsFetched = m_textFetched = m_routed = m_routeFetched = false;
+		m_onDevice = m_ran = m_selected = m_hitsFetched = m_textFetched = m_routed = m_routeFetched = m_column = false;
 		m_lines = true;
+		return *this;
+	}
+	/*
+	 * The same for records: the lines whose COLUMN `field` (from 0, `sep` between the columns) matches -- awk -F'\t' '$3 ~ /re/'
+	 * is RunLinesField(raw, size, 2) --, cut, scanned and selected on the device (pire_hip_run_lines_field_select / _gather).
+	 * Begin() and End() step the marks around the column, so an anchored pattern anchors to it; rest: the column runs to the end
+	 * of the line (cut -f k-).  A line with too few columns is scanned as the empty string.  Hits(), HitSpans() (the WHOLE lines
+	 * in raw), HitText() and the rest are RunLines()'s; Route() is not available after this form.
+	 */
+	BatchRunner& RunLinesField(const char* raw, size_t size, uint32_t field, char sep = '\t', char delim = '\n', bool rest = false)
+	{
+		RunLines(raw, size, delim);
+		m_column = true;
+		m_sep = uint8_t(sep);
+		m_field = field;
+		m_fieldMode = rest ? PIRE_HIP_FIELDS_REST : 0;
 		return *this;
 	}
 	uint64_t LineCount() { FetchHits(); return m_lineCount; }
@@ -358,9 +374,10 @@ private:
 	{
 		m_routed = m_routeFetched = false;
 		m_routePitch = 0;
-		m_selected = m_hitsFetched = m_haveWant = m_lines = m_textFetched = false;
+		m_selected = m_hitsFetched = m_haveWant = m_lines = m_textFetched = m_column = false;
 		m_hitCount = m_lineCount = 0;
-		m_delim = 0;
+		m_delim = m_sep = 0;
+		m_field = m_fieldMode = 0;
 		m_textTail = '\n';
 		m_flags = 0;
 		m_text = nullptr;
@@ -424,9 +441,12 @@ private:
 			m_hits.resize(cap);
 			m_hitSpans.resize(cap * 2);
 			m_hitMasks.resize(cap * w);
-			Check(pire_hip_run_lines_select(m_table->Handle(), m_text, m_len, m_delim, m_flags, m_haveWant ? m_want.data() : nullptr,
-			                                &m_lineCount, m_hits.data(), m_hitSpans.data(), m_hitMasks.data(), cap, &m_hitCount,
-			                                nullptr));
+			const uint64_t* want = m_haveWant ? m_want.data() : nullptr;
+			Check(m_column ? pire_hip_run_lines_field_select(m_table->Handle(), m_text, m_len, m_delim, m_sep, m_field, m_fieldMode, m_flags,
+			                                                 want, &m_lineCount, m_hits.data(), m_hitSpans.data(), m_hitMasks.data(), cap,
+			                                                 &m_hitCount, nullptr)
+			               : pire_hip_run_lines_select(m_table->Handle(), m_text, m_len, m_delim, m_flags, want, &m_lineCount, m_hits.data(),
+			                                           m_hitSpans.data(), m_hitMasks.data(), cap, &m_hitCount, nullptr));
 			if (m_hitCount <= cap)
 				break;
 		}
@@ -450,9 +470,13 @@ private:
 		for (size_t cap = m_selected && m_ran ? size_t(m_hitCount) : m_len / 64 + 1024;; cap = count) {
 			m_hitTextOffsets.resize(cap + 1);
 			m_hitText.resize(m_len + cap + 1);
-			Check(pire_hip_run_lines_gather(m_table->Handle(), m_text, m_len, m_delim, m_flags, m_haveWant ? m_want.data() : nullptr,
-			                                uint8_t(tail), &m_lineCount, nullptr, cap, &count, &m_hitText[0], m_hitText.size(),
-			                                m_hitTextOffsets.data(), &bytes, nullptr));
+			const uint64_t* want = m_haveWant ? m_want.data() : nullptr;
+			Check(m_column ? pire_hip_run_lines_field_gather(m_table->Handle(), m_text, m_len, m_delim, m_sep, m_field, m_fieldMode, m_flags,
+			                                                 want, uint8_t(tail), &m_lineCount, nullptr, cap, &count, &m_hitText[0],
+			                                                 m_hitText.size(), m_hitTextOffsets.data(), &bytes, nullptr)
+			               : pire_hip_run_lines_gather(m_table->Handle(), m_text, m_len, m_delim, m_flags, want, uint8_t(tail), &m_lineCount,
+			                                           nullptr, cap, &count, &m_hitText[0], m_hitText.size(), m_hitTextOffsets.data(),
+			                                           &bytes, nullptr));
 			if (count <= cap && bytes <= m_hitText.size())
 				break;
 		}
@@ -541,6 +565,8 @@ private:
 			return;
 		const size_t regexps = Regexps();
 		m_routeCounts.assign(regexps, 0);
+		if (m_lines && m_column)
+			throw Pire::Error("pire_hip: Route() follows Run*() or RunLines(), not RunLinesField()");
 		if (m_lines) {
 			/* one call; the grow-and-retry of ExecuteLines() on the longest row */
 			std::vector<uint64_t> hits, spans;
@@ -641,7 +667,9 @@ private:
 	std::vector<uint64_t> m_counts;
 	DeviceBuffer m_devIdx, m_devFin, m_devCounts, m_devInit;
 	bool m_selected, m_hitsFetched, m_haveWant, m_lines, m_textFetched;
-	uint8_t m_delim;
+	bool m_column;                // RunLinesField(): the scan is on column m_field of every line
+	uint8_t m_delim, m_sep;
+	uint32_t m_field, m_fieldMode;
 	char m_textTail;
 	std::string m_hitText;
 	std::vector<uint64_t> m_hitTextOffsets;

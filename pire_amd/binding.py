@@ -136,6 +136,8 @@ ABI_VERSION = 6   # include/pire_hip.h PIRE_HIP_ABI_VERSION
 SPLIT_TILE = 16384   # include/pire_hip.h PIRE_HIP_SPLIT_TILE_BYTES: the split pass cuts raw into tiles of this many bytes
 GATHER_TILE = 16384   # include/pire_hip.h PIRE_HIP_GATHER_TILE_BYTES: the gather's copy pass cuts out_text into tiles of this many bytes
 NO_TAIL = (1 << 32) - 1   # include/pire_hip.h PIRE_HIP_GATHER_NO_TAIL: no byte behind the gathered strings
+FIELDS_TILE = 16384   # include/pire_hip.h PIRE_HIP_FIELDS_TILE_BYTES: the fields pass cuts text into tiles of this many bytes
+FIELDS_REST = 1   # include/pire_hip.h PIRE_HIP_FIELDS_REST (in `mode`): the span runs to the end of the string, `cut -f k-`
 
 # every symbol include/pire_hip.h declares: (name, restype, argtypes)
 ABI = [
@@ -198,6 +200,14 @@ ABI = [
     ("pire_hip_run_lines_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
                                             C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                             C.c_void_p, C.c_void_p]),
+    ("pire_hip_fields", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                  C.c_void_p]),
+    ("pire_hip_run_lines_field_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                  C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                  C.c_void_p, C.c_void_p]),
+    ("pire_hip_run_lines_field_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                  C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                  C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_run_half_final", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_prefix", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_uint32,
@@ -419,6 +429,25 @@ def gather_spans_device(raw_ptr: int, size: int, spans_ptr: int, out_bytes_ptr: 
     _check(lib().pire_hip_gather_spans(raw_ptr or None, size, spans_ptr or None, span_count_ptr or None, span_cap, _tail(tail),
                                        FLAG_ON_DEVICE, out_text_ptr or None, text_cap, out_offsets_ptr or None, out_bytes_ptr or None,
                                        stream or None))
+
+
+# --- one column of every string (pire_hip_fields)
+def fields_host(text, offsets, field: int, sep: int = 9, rest: bool = False):
+    """pire_hip_fields on host arrays: spans uint64[n, 2], begin / end of field `field` (from 0) of every string in `text`."""
+    text = _raw_bytes(text)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    spans = np.zeros((n, 2), dtype=np.uint64)
+    _check(lib().pire_hip_fields(text.ctypes.data if text.size else None, offsets.ctypes.data, n, sep, field,
+                                 FIELDS_REST if rest else 0, 0, spans.ctypes.data if n else None, None))
+    return spans
+
+
+def fields_device(text_ptr: int, offsets_ptr: int, n: int, field: int, out_spans_ptr: int, sep: int = 9, rest: bool = False,
+                  stream: int = 0):
+    """pire_hip_fields with PIRE_HIP_RUN_ON_DEVICE: raw device addresses, only enqueues on `stream`."""
+    _check(lib().pire_hip_fields(text_ptr or None, offsets_ptr or None, n, sep, field, FIELDS_REST if rest else 0, FLAG_ON_DEVICE,
+                                 out_spans_ptr or None, stream or None))
 
 
 # --- from capture positions to byte ranges (pire_hip_capture_select)
@@ -957,6 +986,66 @@ class Table:
                                                _tail(delim if tail == -1 else tail), out_line_count_ptr or None, out_hits_ptr or None,
                                                hit_cap, out_hit_count_ptr or None, out_text_ptr or None, text_cap,
                                                out_offsets_ptr or None, out_bytes_ptr or None, stream or None))
+
+    # --- raw bytes in, the lines whose column matches out (pire_hip_run_lines_field_select / _gather): the results of the two
+    # methods above, hits and spans being whole lines
+    def run_lines_field_select_host(self, raw, field: int, sep: int = 9, delim: int = 10, rest: bool = False,
+                                    flags=FLAG_BEGIN | FLAG_END, want=None, hit_cap=None, hit_masks=True):
+        """pire_hip_run_lines_field_select on a host buffer: what run_lines_select_host returns, the scan on column `field`."""
+        raw = _raw_bytes(raw)
+        wm = self.want_mask(want)
+        cap = raw.size if hit_cap is None else int(hit_cap)
+        w = self.mask_words
+        hits = np.zeros(cap, dtype=np.uint64)
+        spans = np.zeros((cap, 2), dtype=np.uint64)
+        masks = np.zeros((cap, w), dtype=np.uint64) if hit_masks else None
+        lines, cnt = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().pire_hip_run_lines_field_select(self._h, raw.ctypes.data if raw.size else None, raw.size, delim, sep, field,
+                                                     FIELDS_REST if rest else 0, flags & ~FLAG_ON_DEVICE, _np_ptr(wm), C.byref(lines),
+                                                     hits.ctypes.data if cap else None, spans.ctypes.data if cap else None,
+                                                     _np_ptr(masks) if cap else None, cap, C.byref(cnt), None))
+        k = min(int(cnt.value), cap)
+        return {"lines": int(lines.value), "hits": hits[:k], "spans": spans[:k], "hit_masks": None if masks is None else masks[:k],
+                "count": int(cnt.value)}
+
+    def run_lines_field_select_device(self, raw_ptr: int, size: int, field: int, flags, out_line_count_ptr: int, out_hit_count_ptr: int,
+                                      sep: int = 9, delim: int = 10, rest: bool = False, want_ptr=0, out_hits_ptr=0,
+                                      out_hit_spans_ptr=0, out_hit_masks_ptr=0, hit_cap=0, stream: int = 0):
+        """pire_hip_run_lines_field_select on device pointers (synchronises `stream` once, as run_lines_select_device does)."""
+        _check(lib().pire_hip_run_lines_field_select(self._h, raw_ptr or None, size, delim, sep, field, FIELDS_REST if rest else 0,
+                                                     flags | FLAG_ON_DEVICE, want_ptr or None, out_line_count_ptr or None,
+                                                     out_hits_ptr or None, out_hit_spans_ptr or None, out_hit_masks_ptr or None,
+                                                     hit_cap, out_hit_count_ptr or None, stream or None))
+
+    def run_lines_field_gather_host(self, raw, field: int, sep: int = 9, delim: int = 10, rest: bool = False,
+                                    flags=FLAG_BEGIN | FLAG_END, want=None, tail=-1, hit_cap=None, text_cap=None):
+        """pire_hip_run_lines_field_gather on a host buffer: what run_lines_gather_host returns, the scan on column `field`."""
+        raw = _raw_bytes(raw)
+        wm = self.want_mask(want)
+        cap = raw.size if hit_cap is None else int(hit_cap)
+        room = raw.size + cap if text_cap is None else int(text_cap)
+        hits = np.zeros(cap, dtype=np.uint64)
+        text = np.zeros(max(room, 1), dtype=np.uint8)
+        offsets = np.zeros(cap + 1, dtype=np.uint64)
+        lines, cnt, total = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().pire_hip_run_lines_field_gather(self._h, raw.ctypes.data if raw.size else None, raw.size, delim, sep, field,
+                                                     FIELDS_REST if rest else 0, flags & ~FLAG_ON_DEVICE, _np_ptr(wm),
+                                                     _tail(delim if tail == -1 else tail), C.byref(lines),
+                                                     hits.ctypes.data if cap else None, cap, C.byref(cnt),
+                                                     text.ctypes.data if room else None, room, offsets.ctypes.data, C.byref(total), None))
+        k = min(int(cnt.value), cap)
+        return {"lines": int(lines.value), "hits": hits[:k], "count": int(cnt.value), "text": text[:min(int(total.value), room)],
+                "offsets": offsets[:k + 1], "bytes": int(total.value)}
+
+    def run_lines_field_gather_device(self, raw_ptr: int, size: int, field: int, flags, out_line_count_ptr: int, out_hit_count_ptr: int,
+                                      out_bytes_ptr: int, sep: int = 9, delim: int = 10, rest: bool = False, tail=-1, want_ptr=0,
+                                      out_hits_ptr=0, hit_cap=0, out_text_ptr=0, text_cap=0, out_offsets_ptr=0, stream: int = 0):
+        """pire_hip_run_lines_field_gather on device pointers (synchronises `stream` once, as run_lines_select_device does)."""
+        _check(lib().pire_hip_run_lines_field_gather(self._h, raw_ptr or None, size, delim, sep, field, FIELDS_REST if rest else 0,
+                                                     flags | FLAG_ON_DEVICE, want_ptr or None, _tail(delim if tail == -1 else tail),
+                                                     out_line_count_ptr or None, out_hits_ptr or None, hit_cap,
+                                                     out_hit_count_ptr or None, out_text_ptr or None, text_cap,
+                                                     out_offsets_ptr or None, out_bytes_ptr or None, stream or None))
 
     def run_half_final(self, text, offsets, flags=FLAG_BEGIN | FLAG_END):
         """The table walked as a Pire::HalfFinalScanner: (StateIndex, Final, Result[n, regexps]) for host strings."""

@@ -2022,7 +2022,22 @@ int SplitLines(const char* who, const uint8_t* dRaw, uint64_t size, uint32_t del
 	return LaunchSplitScatter(plan, out.text.get(), out.offsets.as<uint64_t>(), *n, dN, stream);
 }
 
-// The frame of the three lines entry points (pire_hip_run_lines_select / _gather, pire_hip_run_lines_route,
+// The column a field form of the lines entry points scans instead of the whole line (pire_hip_fields' arguments)
+struct LinesField {
+	uint32_t sep, field, mode;
+};
+
+// What pire_hip_fields and the field forms refuse of the column before any device is touched
+int FieldArgsInvalid(const char* who, uint32_t sep, uint32_t mode)
+{
+	const char* what = sep > 255 ? "sep > 255" : mode & ~PIRE_HIP_FIELDS_REST ? "unknown bits in mode" : nullptr;
+	if (!what)
+		return PIRE_HIP_OK;
+	SetError(std::string(who) + ": " + what);
+	return PIRE_HIP_EINVAL;
+}
+
+// The frame of the lines entry points (pire_hip_run_lines_select / _gather and their field forms, pire_hip_run_lines_route,
 // pire_hip_capture_lines_gather) around their scan + pass: raw bytes in, hit lists (and, in the gather forms, the bytes of the
 // hits) out.  An entry point checks its arguments, then walks the frame's steps in this order:
 //   HostEdge   an empty buffer with host pointers: the line count and the gather's outputs are zeroed, no device is touched
@@ -2031,6 +2046,8 @@ int SplitLines(const char* who, const uint8_t* dRaw, uint64_t size, uint32_t del
 //              wait --; cap: no list is longer than the lines are many
 //   Lists      hits[rows][cap] and spans[rows][cap][2] staged at size 0 where the caller has arrays for them; a gather form:
 //              scratch for the lists it chains on and the caller did not ask for, out_text and out_offsets
+//   Cut        a field form, n > 0: pire_hip_fields on the lines and the gather of the n fields into scratch; Text() and
+//              Offsets() are that batch from here on -- string k of it is the column of line k --, LineOffsets() stays the split's
 //   -- the entry point enqueues its scan + pass on the lines (Text(), Offsets(), n, cap, RunFlags()) into dCounts / dHits / dSpans --
 //   Close      a gather form: the gather straight from raw through the spans; Finish(); host pointers: the line count, and
 //              the lists, offsets and text back only as far as they were written (HitsBack)
@@ -2044,7 +2061,9 @@ struct LinesFrame {
 	bool onDevice;
 	BatchIO io;
 	LinesScratch lines;
-	StreamScratch ownHits, ownSpans;
+	StreamScratch ownHits, ownSpans, cut;
+	const uint8_t* cutText = nullptr;      // the fields back to back, their offsets: what a field form scans
+	const uint64_t* cutOffsets = nullptr;
 	uint64_t n = 0, cap = 0, hitCap = 0, textRoom = 0;   // textRoom of out_text: k lines and their tails are size + k bytes at most
 	uint32_t rows = 0;
 	uint64_t *outLineCount = nullptr, *outCounts = nullptr, *outHits = nullptr, *outSpans = nullptr;
@@ -2055,11 +2074,12 @@ struct LinesFrame {
 	LinesFrame(const char* who_, const void* raw_, uint64_t size_, uint32_t delim_, uint32_t flags_, const LinesGather* gather_, void* stream_)
 		: who(who_), raw(static_cast<const uint8_t*>(raw_)), size(size_), delim(delim_), flags(flags_), gather(gather_),
 		  stream(static_cast<hipStream_t>(stream_)), onDevice((flags_ & PIRE_HIP_RUN_ON_DEVICE) != 0), io(stream, onDevice), lines(stream),
-		  ownHits(stream), ownSpans(stream)
+		  ownHits(stream), ownSpans(stream), cut(stream)
 	{
 	}
-	const void* Text() const { return lines.text.get(); }
-	const uint64_t* Offsets() const { return lines.offsets.as<uint64_t>(); }
+	const void* Text() const { return cutText ? cutText : lines.text.get(); }
+	const uint64_t* Offsets() const { return cutOffsets ? cutOffsets : LineOffsets(); }
+	const uint64_t* LineOffsets() const { return lines.offsets.as<uint64_t>(); }
 	uint32_t RunFlags() const { return (flags & (PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END | PIRE_HIP_RUN_GENERIC)) | PIRE_HIP_RUN_ON_DEVICE; }
 
 	bool HostEdge(uint64_t* lineCount)
@@ -2125,6 +2145,24 @@ struct LinesFrame {
 		}
 		return gather->outOffsets ? io.Result(gather->outOffsets, size_t(cap) + 1, 0, &dOutOffsets) : PIRE_HIP_OK;
 	}
+	int Cut(const LinesField& c)
+	{
+		// one block: spans[n][2], offsets[n + 1], the byte count, the text (no longer than the lines are)
+		const size_t words = size_t(n) * 3 + 2;
+		if (int rc = cut.Alloc(words * 8 + size_t(size) + 16, "hipMallocAsync(fields)"))
+			return rc;
+		uint64_t* spans = cut.as<uint64_t>();
+		uint64_t* offsets = spans + 2 * n;
+		uint64_t* bytes = offsets + n + 1;
+		uint8_t* text = reinterpret_cast<uint8_t*>(bytes + 1);
+		if (int rc = LaunchFields(lines.text.get(), LineOffsets(), n, c.sep, c.field, c.mode, spans, size, stream))
+			return rc;
+		const GatherSource src = {lines.text.as<const uint8_t>(), nullptr, 0, nullptr, spans, size};
+		if (int rc = LaunchGather(src, nullptr, n, PIRE_HIP_GATHER_NO_TAIL, text, size, offsets, bytes, kGatherTotalUnknown, stream))
+			return rc;
+		cutText = text, cutOffsets = offsets;
+		return PIRE_HIP_OK;
+	}
 	// n == 0: the hit counts are zeroed where the entry point has no pass to do it
 	int ZeroCounts(const char* what)
 	{
@@ -2163,9 +2201,10 @@ struct LinesFrame {
 
 int RunLinesImpl(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags, const uint64_t* want,
                  uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_hit_spans, uint64_t* out_hit_masks, uint64_t hit_cap,
-                 uint64_t* out_hit_count, void* streamPtr, const LinesGather* gather)
+                 uint64_t* out_hit_count, void* streamPtr, const LinesGather* gather, const LinesField* column = nullptr)
 {
-	const char* who = gather ? "pire_hip_run_lines_gather" : "pire_hip_run_lines_select";
+	const char* who = column ? (gather ? "pire_hip_run_lines_field_gather" : "pire_hip_run_lines_field_select")
+	                         : (gather ? "pire_hip_run_lines_gather" : "pire_hip_run_lines_select");
 	// (the gather form keeps the hit list to itself where the caller has no array for it)
 	if (int rc = SelectArgsInvalid(t, nullptr, false, 0, out_hits, out_hit_masks, gather && !out_hits ? 0 : hit_cap, out_hit_count))
 		return rc;
@@ -2174,6 +2213,12 @@ int RunLinesImpl(pire_hip_table* t, const void* raw, uint64_t size, uint32_t del
 	if (out_hit_spans && !out_hits) {
 		SetError("pire_hip_run_lines_select: out_hit_spans without out_hits");
 		return PIRE_HIP_EINVAL;
+	}
+	if (column) {
+		if (int rc = FieldArgsInvalid(who, column->sep, column->mode))
+			return rc;
+		if (column->sep == delim)
+			return GatherRefuse(who, "sep == delim");
 	}
 	if (gather) {
 		if (int rc = GatherOutputsInvalid(who, "hit_cap", hit_cap, gather->tail, gather->outText, gather->textCap, gather->outOffsets,
@@ -2206,11 +2251,14 @@ int RunLinesImpl(pire_hip_table* t, const void* raw, uint64_t size, uint32_t del
 		if (int rc = f.ZeroCounts("hipMemsetAsync(hit count)"))
 			return rc;
 	} else {
+		if (column)
+			if (int rc = f.Cut(*column))
+				return rc;
 		if (int rc = pire_hip_run_select(t, f.Text(), f.Offsets(), f.n, f.RunFlags(), nullptr, nullptr, nullptr, nullptr, dWant, nullptr,
 		                                 f.dHits, dHitMasks, f.dHits ? f.cap : 0, f.dCounts, f.stream))
 			return rc;
-		if (f.dSpans)
-			if (int rc = LaunchHitSpans(f.dHits, f.dCounts, 1, f.cap, f.cap, f.Offsets(), f.dSpans, f.stream, "split spans launch"))
+		if (f.dSpans)   // (the whole line, whatever part of it was scanned)
+			if (int rc = LaunchHitSpans(f.dHits, f.dCounts, 1, f.cap, f.cap, f.LineOffsets(), f.dSpans, f.stream, "split spans launch"))
 				return rc;
 	}
 	if (int rc = f.Close("hipMemcpy(hits)"))
@@ -2386,6 +2434,72 @@ try {
 	const LinesGather gather = {tail, out_text, text_cap, out_offsets, out_bytes, true, "hipMallocAsync(hit spans)"};
 	return RunLinesImpl(t, raw, size, delim, flags, want, out_line_count, out_hits, nullptr, nullptr, hit_cap, out_hit_count, stream,
 	                    &gather);
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+// ---- one column of every string (fields.hip) -------------------------------------------------------------------------------
+int pire_hip_fields(const void* text, const uint64_t* offsets, uint64_t n, uint32_t sep, uint32_t field, uint32_t mode,
+                    uint32_t flags, uint64_t* out_spans, void* streamPtr)
+try {
+	const char* who = "pire_hip_fields";
+	if (int rc = FieldArgsInvalid(who, sep, mode))
+		return rc;
+	if (n && !offsets)
+		return GatherRefuse(who, "n > 0 with null offsets");
+	if (n && !out_spans)
+		return GatherRefuse(who, "n > 0 with null out_spans");
+	if (n >= (1ull << 32)) {
+		SetError("pire_hip_fields: 2^32 strings or more in one call");
+		return PIRE_HIP_EUNSUPPORTED;
+	}
+	if (n == 0)
+		return PIRE_HIP_OK;
+	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
+	if (!onDevice) {
+		uint64_t textBytes = 0;
+		if (int rc = CheckHostBatch(text, offsets, n, 0, 0, &textBytes))
+			return rc;
+	}
+	BatchIO io(stream, onDevice);
+	const uint8_t* dText = nullptr;
+	const uint64_t* dOffsets = nullptr;
+	uint64_t* dSpans = nullptr;
+	if (int rc = io.Text(text, offsets, n, 0, 0, &dText, &dOffsets))
+		return rc;
+	if (int rc = io.Result(out_spans, size_t(n) * 2, size_t(n) * 2, &dSpans))
+		return rc;
+	if (int rc = io.Ready())
+		return rc;
+	if (int rc = LaunchFields(dText, dOffsets, n, sep, field, mode, dSpans, onDevice ? kFieldsBytesUnknown : offsets[n] - offsets[0], stream))
+		return rc;
+	return io.Finish();
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_run_lines_field_select(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t sep, uint32_t field,
+                                    uint32_t mode, uint32_t flags, const uint64_t* want, uint64_t* out_line_count, uint64_t* out_hits,
+                                    uint64_t* out_hit_spans, uint64_t* out_hit_masks, uint64_t hit_cap, uint64_t* out_hit_count,
+                                    void* stream)
+try {
+	const LinesField column = {sep, field, mode};
+	return RunLinesImpl(t, raw, size, delim, flags, want, out_line_count, out_hits, out_hit_spans, out_hit_masks, hit_cap,
+	                    out_hit_count, stream, nullptr, &column);
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_run_lines_field_gather(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t sep, uint32_t field,
+                                    uint32_t mode, uint32_t flags, const uint64_t* want, uint32_t tail, uint64_t* out_line_count,
+                                    uint64_t* out_hits, uint64_t hit_cap, uint64_t* out_hit_count, void* out_text, uint64_t text_cap,
+                                    uint64_t* out_offsets, uint64_t* out_bytes, void* stream)
+try {
+	const LinesGather gather = {tail, out_text, text_cap, out_offsets, out_bytes, true, "hipMallocAsync(hit spans)"};
+	const LinesField column = {sep, field, mode};
+	return RunLinesImpl(t, raw, size, delim, flags, want, out_line_count, out_hits, nullptr, nullptr, hit_cap, out_hit_count, stream,
+	                    &gather, &column);
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }

@@ -1,10 +1,13 @@
-// The pieces the hit passes share on the device (select.hip, capture_select.hip, route.hip, split.hip, gather.hip): the
-// prefix sum over a block of 1 024 threads and the ballot compaction of a tile of 1 024 strings.  Device only, force-inlined
-// into the kernels that use them; DESIGN.md section 4.15 says who owns what.
+// The pieces the hit passes share on the device (select.hip, capture_select.hip, route.hip, split.hip, gather.hip,
+// fields.hip): the prefix sum over a block of 1 024 threads, the ballot compaction of a tile of 1 024 strings, the 16-byte
+// lane load of the byte-rate passes and the wave-wide search in an offsets array.  Device only, force-inlined into the
+// kernels that use them; DESIGN.md section 4.15 says who owns what.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstddef>
 #include <cstdint>
 
 namespace pirehip {
@@ -78,6 +81,57 @@ __device__ __forceinline__ uint64_t TileRank(uint32_t tile, const uint64_t* ball
 	const uint64_t mine = (uint64_t(hi) << 32) | lo;
 	*selected = (mine >> lane) & 1;
 	return uint64_t(tileCounts[tile]) + front + __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0));
+}
+
+// The lane's 16 bytes of the byte-rate passes (split.hip, fields.hip) at virtual position v (a multiple of 16; raw[0] is at
+// virtual position head = raw's address modulo 16, the buffer is `size` bytes): w = the bytes (0 where the buffer is not),
+// *valid = which of them are the buffer's; returns which of those are the byte that byte4 holds four times.  A lane inside
+// the buffer loads with one global_load_dwordx4, the lanes that hang over its two ends load their bytes one by one.
+__device__ __forceinline__ uint32_t LoadLane(const uint8_t* raw, uint32_t head, uint64_t size, uint32_t byte4, uint64_t v, uint32_t (&w)[4],
+                                             uint32_t* valid)
+{
+	const uint64_t end = head + size;
+	if (v >= head && v + 16 <= end) {
+		const uint4 q = *reinterpret_cast<const uint4*>(raw + ptrdiff_t(v - head));
+		w[0] = q.x, w[1] = q.y, w[2] = q.z, w[3] = q.w;
+		*valid = 0xFFFFu;
+	} else {
+		uint32_t vm = 0;
+		w[0] = w[1] = w[2] = w[3] = 0;
+		const uint8_t* b = raw + ptrdiff_t(v - head);   // (in front of raw for the first lane of a misaligned buffer: not read there)
+#pragma unroll
+		for (uint32_t i = 0; i < 16; ++i)
+			if (v + i >= head && v + i < end) {
+				w[i >> 2] |= uint32_t(b[i]) << (8 * (i & 3));
+				vm |= 1u << i;
+			}
+		*valid = vm;
+	}
+	uint32_t dm = 0;
+#pragma unroll
+	for (uint32_t k = 0; k < 4; ++k) {
+		const uint32_t x = w[k] ^ byte4;
+		const uint32_t t = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);   // 0x80 in every byte of x that is 0, exactly
+		dm |= (((t >> 7) | (t >> 14) | (t >> 21) | (t >> 28)) & 0xFu) << (4 * k);
+	}
+	return dm & *valid;
+}
+
+// The string that owns byte pos of a batch -- the last j < k with off[j] <= pos; off[0] <= pos < off[k] --, found by one
+// wave: 64 probes a step.  It steps over the repeated entries that empty strings leave.
+__device__ __forceinline__ uint64_t WaveOwner(const uint64_t* off, uint64_t k, uint64_t pos)
+{
+	const uint32_t lane = threadIdx.x & 63;
+	uint64_t lo = 0, hi = k;
+	while (hi - lo > 1) {
+		const uint64_t step = (hi - lo + 63) / 64;
+		const uint64_t q = lo + (lane + 1) * step;
+		const bool le = q < hi && off[q] <= pos;   // true in the first c lanes, false behind them
+		const uint64_t c = uint64_t(__popcll(__ballot(le)));
+		hi = std::min(hi, lo + (c + 1) * step);
+		lo += c * step;
+	}
+	return lo;
 }
 
 }  // namespace pirehip

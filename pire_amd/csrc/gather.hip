@@ -17,7 +17,7 @@
 //             inside the tile.
 //   copy      the work is divided by OUTPUT BYTES.  outText is cut into tiles of 16 KiB on the 16-byte grid of its address;
 //             a block finds the strings that own its tile's first and last byte by search in outOffsets (64 probes a step,
-//             one wave each; the owner of byte x is the LAST j with outOffsets[j] <= x, which steps over the repeated
+//             one wave each, compact.h WaveOwner; the owner of byte x is the LAST j with outOffsets[j] <= x, which steps over the repeated
 //             entries that empty strings leave), stages the tile's string boundaries and source positions in LDS -- one
 //             entry per lane and store, consecutive lanes at consecutive words --, and then every lane owns 16 output
 //             bytes: it finds its string by binary search in the staged boundaries; if its 16 bytes lie inside one string
@@ -151,23 +151,6 @@ __global__ __launch_bounds__(kGatThreads) void GatherOffsetsKernel(GatherParams 
 		if (j < k)
 			p.outOffsets[j + 1] = front + incl;
 	}
-}
-
-// The string that owns output byte pos -- the last j < k with off[j] <= pos; off[0] <= pos < off[k] --, found by one wave:
-// 64 probes a step.
-__device__ __forceinline__ uint64_t WaveOwner(const uint64_t* off, uint64_t k, uint64_t pos)
-{
-	const uint32_t lane = threadIdx.x & 63;
-	uint64_t lo = 0, hi = k;
-	while (hi - lo > 1) {
-		const uint64_t step = (hi - lo + 63) / 64;
-		const uint64_t q = lo + (lane + 1) * step;
-		const bool le = q < hi && off[q] <= pos;   // true in the first c lanes, false behind them
-		const uint64_t c = uint64_t(__popcll(__ballot(le)));
-		hi = std::min(hi, lo + (c + 1) * step);
-		lo += c * step;
-	}
-	return lo;
 }
 
 // An entry of outOffsets as the lanes of a tile want it: relative to the tile's first byte, cut to [0, tile + 16]

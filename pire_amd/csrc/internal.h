@@ -1142,6 +1142,13 @@ struct GatherSource {
 constexpr uint64_t kGatherTotalUnknown = ~0ull;
 int LaunchGather(const GatherSource& src, const uint64_t* count, uint64_t cap, uint32_t tail, void* outText, uint64_t textCap,
                  uint64_t* outOffsets, uint64_t* outBytes, uint64_t hostTotal, hipStream_t stream);
+// fields.hip: where field `field` of every string is (pire_hip_fields).  Device pointers only, four kernels enqueued on
+// `stream`, 16 bytes of scratch per block of the grid (<= 2 048) from the stream-ordered allocator.  bytesHint: an upper bound
+// of offsets[n] - offsets[0] where the host knows one (it sizes the grid), kFieldsBytesUnknown where it does not (the grid is
+// then the largest, and the blocks without a tile leave).
+constexpr uint64_t kFieldsBytesUnknown = ~0ull;
+int LaunchFields(const void* text, const uint64_t* offsets, uint64_t n, uint32_t sep, uint32_t field, uint32_t mode, uint64_t* outSpans,
+                 uint64_t bytesHint, hipStream_t stream);
 void NoteKernel(const char* name, const char* symbol = nullptr);   // what pire_hip_last_kernel[_symbol]() report (thread local)
 bool RaggedActEligible(const ScanParams& p);
 int LaunchRaggedHalfFinal(const ScanParams& p, unsigned long long* workCounter, uint32_t* outResults, hipStream_t stream);

@@ -11,7 +11,7 @@
 //   out_text = raw without its delimiter bytes        =>  line i is raw[offsets[i] + i, offsets[i + 1] + i)
 //
 //   count     raw is cut into tiles of 16 KiB ON THE 16-BYTE GRID OF ITS ADDRESS (a misaligned raw has a short first tile):
-//             a lane loads its 16 bytes with one global_load_dwordx4 -- the lanes that hang over the buffer's two ends load
+//             a lane loads its 16 bytes with one global_load_dwordx4 (compact.h LoadLane) -- the lanes that hang over the buffer's two ends load
 //             their bytes one by one --, compares them with the delimiter (a 16-bit mask), popcounts; one count per tile.
 //   scan      exclusive scan of the tile counts, one block, 1 024 tiles (16 MiB of text) a step, a 64-bit carry between the
 //             steps; the total and the trailing-fragment term are *out_n.
@@ -49,43 +49,12 @@ constexpr uint32_t kSplitTile = PIRE_HIP_SPLIT_TILE_BYTES;   // 16 bytes a lane
 constexpr uint32_t kSplitMaxBlocks = 2048;                   // 2 blocks on each of 256 CUs, four rounds; tiles in a grid-stride loop
 static_assert(kSplitTile == kSplitThreads * 16, "one dwordx4 per lane and tile");
 
-// The lane's 16 bytes at virtual position v (a multiple of 16; raw[0] is at virtual position p.head): w = the bytes (0
-// where the buffer is not), *valid = which of them are the buffer's; returns which of those are the delimiter.
-__device__ __forceinline__ uint32_t LoadLane(const SplitPlan& p, uint64_t v, uint32_t (&w)[4], uint32_t* valid)
-{
-	const uint64_t end = p.head + p.size;
-	if (v >= p.head && v + 16 <= end) {
-		const uint4 q = *reinterpret_cast<const uint4*>(p.raw + ptrdiff_t(v - p.head));
-		w[0] = q.x, w[1] = q.y, w[2] = q.z, w[3] = q.w;
-		*valid = 0xFFFFu;
-	} else {
-		uint32_t vm = 0;
-		w[0] = w[1] = w[2] = w[3] = 0;
-		const uint8_t* b = p.raw + ptrdiff_t(v - p.head);   // (in front of raw for the first lane of a misaligned buffer: not read there)
-#pragma unroll
-		for (uint32_t i = 0; i < 16; ++i)
-			if (v + i >= p.head && v + i < end) {
-				w[i >> 2] |= uint32_t(b[i]) << (8 * (i & 3));
-				vm |= 1u << i;
-			}
-		*valid = vm;
-	}
-	uint32_t dm = 0;
-#pragma unroll
-	for (uint32_t k = 0; k < 4; ++k) {
-		const uint32_t x = w[k] ^ p.delim4;
-		const uint32_t t = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);   // 0x80 in every byte of x that is 0, exactly
-		dm |= (((t >> 7) | (t >> 14) | (t >> 21) | (t >> 28)) & 0xFu) << (4 * k);
-	}
-	return dm & *valid;
-}
-
 __global__ __launch_bounds__(kSplitThreads) void SplitCountKernel(SplitPlan p)
 {
 	__shared__ uint32_t waveSum[kSplitWaves];
 	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
 		uint32_t w[4], valid, total;
-		const uint32_t dm = LoadLane(p, uint64_t(tile) * kSplitTile + threadIdx.x * 16, w, &valid);
+		const uint32_t dm = LoadLane(p.raw, p.head, p.size, p.delim4, uint64_t(tile) * kSplitTile + threadIdx.x * 16, w, &valid);
 		(void)BlockExclusive(uint32_t(__popc(dm)), waveSum, &total);
 		if (threadIdx.x == 0)
 			p.counts[tile] = total;
@@ -132,7 +101,7 @@ __global__ __launch_bounds__(kSplitThreads) void SplitScatterKernel(SplitPlan p,
 	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
 		const uint64_t v = uint64_t(tile) * kSplitTile + threadIdx.x * 16;
 		uint32_t w[4], valid, total;
-		const uint32_t dm = LoadLane(p, v, w, &valid);
+		const uint32_t dm = LoadLane(p.raw, p.head, p.size, p.delim4, v, w, &valid);
 		const uint32_t front = BlockExclusive(uint32_t(__popc(dm)), waveSum, &total);
 		const uint64_t tilePrefix = p.prefix[tile];
 		const uint64_t rank0 = tilePrefix + front;   // delimiters in front of this lane's bytes
