@@ -410,8 +410,10 @@ int pire_hip_run(pire_hip_table* t, const void* text, const uint64_t* offsets, u
 
 /*
  * Same walk over fixed-length records: string i = text[i*stride, i*stride + len).  This is the layout the
- * tiled LDS-resident kernel is specialised for (len a multiple of 16, stride a multiple of 16, text
- * 16-byte aligned, device pointers); anything else is routed to the generic kernel with the same results.
+ * tiled LDS-resident kernel is specialised for: stride a multiple of 16, text 16-byte aligned, len >= 128 (any
+ * len: what the whole 128-byte tiles leave of a record is walked byte by byte), n >= 64, 64 * stride < 2^31;
+ * anything else is routed to the generic kernel with the same results.  Bytes behind a record's len, up to its
+ * stride, are never walked.
  */
 int pire_hip_run_strided(pire_hip_table* t, const void* text, uint64_t n, uint64_t len, uint64_t stride,
                          uint32_t flags, const uint32_t* init_state_idx,
