@@ -1076,6 +1076,74 @@ int pire_hip_capture_lines_gather(pire_hip_counting_table* t, const void* raw, u
                                   void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes,
                                   void* stream);
 
+/* ---- the strings that count, on the device ---------------------------------------------------------------------- */
+
+/*
+ * From result rows to the strings whose counters reach their thresholds -- a compacted, ascending list of their indices and
+ * rows -- and the occurrences of every regexp over the batch.  It takes no table and no text: it reads what
+ * pire_hip_counting_run or pire_hip_run_half_final wrote (results[n][regexps]), behind any of the counting kernels.  With
+ * R = regexps and c(i, r) = results[i * R + r]:
+ *   m(r)        = min_count ? min_count[r] : 1                  min_count (nullable): R entries
+ *   wanted(r)   = m(r) > 0
+ *   pass(i, r)  = c(i, r) >= m(r)
+ *   selected(i) = some wanted r passes                          (default, ANY)
+ *   selected(i) = some r is wanted and every wanted r passes    (mode & PIRE_HIP_COUNT_ALL)
+ * With no wanted r nothing is selected.
+ * out_totals[R] (nullable): the sum of c(i, r) over ALL n strings, selected or not, exact in 64 bits; written, not
+ * accumulated; n == 0 writes R zeros.  out_hits[hit_cap] (nullable): the indices of the selected strings, ascending.
+ * out_hit_results[hit_cap][R] (nullable, and it does not need out_hits): the result row of hit k.  *out_hit_count
+ * (required): the number of selected strings, also when it exceeds hit_cap; only the first min(count, hit_cap) entries of
+ * the two lists are written, nothing behind them.  R == 0: PIRE_HIP_OK, a count of 0 and nothing else written.
+ * flags: PIRE_HIP_RUN_ON_DEVICE -> every pointer (min_count included) is a device pointer and the call only enqueues on
+ *        `stream`: classify per tile of 1 024 strings, the one-block scan of pire_hip_select, scatter and -- for out_totals --
+ *        one uint64 sum per tile and regexp and their reduction; no atomics, no block waits for another: the same input gives
+ *        the same bits.  Scratch (n / 8 + n / 256 bytes, + R * ceil(n / 1024) * 8 for the totals) comes from the
+ *        stream-ordered allocator: the rule and the capture-mode caveat stated at pire_hip_select.  `results` needs 4-byte
+ *        alignment only.  Otherwise host pointers: staged, synchronises, the lists come back only as far as they were written.
+ * PIRE_HIP_EINVAL before any device is touched: null out_hit_count; n > 0 and R > 0 with null results; unknown bits in
+ * mode; hit_cap > 0 with null out_hits and null out_hit_results.  PIRE_HIP_EUNSUPPORTED: n >= 2^32, R > 1024.
+ * pire_hip_last_kernel() is not changed by the pass.  No first-use self-test (as pire_hip_select).
+ */
+#define PIRE_HIP_COUNT_ALL 0x1u      /* in `mode` */
+int pire_hip_count_select(const uint32_t* results, uint64_t n, uint32_t regexps, const uint32_t* min_count, uint32_t mode,
+                          uint32_t flags, uint64_t* out_totals, uint64_t* out_hits, uint32_t* out_hit_results,
+                          uint64_t hit_cap, uint64_t* out_hit_count, void* stream);
+
+/*
+ * pire_hip_counting_run / pire_hip_run_half_final followed by pire_hip_count_select on the same stream, behind whichever
+ * kernel the scan takes.  t .. out_results: as the run call; R is the table's.  out_results is nullable here: the rows then
+ * live in stream-ordered scratch of the library's own.  With host pointers the text is staged once, and scan and pass run
+ * on the staged copy before anything comes back.  Hit indices are relative to the whole batch.  They refuse what the run
+ * call refuses (the null out_results excepted) and what pire_hip_count_select refuses.  pire_hip_last_kernel() names the
+ * scan's kernel.
+ */
+int pire_hip_counting_run_select(pire_hip_counting_table* t, int kind, const void* text, const uint64_t* offsets, uint64_t n,
+                                 uint32_t flags, uint32_t* out_state_idx, uint32_t* out_results,
+                                 const uint32_t* min_count, uint32_t mode, uint64_t* out_totals, uint64_t* out_hits,
+                                 uint32_t* out_hit_results, uint64_t hit_cap, uint64_t* out_hit_count, void* stream);
+int pire_hip_run_half_final_select(pire_hip_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
+                                   uint32_t* out_state_idx, uint8_t* out_final, uint32_t* out_results,
+                                   const uint32_t* min_count, uint32_t mode, uint64_t* out_totals, uint64_t* out_hits,
+                                   uint32_t* out_hit_results, uint64_t hit_cap, uint64_t* out_hit_count, void* stream);
+
+/*
+ * Raw bytes in, the lines that count out: the split into scratch, the counting scan on the lines with the rows in scratch,
+ * the pass.  out_line_count (required), delim, the one synchronisation of `stream` (the split's; the call adds none) and
+ * the refusal of 2^32 lines: as pire_hip_run_lines_select.  min_count, mode, out_totals, out_hits (the numbers of the
+ * lines), out_hit_results, hit_cap, out_hit_count: as pire_hip_count_select.  out_hit_spans[hit_cap][2] (nullable, needs
+ * out_hits): the whole line of hit k as a byte range of raw, delimiter not included -- the input of pire_hip_gather_spans,
+ * which chains on it with device pointers (the gather stays the caller's).  Host pointers with size == 0: zeros, no device
+ * is touched.  They also refuse delim > 255, null out_line_count and size > 0 with null raw.
+ */
+int pire_hip_counting_lines_select(pire_hip_counting_table* t, int kind, const void* raw, uint64_t size, uint32_t delim,
+                                   uint32_t flags, const uint32_t* min_count, uint32_t mode, uint64_t* out_line_count,
+                                   uint64_t* out_totals, uint64_t* out_hits, uint64_t* out_hit_spans,
+                                   uint32_t* out_hit_results, uint64_t hit_cap, uint64_t* out_hit_count, void* stream);
+int pire_hip_half_final_lines_select(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
+                                     const uint32_t* min_count, uint32_t mode, uint64_t* out_line_count,
+                                     uint64_t* out_totals, uint64_t* out_hits, uint64_t* out_hit_spans,
+                                     uint32_t* out_hit_results, uint64_t hit_cap, uint64_t* out_hit_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -948,6 +948,44 @@ private:
 };
 
 /*
+ * What Select() and RunLines() of the two counting runners below leave: the strings (lines) whose counts reach their
+ * thresholds and the occurrences of every regexp over the batch, answered on the device (include/pire_hip.h, "the strings
+ * that count, on the device").  One call with room for `room` hits, and a second one where there are more.
+ */
+struct CountedHits {
+	std::vector<uint32_t> min, rows;
+	std::vector<uint64_t> hits, spans, totals;
+	uint64_t count, lineCount;
+	bool all, fetched;
+	CountedHits() : count(0), lineCount(0), all(false), fetched(false) {}
+	void Choose(const std::vector<uint32_t>& m, bool a) { min = m; all = a; fetched = false; }
+	template <class Owner>
+	void Fetch(Owner& owner, size_t regexps, uint64_t room, bool lines)
+	{
+		if (fetched)
+			return;
+		if (!min.empty() && min.size() != regexps)
+			throw Pire::Error("pire_hip: Select() takes one threshold per regexp");
+		totals.assign(regexps, 0);
+		for (int attempt = 0; attempt < 2; ++attempt) {
+			hits.assign(size_t(room), 0);
+			rows.assign(size_t(room) * regexps, 0);
+			spans.assign(lines ? 2 * size_t(room) : 0, 0);
+			owner.CountSelectCall(min.empty() ? nullptr : min.data(), all ? PIRE_HIP_COUNT_ALL : 0u, regexps ? totals.data() : nullptr,
+			                      room ? hits.data() : nullptr, room && lines ? spans.data() : nullptr,
+			                      room && regexps ? rows.data() : nullptr, room, &count, &lineCount);
+			if (count <= room)
+				break;
+			room = count;
+		}
+		hits.resize(size_t(count));
+		rows.resize(size_t(count) * regexps);
+		spans.resize(lines ? 2 * size_t(count) : 0);
+		fetched = true;
+	}
+};
+
+/*
  * Batched Runner over a Pire::HalfFinalScanner (scanners/half_final.h): per string the per-regexp match counts
  * State::Result(r) (half_final.h:90-92) that Initialize + Begin() + Run() + End() accumulate through TakeAction
  * (half_final.h:137-164), plus Final and StateIndex of the end state.  The scanner's State is an opaque class with
@@ -957,7 +995,7 @@ template <class HalfScanner = Pire::HalfFinalScanner>
 class HalfFinalBatchRunner {
 public:
 	explicit HalfFinalBatchRunner(const HalfScanner& sc)
-	    : m_table(nullptr), m_regexps(sc.RegexpsCount()), m_flags(0), m_text(nullptr), m_offsets(nullptr), m_n(0), m_ran(false)
+	    : m_table(nullptr), m_regexps(sc.RegexpsCount()), m_flags(0), m_text(nullptr), m_offsets(nullptr), m_n(0), m_ran(false), m_len(0), m_delim('\n'), m_lines(false)
 	{
 		std::ostringstream out;
 		sc.Save(&out);                                    // Scanner::Save, multi.h:557-573 (inherited)
@@ -974,6 +1012,8 @@ public:
 		m_offsets = offsets;
 		m_n = n;
 		m_ran = false;
+		m_lines = false;
+		m_sel.fetched = false;
 		return *this;
 	}
 	HalfFinalBatchRunner& Run(const std::vector<ystring>& strings)
@@ -993,11 +1033,72 @@ public:
 	const std::vector<char>& Finals() { Execute(); return m_final; }              // Final(State()) per string
 	const std::vector<uint32_t>& StateIndices() { Execute(); return m_idx; }      // StateIndex(State()) per string
 
+	/*
+	 * The strings whose counts reach their thresholds, without a loop on the host (pire_hip_count_select behind the scan):
+	 *     run.Begin().Run(text, offsets, n).End().Select();    // the strings in which some regexp occurred
+	 *     run.Select({3, 0, 1});                                // ... regexp 0 three times or regexp 2 once (0 = not asked)
+	 *     run.Select({3, 0, 1}, true);                          // ... and regexp 2 once
+	 *     run.Hits()        the selected strings, ascending      run.HitResults()  their result rows, [k][RegexpsCount()]
+	 *     run.HitCount()    how many                             run.Totals()      occurrences per regexp over ALL strings
+	 *     run.Begin().RunLines(raw, size).End();                // the same per line of raw, split on the device, and
+	 *     run.HitSpans()    [2 * k], [2 * k + 1]: line Hits()[k] is raw[begin, end)        run.LineCount()  lines in the buffer
+	 * After RunLines() there are hits only: Result() / Results() / StateIndices() throw.
+	 */
+	HalfFinalBatchRunner& Select(const std::vector<uint32_t>& min = std::vector<uint32_t>(), bool all = false)
+	{
+		m_sel.Choose(min, all);
+		return *this;
+	}
+	HalfFinalBatchRunner& RunLines(const char* raw, size_t size, char delim = '\n')
+	{
+		m_text = raw;
+		m_len = size;
+		m_delim = delim;
+		m_lines = true;
+		m_ran = false;
+		m_sel.fetched = false;
+		return *this;
+	}
+	const std::vector<uint64_t>& Hits() { FetchHits(); return m_sel.hits; }
+	const std::vector<uint32_t>& HitResults() { FetchHits(); return m_sel.rows; }
+	size_t HitCount() { FetchHits(); return size_t(m_sel.count); }
+	const std::vector<uint64_t>& Totals() { FetchHits(); return m_sel.totals; }
+	const std::vector<uint64_t>& HitSpans()
+	{
+		if (!m_lines)
+			throw Pire::Error("pire_hip: HitSpans() follows RunLines()");
+		FetchHits();
+		return m_sel.spans;
+	}
+	size_t LineCount()
+	{
+		if (!m_lines)
+			throw Pire::Error("pire_hip: LineCount() follows RunLines()");
+		FetchHits();
+		return size_t(m_sel.lineCount);
+	}
+
 private:
+	friend struct CountedHits;
+	/* RunLines(): room for a hit on every line of 64 bytes or more, and a second call where there are more */
+	void FetchHits() { m_sel.Fetch(*this, m_regexps, m_lines ? m_len / 64 + 16 : m_n, m_lines); }
+	void CountSelectCall(const uint32_t* min, uint32_t mode, uint64_t* totals, uint64_t* hits, uint64_t* spans, uint32_t* rows, uint64_t cap,
+	                     uint64_t* count, uint64_t* lineCount)
+	{
+		static const uint64_t kNoOffsets[1] = {0};
+		if (m_lines)
+			Check(pire_hip_half_final_lines_select(m_table, m_text, m_len, uint8_t(m_delim), m_flags, min, mode, lineCount, totals, hits, spans, rows,
+			                                       cap, count, nullptr));
+		else
+			Check(pire_hip_run_half_final_select(m_table, m_text, m_n ? m_offsets : kNoOffsets, m_n, m_flags, nullptr, nullptr, nullptr, min, mode,
+			                                     totals, hits, rows, cap, count, nullptr));
+	}
 	void Execute()
 	{
 		if (m_ran)
 			return;
+		if (m_lines)
+			throw Pire::Error("pire_hip: RunLines() has hits, no results per string");
 		m_idx.assign(m_n, 0);
 		std::vector<uint8_t> fin(m_n);
 		m_results.assign(m_n * (m_regexps ? m_regexps : 1), 0);
@@ -1017,6 +1118,10 @@ private:
 	const uint64_t* m_offsets;
 	size_t m_n;
 	bool m_ran;
+	size_t m_len;                 // RunLines(): m_text is the raw buffer of m_len bytes
+	char m_delim;
+	bool m_lines;
+	CountedHits m_sel;
 	std::vector<uint32_t> m_idx, m_results;
 	std::vector<char> m_final;
 	ystring m_ownText;
@@ -1048,7 +1153,7 @@ template <class CountScanner>
 class CountingBatchRunner {
 public:
 	explicit CountingBatchRunner(const CountScanner& sc)
-	    : m_table(nullptr), m_regexps(sc.RegexpsCount()), m_flags(0), m_text(nullptr), m_offsets(nullptr), m_n(0), m_ran(false)
+	    : m_table(nullptr), m_regexps(sc.RegexpsCount()), m_flags(0), m_text(nullptr), m_offsets(nullptr), m_n(0), m_ran(false), m_len(0), m_delim('\n'), m_lines(false)
 	{
 		std::ostringstream out;
 		sc.Save(&out);                                    // LoadedScanner::Save, scanner_io.cpp:172-189 / count.cpp:1009-1018
@@ -1065,6 +1170,8 @@ public:
 		m_offsets = offsets;
 		m_n = n;
 		m_ran = false;
+		m_lines = false;
+		m_sel.fetched = false;
 		return *this;
 	}
 	CountingBatchRunner& Run(const std::vector<ystring>& strings)
@@ -1083,11 +1190,72 @@ public:
 	const std::vector<uint32_t>& Results() { Execute(); return m_results; }       // [n][RegexpsCount()]
 	const std::vector<uint32_t>& StateIndices() { Execute(); return m_idx; }      // StateIndex(State()) per string
 
+	/*
+	 * The strings whose counts reach their thresholds, without a loop on the host (pire_hip_count_select behind the scan):
+	 *     run.Begin().Run(text, offsets, n).End().Select();    // the strings in which some regexp occurred
+	 *     run.Select({3, 0, 1});                                // ... regexp 0 three times or regexp 2 once (0 = not asked)
+	 *     run.Select({3, 0, 1}, true);                          // ... and regexp 2 once
+	 *     run.Hits()        the selected strings, ascending      run.HitResults()  their result rows, [k][RegexpsCount()]
+	 *     run.HitCount()    how many                             run.Totals()      occurrences per regexp over ALL strings
+	 *     run.Begin().RunLines(raw, size).End();                // the same per line of raw, split on the device, and
+	 *     run.HitSpans()    [2 * k], [2 * k + 1]: line Hits()[k] is raw[begin, end)        run.LineCount()  lines in the buffer
+	 * After RunLines() there are hits only: Result() / Results() / StateIndices() throw.
+	 */
+	CountingBatchRunner& Select(const std::vector<uint32_t>& min = std::vector<uint32_t>(), bool all = false)
+	{
+		m_sel.Choose(min, all);
+		return *this;
+	}
+	CountingBatchRunner& RunLines(const char* raw, size_t size, char delim = '\n')
+	{
+		m_text = raw;
+		m_len = size;
+		m_delim = delim;
+		m_lines = true;
+		m_ran = false;
+		m_sel.fetched = false;
+		return *this;
+	}
+	const std::vector<uint64_t>& Hits() { FetchHits(); return m_sel.hits; }
+	const std::vector<uint32_t>& HitResults() { FetchHits(); return m_sel.rows; }
+	size_t HitCount() { FetchHits(); return size_t(m_sel.count); }
+	const std::vector<uint64_t>& Totals() { FetchHits(); return m_sel.totals; }
+	const std::vector<uint64_t>& HitSpans()
+	{
+		if (!m_lines)
+			throw Pire::Error("pire_hip: HitSpans() follows RunLines()");
+		FetchHits();
+		return m_sel.spans;
+	}
+	size_t LineCount()
+	{
+		if (!m_lines)
+			throw Pire::Error("pire_hip: LineCount() follows RunLines()");
+		FetchHits();
+		return size_t(m_sel.lineCount);
+	}
+
 private:
+	friend struct CountedHits;
+	/* RunLines(): room for a hit on every line of 64 bytes or more, and a second call where there are more */
+	void FetchHits() { m_sel.Fetch(*this, m_regexps, m_lines ? m_len / 64 + 16 : m_n, m_lines); }
+	void CountSelectCall(const uint32_t* min, uint32_t mode, uint64_t* totals, uint64_t* hits, uint64_t* spans, uint32_t* rows, uint64_t cap,
+	                     uint64_t* count, uint64_t* lineCount)
+	{
+		static const uint64_t kNoOffsets[1] = {0};
+		if (m_lines)
+			Check(pire_hip_counting_lines_select(m_table, CountingKind<CountScanner>::Value, m_text, m_len, uint8_t(m_delim), m_flags, min, mode,
+			                                     lineCount, totals, hits, spans, rows, cap, count, nullptr));
+		else
+			Check(pire_hip_counting_run_select(m_table, CountingKind<CountScanner>::Value, m_text, m_n ? m_offsets : kNoOffsets, m_n, m_flags,
+			                                   nullptr, nullptr, min, mode, totals, hits, rows, cap, count, nullptr));
+	}
 	void Execute()
 	{
 		if (m_ran)
 			return;
+		if (m_lines)
+			throw Pire::Error("pire_hip: RunLines() has hits, no results per string");
 		m_idx.assign(m_n, 0);
 		m_results.assign(m_n * (m_regexps ? m_regexps : 1), 0);
 		static const uint64_t kNoOffsets[1] = {0};
@@ -1105,6 +1273,10 @@ private:
 	const uint64_t* m_offsets;
 	size_t m_n;
 	bool m_ran;
+	size_t m_len;                 // RunLines(): m_text is the raw buffer of m_len bytes
+	char m_delim;
+	bool m_lines;
+	CountedHits m_sel;
 	std::vector<uint32_t> m_idx, m_results;
 	ystring m_ownText;
 	std::vector<uint64_t> m_ownOffsets;

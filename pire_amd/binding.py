@@ -137,6 +137,7 @@ SPLIT_TILE = 16384   # include/pire_hip.h PIRE_HIP_SPLIT_TILE_BYTES: the split p
 GATHER_TILE = 16384   # include/pire_hip.h PIRE_HIP_GATHER_TILE_BYTES: the gather's copy pass cuts out_text into tiles of this many bytes
 NO_TAIL = (1 << 32) - 1   # include/pire_hip.h PIRE_HIP_GATHER_NO_TAIL: no byte behind the gathered strings
 FIELDS_TILE = 16384   # include/pire_hip.h PIRE_HIP_FIELDS_TILE_BYTES: the fields pass cuts text into tiles of this many bytes
+COUNT_ALL = 1   # include/pire_hip.h PIRE_HIP_COUNT_ALL (in `mode`): every wanted regexp reaches its threshold
 FIELDS_REST = 1   # include/pire_hip.h PIRE_HIP_FIELDS_REST (in `mode`): the span runs to the end of the string, `cut -f k-`
 
 # every symbol include/pire_hip.h declares: (name, restype, argtypes)
@@ -237,6 +238,11 @@ ABI = [
     ("pire_hip_capture_lines_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_count_select", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_counting_run_select", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_run_half_final_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_counting_lines_select", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_half_final_lines_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_multi_create", C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
     ("pire_hip_multi_destroy", None, [C.c_void_p]),
     ("pire_hip_multi_device_count", C.c_int, [C.c_void_p]),
@@ -448,6 +454,59 @@ def fields_device(text_ptr: int, offsets_ptr: int, n: int, field: int, out_spans
     """pire_hip_fields with PIRE_HIP_RUN_ON_DEVICE: raw device addresses, only enqueues on `stream`."""
     _check(lib().pire_hip_fields(text_ptr or None, offsets_ptr or None, n, sep, field, FIELDS_REST if rest else 0, FLAG_ON_DEVICE,
                                  out_spans_ptr or None, stream or None))
+
+
+# --- from result rows to the strings that count (pire_hip_count_select)
+def _min_count(min_count, regexps):
+    if min_count is None:
+        return None
+    m = np.ascontiguousarray(min_count, dtype=np.uint32)
+    if m.shape != (regexps,):
+        raise ValueError("min_count needs one entry per regexp")
+    return m
+
+
+class _CountOut:
+    """The host arrays of one count-select call and what comes back in them."""
+
+    def __init__(self, regexps, room, hit_cap, totals, hits, hit_results):
+        self.regexps = regexps
+        self.cap = room if hit_cap is None else int(hit_cap)
+        self.totals = np.zeros(regexps, dtype=np.uint64) if totals else None
+        self.hits = np.zeros(self.cap, dtype=np.uint64) if hits else None
+        self.rows = np.zeros((self.cap, regexps), dtype=np.uint32) if hit_results else None
+        self.cnt = C.c_uint64(0)
+
+    def args(self):
+        lists = self.cap > 0
+        return (_np_ptr(self.totals) if self.regexps else None, _np_ptr(self.hits) if lists else None,
+                _np_ptr(self.rows) if lists and self.regexps else None, self.cap, C.byref(self.cnt))
+
+    def result(self):
+        count = int(self.cnt.value)
+        k = min(count, self.cap)
+        return {"totals": self.totals, "hits": None if self.hits is None else self.hits[:k],
+                "hit_results": None if self.rows is None else self.rows[:k], "count": count}
+
+
+def count_select_host(results, min_count=None, all=False, hit_cap: Optional[int] = None, totals=True, hits=True, hit_results=True):
+    """pire_hip_count_select on a host array results[n, regexps]: {"totals" u64[R], "hits" u64[k], "hit_results" u32[k, R],
+    "count"}, k = min(count, hit_cap); what was not asked for is None.  hit_cap None = room for every string."""
+    results = np.ascontiguousarray(results, dtype=np.uint32)
+    n, regexps = results.shape
+    m = _min_count(min_count, regexps)
+    out = _CountOut(regexps, n, hit_cap, totals, hits, hit_results)
+    _check(lib().pire_hip_count_select(results.ctypes.data if results.size else None, n, regexps, _np_ptr(m), COUNT_ALL if all else 0, 0,
+                                       *out.args(), None))
+    return out.result()
+
+
+def count_select_device(results_ptr: int, n: int, regexps: int, out_hit_count_ptr: int, min_count_ptr=0, all=False, out_totals_ptr=0,
+                        out_hits_ptr=0, out_hit_results_ptr=0, hit_cap=0, stream: int = 0):
+    """pire_hip_count_select with PIRE_HIP_RUN_ON_DEVICE: raw device addresses, only enqueues on `stream`."""
+    _check(lib().pire_hip_count_select(results_ptr or None, n, regexps, min_count_ptr or None, COUNT_ALL if all else 0, FLAG_ON_DEVICE,
+                                       out_totals_ptr or None, out_hits_ptr or None, out_hit_results_ptr or None, hit_cap,
+                                       out_hit_count_ptr or None, stream or None))
 
 
 # --- from capture positions to byte ranges (pire_hip_capture_select)
@@ -1067,6 +1126,61 @@ class Table:
                                              out_idx_ptr or None, out_final_ptr or None, out_results_ptr or None,
                                              stream or None))
 
+    # --- the strings that count (pire_hip_run_half_final_select, pire_hip_half_final_lines_select)
+    def run_half_final_select(self, text, offsets, flags=FLAG_BEGIN | FLAG_END, min_count=None, all=False, hit_cap: Optional[int] = None,
+                              results=True):
+        """pire_hip_run_half_final_select on host strings: what count_select_host returns and, with results, {"idx", "final",
+        "results"}; without, the library keeps the rows to itself."""
+        text = _raw_bytes(text)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n, regexps = len(offsets) - 1, self.RegexpsCount
+        idx, fin = (np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint8)) if results else (None, None)
+        res = np.zeros((n, max(regexps, 1)), dtype=np.uint32) if results else None
+        out = _CountOut(regexps, n, hit_cap, True, True, True)
+        _check(lib().pire_hip_run_half_final_select(self._h, text.ctypes.data if text.size else None, offsets.ctypes.data, n,
+                                                    flags & ~FLAG_ON_DEVICE, _np_ptr(idx), _np_ptr(fin), _np_ptr(res),
+                                                    _np_ptr(_min_count(min_count, regexps)), COUNT_ALL if all else 0, *out.args(), None))
+        got = out.result()
+        if results:
+            got.update(idx=idx, final=fin, results=res[:, :regexps])
+        return got
+
+    def run_half_final_select_device(self, text_ptr: int, offsets_ptr: int, n: int, flags, out_hit_count_ptr: int, min_count_ptr=0,
+                                     all=False, out_idx_ptr=0, out_final_ptr=0, out_results_ptr=0, out_totals_ptr=0, out_hits_ptr=0,
+                                     out_hit_results_ptr=0, hit_cap=0, stream: int = 0):
+        """pire_hip_run_half_final_select on device pointers: only enqueues on `stream`."""
+        _check(lib().pire_hip_run_half_final_select(self._h, text_ptr or None, offsets_ptr or None, n, flags | FLAG_ON_DEVICE,
+                                                    out_idx_ptr or None, out_final_ptr or None, out_results_ptr or None,
+                                                    min_count_ptr or None, COUNT_ALL if all else 0, out_totals_ptr or None,
+                                                    out_hits_ptr or None, out_hit_results_ptr or None, hit_cap,
+                                                    out_hit_count_ptr or None, stream or None))
+
+    def half_final_lines_select_host(self, raw, delim: int = 10, flags=FLAG_BEGIN | FLAG_END, min_count=None, all=False, hit_cap=None):
+        """pire_hip_half_final_lines_select on a host buffer: what count_select_host returns and {"lines", "spans"}; hit_cap None =
+        room for a hit on every line (no more lines than bytes)."""
+        raw = _raw_bytes(raw)
+        regexps = self.RegexpsCount
+        out = _CountOut(regexps, raw.size, hit_cap, True, True, True)
+        spans = np.zeros((out.cap, 2), dtype=np.uint64)
+        lines = C.c_uint64(0)
+        a = out.args()
+        _check(lib().pire_hip_half_final_lines_select(self._h, raw.ctypes.data if raw.size else None, raw.size, delim,
+                                                      flags & ~FLAG_ON_DEVICE, _np_ptr(_min_count(min_count, regexps)),
+                                                      COUNT_ALL if all else 0, C.byref(lines), a[0], a[1],
+                                                      spans.ctypes.data if out.cap else None, a[2], a[3], a[4], None))
+        got = out.result()
+        got.update(lines=int(lines.value), spans=spans[:len(got["hits"])])
+        return got
+
+    def half_final_lines_select_device(self, raw_ptr: int, size: int, flags, out_line_count_ptr: int, out_hit_count_ptr: int,
+                                       delim: int = 10, min_count_ptr=0, all=False, out_totals_ptr=0, out_hits_ptr=0, out_hit_spans_ptr=0,
+                                       out_hit_results_ptr=0, hit_cap=0, stream: int = 0):
+        """pire_hip_half_final_lines_select on device pointers (synchronises `stream` once, as run_lines_select_device does)."""
+        _check(lib().pire_hip_half_final_lines_select(self._h, raw_ptr or None, size, delim, flags | FLAG_ON_DEVICE, min_count_ptr or None,
+                                                      COUNT_ALL if all else 0, out_line_count_ptr or None, out_totals_ptr or None,
+                                                      out_hits_ptr or None, out_hit_spans_ptr or None, out_hit_results_ptr or None,
+                                                      hit_cap, out_hit_count_ptr or None, stream or None))
+
     def run_half_final_device_host_offsets(self, text_ptr: int, offsets: np.ndarray, flags, out_idx_ptr=0,
                                            out_final_ptr=0, out_results_ptr=0, stream: int = 0):
         """Resident text, offsets on the host (PIRE_HIP_RUN_HOST_OFFSETS); outputs on the device."""
@@ -1312,6 +1426,60 @@ class CountingTable:
                                                    out_line_count_ptr or None, out_hits_ptr or None, out_spans_ptr or None, hit_cap,
                                                    out_hit_count_ptr or None, out_text_ptr or None, text_cap,
                                                    out_offsets_ptr or None, out_bytes_ptr or None, stream or None))
+
+    # --- the strings that count (pire_hip_counting_run_select, pire_hip_counting_lines_select)
+    def run_select(self, text, offsets, flags=FLAG_BEGIN | FLAG_END, min_count=None, all=False, hit_cap: Optional[int] = None,
+                              results=True):
+        """pire_hip_counting_run_select on host strings: what count_select_host returns and, with results, {"idx", "results"}; without, the library keeps the rows to itself."""
+        text = _raw_bytes(text)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n, regexps = len(offsets) - 1, self.RegexpsCount
+        idx = np.empty(n, dtype=np.uint32) if results else None
+        res = np.zeros((n, max(regexps, 1)), dtype=np.uint32) if results else None
+        out = _CountOut(regexps, n, hit_cap, True, True, True)
+        _check(lib().pire_hip_counting_run_select(self._h, self.kind, text.ctypes.data if text.size else None, offsets.ctypes.data, n,
+                                                    flags & ~FLAG_ON_DEVICE, _np_ptr(idx), _np_ptr(res),
+                                                    _np_ptr(_min_count(min_count, regexps)), COUNT_ALL if all else 0, *out.args(), None))
+        got = out.result()
+        if results:
+            got.update(idx=idx, results=res[:, :regexps])
+        return got
+
+    def run_select_device(self, text_ptr: int, offsets_ptr: int, n: int, flags, out_hit_count_ptr: int, min_count_ptr=0,
+                                     all=False, out_idx_ptr=0, out_results_ptr=0, out_totals_ptr=0, out_hits_ptr=0,
+                                     out_hit_results_ptr=0, hit_cap=0, stream: int = 0):
+        """pire_hip_counting_run_select on device pointers: only enqueues on `stream`."""
+        _check(lib().pire_hip_counting_run_select(self._h, self.kind, text_ptr or None, offsets_ptr or None, n, flags | FLAG_ON_DEVICE,
+                                                    out_idx_ptr or None, out_results_ptr or None,
+                                                    min_count_ptr or None, COUNT_ALL if all else 0, out_totals_ptr or None,
+                                                    out_hits_ptr or None, out_hit_results_ptr or None, hit_cap,
+                                                    out_hit_count_ptr or None, stream or None))
+
+    def lines_select_host(self, raw, delim: int = 10, flags=FLAG_BEGIN | FLAG_END, min_count=None, all=False, hit_cap=None):
+        """pire_hip_counting_lines_select on a host buffer: what count_select_host returns and {"lines", "spans"}; hit_cap None =
+        room for a hit on every line (no more lines than bytes)."""
+        raw = _raw_bytes(raw)
+        regexps = self.RegexpsCount
+        out = _CountOut(regexps, raw.size, hit_cap, True, True, True)
+        spans = np.zeros((out.cap, 2), dtype=np.uint64)
+        lines = C.c_uint64(0)
+        a = out.args()
+        _check(lib().pire_hip_counting_lines_select(self._h, self.kind, raw.ctypes.data if raw.size else None, raw.size, delim,
+                                                      flags & ~FLAG_ON_DEVICE, _np_ptr(_min_count(min_count, regexps)),
+                                                      COUNT_ALL if all else 0, C.byref(lines), a[0], a[1],
+                                                      spans.ctypes.data if out.cap else None, a[2], a[3], a[4], None))
+        got = out.result()
+        got.update(lines=int(lines.value), spans=spans[:len(got["hits"])])
+        return got
+
+    def lines_select_device(self, raw_ptr: int, size: int, flags, out_line_count_ptr: int, out_hit_count_ptr: int,
+                                       delim: int = 10, min_count_ptr=0, all=False, out_totals_ptr=0, out_hits_ptr=0, out_hit_spans_ptr=0,
+                                       out_hit_results_ptr=0, hit_cap=0, stream: int = 0):
+        """pire_hip_counting_lines_select on device pointers (synchronises `stream` once, as run_lines_select_device does)."""
+        _check(lib().pire_hip_counting_lines_select(self._h, self.kind, raw_ptr or None, size, delim, flags | FLAG_ON_DEVICE, min_count_ptr or None,
+                                                      COUNT_ALL if all else 0, out_line_count_ptr or None, out_totals_ptr or None,
+                                                      out_hits_ptr or None, out_hit_spans_ptr or None, out_hit_results_ptr or None,
+                                                      hit_cap, out_hit_count_ptr or None, stream or None))
 
     def run_device(self, text_ptr: int, offsets_ptr: int, n: int, flags, out_idx_ptr=0, out_results_ptr=0, stream: int = 0):
         _check(lib().pire_hip_counting_run(self._h, self.kind, text_ptr or None, offsets_ptr or None, n,

@@ -2763,16 +2763,25 @@ int SelfTestHalfFinal(pire_hip_table* t, uint32_t flags, hipStream_t stream)
 	return PIRE_HIP_OK;
 }
 
-}  // namespace
-
-int pire_hip_run_half_final(pire_hip_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
-                            uint32_t* out_state_idx, uint8_t* out_final, uint32_t* out_results, void* streamPtr)
-try {
-	if (!t || (n && (!offsets || !out_results))) {
-		SetError("null argument");
+// sel == nullptr: pire_hip_run_half_final.  Else out_results may be null, and the pass of count_select.hip follows the scan on
+// the same stream, whichever way the counts were taken (pire_hip_run_half_final_select, pire_hip_half_final_lines_select).
+int HalfFinalRunImpl(const char* who, pire_hip_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
+                     uint32_t* out_state_idx, uint8_t* out_final, uint32_t* out_results, const CountSelectOut* sel, hipStream_t stream)
+{
+	if (!t || (n && (!offsets || (!sel && !out_results)))) {
+		SetError(sel ? std::string(who) + ": null argument" : std::string("null argument"));
 		return PIRE_HIP_EINVAL;
 	}
-	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
+	std::optional<CountSelectStage> pass;
+	if (sel) {
+		const uint32_t regexps = HostRegexps(t);
+		if (int rc = CountSelectArgsInvalid(who, n, regexps, true, *sel))
+			return rc;
+		pass.emplace(*sel, regexps, onDevice);
+		if (n == 0)
+			return pass->Empty(stream);
+	}
 	if (n)
 		if (int rc = SelfTestHalfFinal(t, flags, stream))   // first use on this device: every kernel of this entry point, known answers
 			return rc;
@@ -2841,13 +2850,26 @@ try {
 		}
 		return LaunchHalfFinal(p, dResults, stream, exactOnly ? nullptr : NextWorkSlot(t, p));
 	};
-	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
 	BatchIO io(stream, onDevice);
 	uint32_t* dRes = nullptr;
 	int rc;
-	if ((rc = io.Text(text, offsets, n, 0, 0, &p.text, &p.offsets)) || (rc = io.Result(out_state_idx, size_t(n), size_t(n), &p.outIdx)) ||
-	    (rc = io.Result(out_final, size_t(n), size_t(n), &p.outFinal)) ||
-	    (rc = io.Result(out_results, size_t(n) * std::max<uint32_t>(R, 1), size_t(n) * R, &dRes)) || (rc = io.Ready()))
+	if ((rc = io.Text(text, offsets, n, 0, 0, &p.text, &p.offsets)) || (pass && (rc = pass->In(io))) ||
+	    (rc = io.Result(out_state_idx, size_t(n), size_t(n), &p.outIdx)) || (rc = io.Result(out_final, size_t(n), size_t(n), &p.outFinal)) ||
+	    (rc = io.Result(out_results, size_t(n) * std::max<uint32_t>(R, 1), size_t(n) * R, &dRes)))
+		return rc;
+	// the pass behind the scan: the rows it reads and the caller has no array for live in scratch (a host-pointer call's
+	// Result() has allocated them already)
+	StreamScratch ownResults(stream);
+	if (pass) {
+		if (!dRes) {
+			if ((rc = ownResults.Alloc(size_t(n) * std::max<uint32_t>(R, 1) * 4, "hipMallocAsync(half-final results)")))
+				return rc;
+			dRes = ownResults.as<uint32_t>();
+		}
+		if ((rc = pass->Results(io, n)))
+			return rc;
+	}
+	if ((rc = io.Ready()))
 		return rc;
 	// the lengths on the host (its own arrays, or PIRE_HIP_RUN_HOST_OFFSETS: resident text, see pire_hip_run): the
 	// segmented scan first
@@ -2866,7 +2888,121 @@ try {
 		});
 	else
 		rc = count();
-	return rc ? rc : io.Finish();
+	if (rc || (pass && (rc = pass->Launch(dRes, n, stream))) || (rc = io.Finish()))
+		return rc;
+	return pass ? pass->Back() : PIRE_HIP_OK;
+}
+
+}  // namespace
+
+int pire_hip_run_half_final(pire_hip_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
+                            uint32_t* out_state_idx, uint8_t* out_final, uint32_t* out_results, void* stream)
+try {
+	return HalfFinalRunImpl("pire_hip_run_half_final", t, text, offsets, n, flags, out_state_idx, out_final, out_results, nullptr,
+	                        static_cast<hipStream_t>(stream));
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_run_half_final_select(pire_hip_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
+                                   uint32_t* out_state_idx, uint8_t* out_final, uint32_t* out_results, const uint32_t* min_count,
+                                   uint32_t mode, uint64_t* out_totals, uint64_t* out_hits, uint32_t* out_hit_results, uint64_t hit_cap,
+                                   uint64_t* out_hit_count, void* stream)
+try {
+	const CountSelectOut sel = {min_count, mode, out_totals, out_hits, out_hit_results, hit_cap, out_hit_count};
+	return HalfFinalRunImpl("pire_hip_run_half_final_select", t, text, offsets, n, flags, out_state_idx, out_final, out_results, &sel,
+	                        static_cast<hipStream_t>(stream));
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+// ---- raw bytes in, the lines that count out (split.hip, counting.hip, count_select.hip) -------------------------------------
+// The frame around a counting scan: the scan on the lines with the rows in scratch, the pass, the whole lines of the hits as
+// byte ranges of raw.  `scan`: the run + pass call on device pointers (the line batch, the pass's arguments on the device).
+namespace {
+
+int CountLinesImpl(const char* who, uint32_t regexps, const void* raw, uint64_t size, uint32_t delim, uint32_t flags, const CountSelectOut& o,
+                   uint64_t* out_line_count, uint64_t* out_hit_spans, void* streamPtr,
+                   const std::function<int(const LinesFrame&, const CountSelectOut&)>& scan)
+{
+	if (int rc = SplitArgsInvalid(who, raw, size, delim, out_line_count, "out_line_count"))
+		return rc;
+	if (int rc = CountSelectArgsInvalid(who, 0, regexps, true, o))
+		return rc;
+	if (out_hit_spans && !o.outHits) {
+		SetError(std::string(who) + ": out_hit_spans without out_hits");
+		return PIRE_HIP_EINVAL;
+	}
+	LinesFrame f(who, raw, size, delim, flags, nullptr, streamPtr);
+	if (f.HostEdge(out_line_count))
+		return CountSelectStage(o, regexps, false).Empty(f.stream);
+	const uint32_t* dMin = o.minCount;
+	uint64_t* dTotals = o.outTotals;
+	uint32_t* dHitResults = nullptr;
+	if (int rc = f.Open())
+		return rc;
+	if (o.minCount)
+		if (int rc = f.io.In(o.minCount, size_t(regexps), &dMin))
+			return rc;
+	if (int rc = f.Split(out_line_count, o.outHitCount, 1, o.hitCap, true))
+		return rc;
+	if (int rc = f.Lists(o.outHits, out_hit_spans))
+		return rc;
+	if (o.outTotals && regexps)
+		if (int rc = f.io.Result(o.outTotals, size_t(regexps), size_t(regexps), &dTotals))
+			return rc;
+	if (o.outHitResults && f.cap && regexps)
+		if (int rc = f.io.Result(o.outHitResults, size_t(f.cap) * regexps, 0, &dHitResults))
+			return rc;
+	// (no lines: the pass itself zeroes the count and the totals)
+	const CountSelectOut onLines = {dMin, o.mode, dTotals, f.dHits, dHitResults, f.dHits || dHitResults ? f.cap : 0, f.dCounts};
+	if (int rc = scan(f, onLines))
+		return rc;
+	if (f.dSpans && f.n)   // (the whole line)
+		if (int rc = LaunchHitSpans(f.dHits, f.dCounts, 1, f.cap, f.cap, f.LineOffsets(), f.dSpans, f.stream, "split spans launch"))
+			return rc;
+	if (int rc = f.Close("hipMemcpy(hits)"))
+		return rc;
+	if (f.onDevice || !dHitResults)
+		return PIRE_HIP_OK;
+	const uint64_t written = std::min(*o.outHitCount, f.cap);
+	const hipError_t e = written ? hipMemcpy(o.outHitResults, dHitResults, size_t(written) * regexps * 4, hipMemcpyDeviceToHost) : hipSuccess;
+	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(hits)");
+}
+
+}  // namespace
+
+int pire_hip_counting_lines_select(pire_hip_counting_table* t, int kind, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
+                                   const uint32_t* min_count, uint32_t mode, uint64_t* out_line_count, uint64_t* out_totals,
+                                   uint64_t* out_hits, uint64_t* out_hit_spans, uint32_t* out_hit_results, uint64_t hit_cap,
+                                   uint64_t* out_hit_count, void* stream)
+try {
+	const char* who = "pire_hip_counting_lines_select";
+	pire_hip_counting_info info;
+	if (!t || pire_hip_counting_table_get_info(t, &info) != PIRE_HIP_OK)
+		return GatherRefuse(who, "null table");
+	const CountSelectOut o = {min_count, mode, out_totals, out_hits, out_hit_results, hit_cap, out_hit_count};
+	return CountLinesImpl(who, info.regexps, raw, size, delim, flags, o, out_line_count, out_hit_spans, stream,
+	                      [&](const LinesFrame& f, const CountSelectOut& onLines) {
+		                      return CountingRunImpl(who, t, kind, f.Text(), f.Offsets(), f.n, f.RunFlags(), nullptr, nullptr, &onLines, f.stream);
+	                      });
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_half_final_lines_select(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
+                                     const uint32_t* min_count, uint32_t mode, uint64_t* out_line_count, uint64_t* out_totals,
+                                     uint64_t* out_hits, uint64_t* out_hit_spans, uint32_t* out_hit_results, uint64_t hit_cap,
+                                     uint64_t* out_hit_count, void* stream)
+try {
+	const char* who = "pire_hip_half_final_lines_select";
+	if (!t)
+		return GatherRefuse(who, "null table");
+	const CountSelectOut o = {min_count, mode, out_totals, out_hits, out_hit_results, hit_cap, out_hit_count};
+	return CountLinesImpl(who, HostRegexps(t), raw, size, delim, flags, o, out_line_count, out_hit_spans, stream,
+	                      [&](const LinesFrame& f, const CountSelectOut& onLines) {
+		                      return HalfFinalRunImpl(who, t, f.Text(), f.Offsets(), f.n, f.RunFlags(), nullptr, nullptr, nullptr, &onLines, f.stream);
+	                      });
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }

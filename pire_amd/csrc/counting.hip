@@ -2034,11 +2034,17 @@ int SelfTestCapture(pire_hip_counting_table* t, uint32_t flags, hipStream_t stre
 
 }  // namespace
 
-int pire_hip_counting_run(pire_hip_counting_table* t, int kind, const void* text, const uint64_t* offsets, uint64_t n,
-                          uint32_t flags, uint32_t* out_state_idx, uint32_t* out_results, void* streamPtr)
-try {
-	if (!t || (n && (!offsets || !out_results)) || (kind != PIRE_HIP_COUNTING_BASIC && kind != PIRE_HIP_COUNTING_ADVANCED && kind != PIRE_HIP_COUNTING_NOGLUELIMIT)) {
-		SetError("bad argument");
+}  // extern "C"
+
+namespace pirehip {
+
+// sel == nullptr: pire_hip_counting_run.  Else out_results may be null, and the pass of count_select.hip follows the scan on
+// the same stream, whichever counting kernel LaunchCounting picks (pire_hip_counting_run_select, pire_hip_counting_lines_select).
+int CountingRunImpl(const char* who, pire_hip_counting_table* t, int kind, const void* text, const uint64_t* offsets, uint64_t n,
+                    uint32_t flags, uint32_t* out_state_idx, uint32_t* out_results, const CountSelectOut* sel, hipStream_t stream)
+{
+	if (!t || (n && (!offsets || (!sel && !out_results))) || (kind != PIRE_HIP_COUNTING_BASIC && kind != PIRE_HIP_COUNTING_ADVANCED && kind != PIRE_HIP_COUNTING_NOGLUELIMIT)) {
+		SetError(sel ? std::string(who) + ": bad argument" : std::string("bad argument"));
 		return PIRE_HIP_EINVAL;
 	}
 	// the serialised form decides between the classes: a type-5 blob is a NoGlueLimitCountingScanner and nothing
@@ -2052,9 +2058,15 @@ try {
 			return PIRE_HIP_EINVAL;
 		}
 	}
+	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
+	std::optional<CountSelectStage> pass;
+	if (sel) {
+		if (int rc = CountSelectArgsInvalid(who, n, t->host.regexps, true, *sel))
+			return rc;
+		pass.emplace(*sel, t->host.regexps, onDevice);
+	}
 	if (n == 0)
-		return PIRE_HIP_OK;
-	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+		return pass ? pass->Empty(stream) : PIRE_HIP_OK;
 	if (int rc = SelfTestCounting(t, kind, flags, stream))   // first use on this device: every kernel of this entry point, known answers (selftest.h)
 		return rc;
 	CountingDevice image;
@@ -2082,14 +2094,53 @@ try {
 	// PIRE_HIP_RUN_GENERIC keeps the 32-bit kernel alone (the tests compare the two)
 	const uint32_t nreg = (flags & PIRE_HIP_RUN_GENERIC) ? 0 : t->host.nreg;
 	const uint32_t R = std::max<uint32_t>(t->host.regexps, 1);
-	BatchIO io(stream, (flags & PIRE_HIP_RUN_ON_DEVICE) != 0);
+	BatchIO io(stream, onDevice);
 	int rc;
-	if ((rc = io.Text(text, offsets, n, 0, 0, &p.text, &p.offsets)) || (rc = io.Result(out_state_idx, n, n, &p.outIdx)) ||
-	    (rc = io.Result(out_results, n * R, n * t->host.regexps, &p.outResults)) || (rc = io.Ready()))
+	if ((rc = io.Text(text, offsets, n, 0, 0, &p.text, &p.offsets)) || (pass && (rc = pass->In(io))) ||
+	    (rc = io.Result(out_state_idx, n, n, &p.outIdx)) || (rc = io.Result(out_results, n * R, n * t->host.regexps, &p.outResults)))
 		return rc;
-	if ((rc = LaunchCounting(p, kind, stream, nreg)))
+	// the pass behind the scan: the rows it reads and the caller has no array for live in scratch (a host-pointer call's
+	// Result() has allocated them already)
+	StreamScratch ownResults(stream);
+	if (pass) {
+		if (!p.outResults) {
+			if ((rc = ownResults.Alloc(size_t(n) * R * 4, "hipMallocAsync(counting results)")))
+				return rc;
+			p.outResults = ownResults.as<uint32_t>();
+		}
+		if ((rc = pass->Results(io, n)))
+			return rc;
+	}
+	if ((rc = io.Ready()) || (rc = LaunchCounting(p, kind, stream, nreg)))
 		return rc;
-	return io.Finish();
+	if (pass && (rc = pass->Launch(p.outResults, n, stream)))
+		return rc;
+	if ((rc = io.Finish()))
+		return rc;
+	return pass ? pass->Back() : PIRE_HIP_OK;
+}
+
+}  // namespace pirehip
+
+extern "C" {
+
+int pire_hip_counting_run(pire_hip_counting_table* t, int kind, const void* text, const uint64_t* offsets, uint64_t n,
+                          uint32_t flags, uint32_t* out_state_idx, uint32_t* out_results, void* stream)
+try {
+	return CountingRunImpl("pire_hip_counting_run", t, kind, text, offsets, n, flags, out_state_idx, out_results, nullptr,
+	                       static_cast<hipStream_t>(stream));
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_counting_run_select(pire_hip_counting_table* t, int kind, const void* text, const uint64_t* offsets, uint64_t n,
+                                 uint32_t flags, uint32_t* out_state_idx, uint32_t* out_results, const uint32_t* min_count, uint32_t mode,
+                                 uint64_t* out_totals, uint64_t* out_hits, uint32_t* out_hit_results, uint64_t hit_cap,
+                                 uint64_t* out_hit_count, void* stream)
+try {
+	const CountSelectOut sel = {min_count, mode, out_totals, out_hits, out_hit_results, hit_cap, out_hit_count};
+	return CountingRunImpl("pire_hip_counting_run_select", t, kind, text, offsets, n, flags, out_state_idx, out_results, &sel,
+	                       static_cast<hipStream_t>(stream));
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }

@@ -1085,6 +1085,47 @@ int LaunchCaptureSelect(const uint64_t* offsets, uint64_t n, bool beginMark, con
 // What pire_hip_capture_select refuses of its outputs before any device is touched (haveList: the hits have somewhere to go)
 int CaptureSelectOutputsInvalid(const char* who, uint64_t n, int needFinal, bool haveFinal, bool haveList, uint64_t hitCap,
                                 const void* outHitCount);
+// count_select.hip: from result rows to a compacted, ascending list of the strings whose counters reach their thresholds, and
+// the occurrences of every regexp over the batch (pire_hip_count_select).  Device pointers only, three to four kernels
+// enqueued on `stream`, scratch from the stream-ordered allocator: the compaction's, and regexps * ceil(n / 1024) * 8 bytes of
+// tile sums where outTotals is not null.  n == 0 or regexps == 0: the count (and the totals) zeroed on the stream.
+int LaunchCountSelect(const uint32_t* results, uint64_t n, uint32_t regexps, const uint32_t* minCount, uint32_t mode, uint64_t* outTotals,
+                      uint64_t* outHits, uint32_t* outHitResults, uint64_t hitCap, uint64_t* outHitCount, hipStream_t stream);
+// The pass's own arguments, as the caller of an entry point gave them
+struct CountSelectOut {
+	const uint32_t* minCount;
+	uint32_t mode;
+	uint64_t* outTotals;
+	uint64_t* outHits;
+	uint32_t* outHitResults;
+	uint64_t hitCap;
+	uint64_t* outHitCount;
+};
+// What pire_hip_count_select refuses before any device is touched, in `who`'s name (haveResults: there are rows to read)
+int CountSelectArgsInvalid(const char* who, uint64_t n, uint32_t regexps, bool haveResults, const CountSelectOut& o);
+// The pass inside ONE call of an entry point (pire_hip_count_select itself, and the scans it follows on their stream), on
+// whichever side the caller's pointers live.  Order: Empty() instead of everything where there is nothing to read; else
+// In() with the call's inputs, Results() with its result arrays, io.Ready(), the scan, Launch(), io.Finish(), Back().
+struct CountSelectStage {
+	const CountSelectOut o;
+	const uint32_t regexps;
+	const bool onDevice;
+	const uint32_t* dMin = nullptr;
+	uint64_t *dCount = nullptr, *dTotals = nullptr, *dHits = nullptr;
+	uint32_t* dHitResults = nullptr;
+	uint64_t cap = 0, count = 0;   // host pointers: no list is staged longer than the strings are many; the count comes back here first
+	CountSelectStage(const CountSelectOut& o_, uint32_t regexps_, bool onDevice_) : o(o_), regexps(regexps_), onDevice(onDevice_) {}
+	int Empty(hipStream_t stream);   // no strings or no regexps: zeros -- host pointers: no device is touched
+	int In(BatchIO& io);             // min_count
+	int Results(BatchIO& io, uint64_t n);
+	int Launch(const uint32_t* results, uint64_t n, hipStream_t stream);
+	int Back();                      // host pointers: the count, and the lists only as far as they were written
+};
+// counting.hip: pire_hip_counting_run, and behind it -- where sel is not null -- the pass above on the same stream, on the
+// staged copy of a host-pointer call; outResults may then be null (the rows live in stream-ordered scratch).  `who` names the
+// entry point in what is refused.
+int CountingRunImpl(const char* who, pire_hip_counting_table* t, int kind, const void* text, const uint64_t* offsets, uint64_t n,
+                    uint32_t flags, uint32_t* outIdx, uint32_t* outResults, const CountSelectOut* sel, hipStream_t stream);
 // counting.hip: pire_hip_capture_run, and behind it -- where sel is not null -- the pass above on the same stream, on the
 // staged copy of a host-pointer call.  The position and Final arrays the pass needs and the caller has no room for live in
 // stream-ordered scratch.

@@ -1,0 +1,35 @@
+"""Select() / RunLines() of HalfFinalBatchRunner and CountingBatchRunner (include/pire_hip/batch_runner.hpp), compiled against
+the UNMODIFIED reference headers (tests/cpp/count_select_shim_test.cpp) the way tests/test_fields_shim.py compiles its program,
+and run without a GPU: it checks what is decided before a device is touched -- refusals rethrown as Pire::Error, empty
+batches.  (What the runners answer on a device is tests/test_count_select.py's, through the same C entry points.)"""
+import os
+import subprocess
+
+import pytest
+
+from oracle import binding as ob
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REF_DIR = os.path.join(ROOT, "oracle", "_ref")
+BIN = os.path.join(REF_DIR, "bin", "count_select_shim_test")
+REF_PRESENT = os.path.exists(os.path.join(ob.REFERENCE_ROOT, "pire", "run.h"))
+
+
+@pytest.mark.skipif(not REF_PRESENT, reason="the reference tree is not present: nothing to compile against")
+def test_count_select_shim_compiles_against_reference_headers_and_runs_without_a_device():
+    """tests/cpp/count_select_shim_test.cpp with the flags oracle/Makefile gives tests/cpp/shim_test.cpp, next to it in oracle/_ref/bin"""
+    ob.build()
+    ref = ob.REFERENCE_ROOT
+    r = subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "ref"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                       text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-3000:]
+    os.makedirs(os.path.dirname(BIN), exist_ok=True)
+    cmd = [os.environ.get("CXX", "g++"), "-std=c++14", "-O1", "-DPIRE_NO_CONFIG", "-w", "-include", "limits", "-I" + ref,
+           "-I" + os.path.join(ref, "pire"), "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "count_select_shim_test.cpp"),
+           "-o", BIN, "-L" + REF_DIR, "-lpire_ref", "-Wl,-rpath,$ORIGIN/..", "-L" + os.path.join(ROOT, "pire_amd"), "-lpire_hip",
+           "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,$ORIGIN/../../../pire_amd", "-Wl,-rpath,/opt/rocm/lib"]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-3000:]
+    r = subprocess.run([BIN], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-3000:]
+    assert "OK(count select shim" in r.stdout
