@@ -18,10 +18,22 @@
  *
  * Errors: the C ABI's negative codes are re-thrown as Pire::Error (pire/stub/stl.h:213-217), the reference's own
  * exception type for this library.
+ *
+ * The map.  What the runners have in common has one definition each:
+ *     SavedBlob()       a scanner's Save() form, for every *_table_create            Table, CountedBatchRunner's two, Capture, Slow
+ *     OwnedStrings      a std::vector<ystring> as one text and offsets; OffsetsOr(): the {0} that stands in for the offsets of no
+ *                       strings                                                      every Run(vector), every call that takes offsets
+ *     GrowAndRetry()    one call at a first capacity, one more where the answer did not fit       BatchRunner's lines, text and route
+ *                       forms, CountedBatchRunner, CaptureBatchRunner
+ *     Table             the device table, State <-> StateIndex (ToStates), Regexps()              BatchRunner, Multi-, PairBatchRunner
+ *     CountedBatchRunner   all of HalfFinalBatchRunner and CountingBatchRunner but their table and their three C calls
+ * Which C calls these make, in which order and with which arguments, is recorded: tests/cpp/shim_calls_test.cpp,
+ * tests/cpp/shim_calls.expected.txt.
  */
 #ifndef PIRE_HIP_BATCH_RUNNER_HPP
 #define PIRE_HIP_BATCH_RUNNER_HPP
 
+#include <algorithm>
 #include <cstdint>
 #include <sstream>
 #include <string>
@@ -38,6 +50,58 @@ inline void Check(int rc)
 {
 	if (rc < 0)
 		throw Pire::Error(std::string("pire_hip: ") + pire_hip_last_error());
+}
+
+/* The PUBLIC hand-off of every scanner: its Save() form (Scanner::Save, multi.h:307, 557-573; NonrelocScanner saves as
+ * Relocatable, 604-608; SimpleScanner, scanner_io.cpp:35-49; SlowScanner, 71-111; LoadedScanner, 172-189 / count.cpp:1009-1018) */
+template <class AnyScanner>
+std::string SavedBlob(const AnyScanner& sc)
+{
+	std::ostringstream out;
+	sc.Save(&out);
+	return out.str();
+}
+
+/* A caller's std::vector<ystring> as the C calls take strings: one text, n + 1 offsets. */
+class OwnedStrings {
+public:
+	void Assign(const std::vector<ystring>& strings)
+	{
+		m_text.clear();
+		m_offsets.assign(1, 0);
+		for (size_t i = 0; i < strings.size(); ++i) {
+			m_text.append(strings[i]);
+			m_offsets.push_back(m_text.size());
+		}
+	}
+	const char* Text() const { return m_text.data(); }
+	const uint64_t* Offsets() const { return m_offsets.data(); }
+
+	/* The offsets of a batch of host strings: with no strings the caller need not have any. */
+	static const uint64_t* OffsetsOr(const uint64_t* offsets, size_t n)
+	{
+		static const uint64_t kNoOffsets[1] = {0};
+		return n ? offsets : kNoOffsets;
+	}
+
+private:
+	ystring m_text;
+	std::vector<uint64_t> m_offsets;
+};
+
+/*
+ * One call with room for `first` answers, and a second one where there were more: call(cap) makes the call with room for cap
+ * and returns how many it needed (a call with that much room fits).  Returns the capacity of the call that fit.
+ */
+template <class Call>
+size_t GrowAndRetry(size_t first, Call call)
+{
+	for (size_t cap = first;;) {
+		const size_t needed = call(cap);
+		if (needed <= cap)
+			return cap;
+		cap = needed;
+	}
 }
 
 /* Bytes between the State values of consecutive StateIndex numbers, from public API only. */
@@ -67,13 +131,9 @@ public:
 	explicit Table(const Scanner& sc)
 	    : m_table(nullptr)
 	{
-		// the PUBLIC hand-off: Scanner::Save (multi.h:307, 557-573); NonrelocScanner saves as Relocatable (604-608);
-		// SimpleScanner::Save (scanner_io.cpp:35-49)
 		if (pire_hip_abi_version() != PIRE_HIP_ABI_VERSION)   // structs of this header vs. the loaded library's: refuse, do not guess
 			throw Pire::Error("pire_hip: libpire_hip.so was built with another ABI version than this header");
-		std::ostringstream out;
-		sc.Save(&out);
-		const std::string blob = out.str();
+		const std::string blob = SavedBlob(sc);
 		Check(pire_hip_table_create(blob.data(), blob.size(), &m_table));
 
 		// State <-> StateIndex geometry of THIS host scanner, public API only
@@ -108,6 +168,20 @@ public:
 	}
 	typename Scanner::State ToState(uint32_t idx) const { return m_base + size_t(idx) * m_stride; }
 	uint32_t ToIndex(typename Scanner::State st) const { return uint32_t((st - m_base) / m_stride); }
+	/* What a scan leaves per string, as the reference has it: StateIndex -> State */
+	void ToStates(const std::vector<uint32_t>& idx, std::vector<typename Scanner::State>& states) const
+	{
+		states.resize(idx.size());
+		for (size_t i = 0; i < idx.size(); ++i)
+			states[i] = ToState(idx[i]);
+	}
+	/* RegexpsCount() as the library has it */
+	size_t Regexps() const
+	{
+		pire_hip_table_info info;
+		Check(pire_hip_table_get_info(m_table, &info));
+		return size_t(info.regexps);
+	}
 
 private:
 	Table(const Table&);
@@ -178,53 +252,27 @@ public:
 	BatchRunner& End() { m_flags |= PIRE_HIP_RUN_END; return *this; }         // run.h:376
 
 	/* Run(begin,end) for n strings: string i = text[offsets[i], offsets[i+1]).  Host pointers. */
-	BatchRunner& Run(const char* text, const uint64_t* offsets, size_t n)
-	{
-		m_text = text;
-		m_offsets = offsets;
-		m_n = n;
-		m_onDevice = false;
-		m_ran = m_lines = m_routed = m_routeFetched = false;
-		return *this;
-	}
+	BatchRunner& Run(const char* text, const uint64_t* offsets, size_t n) { return SetBatch(kHostOffsets, text, offsets, n); }
 
 	/* The same with DEVICE pointers (text and offsets resident in HBM); `stream` is a hipStream_t or null. */
 	BatchRunner& RunDevice(const void* deviceText, const uint64_t* deviceOffsets, size_t n, void* stream = nullptr)
 	{
-		m_text = static_cast<const char*>(deviceText);
-		m_offsets = deviceOffsets;
-		m_n = n;
-		m_len = m_stride = 0;
 		m_stream = stream;
-		m_onDevice = true;
-		m_ran = m_lines = m_routed = m_routeFetched = false;
-		return *this;
+		return SetBatch(kDeviceOffsets, deviceText, deviceOffsets, n);
 	}
 
 	/* Device-resident fixed-length records: string i = text[i * stride, i * stride + len). */
 	BatchRunner& RunDeviceStrided(const void* deviceText, size_t n, size_t len, size_t stride, void* stream = nullptr)
 	{
-		m_text = static_cast<const char*>(deviceText);
-		m_offsets = nullptr;
-		m_n = n;
-		m_len = len;
-		m_stride = stride;
 		m_stream = stream;
-		m_onDevice = true;
-		m_ran = m_lines = m_routed = m_routeFetched = false;
-		return *this;
+		return SetBatch(kDeviceStrided, deviceText, nullptr, n, len, stride);
 	}
 
 	/* Convenience: a vector of strings (copied into one buffer). */
 	BatchRunner& Run(const std::vector<ystring>& strings)
 	{
-		m_ownText.clear();
-		m_ownOffsets.assign(1, 0);
-		for (size_t i = 0; i < strings.size(); ++i) {
-			m_ownText.append(strings[i]);
-			m_ownOffsets.push_back(m_ownText.size());
-		}
-		return Run(m_ownText.data(), m_ownOffsets.data(), strings.size());
+		m_ownStrings.Assign(strings);
+		return Run(m_ownStrings.Text(), m_ownStrings.Offsets(), strings.size());
 	}
 
 	/*
@@ -240,14 +288,8 @@ public:
 	 */
 	BatchRunner& RunLines(const char* raw, size_t size, char delim = '\n')
 	{
-		m_text = raw;
-		m_offsets = nullptr;
-		m_n = 0;
-		m_len = size;
 		m_delim = uint8_t(delim);
-		m_onDevice = m_ran = m_selected = m_hitsFetched = m_textFetched = m_routed = m_routeFetched = m_column = false;
-		m_lines = true;
-		return *this;
+		return SetBatch(kLines, raw, nullptr, 0, size);
 	}
 	/*
 	 * The same for records: the lines whose COLUMN `field` (from 0, `sep` between the columns) matches -- awk -F'\t' '$3 ~ /re/'
@@ -258,12 +300,11 @@ public:
 	 */
 	BatchRunner& RunLinesField(const char* raw, size_t size, uint32_t field, char sep = '\t', char delim = '\n', bool rest = false)
 	{
-		RunLines(raw, size, delim);
-		m_column = true;
+		m_delim = uint8_t(delim);
 		m_sep = uint8_t(sep);
 		m_field = field;
 		m_fieldMode = rest ? PIRE_HIP_FIELDS_REST : 0;
-		return *this;
+		return SetBatch(kLinesField, raw, nullptr, 0, size);
 	}
 	uint64_t LineCount() { FetchHits(); return m_lineCount; }
 	const std::vector<uint64_t>& HitSpans() { FetchHits(); return m_hitSpans; }
@@ -273,7 +314,7 @@ public:
 	const std::string& HitText(char tail = '\n') { FetchHitText(tail); return m_hitText; }
 	const std::vector<uint64_t>& HitTextOffsets()
 	{
-		if (!m_textFetched)
+		if (!Has(kHitText))
 			FetchHitText('\n');
 		return m_hitTextOffsets;
 	}
@@ -296,10 +337,10 @@ public:
 	const std::vector<uint64_t>& MatchCounts()
 	{
 		Execute();
-		if (m_onDevice && !m_countsFetched) {
+		if (!Has(kCounts)) {
 			Check(pire_hip_copy_to_host(m_counts.data(), m_devCounts.Get(), m_counts.size() * 8, m_stream));
 			Check(pire_hip_stream_synchronize(m_stream));
-			m_countsFetched = true;
+			m_current |= kCounts;
 		}
 		return m_counts;
 	}
@@ -326,7 +367,7 @@ public:
 		for (size_t i = 0; i < want.size(); ++i)
 			if (want[i] < m_want.size() * 64)
 				m_want[want[i] / 64] |= uint64_t(1) << (want[i] % 64);
-		m_selected = m_hitsFetched = m_textFetched = false;
+		Stale(kSelection | kHits | kHitText);
 		return *this;
 	}
 	size_t MaskWords() const { return pire_hip_table_mask_words(m_table->Handle()); }
@@ -350,14 +391,14 @@ public:
 	 */
 	BatchRunner& Route()
 	{
-		m_routed = m_routeFetched = false;
+		Stale(kRoute | kRouteRows);
 		return *this;
 	}
 	uint64_t RouteCount(size_t r) { FetchRoute(); return m_routeCounts.at(r); }
 	const std::vector<uint64_t>& RouteHits(size_t r) { FetchRoute(); return m_routeHits.at(r); }
 	const std::vector<uint64_t>& RouteSpans(size_t r)
 	{
-		if (!m_lines)
+		if (!Lines())
 			throw Pire::Error("pire_hip: RouteSpans() follows RunLines()");
 		FetchRoute();
 		return m_routeSpans.at(r);
@@ -370,11 +411,57 @@ public:
 	uint32_t Flags() const { return m_flags; }
 
 private:
+	/* ---- the batch and what is known of it -------------------------------------------------------------------------------
+	 * The batch is one of five forms, set by SetBatch() alone.  What was computed from it is a set of Result bits: a step sets
+	 * its bit where it ends, and a bit goes away in two ways.  What the caller does:
+	 *     SetBatch()   Run*() of strings: the scan and everything but the selection;  RunLines*(): everything
+	 *     Select()     the selection, the hits on the host, the hit text
+	 *     Route()      the hit lists per regexp, on the device and on the host
+	 * And a step that runs again ends the host copy of what it is about to make anew, with a Stale() of its own:
+	 *     Execute()         kStates, kCounts (kCounts is set again at once where the counts came back with the scan)
+	 *     ExecuteSelect()   kHits, after RunDevice*(): the hits wait on the device for FetchHits()
+	 *     ExecuteRoute()    kRouteRows, after RunDevice*(): the rows wait on the device for FetchRoute()
+	 * A result is current while its bit AND the scan's are set -- asked BEFORE the scan is brought up to date, see
+	 * SelectionCurrent() --, so a new result is one name in Result and one in the Stale() that ends it. */
+	enum Form { kHostOffsets, kDeviceOffsets, kDeviceStrided, kLines, kLinesField };
+	enum Result {
+		kScan = 1 << 0,        // the scan ran (for the lines forms: a call that scans ran)
+		kStates = 1 << 1,      // m_idx / m_fin / m_states / m_final are this scan's
+		kCounts = 1 << 2,      // m_counts is
+		kSelection = 1 << 3,   // the selection was made (on the device after RunDevice*)
+		kHits = 1 << 4,        // m_hitCount / m_hits / m_hitMasks are this selection's
+		kHitText = 1 << 5,     // m_hitText / m_hitTextOffsets are, with the tail m_textTail
+		kRoute = 1 << 6,       // the hit lists per regexp were made (on the device after RunDevice*)
+		kRouteRows = 1 << 7,   // m_routeCounts / m_routeHits / m_routeSpans are theirs
+		kEverything = (1 << 8) - 1
+	};
+	bool Has(unsigned results) const { return (m_current & results) == results; }
+	void Stale(unsigned results) { m_current &= ~results; }
+	bool Lines() const { return m_form == kLines || m_form == kLinesField; }
+	bool OnDevice() const { return m_form == kDeviceOffsets || m_form == kDeviceStrided; }
+	bool SelectionCurrent() const { return Has(kScan | kSelection); }
+	bool RouteCurrent() const { return Has(kScan | kRoute); }
+
+	BatchRunner& SetBatch(Form form, const void* text, const uint64_t* offsets, size_t n, size_t len = 0, size_t stride = 0)
+	{
+		m_form = form;
+		m_text = static_cast<const char*>(text);
+		m_offsets = offsets;
+		m_n = n;
+		m_len = len;
+		m_stride = stride;
+		// (a selection outlives a new batch of strings, as it always has here: SelectionCurrent() looks at the scan first, so Hits()
+		// right after Run*() select anew, and Hits() after its States() are those of the batch before -- tests/cpp/shim_calls_test.cpp)
+		Stale(Lines() ? kEverything : kEverything & ~(kSelection | kHits | kHitText));
+		return *this;
+	}
+
 	void Reset()
 	{
-		m_routed = m_routeFetched = false;
+		m_form = kHostOffsets;
+		m_current = 0;
 		m_routePitch = 0;
-		m_selected = m_hitsFetched = m_haveWant = m_lines = m_textFetched = m_column = false;
+		m_haveWant = false;
 		m_hitCount = m_lineCount = 0;
 		m_delim = m_sep = 0;
 		m_field = m_fieldMode = 0;
@@ -384,22 +471,26 @@ private:
 		m_offsets = nullptr;
 		m_n = m_len = m_stride = 0;
 		m_stream = nullptr;
-		m_onDevice = m_ran = m_fetched = m_countsFetched = false;
+	}
+
+	const uint64_t* Want() const { return m_haveWant ? m_want.data() : nullptr; }
+	void SelectFinalsByDefault()
+	{
+		if (m_want.empty())
+			Select();
 	}
 
 	void Execute()
 	{
-		if (m_lines)
+		if (Lines())
 			throw Pire::Error("pire_hip: RunLines() has hits, no states");
-		if (m_ran)
+		if (Has(kScan))
 			return;
 		if (!m_init.empty() && m_init.size() != m_n)
 			throw Pire::Error("pire_hip: From() and Run() disagree on the number of strings");
-		pire_hip_table_info info;
-		Check(pire_hip_table_get_info(m_table->Handle(), &info));
-		m_counts.assign(size_t(info.regexps) + 2, 0);
-		static const uint64_t kNoOffsets[1] = {0};
-		if (m_onDevice) {
+		m_counts.assign(m_table->Regexps() + 2, 0);
+		Stale(kStates | kCounts);
+		if (OnDevice()) {
 			uint32_t* idx = static_cast<uint32_t*>(m_devIdx.Reserve(m_n * 4));
 			uint8_t* fin = static_cast<uint8_t*>(m_devFin.Reserve(m_n));
 			uint64_t* cnt = static_cast<uint64_t*>(m_devCounts.Reserve(m_counts.size() * 8));
@@ -410,96 +501,89 @@ private:
 				Check(pire_hip_copy_to_device(m_devInit.Get(), m_init.data(), m_n * 4, m_stream));
 			}
 			const uint32_t flags = m_flags | PIRE_HIP_RUN_ON_DEVICE;
-			if (m_offsets || !m_n)
+			if (m_offsets || !m_n)   // (RunDevice() with no offsets is scanned as n records of no bytes, as it always was)
 				Check(pire_hip_run(m_table->Handle(), m_text, m_offsets, m_n, flags, init, idx, fin, cnt, m_stream));
 			else
 				Check(pire_hip_run_strided(m_table->Handle(), m_text, m_n, m_len, m_stride, flags, init, idx, fin, cnt,
 				                           m_stream));
 			if (!m_init.empty())
 				Check(pire_hip_stream_synchronize(m_stream));   // m_init was the source of an asynchronous copy
-			m_fetched = m_countsFetched = false;
 		} else {
 			m_idx.resize(m_n);
 			m_fin.resize(m_n);
-			Check(pire_hip_run(m_table->Handle(), m_text, m_n ? m_offsets : kNoOffsets, m_n, m_flags,
+			Check(pire_hip_run(m_table->Handle(), m_text, OwnedStrings::OffsetsOr(m_offsets, m_n), m_n, m_flags,
 			                   m_init.empty() ? nullptr : m_init.data(), m_idx.data(), m_fin.data(), m_counts.data(), nullptr));
-			m_fetched = false;
-			m_countsFetched = true;
+			m_current |= kCounts;
 		}
-		m_ran = true;
+		m_current |= kScan;
 	}
 
 	/* RunLines(): one call; room for a hit on every line of 64 bytes or more, and a second call where there are more */
 	void ExecuteLines()
 	{
-		if (m_selected && m_ran)
+		if (SelectionCurrent())
 			return;
-		if (m_want.empty())
-			Select();
+		SelectFinalsByDefault();
 		const size_t w = m_want.size();
-		for (size_t cap = m_len / 64 + 1024;; cap = m_hitCount) {
+		GrowAndRetry(m_len / 64 + 1024, [&](size_t cap) {
 			m_hits.resize(cap);
 			m_hitSpans.resize(cap * 2);
 			m_hitMasks.resize(cap * w);
-			const uint64_t* want = m_haveWant ? m_want.data() : nullptr;
-			Check(m_column ? pire_hip_run_lines_field_select(m_table->Handle(), m_text, m_len, m_delim, m_sep, m_field, m_fieldMode, m_flags,
-			                                                 want, &m_lineCount, m_hits.data(), m_hitSpans.data(), m_hitMasks.data(), cap,
-			                                                 &m_hitCount, nullptr)
-			               : pire_hip_run_lines_select(m_table->Handle(), m_text, m_len, m_delim, m_flags, want, &m_lineCount, m_hits.data(),
-			                                           m_hitSpans.data(), m_hitMasks.data(), cap, &m_hitCount, nullptr));
-			if (m_hitCount <= cap)
-				break;
-		}
+			Check(m_form == kLinesField
+			          ? pire_hip_run_lines_field_select(m_table->Handle(), m_text, m_len, m_delim, m_sep, m_field, m_fieldMode, m_flags, Want(),
+			                                            &m_lineCount, m_hits.data(), m_hitSpans.data(), m_hitMasks.data(), cap, &m_hitCount,
+			                                            nullptr)
+			          : pire_hip_run_lines_select(m_table->Handle(), m_text, m_len, m_delim, m_flags, Want(), &m_lineCount, m_hits.data(),
+			                                      m_hitSpans.data(), m_hitMasks.data(), cap, &m_hitCount, nullptr));
+			return size_t(m_hitCount);
+		});
 		m_hits.resize(m_hitCount);
 		m_hitSpans.resize(m_hitCount * 2);
 		m_hitMasks.resize(m_hitCount * w);
-		m_ran = m_selected = m_hitsFetched = true;
+		m_current |= kScan | kSelection | kHits;
 	}
 
-	/* RunLines(): the selected lines as bytes; room for every byte they can have, the grow-and-retry of ExecuteLines() on the
-	 * number of hits */
+	/* RunLines(): the selected lines as bytes; room for every byte they can have, and for the hits that are known, or else
+	 * ExecuteLines()'s */
 	void FetchHitText(char tail)
 	{
-		if (!m_lines)
+		if (!Lines())
 			throw Pire::Error("pire_hip: HitText() follows RunLines()");
-		if (m_textFetched && m_textTail == tail)
+		if (Has(kHitText) && m_textTail == tail)
 			return;
-		if (m_want.empty())
-			Select();
+		SelectFinalsByDefault();
 		uint64_t count = 0, bytes = 0;
-		for (size_t cap = m_selected && m_ran ? size_t(m_hitCount) : m_len / 64 + 1024;; cap = count) {
+		GrowAndRetry(SelectionCurrent() ? size_t(m_hitCount) : m_len / 64 + 1024, [&](size_t cap) {
 			m_hitTextOffsets.resize(cap + 1);
 			m_hitText.resize(m_len + cap + 1);
-			const uint64_t* want = m_haveWant ? m_want.data() : nullptr;
-			Check(m_column ? pire_hip_run_lines_field_gather(m_table->Handle(), m_text, m_len, m_delim, m_sep, m_field, m_fieldMode, m_flags,
-			                                                 want, uint8_t(tail), &m_lineCount, nullptr, cap, &count, &m_hitText[0],
-			                                                 m_hitText.size(), m_hitTextOffsets.data(), &bytes, nullptr)
-			               : pire_hip_run_lines_gather(m_table->Handle(), m_text, m_len, m_delim, m_flags, want, uint8_t(tail), &m_lineCount,
-			                                           nullptr, cap, &count, &m_hitText[0], m_hitText.size(), m_hitTextOffsets.data(),
-			                                           &bytes, nullptr));
-			if (count <= cap && bytes <= m_hitText.size())
-				break;
-		}
+			Check(m_form == kLinesField
+			          ? pire_hip_run_lines_field_gather(m_table->Handle(), m_text, m_len, m_delim, m_sep, m_field, m_fieldMode, m_flags, Want(),
+			                                            uint8_t(tail), &m_lineCount, nullptr, cap, &count, &m_hitText[0], m_hitText.size(),
+			                                            m_hitTextOffsets.data(), &bytes, nullptr)
+			          : pire_hip_run_lines_gather(m_table->Handle(), m_text, m_len, m_delim, m_flags, Want(), uint8_t(tail), &m_lineCount,
+			                                      nullptr, cap, &count, &m_hitText[0], m_hitText.size(), m_hitTextOffsets.data(), &bytes,
+			                                      nullptr));
+			return size_t(count);   // (the text has room for the whole buffer and a tail per hit: where the hits fit, the bytes do)
+		});
 		m_hitText.resize(bytes);
 		m_hitTextOffsets.resize(count + 1);
 		m_textTail = tail;
-		m_textFetched = true;
+		m_current |= kHitText;
 	}
 
 	void ExecuteSelect()
 	{
-		if (m_lines) {
+		if (Lines()) {
 			ExecuteLines();
 			return;
 		}
-		const bool ranBefore = m_ran;
+		const bool current = SelectionCurrent();      // of the scan as it is: Execute() below makes every scan current
 		Execute();
-		if (m_selected && ranBefore)
+		if (current)
 			return;
-		if (m_want.empty())
-			Select();
+		SelectFinalsByDefault();
 		const size_t w = m_want.size();
-		if (m_onDevice) {
+		if (OnDevice()) {
 			uint64_t* hits = static_cast<uint64_t*>(m_devHits.Reserve((m_n + 1) * 8));
 			uint64_t* masks = static_cast<uint64_t*>(m_devHitMasks.Reserve((m_n + 1) * w * 8));
 			uint64_t* count = static_cast<uint64_t*>(m_devHitCount.Reserve(8));
@@ -512,23 +596,23 @@ private:
 			                      PIRE_HIP_RUN_ON_DEVICE, nullptr, hits, masks, m_n, count, m_stream));
 			if (m_haveWant)
 				Check(pire_hip_stream_synchronize(m_stream));   // m_want was the source of an asynchronous copy
-			m_hitsFetched = false;
+			Stale(kHits);
 		} else {
 			m_hits.resize(m_n);
 			m_hitMasks.resize(m_n * w);
-			Check(pire_hip_select(m_table->Handle(), m_idx.data(), m_n, m_haveWant ? m_want.data() : nullptr, 0, nullptr,
-			                      m_hits.data(), m_hitMasks.data(), m_n, &m_hitCount, nullptr));
+			Check(pire_hip_select(m_table->Handle(), m_idx.data(), m_n, Want(), 0, nullptr, m_hits.data(), m_hitMasks.data(), m_n,
+			                      &m_hitCount, nullptr));
 			m_hits.resize(m_hitCount);
 			m_hitMasks.resize(m_hitCount * w);
-			m_hitsFetched = true;
+			m_current |= kHits;
 		}
-		m_selected = true;
+		m_current |= kSelection;
 	}
 
 	void FetchHits()
 	{
 		ExecuteSelect();
-		if (m_hitsFetched)
+		if (Has(kHits))
 			return;
 		const size_t w = m_want.size();
 		Check(pire_hip_copy_to_host(&m_hitCount, m_devHitCount.Get(), 8, m_stream));
@@ -540,14 +624,7 @@ private:
 			Check(pire_hip_copy_to_host(m_hitMasks.data(), m_devHitMasks.Get(), m_hitCount * w * 8, m_stream));
 			Check(pire_hip_stream_synchronize(m_stream));
 		}
-		m_hitsFetched = true;
-	}
-
-	size_t Regexps() const
-	{
-		pire_hip_table_info info;
-		Check(pire_hip_table_get_info(m_table->Handle(), &info));
-		return size_t(info.regexps);
+		m_current |= kHits;
 	}
 
 	/* Rows of a pitch of `pitch` entries (x `width` words) cut to their counts */
@@ -561,55 +638,48 @@ private:
 
 	void ExecuteRoute()
 	{
-		if (m_routed && m_ran)
+		if (RouteCurrent())
 			return;
-		const size_t regexps = Regexps();
+		const size_t regexps = m_table->Regexps();
 		m_routeCounts.assign(regexps, 0);
-		if (m_lines && m_column)
+		if (m_form == kLinesField)
 			throw Pire::Error("pire_hip: Route() follows Run*() or RunLines(), not RunLinesField()");
-		if (m_lines) {
+		if (Lines()) {
 			/* one call; the grow-and-retry of ExecuteLines() on the longest row */
 			std::vector<uint64_t> hits, spans;
-			for (size_t cap = m_len / 64 + 1024;; ) {
+			m_routePitch = GrowAndRetry(m_len / 64 + 1024, [&](size_t cap) {
 				hits.resize(regexps * cap);
 				spans.resize(regexps * cap * 2);
 				Check(pire_hip_run_lines_route(m_table->Handle(), m_text, m_len, m_delim, m_flags, &m_lineCount, hits.data(), spans.data(),
 				                               cap, m_routeCounts.data(), nullptr));
-				uint64_t longest = 0;
-				for (size_t r = 0; r < regexps; ++r)
-					longest = m_routeCounts[r] > longest ? m_routeCounts[r] : longest;
-				if (longest <= cap) {
-					m_routePitch = cap;
-					break;
-				}
-				cap = size_t(longest);
-			}
+				return regexps ? size_t(*std::max_element(m_routeCounts.begin(), m_routeCounts.end())) : size_t(0);
+			});
 			CutRows(hits, m_routeCounts, m_routePitch, 1, m_routeHits);
 			CutRows(spans, m_routeCounts, m_routePitch, 2, m_routeSpans);
-			m_ran = m_routed = m_routeFetched = true;
+			m_current |= kScan | kRoute | kRouteRows;
 			return;
 		}
 		Execute();
 		m_routePitch = m_n;
-		if (m_onDevice) {
+		if (OnDevice()) {
 			uint64_t* hits = static_cast<uint64_t*>(m_devRouteHits.Reserve((regexps * m_n + 1) * 8));
 			uint64_t* counts = static_cast<uint64_t*>(m_devRouteCounts.Reserve((regexps + 1) * 8));
 			Check(pire_hip_route(m_table->Handle(), static_cast<const uint32_t*>(m_devIdx.Get()), m_n, PIRE_HIP_RUN_ON_DEVICE,
 			                     m_n ? hits : nullptr, m_n, counts, m_stream));
-			m_routeFetched = false;
+			Stale(kRouteRows);
 		} else {
 			std::vector<uint64_t> hits(regexps * m_n);
 			Check(pire_hip_route(m_table->Handle(), m_idx.data(), m_n, 0, m_n ? hits.data() : nullptr, m_n, m_routeCounts.data(), nullptr));
 			CutRows(hits, m_routeCounts, m_routePitch, 1, m_routeHits);
-			m_routeFetched = true;
+			m_current |= kRouteRows;
 		}
-		m_routed = true;
+		m_current |= kRoute;
 	}
 
 	void FetchRoute()
 	{
 		ExecuteRoute();
-		if (m_routeFetched)
+		if (Has(kRouteRows))
 			return;
 		const size_t regexps = m_routeCounts.size();
 		if (regexps) {
@@ -624,29 +694,25 @@ private:
 				                            size_t(m_routeCounts[r]) * 8, m_stream));
 		}
 		Check(pire_hip_stream_synchronize(m_stream));
-		m_routeFetched = true;
+		m_current |= kRouteRows;
 	}
 
 	/* Per-string results on the host, as Scanner::State values. */
 	void Fetch()
 	{
 		Execute();
-		if (m_fetched)
+		if (Has(kStates))
 			return;
-		if (m_onDevice) {
+		if (OnDevice()) {
 			m_idx.resize(m_n);
 			m_fin.resize(m_n);
 			Check(pire_hip_copy_to_host(m_idx.data(), m_devIdx.Get(), m_n * 4, m_stream));
 			Check(pire_hip_copy_to_host(m_fin.data(), m_devFin.Get(), m_n, m_stream));
 			Check(pire_hip_stream_synchronize(m_stream));
 		}
-		m_states.resize(m_n);
-		m_final.resize(m_n);
-		for (size_t i = 0; i < m_n; ++i) {
-			m_states[i] = m_table->ToState(m_idx[i]);
-			m_final[i] = char(m_fin[i]);
-		}
-		m_fetched = true;
+		m_table->ToStates(m_idx, m_states);
+		m_final.assign(m_fin.begin(), m_fin.end());
+		m_current |= kStates;
 	}
 
 	BatchRunner(const BatchRunner&);
@@ -655,19 +721,19 @@ private:
 	Table<Scanner>* m_own;
 	const Table<Scanner>* m_table;
 	uint32_t m_flags;
+	Form m_form;                  // the batch: which Run*() set it, and its pointers and sizes
 	const char* m_text;
 	const uint64_t* m_offsets;
 	size_t m_n, m_len, m_stride;
 	void* m_stream;
-	bool m_onDevice, m_ran, m_fetched, m_countsFetched;
+	unsigned m_current;           // Result bits: what is known of the batch
 	std::vector<uint32_t> m_init, m_idx;
 	std::vector<uint8_t> m_fin;
 	std::vector<State> m_states;
 	std::vector<char> m_final;
 	std::vector<uint64_t> m_counts;
 	DeviceBuffer m_devIdx, m_devFin, m_devCounts, m_devInit;
-	bool m_selected, m_hitsFetched, m_haveWant, m_lines, m_textFetched;
-	bool m_column;                // RunLinesField(): the scan is on column m_field of every line
+	bool m_haveWant;              // Select() named regexps: m_want goes to the library
 	uint8_t m_delim, m_sep;
 	uint32_t m_field, m_fieldMode;
 	char m_textTail;
@@ -676,13 +742,11 @@ private:
 	uint64_t m_hitCount, m_lineCount;
 	std::vector<uint64_t> m_want, m_hits, m_hitMasks, m_hitSpans;
 	DeviceBuffer m_devHits, m_devHitMasks, m_devHitCount, m_devWant;
-	bool m_routed, m_routeFetched;
 	size_t m_routePitch;
 	std::vector<uint64_t> m_routeCounts;
 	std::vector<std::vector<uint64_t> > m_routeHits, m_routeSpans;
 	DeviceBuffer m_devRouteHits, m_devRouteCounts;
-	ystring m_ownText;
-	std::vector<uint64_t> m_ownOffsets;
+	OwnedStrings m_ownStrings;
 };
 
 template <class Scanner>
@@ -697,8 +761,7 @@ std::vector<const char*> BatchPrefix(const Table<Scanner>& table, bool longest, 
                                      size_t n, bool throughBeginMark = false, bool throughEndMark = false)
 {
 	std::vector<int64_t> len(n);
-	static const uint64_t kNoOffsets[1] = {0};
-	Check(pire_hip_prefix(table.Handle(), text, n ? offsets : kNoOffsets, n, longest ? 1 : 0, throughBeginMark ? 1 : 0,
+	Check(pire_hip_prefix(table.Handle(), text, OwnedStrings::OffsetsOr(offsets, n), n, longest ? 1 : 0, throughBeginMark ? 1 : 0,
 	                      throughEndMark ? 1 : 0, 0, len.data(), nullptr));
 	std::vector<const char*> out(n);
 	for (size_t i = 0; i < n; ++i)
@@ -730,8 +793,7 @@ std::vector<const char*> BatchSuffix(const Table<Scanner>& table, bool longest, 
                                      size_t n, bool throughEndMark = false, bool throughBeginMark = false)
 {
 	std::vector<int64_t> len(n);
-	static const uint64_t kNoOffsets[1] = {0};
-	Check(pire_hip_suffix(table.Handle(), text, n ? offsets : kNoOffsets, n, longest ? 1 : 0, throughEndMark ? 1 : 0,
+	Check(pire_hip_suffix(table.Handle(), text, OwnedStrings::OffsetsOr(offsets, n), n, longest ? 1 : 0, throughEndMark ? 1 : 0,
 	                      throughBeginMark ? 1 : 0, 0, len.data(), nullptr));
 	std::vector<const char*> out(n);
 	for (size_t i = 0; i < n; ++i)
@@ -784,13 +846,8 @@ public:
 	}
 	MultiBatchRunner& Run(const std::vector<ystring>& strings)
 	{
-		m_ownText.clear();
-		m_ownOffsets.assign(1, 0);
-		for (size_t i = 0; i < strings.size(); ++i) {
-			m_ownText.append(strings[i]);
-			m_ownOffsets.push_back(m_ownText.size());
-		}
-		return Run(m_ownText.data(), m_ownOffsets.data(), strings.size());
+		m_ownStrings.Assign(strings);
+		return Run(m_ownStrings.Text(), m_ownStrings.Offsets(), strings.size());
 	}
 	const std::vector<State>& States() { Execute(); return m_states; }
 	const std::vector<char>& Finals() { Execute(); return m_final; }
@@ -806,20 +863,13 @@ private:
 	{
 		if (m_ran)
 			return;
-		pire_hip_table_info info;
-		Check(pire_hip_table_get_info(m_table.Handle(), &info));
 		std::vector<uint32_t> idx(m_n);
 		std::vector<uint8_t> fin(m_n);
-		m_counts.assign(info.regexps + 2, 0);
-		static const uint64_t none[1] = {0};
-		Check(pire_hip_multi_run_host(m_multi, m_table.Handle(), m_text, m_n ? m_offsets : none, m_n, m_flags, nullptr,
+		m_counts.assign(m_table.Regexps() + 2, 0);
+		Check(pire_hip_multi_run_host(m_multi, m_table.Handle(), m_text, OwnedStrings::OffsetsOr(m_offsets, m_n), m_n, m_flags, nullptr,
 		                              idx.data(), fin.data(), m_counts.data()));
-		m_states.resize(m_n);
-		m_final.resize(m_n);
-		for (size_t i = 0; i < m_n; ++i) {
-			m_states[i] = m_table.ToState(idx[i]);
-			m_final[i] = char(fin[i]);
-		}
+		m_table.ToStates(idx, m_states);
+		m_final.assign(fin.begin(), fin.end());
 		m_ran = true;
 	}
 
@@ -830,8 +880,7 @@ private:
 	const uint64_t* m_offsets;
 	size_t m_n;
 	bool m_ran;
-	std::string m_ownText;
-	std::vector<uint64_t> m_ownOffsets;
+	OwnedStrings m_ownStrings;
 	std::vector<State> m_states;
 	std::vector<char> m_final;
 	std::vector<uint64_t> m_counts;
@@ -884,17 +933,11 @@ public:
 	/* RunHelper<ScannerPair>::State() per string. */
 	std::vector<State> States()
 	{
-		std::vector<State> out;
-		if (m_fused) {
+		if (m_fused)
 			ExecuteFused();
-			out.resize(m_n);
-			for (size_t i = 0; i < m_n; ++i)
-				out[i] = ymake_pair(m_first.GetTable().ToState(m_idx1[i]), m_second.GetTable().ToState(m_idx2[i]));
-			return out;
-		}
-		const std::vector<typename Scanner1::State>& a = m_first.States();
-		const std::vector<typename Scanner2::State>& b = m_second.States();
-		out.resize(a.size());
+		const std::vector<typename Scanner1::State>& a = m_fused ? m_states1 : m_first.States();
+		const std::vector<typename Scanner2::State>& b = m_fused ? m_states2 : m_second.States();
+		std::vector<State> out(a.size());
 		for (size_t i = 0; i < a.size(); ++i)
 			out[i] = ymake_pair(a[i], b[i]);
 		return out;
@@ -926,13 +969,14 @@ private:
 		uint8_t* df = static_cast<uint8_t*>(m_devFin.Reserve(m_n));
 		Check(pire_hip_run_pair_strided(m_first.GetTable().Handle(), m_second.GetTable().Handle(), m_text, m_n, m_len, m_stride,
 		                                m_first.Flags() | PIRE_HIP_RUN_ON_DEVICE, d1, d2, df, m_stream));
-		m_idx1.resize(m_n);
-		m_idx2.resize(m_n);
+		std::vector<uint32_t> idx1(m_n), idx2(m_n);
 		m_fin.resize(m_n);
-		Check(pire_hip_copy_to_host(m_idx1.data(), d1, m_n * 4, m_stream));
-		Check(pire_hip_copy_to_host(m_idx2.data(), d2, m_n * 4, m_stream));
+		Check(pire_hip_copy_to_host(idx1.data(), d1, m_n * 4, m_stream));
+		Check(pire_hip_copy_to_host(idx2.data(), d2, m_n * 4, m_stream));
 		Check(pire_hip_copy_to_host(m_fin.data(), df, m_n, m_stream));
 		Check(pire_hip_stream_synchronize(m_stream));
+		m_first.GetTable().ToStates(idx1, m_states1);
+		m_second.GetTable().ToStates(idx2, m_states2);
 		m_ran = true;
 	}
 
@@ -942,99 +986,49 @@ private:
 	const void* m_text;
 	size_t m_n, m_len, m_stride;
 	void* m_stream;
-	std::vector<uint32_t> m_idx1, m_idx2;
+	std::vector<typename Scanner1::State> m_states1;
+	std::vector<typename Scanner2::State> m_states2;
 	std::vector<uint8_t> m_fin;
 	DeviceBuffer m_dev1, m_dev2, m_devFin;
 };
 
 /*
- * What Select() and RunLines() of the two counting runners below leave: the strings (lines) whose counts reach their
- * thresholds and the occurrences of every regexp over the batch, answered on the device (include/pire_hip.h, "the strings
- * that count, on the device").  One call with room for `room` hits, and a second one where there are more.
+ * What HalfFinalBatchRunner and CountingBatchRunner below are: a batched Runner whose scanner counts -- per string the
+ * per-regexp counts State::Result(r), plus StateIndex of the end state.  A scanner's State is an opaque class with private
+ * members, so the results come back as plain numbers.  Derived keeps its table and its three C calls, as
+ *     int Scan(offsets, out_idx, out_results)                                 the scan of m_n strings of m_text
+ *     int SelectStrings(offsets, min, mode, totals, hits, rows, cap, count)   the same, selected on the device
+ *     int SelectLines(min, mode, lineCount, totals, hits, spans, rows, cap, count)    of the m_len bytes of m_text, cut at m_delim
+ * and is what the fluent calls return.
  */
-struct CountedHits {
-	std::vector<uint32_t> min, rows;
-	std::vector<uint64_t> hits, spans, totals;
-	uint64_t count, lineCount;
-	bool all, fetched;
-	CountedHits() : count(0), lineCount(0), all(false), fetched(false) {}
-	void Choose(const std::vector<uint32_t>& m, bool a) { min = m; all = a; fetched = false; }
-	template <class Owner>
-	void Fetch(Owner& owner, size_t regexps, uint64_t room, bool lines)
-	{
-		if (fetched)
-			return;
-		if (!min.empty() && min.size() != regexps)
-			throw Pire::Error("pire_hip: Select() takes one threshold per regexp");
-		totals.assign(regexps, 0);
-		for (int attempt = 0; attempt < 2; ++attempt) {
-			hits.assign(size_t(room), 0);
-			rows.assign(size_t(room) * regexps, 0);
-			spans.assign(lines ? 2 * size_t(room) : 0, 0);
-			owner.CountSelectCall(min.empty() ? nullptr : min.data(), all ? PIRE_HIP_COUNT_ALL : 0u, regexps ? totals.data() : nullptr,
-			                      room ? hits.data() : nullptr, room && lines ? spans.data() : nullptr,
-			                      room && regexps ? rows.data() : nullptr, room, &count, &lineCount);
-			if (count <= room)
-				break;
-			room = count;
-		}
-		hits.resize(size_t(count));
-		rows.resize(size_t(count) * regexps);
-		spans.resize(lines ? 2 * size_t(count) : 0);
-		fetched = true;
-	}
-};
-
-/*
- * Batched Runner over a Pire::HalfFinalScanner (scanners/half_final.h): per string the per-regexp match counts
- * State::Result(r) (half_final.h:90-92) that Initialize + Begin() + Run() + End() accumulate through TakeAction
- * (half_final.h:137-164), plus Final and StateIndex of the end state.  The scanner's State is an opaque class with
- * private members, so the results come back as plain numbers.
- */
-template <class HalfScanner = Pire::HalfFinalScanner>
-class HalfFinalBatchRunner {
+template <class Derived>
+class CountedBatchRunner {
 public:
-	explicit HalfFinalBatchRunner(const HalfScanner& sc)
-	    : m_table(nullptr), m_regexps(sc.RegexpsCount()), m_flags(0), m_text(nullptr), m_offsets(nullptr), m_n(0), m_ran(false), m_len(0), m_delim('\n'), m_lines(false)
-	{
-		std::ostringstream out;
-		sc.Save(&out);                                    // Scanner::Save, multi.h:557-573 (inherited)
-		const std::string blob = out.str();
-		Check(pire_hip_table_create(blob.data(), blob.size(), &m_table));
-	}
-	~HalfFinalBatchRunner() { pire_hip_table_destroy(m_table); }
-
-	HalfFinalBatchRunner& Begin() { m_flags |= PIRE_HIP_RUN_BEGIN; return *this; }
-	HalfFinalBatchRunner& End() { m_flags |= PIRE_HIP_RUN_END; return *this; }
-	HalfFinalBatchRunner& Run(const char* text, const uint64_t* offsets, size_t n)
+	Derived& Begin() { m_flags |= PIRE_HIP_RUN_BEGIN; return Self(); }
+	Derived& End() { m_flags |= PIRE_HIP_RUN_END; return Self(); }
+	Derived& Run(const char* text, const uint64_t* offsets, size_t n)
 	{
 		m_text = text;
 		m_offsets = offsets;
 		m_n = n;
-		m_ran = false;
 		m_lines = false;
-		m_sel.fetched = false;
-		return *this;
+		m_ran = m_selected = false;
+		return Self();
 	}
-	HalfFinalBatchRunner& Run(const std::vector<ystring>& strings)
+	Derived& Run(const std::vector<ystring>& strings)
 	{
-		m_ownText.clear();
-		m_ownOffsets.assign(1, 0);
-		for (size_t i = 0; i < strings.size(); ++i) {
-			m_ownText.append(strings[i]);
-			m_ownOffsets.push_back(m_ownText.size());
-		}
-		return Run(m_ownText.data(), m_ownOffsets.data(), strings.size());
+		m_ownStrings.Assign(strings);
+		return Run(m_ownStrings.Text(), m_ownStrings.Offsets(), strings.size());
 	}
 
 	/* State::Result(r) of string i. */
 	size_t Result(size_t i, size_t r) { Execute(); return m_results[i * m_regexps + r]; }
 	const std::vector<uint32_t>& Results() { Execute(); return m_results; }       // [n][RegexpsCount()]
-	const std::vector<char>& Finals() { Execute(); return m_final; }              // Final(State()) per string
 	const std::vector<uint32_t>& StateIndices() { Execute(); return m_idx; }      // StateIndex(State()) per string
 
 	/*
-	 * The strings whose counts reach their thresholds, without a loop on the host (pire_hip_count_select behind the scan):
+	 * The strings whose counts reach their thresholds, without a loop on the host (pire_hip_count_select behind the scan;
+	 * include/pire_hip.h, "the strings that count, on the device"):
 	 *     run.Begin().Run(text, offsets, n).End().Select();    // the strings in which some regexp occurred
 	 *     run.Select({3, 0, 1});                                // ... regexp 0 three times or regexp 2 once (0 = not asked)
 	 *     run.Select({3, 0, 1}, true);                          // ... and regexp 2 once
@@ -1044,55 +1038,46 @@ public:
 	 *     run.HitSpans()    [2 * k], [2 * k + 1]: line Hits()[k] is raw[begin, end)        run.LineCount()  lines in the buffer
 	 * After RunLines() there are hits only: Result() / Results() / StateIndices() throw.
 	 */
-	HalfFinalBatchRunner& Select(const std::vector<uint32_t>& min = std::vector<uint32_t>(), bool all = false)
+	Derived& Select(const std::vector<uint32_t>& min = std::vector<uint32_t>(), bool all = false)
 	{
-		m_sel.Choose(min, all);
-		return *this;
+		m_min = min;
+		m_all = all;
+		m_selected = false;
+		return Self();
 	}
-	HalfFinalBatchRunner& RunLines(const char* raw, size_t size, char delim = '\n')
+	Derived& RunLines(const char* raw, size_t size, char delim = '\n')
 	{
 		m_text = raw;
 		m_len = size;
-		m_delim = delim;
+		m_delim = uint8_t(delim);
 		m_lines = true;
-		m_ran = false;
-		m_sel.fetched = false;
-		return *this;
+		m_ran = m_selected = false;
+		return Self();
 	}
-	const std::vector<uint64_t>& Hits() { FetchHits(); return m_sel.hits; }
-	const std::vector<uint32_t>& HitResults() { FetchHits(); return m_sel.rows; }
-	size_t HitCount() { FetchHits(); return size_t(m_sel.count); }
-	const std::vector<uint64_t>& Totals() { FetchHits(); return m_sel.totals; }
+	const std::vector<uint64_t>& Hits() { FetchHits(); return m_hits; }
+	const std::vector<uint32_t>& HitResults() { FetchHits(); return m_rows; }
+	size_t HitCount() { FetchHits(); return size_t(m_hitCount); }
+	const std::vector<uint64_t>& Totals() { FetchHits(); return m_totals; }
 	const std::vector<uint64_t>& HitSpans()
 	{
 		if (!m_lines)
 			throw Pire::Error("pire_hip: HitSpans() follows RunLines()");
 		FetchHits();
-		return m_sel.spans;
+		return m_spans;
 	}
 	size_t LineCount()
 	{
 		if (!m_lines)
 			throw Pire::Error("pire_hip: LineCount() follows RunLines()");
 		FetchHits();
-		return size_t(m_sel.lineCount);
+		return size_t(m_lineCount);
 	}
 
-private:
-	friend struct CountedHits;
-	/* RunLines(): room for a hit on every line of 64 bytes or more, and a second call where there are more */
-	void FetchHits() { m_sel.Fetch(*this, m_regexps, m_lines ? m_len / 64 + 16 : m_n, m_lines); }
-	void CountSelectCall(const uint32_t* min, uint32_t mode, uint64_t* totals, uint64_t* hits, uint64_t* spans, uint32_t* rows, uint64_t cap,
-	                     uint64_t* count, uint64_t* lineCount)
-	{
-		static const uint64_t kNoOffsets[1] = {0};
-		if (m_lines)
-			Check(pire_hip_half_final_lines_select(m_table, m_text, m_len, uint8_t(m_delim), m_flags, min, mode, lineCount, totals, hits, spans, rows,
-			                                       cap, count, nullptr));
-		else
-			Check(pire_hip_run_half_final_select(m_table, m_text, m_n ? m_offsets : kNoOffsets, m_n, m_flags, nullptr, nullptr, nullptr, min, mode,
-			                                     totals, hits, rows, cap, count, nullptr));
-	}
+protected:
+	explicit CountedBatchRunner(size_t regexps)
+	    : m_regexps(regexps), m_flags(0), m_text(nullptr), m_offsets(nullptr), m_n(0), m_len(0), m_delim('\n'), m_lines(false), m_ran(false),
+	      m_selected(false), m_all(false), m_hitCount(0), m_lineCount(0) {}
+
 	void Execute()
 	{
 		if (m_ran)
@@ -1100,38 +1085,108 @@ private:
 		if (m_lines)
 			throw Pire::Error("pire_hip: RunLines() has hits, no results per string");
 		m_idx.assign(m_n, 0);
-		std::vector<uint8_t> fin(m_n);
 		m_results.assign(m_n * (m_regexps ? m_regexps : 1), 0);
-		static const uint64_t kNoOffsets[1] = {0};
-		Check(pire_hip_run_half_final(m_table, m_text, m_n ? m_offsets : kNoOffsets, m_n, m_flags, m_idx.data(), fin.data(),
-		                              m_results.data(), nullptr));
-		m_final.assign(fin.begin(), fin.end());
+		Check(Self().Scan(OwnedStrings::OffsetsOr(m_offsets, m_n), m_idx.data(), m_results.data()));
 		m_ran = true;
+	}
+
+	size_t m_regexps;
+	uint32_t m_flags;
+	const char* m_text;           // Run(): the strings' text; RunLines(): the raw buffer of m_len bytes
+	const uint64_t* m_offsets;
+	size_t m_n, m_len;
+	uint8_t m_delim;
+
+private:
+	Derived& Self() { return static_cast<Derived&>(*this); }
+
+	/* One call with room for every string -- RunLines(): for a hit on every line of 64 bytes or more --, and a second one where
+	 * there are more */
+	void FetchHits()
+	{
+		if (m_selected)
+			return;
+		if (!m_min.empty() && m_min.size() != m_regexps)
+			throw Pire::Error("pire_hip: Select() takes one threshold per regexp");
+		m_totals.assign(m_regexps, 0);
+		GrowAndRetry(m_lines ? m_len / 64 + 16 : m_n, [&](size_t room) {
+			m_hits.assign(room, 0);
+			m_rows.assign(room * m_regexps, 0);
+			m_spans.assign(m_lines ? 2 * room : 0, 0);
+			const uint32_t* min = m_min.empty() ? nullptr : m_min.data();
+			const uint32_t mode = m_all ? PIRE_HIP_COUNT_ALL : 0u;
+			uint64_t* totals = m_regexps ? m_totals.data() : nullptr;
+			uint64_t* hits = room ? m_hits.data() : nullptr;
+			uint32_t* rows = room && m_regexps ? m_rows.data() : nullptr;
+			Check(m_lines ? Self().SelectLines(min, mode, &m_lineCount, totals, hits, room ? m_spans.data() : nullptr, rows, room, &m_hitCount)
+			              : Self().SelectStrings(OwnedStrings::OffsetsOr(m_offsets, m_n), min, mode, totals, hits, rows, room, &m_hitCount));
+			return size_t(m_hitCount);
+		});
+		m_hits.resize(size_t(m_hitCount));
+		m_rows.resize(size_t(m_hitCount) * m_regexps);
+		m_spans.resize(m_lines ? 2 * size_t(m_hitCount) : 0);
+		m_selected = true;
+	}
+
+	bool m_lines, m_ran, m_selected;
+	bool m_all;                   // Select(): the thresholds, and whether all of them have to be reached
+	std::vector<uint32_t> m_min;
+	std::vector<uint32_t> m_idx, m_results, m_rows;
+	std::vector<uint64_t> m_hits, m_spans, m_totals;
+	uint64_t m_hitCount, m_lineCount;
+	OwnedStrings m_ownStrings;
+};
+
+/*
+ * Batched Runner over a Pire::HalfFinalScanner (scanners/half_final.h): per string the per-regexp match counts
+ * State::Result(r) (half_final.h:90-92) that Initialize + Begin() + Run() + End() accumulate through TakeAction
+ * (half_final.h:137-164), plus Final and StateIndex of the end state.  The calls are CountedBatchRunner's.
+ */
+template <class HalfScanner = Pire::HalfFinalScanner>
+class HalfFinalBatchRunner : public CountedBatchRunner<HalfFinalBatchRunner<HalfScanner> > {
+public:
+	explicit HalfFinalBatchRunner(const HalfScanner& sc)
+	    : CountedBatchRunner<HalfFinalBatchRunner>(sc.RegexpsCount()), m_table(nullptr)
+	{
+		const std::string blob = SavedBlob(sc);
+		Check(pire_hip_table_create(blob.data(), blob.size(), &m_table));
+	}
+	~HalfFinalBatchRunner() { pire_hip_table_destroy(m_table); }
+
+	const std::vector<char>& Finals() { this->Execute(); return m_final; }        // Final(State()) per string
+
+private:
+	friend class CountedBatchRunner<HalfFinalBatchRunner>;
+	int Scan(const uint64_t* offsets, uint32_t* idx, uint32_t* results)
+	{
+		std::vector<uint8_t> fin(this->m_n);
+		const int rc = pire_hip_run_half_final(m_table, this->m_text, offsets, this->m_n, this->m_flags, idx, fin.data(), results, nullptr);
+		m_final.assign(fin.begin(), fin.end());
+		return rc;
+	}
+	int SelectStrings(const uint64_t* offsets, const uint32_t* min, uint32_t mode, uint64_t* totals, uint64_t* hits, uint32_t* rows, uint64_t cap,
+	                  uint64_t* count)
+	{
+		return pire_hip_run_half_final_select(m_table, this->m_text, offsets, this->m_n, this->m_flags, nullptr, nullptr, nullptr, min, mode,
+		                                      totals, hits, rows, cap, count, nullptr);
+	}
+	int SelectLines(const uint32_t* min, uint32_t mode, uint64_t* lineCount, uint64_t* totals, uint64_t* hits, uint64_t* spans, uint32_t* rows,
+	                uint64_t cap, uint64_t* count)
+	{
+		return pire_hip_half_final_lines_select(m_table, this->m_text, this->m_len, this->m_delim, this->m_flags, min, mode, lineCount, totals,
+		                                        hits, spans, rows, cap, count, nullptr);
 	}
 
 	HalfFinalBatchRunner(const HalfFinalBatchRunner&);
 	HalfFinalBatchRunner& operator=(const HalfFinalBatchRunner&);
 	pire_hip_table* m_table;
-	size_t m_regexps;
-	uint32_t m_flags;
-	const char* m_text;
-	const uint64_t* m_offsets;
-	size_t m_n;
-	bool m_ran;
-	size_t m_len;                 // RunLines(): m_text is the raw buffer of m_len bytes
-	char m_delim;
-	bool m_lines;
-	CountedHits m_sel;
-	std::vector<uint32_t> m_idx, m_results;
 	std::vector<char> m_final;
-	ystring m_ownText;
-	std::vector<uint64_t> m_ownOffsets;
 };
 
 /*
  * Batched Runner over a Pire::CountingScanner, AdvancedCountingScanner or NoGlueLimitCountingScanner (extra/count.h; include <pire/extra.h>
  * before this header): per string State::Result(r) for every glued regexp (count.h:206) after
- * Initialize + Begin() + Run() + End(), as tests/count_ut.cpp:54-63 drives them.
+ * Initialize + Begin() + Run() + End(), as tests/count_ut.cpp:54-63 drives them.  The calls are CountedBatchRunner's.
  */
 #ifdef PIRE_EXTRA_COUNT_H
 template <class CountScanner>
@@ -1150,136 +1205,39 @@ struct CountingKind<Pire::NoGlueLimitCountingScanner> {
 };
 
 template <class CountScanner>
-class CountingBatchRunner {
+class CountingBatchRunner : public CountedBatchRunner<CountingBatchRunner<CountScanner> > {
 public:
 	explicit CountingBatchRunner(const CountScanner& sc)
-	    : m_table(nullptr), m_regexps(sc.RegexpsCount()), m_flags(0), m_text(nullptr), m_offsets(nullptr), m_n(0), m_ran(false), m_len(0), m_delim('\n'), m_lines(false)
+	    : CountedBatchRunner<CountingBatchRunner>(sc.RegexpsCount()), m_table(nullptr)
 	{
-		std::ostringstream out;
-		sc.Save(&out);                                    // LoadedScanner::Save, scanner_io.cpp:172-189 / count.cpp:1009-1018
-		const std::string blob = out.str();
+		const std::string blob = SavedBlob(sc);
 		Check(pire_hip_counting_table_create(blob.data(), blob.size(), &m_table));
 	}
 	~CountingBatchRunner() { pire_hip_counting_table_destroy(m_table); }
 
-	CountingBatchRunner& Begin() { m_flags |= PIRE_HIP_RUN_BEGIN; return *this; }
-	CountingBatchRunner& End() { m_flags |= PIRE_HIP_RUN_END; return *this; }
-	CountingBatchRunner& Run(const char* text, const uint64_t* offsets, size_t n)
-	{
-		m_text = text;
-		m_offsets = offsets;
-		m_n = n;
-		m_ran = false;
-		m_lines = false;
-		m_sel.fetched = false;
-		return *this;
-	}
-	CountingBatchRunner& Run(const std::vector<ystring>& strings)
-	{
-		m_ownText.clear();
-		m_ownOffsets.assign(1, 0);
-		for (size_t i = 0; i < strings.size(); ++i) {
-			m_ownText.append(strings[i]);
-			m_ownOffsets.push_back(m_ownText.size());
-		}
-		return Run(m_ownText.data(), m_ownOffsets.data(), strings.size());
-	}
-
-	/* State::Result(r) of string i. */
-	size_t Result(size_t i, size_t r) { Execute(); return m_results[i * m_regexps + r]; }
-	const std::vector<uint32_t>& Results() { Execute(); return m_results; }       // [n][RegexpsCount()]
-	const std::vector<uint32_t>& StateIndices() { Execute(); return m_idx; }      // StateIndex(State()) per string
-
-	/*
-	 * The strings whose counts reach their thresholds, without a loop on the host (pire_hip_count_select behind the scan):
-	 *     run.Begin().Run(text, offsets, n).End().Select();    // the strings in which some regexp occurred
-	 *     run.Select({3, 0, 1});                                // ... regexp 0 three times or regexp 2 once (0 = not asked)
-	 *     run.Select({3, 0, 1}, true);                          // ... and regexp 2 once
-	 *     run.Hits()        the selected strings, ascending      run.HitResults()  their result rows, [k][RegexpsCount()]
-	 *     run.HitCount()    how many                             run.Totals()      occurrences per regexp over ALL strings
-	 *     run.Begin().RunLines(raw, size).End();                // the same per line of raw, split on the device, and
-	 *     run.HitSpans()    [2 * k], [2 * k + 1]: line Hits()[k] is raw[begin, end)        run.LineCount()  lines in the buffer
-	 * After RunLines() there are hits only: Result() / Results() / StateIndices() throw.
-	 */
-	CountingBatchRunner& Select(const std::vector<uint32_t>& min = std::vector<uint32_t>(), bool all = false)
-	{
-		m_sel.Choose(min, all);
-		return *this;
-	}
-	CountingBatchRunner& RunLines(const char* raw, size_t size, char delim = '\n')
-	{
-		m_text = raw;
-		m_len = size;
-		m_delim = delim;
-		m_lines = true;
-		m_ran = false;
-		m_sel.fetched = false;
-		return *this;
-	}
-	const std::vector<uint64_t>& Hits() { FetchHits(); return m_sel.hits; }
-	const std::vector<uint32_t>& HitResults() { FetchHits(); return m_sel.rows; }
-	size_t HitCount() { FetchHits(); return size_t(m_sel.count); }
-	const std::vector<uint64_t>& Totals() { FetchHits(); return m_sel.totals; }
-	const std::vector<uint64_t>& HitSpans()
-	{
-		if (!m_lines)
-			throw Pire::Error("pire_hip: HitSpans() follows RunLines()");
-		FetchHits();
-		return m_sel.spans;
-	}
-	size_t LineCount()
-	{
-		if (!m_lines)
-			throw Pire::Error("pire_hip: LineCount() follows RunLines()");
-		FetchHits();
-		return size_t(m_sel.lineCount);
-	}
-
 private:
-	friend struct CountedHits;
-	/* RunLines(): room for a hit on every line of 64 bytes or more, and a second call where there are more */
-	void FetchHits() { m_sel.Fetch(*this, m_regexps, m_lines ? m_len / 64 + 16 : m_n, m_lines); }
-	void CountSelectCall(const uint32_t* min, uint32_t mode, uint64_t* totals, uint64_t* hits, uint64_t* spans, uint32_t* rows, uint64_t cap,
-	                     uint64_t* count, uint64_t* lineCount)
+	friend class CountedBatchRunner<CountingBatchRunner>;
+	enum { Kind = CountingKind<CountScanner>::Value };
+	int Scan(const uint64_t* offsets, uint32_t* idx, uint32_t* results)
 	{
-		static const uint64_t kNoOffsets[1] = {0};
-		if (m_lines)
-			Check(pire_hip_counting_lines_select(m_table, CountingKind<CountScanner>::Value, m_text, m_len, uint8_t(m_delim), m_flags, min, mode,
-			                                     lineCount, totals, hits, spans, rows, cap, count, nullptr));
-		else
-			Check(pire_hip_counting_run_select(m_table, CountingKind<CountScanner>::Value, m_text, m_n ? m_offsets : kNoOffsets, m_n, m_flags,
-			                                   nullptr, nullptr, min, mode, totals, hits, rows, cap, count, nullptr));
+		return pire_hip_counting_run(m_table, Kind, this->m_text, offsets, this->m_n, this->m_flags, idx, results, nullptr);
 	}
-	void Execute()
+	int SelectStrings(const uint64_t* offsets, const uint32_t* min, uint32_t mode, uint64_t* totals, uint64_t* hits, uint32_t* rows, uint64_t cap,
+	                  uint64_t* count)
 	{
-		if (m_ran)
-			return;
-		if (m_lines)
-			throw Pire::Error("pire_hip: RunLines() has hits, no results per string");
-		m_idx.assign(m_n, 0);
-		m_results.assign(m_n * (m_regexps ? m_regexps : 1), 0);
-		static const uint64_t kNoOffsets[1] = {0};
-		Check(pire_hip_counting_run(m_table, CountingKind<CountScanner>::Value, m_text, m_n ? m_offsets : kNoOffsets, m_n,
-		                            m_flags, m_idx.data(), m_results.data(), nullptr));
-		m_ran = true;
+		return pire_hip_counting_run_select(m_table, Kind, this->m_text, offsets, this->m_n, this->m_flags, nullptr, nullptr, min, mode, totals,
+		                                    hits, rows, cap, count, nullptr);
+	}
+	int SelectLines(const uint32_t* min, uint32_t mode, uint64_t* lineCount, uint64_t* totals, uint64_t* hits, uint64_t* spans, uint32_t* rows,
+	                uint64_t cap, uint64_t* count)
+	{
+		return pire_hip_counting_lines_select(m_table, Kind, this->m_text, this->m_len, this->m_delim, this->m_flags, min, mode, lineCount,
+		                                      totals, hits, spans, rows, cap, count, nullptr);
 	}
 
 	CountingBatchRunner(const CountingBatchRunner&);
 	CountingBatchRunner& operator=(const CountingBatchRunner&);
 	pire_hip_counting_table* m_table;
-	size_t m_regexps;
-	uint32_t m_flags;
-	const char* m_text;
-	const uint64_t* m_offsets;
-	size_t m_n;
-	bool m_ran;
-	size_t m_len;                 // RunLines(): m_text is the raw buffer of m_len bytes
-	char m_delim;
-	bool m_lines;
-	CountedHits m_sel;
-	std::vector<uint32_t> m_idx, m_results;
-	ystring m_ownText;
-	std::vector<uint64_t> m_ownOffsets;
 };
 #endif  // PIRE_EXTRA_COUNT_H
 
@@ -1303,9 +1261,7 @@ public:
 	    : m_table(nullptr), m_flags(0), m_text(nullptr), m_offsets(nullptr), m_n(0), m_ran(false), m_lines(false), m_len(0),
 	      m_delim('\n'), m_listed(false), m_textFetched(false), m_textTail('\n'), m_lineCount(0)
 	{
-		std::ostringstream out;
-		sc.Save(&out);                                    // LoadedScanner::Save, scanner_io.cpp:172-189
-		const std::string blob = out.str();
+		const std::string blob = SavedBlob(sc);
 		Check(pire_hip_counting_table_create(blob.data(), blob.size(), &m_table));
 	}
 	~CaptureBatchRunner() { pire_hip_counting_table_destroy(m_table); }
@@ -1332,13 +1288,8 @@ public:
 	}
 	CaptureBatchRunner& Run(const std::vector<ystring>& strings)
 	{
-		m_ownText.clear();
-		m_ownOffsets.assign(1, 0);
-		for (size_t i = 0; i < strings.size(); ++i) {
-			m_ownText.append(strings[i]);
-			m_ownOffsets.push_back(m_ownText.size());
-		}
-		return Run(m_ownText.data(), m_ownOffsets.data(), strings.size());
+		m_ownStrings.Assign(strings);
+		return Run(m_ownStrings.Text(), m_ownStrings.Offsets(), strings.size());
 	}
 
 	bool Captured(size_t i) { Execute(); return m_begin[i] >= 0 && m_end[i] >= 0; }     // State::Captured()
@@ -1359,18 +1310,22 @@ public:
 	}
 
 private:
+	void ResultsPerString()
+	{
+		m_idx.assign(m_n, 0);
+		m_final.assign(m_n, 0);
+		m_begin.assign(m_n, -1);
+		m_end.assign(m_n, -1);
+	}
+
 	void Execute()
 	{
 		if (m_lines)
 			throw Pire::Error("pire_hip: the accessors per string follow Run(), not RunLines()");
 		if (m_ran)
 			return;
-		m_idx.assign(m_n, 0);
-		m_final.assign(m_n, 0);
-		m_begin.assign(m_n, -1);
-		m_end.assign(m_n, -1);
-		static const uint64_t kNoOffsets[1] = {0};
-		Check(pire_hip_capture_run(m_table, m_text, m_n ? m_offsets : kNoOffsets, m_n, m_flags, m_idx.data(), m_final.data(),
+		ResultsPerString();
+		Check(pire_hip_capture_run(m_table, m_text, OwnedStrings::OffsetsOr(m_offsets, m_n), m_n, m_flags, m_idx.data(), m_final.data(),
 		                           m_begin.data(), m_end.data(), nullptr));
 		m_ran = true;
 	}
@@ -1383,33 +1338,28 @@ private:
 			return;
 		uint64_t count = 0;
 		if (!m_lines) {
-			m_idx.assign(m_n, 0);
-			m_final.assign(m_n, 0);
-			m_begin.assign(m_n, -1);
-			m_end.assign(m_n, -1);
+			ResultsPerString();
 			m_hits.resize(m_n);
 			m_spans.resize(m_n * 2);
-			static const uint64_t kNoOffsets[1] = {0};
-			Check(pire_hip_capture_run_select(m_table, m_text, m_n ? m_offsets : kNoOffsets, m_n, m_flags, 0, m_idx.data(), m_final.data(),
-			                                  m_begin.data(), m_end.data(), m_hits.data(), m_spans.data(), m_n, &count, nullptr));
+			Check(pire_hip_capture_run_select(m_table, m_text, OwnedStrings::OffsetsOr(m_offsets, m_n), m_n, m_flags, 0, m_idx.data(),
+			                                  m_final.data(), m_begin.data(), m_end.data(), m_hits.data(), m_spans.data(), m_n, &count, nullptr));
 			m_lineCount = m_n;
 			m_ran = true;
 		} else {
-			for (size_t cap = m_len / 64 + 1024;; cap = count) {
+			GrowAndRetry(m_len / 64 + 1024, [&](size_t cap) {
 				m_hits.resize(cap);
 				m_spans.resize(cap * 2);
 				Check(pire_hip_capture_lines_gather(m_table, m_text, m_len, m_delim, m_flags, 0, PIRE_HIP_GATHER_NO_TAIL, &m_lineCount,
 				                                    m_hits.data(), m_spans.data(), cap, &count, nullptr, 0, nullptr, nullptr, nullptr));
-				if (count <= cap)
-					break;
-			}
+				return size_t(count);
+			});
 		}
 		m_hits.resize(count);
 		m_spans.resize(count * 2);
 		m_listed = true;
 	}
 
-	/* RunLines(): the captured fields as bytes (and the list with them); the grow-and-retry of FetchList() */
+	/* RunLines(): the captured fields as bytes (and the list with them); room for the list that is known, or else FetchList()'s */
 	void FetchText(char tail)
 	{
 		if (!m_lines)
@@ -1417,7 +1367,7 @@ private:
 		if (m_textFetched && m_textTail == tail)
 			return;
 		uint64_t count = 0, bytes = 0;
-		for (size_t cap = m_listed ? m_hits.size() : m_len / 64 + 1024;; cap = count) {
+		GrowAndRetry(m_listed ? m_hits.size() : m_len / 64 + 1024, [&](size_t cap) {
 			m_hits.resize(cap);
 			m_spans.resize(cap * 2);
 			m_capturedOffsets.resize(cap + 1);
@@ -1425,9 +1375,8 @@ private:
 			Check(pire_hip_capture_lines_gather(m_table, m_text, m_len, m_delim, m_flags, 0, uint8_t(tail), &m_lineCount, m_hits.data(),
 			                                    m_spans.data(), cap, &count, &m_capturedText[0], m_capturedText.size(),
 			                                    m_capturedOffsets.data(), &bytes, nullptr));
-			if (count <= cap && bytes <= m_capturedText.size())
-				break;
-		}
+			return size_t(count);   // (the bytes fit where the hits do, as in BatchRunner::FetchHitText())
+		});
 		m_hits.resize(count);
 		m_spans.resize(count * 2);
 		m_capturedText.resize(bytes);
@@ -1447,8 +1396,7 @@ private:
 	std::vector<uint32_t> m_idx;
 	std::vector<uint8_t> m_final;
 	std::vector<int64_t> m_begin, m_end;
-	ystring m_ownText;
-	std::vector<uint64_t> m_ownOffsets;
+	OwnedStrings m_ownStrings;
 	bool m_lines;                 // RunLines(): m_text is the raw buffer of m_len bytes
 	size_t m_len;
 	uint8_t m_delim;
@@ -1469,9 +1417,7 @@ public:
 	explicit SlowBatchRunner(const Pire::SlowScanner& sc)
 	    : m_table(nullptr)
 	{
-		std::ostringstream out;
-		sc.Save(&out);                                    // scanner_io.cpp:71-111
-		const std::string blob = out.str();
+		const std::string blob = SavedBlob(sc);
 		Check(pire_hip_slow_table_create(blob.data(), blob.size(), &m_table));
 	}
 	~SlowBatchRunner() { pire_hip_slow_table_destroy(m_table); }
@@ -1480,8 +1426,7 @@ public:
 	std::vector<char> Matches(const char* text, const uint64_t* offsets, size_t n)
 	{
 		std::vector<uint8_t> fin(n);
-		static const uint64_t kNoOffsets[1] = {0};
-		Check(pire_hip_slow_run(m_table, text, n ? offsets : kNoOffsets, n, PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END,
+		Check(pire_hip_slow_run(m_table, text, OwnedStrings::OffsetsOr(offsets, n), n, PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END,
 		                        fin.data(), nullptr, nullptr, nullptr));
 		return std::vector<char>(fin.begin(), fin.end());
 	}

@@ -2,6 +2,7 @@
 import gzip
 import json
 import os
+import subprocess
 
 import numpy as np
 
@@ -43,6 +44,13 @@ def pack(strings):
         offs[1:] = np.cumsum([len(s) for s in strings], dtype=np.uint64)
     text = np.frombuffer(b"".join(strings), dtype=np.uint8) if strings else np.zeros(0, np.uint8)
     return text, offs
+
+
+def make_shim_program(name, *args):
+    """`make -C tests/cpp NAME`: tests/cpp/NAME.cpp against the reference headers into oracle/_ref/bin/NAME, with the flags every
+    program that includes the shim gets (tests/cpp/shim.mk); oracle/_ref/libpire_ref.so is there before.  The finished process."""
+    return subprocess.run(["make", "-C", os.path.join(os.path.dirname(GOLDEN), "cpp"), name] + list(args), stdout=subprocess.PIPE,
+                          stderr=subprocess.STDOUT, text=True, timeout=900)
 
 
 def plants_for(big):

@@ -738,13 +738,7 @@ REF_PRESENT = os.path.exists(os.path.join(ob.REFERENCE_ROOT, "pire", "extra.h"))
 def test_capture_lines_program_compiles_against_reference_headers():
     """tests/cpp/capture_lines_test.cpp with the flags oracle/Makefile gives tests/cpp/shim_test.cpp, next to it in oracle/_ref/bin"""
     ob.build()
-    ref = ob.REFERENCE_ROOT
-    os.makedirs(os.path.dirname(SHIM_BIN), exist_ok=True)
-    cmd = [os.environ.get("CXX", "g++"), "-std=c++14", "-O1", "-DPIRE_NO_CONFIG", "-w", "-include", "limits", "-I" + ref, "-I" + os.path.join(ref, "pire"),
-           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "capture_lines_test.cpp"), "-o", SHIM_BIN,
-           "-L" + REF_DIR, "-lpire_ref", "-Wl,-rpath,$ORIGIN/..", "-L" + os.path.join(ROOT, "pire_amd"), "-lpire_hip", "-L/opt/rocm/lib", "-lamdhip64",
-           "-Wl,-rpath,$ORIGIN/../../../pire_amd", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
+    r = H.make_shim_program("capture_lines_test")
     assert r.returncode == 0, r.stdout[-3000:]
     assert os.path.exists(SHIM_BIN)
 

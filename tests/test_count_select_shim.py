@@ -8,6 +8,7 @@ import subprocess
 import pytest
 
 from oracle import binding as ob
+from tests import helpers as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_DIR = os.path.join(ROOT, "oracle", "_ref")
@@ -19,16 +20,10 @@ REF_PRESENT = os.path.exists(os.path.join(ob.REFERENCE_ROOT, "pire", "run.h"))
 def test_count_select_shim_compiles_against_reference_headers_and_runs_without_a_device():
     """tests/cpp/count_select_shim_test.cpp with the flags oracle/Makefile gives tests/cpp/shim_test.cpp, next to it in oracle/_ref/bin"""
     ob.build()
-    ref = ob.REFERENCE_ROOT
     r = subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "ref"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:]
-    os.makedirs(os.path.dirname(BIN), exist_ok=True)
-    cmd = [os.environ.get("CXX", "g++"), "-std=c++14", "-O1", "-DPIRE_NO_CONFIG", "-w", "-include", "limits", "-I" + ref,
-           "-I" + os.path.join(ref, "pire"), "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "count_select_shim_test.cpp"),
-           "-o", BIN, "-L" + REF_DIR, "-lpire_ref", "-Wl,-rpath,$ORIGIN/..", "-L" + os.path.join(ROOT, "pire_amd"), "-lpire_hip",
-           "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,$ORIGIN/../../../pire_amd", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
+    r = H.make_shim_program("count_select_shim_test")
     assert r.returncode == 0, r.stdout[-3000:]
     r = subprocess.run([BIN], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-3000:]
