@@ -822,6 +822,17 @@ typedef struct pire_hip_slow_info {
 int pire_hip_slow_table_create(const void* save_blob, size_t len, pire_hip_slow_table** out);
 void pire_hip_slow_table_destroy(pire_hip_slow_table* t);
 int pire_hip_slow_table_get_info(const pire_hip_slow_table* t, pire_hip_slow_info* out);
+/* What a run of n strings would launch (performance only; every form gives the same results), under the current
+ * configuration: `ragged` != 0 for the offsets form, 0 for fixed-length records; `cus` = compute units to plan for, 0 = those
+ * of the current device (any other value needs no device).  out[0] = the kernel that runs first (0 the 16-slot list kernel,
+ * 1 the bitset kernel, 2 the wave-per-string kernel), out[1] = the kernel that walks whole strings (1 or 2: after the list
+ * kernel it takes the strings that left it), out[2] = words per lane of the bitset kernel (1, 2, 4, 8; 0: more than 256
+ * states), out[3] = 1 if the table has a list form, out[4] / out[5] = 1 if the bitset kernel keeps its first-targets table /
+ * its masks in LDS, out[6..9] = threads per block, blocks, LDS bytes and grid-stride passes of the first kernel,
+ * out[10] = waves per block of the wave-per-string kernel, out[11] / out[12] / out[13] = 1 if that kernel keeps the jump
+ * positions / the jumps / the state sets in LDS, out[14] = 1 if the list kernel takes the strings by length class,
+ * out[15..18] = as out[6..9] for the kernel of out[1], out[19] = the compute units planned for, out[20..23] = 0. */
+int pire_hip_slow_table_plan(const pire_hip_slow_table* t, uint64_t n, uint32_t ragged, uint32_t cus, uint32_t out[24]);
 
 /*
  * For each string: Initialize (slow.h:89-95); Begin() if flags&BEGIN; Run (the SlowScanner specialisation,

@@ -218,6 +218,7 @@ ABI = [
     ("pire_hip_slow_table_create", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     ("pire_hip_slow_table_destroy", None, [C.c_void_p]),
     ("pire_hip_slow_table_get_info", C.c_int, [C.c_void_p, C.POINTER(SlowInfo)]),
+    ("pire_hip_slow_table_plan", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32 * 24)]),
     ("pire_hip_slow_run", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     ("pire_hip_slow_run_strided", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
@@ -1259,6 +1260,19 @@ class SlowTable:
     Empty = property(lambda s: bool(s.info.empty))
     words = property(lambda s: s.info.words)
 
+    PLAN_KERNELS = ("slow_list", "slow", "slow_wide")   # as last_kernel() names them
+
+    def plan(self, n: int, ragged: bool = True, cus: int = 0) -> dict:
+        """What a run of n strings would launch under the current configuration (pire_hip_slow_table_plan); cus = 0: the
+        current device's compute units, any other value needs no device."""
+        out = (C.c_uint32 * 24)()
+        _check(lib().pire_hip_slow_table_plan(self._h, n, int(bool(ragged)), cus, C.byref(out)))
+        grid = lambda i: {"threads": out[i], "blocks": out[i + 1], "lds_bytes": out[i + 2], "passes": out[i + 3]}
+        return {"kernel": self.PLAN_KERNELS[out[0]], "walker": self.PLAN_KERNELS[out[1]], "k": out[2],
+                "list_table": bool(out[3]), "single_in_lds": bool(out[4]), "masks_in_lds": bool(out[5]), **grid(6),
+                "waves": out[10], "pos_in_lds": bool(out[11]), "jumps_in_lds": bool(out[12]), "sets_in_lds": bool(out[13]),
+                "by_length": bool(out[14]), "walk": grid(15), "cus": out[19]}
+
     def run(self, text, offsets, flags=FLAG_BEGIN | FLAG_END, counts=False):
         text = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray))
                                     else text, dtype=np.uint8)
@@ -1276,6 +1290,11 @@ class SlowTable:
         if strings:
             offs[1:] = np.cumsum([len(s) for s in strings], dtype=np.uint64)
         return self.run(np.frombuffer(b"".join(strings), dtype=np.uint8), offs, **kw)
+
+    def run_device(self, text_ptr, offsets_ptr, n, flags, out_final_ptr=0, out_bits_ptr=0, out_counts_ptr=0, stream=0):
+        """pire_hip_slow_run with every pointer on the device (offsets: n + 1 uint64)."""
+        _check(lib().pire_hip_slow_run(self._h, text_ptr or None, offsets_ptr or None, n, flags | FLAG_ON_DEVICE,
+                                       out_final_ptr or None, out_bits_ptr or None, out_counts_ptr or None, stream or None))
 
     def run_strided_device(self, text_ptr, n, length, stride, flags, out_final_ptr=0, out_bits_ptr=0, out_counts_ptr=0,
                            stream=0):

@@ -1057,6 +1057,8 @@ __host__ __device__ inline uint64_t OrderedIndex(uint64_t pass, uint64_t t, uint
 // whether the kernels should walk it with OrderedIndex's serpentine (the global order) or plainly.  Else leaves both alone.
 int OrderByLength(const uint64_t* offsets, uint64_t n, hipStream_t stream, StreamScratch& scratch, const uint32_t** order,
                   uint32_t* serpentine);
+// Whether OrderByLength builds an order for a batch of n strings (for a launch plan that has to say so beforehand).
+bool OrdersByLength(uint64_t n, const pire_hip_config& c);
 // select.hip: from end states to matches (pire_hip_select).  UploadSelect: the mask image of the CURRENT device, built on
 // first use (the caller holds t->adaptMutex, shared: the host image is built from t->host), copied out to *image (nullable).
 // LaunchSelect: device pointers only, enqueues three small kernels on `stream`, scratch from the stream-ordered allocator.

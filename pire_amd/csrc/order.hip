@@ -126,11 +126,16 @@ uint32_t OrderBlocks(uint64_t n)
 
 }  // namespace
 
+bool OrdersByLength(uint64_t n, const pire_hip_config& c)
+{
+	// below a few lane-fills of the chip the launches cost more than the idle lanes; indices are 32 bits
+	return !(n < 32768 || n >= (1ull << 32) || c.no_length_order);
+}
+
 int OrderByLength(const uint64_t* offsets, uint64_t n, hipStream_t stream, StreamScratch& scratch, const uint32_t** order,
                   uint32_t* serpentine)
 {
-	// below a few lane-fills of the chip the launches cost more than the idle lanes; indices are 32 bits
-	if (n < 32768 || n >= (1ull << 32) || GetConfig().no_length_order)
+	if (!OrdersByLength(n, GetConfig()))
 		return PIRE_HIP_OK;
 	const size_t permBytes = (size_t(n) * 4 + 255) & ~size_t(255);
 	const uint32_t blocks = OrderBlocks(n);

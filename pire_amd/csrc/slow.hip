@@ -962,81 +962,145 @@ int UploadSlow(pire_hip_slow_table* t, SlowDevice* image)
 	return PIRE_HIP_OK;
 }
 
-template <int K>
-int LaunchSlowK(const SlowParams& p0, hipStream_t stream)
+// ---- the launch plan ------------------------------------------------------------------------------------------------
+// Everything a launch decides from the automaton's geometry and the batch, in ONE place: the launchers below read a
+// SlowPlan and decide nothing themselves, and pire_hip_slow_table_plan hands the same plan to a test, so that a test can
+// say which form an input reaches (and notice when a constant moves and a form loses its fixture).
+struct SlowGeometry {
+	uint32_t states, letters, words, njumps;
+	bool listTable;   // SlowHost::pair16 was built: (states + 1) * letters <= kListMaxRows
+};
+
+struct SlowGrid {
+	uint32_t threads = 0, blocks = 0, ldsBytes = 0;
+	uint64_t passes = 0;   // trips of a lane (list, bitset kernel) or wave (wave per string) through its grid-stride loop
+};
+
+enum : uint32_t { kSlowFirstList = 0, kSlowFirstScan = 1, kSlowFirstWide = 2 };
+
+struct SlowPlan {
+	uint32_t first = 0;      // the kernel that runs first: kSlowFirst*
+	uint32_t walker = 0;     // the kernel that walks whole strings: kSlowFirstScan or kSlowFirstWide (after the list kernel: over
+	                         // the strings that left it, with the grid of the whole batch)
+	uint32_t K = 0;          // SlowScanKernel<K>; 0: wide
+	uint32_t listTable = 0;
+	uint32_t byLength = 0;   // list kernel: strings by length class, passes in a serpentine
+	SlowGrid list;           // first == kSlowFirstList
+	uint32_t singleInLds = 0, masksInLds = 0;                        // SlowScanKernel
+	uint32_t waves = 0, posInLds = 0, jumpsInLds = 0, setsInLds = 0; // SlowWideKernel
+	SlowGrid walk;
+};
+
+constexpr size_t kSlowSingleLdsMax = 64 * 1024;          // SlowScanKernel: `single` in LDS up to this size ...
+constexpr size_t kSlowTablesLdsMax = 150 * 1024;         // ... and the masks when both fit this
+constexpr uint64_t kSlowScanBigBatch = 128 * 1024;       // SlowScanKernel: 1024-thread blocks from here
+constexpr size_t kSlowWideLdsRoom = 158 * 1024 - 272;    // SlowWideKernel: sets, jumpPos, jumps
+constexpr uint32_t kSlowWideWaves = 16;
+
+uint64_t GridPasses(uint64_t n, uint64_t lanes)
 {
-	SlowParams p = p0;
-	const size_t maskBytes = size_t(p.states) * p.letters * K * 4;
-	const size_t singleBytes = size_t(p.states + 1) * p.letters * 8;
-	p.singleInLds = singleBytes <= 64 * 1024 ? 1 : 0;
-	p.masksInLds = maskBytes + (p.singleInLds ? singleBytes : 0) <= 150 * 1024 ? 1 : 0;
-	const uint32_t ldsBytes = uint32_t(272 + (p.singleInLds ? singleBytes : 0) + (p.masksInLds ? maskBytes : 0));
-	int cus = 0;
-	if (int rc = DeviceCUs(&cus))
-		return rc;
-	// big batches: 1024-thread blocks, as many per CU as the LDS copy of the masks allows (32 waves per CU at most);
-	// small ones: 256-thread blocks so that more CUs take part
-	const unsigned threads = p.n >= 128 * 1024 ? 1024 : 256;
-	return Launch(SlowScanKernel<K>, GridBlocks(p.n, cus, threads, ldsBytes), threads, ldsBytes, stream, "slow kernel launch", p);
+	return (n + lanes - 1) / lanes;
 }
 
-// One wave per string.  LDS budget, in this order: the two sets of every wave (16 waves per block, fewer when the sets
-// are large; device memory from the stream-ordered pool when not even one wave's fit), then jumpPos, then the jumps.
-int LaunchSlowWide(const SlowParams& p0, uint32_t njumps, hipStream_t stream)
+SlowPlan PlanSlow(const SlowGeometry& g, uint64_t n, bool ragged, int cus, const pire_hip_config& c)
+{
+	SlowPlan plan;
+	const bool wide = g.words > 8;
+	plan.K = wide ? 0 : uint32_t(DeviceK(g.words));
+	plan.listTable = g.listTable ? 1 : 0;
+	plan.walker = wide ? kSlowFirstWide : kSlowFirstScan;
+	plan.first = g.listTable && n < (1ull << 32) - 1 && !c.slow_no_list ? uint32_t(kSlowFirstList) : plan.walker;
+	if (plan.first == kSlowFirstList) {
+		// ragged batches: the strings by length class (order.hip) -- this kernel is all VALU, a wave waiting for its longest
+		// string is its one avoidable cost
+		plan.byLength = ragged && OrdersByLength(n, c) ? 1 : 0;
+		SlowGrid& l = plan.list;
+		l.ldsBytes = uint32_t(1056 + 16 + size_t(g.states + 1) * g.letters * 4);
+		// one string per lane and ~100 VALU instructions per byte: spread the waves over every SIMD of the chip before
+		// stacking them (65 536 strings are 1 024 waves = one per SIMD: 256-thread blocks, one per CU)
+		l.threads = n >= uint64_t(cus) * 2048 ? 1024 : n >= uint64_t(cus) * 512 ? 512 : 256;
+		l.blocks = GridBlocks(n, cus, l.threads, l.ldsBytes);
+		l.passes = GridPasses(n, uint64_t(l.blocks) * l.threads);
+	}
+	SlowGrid& w = plan.walk;
+	if (!wide) {
+		const size_t maskBytes = size_t(g.states) * g.letters * plan.K * 4;
+		const size_t singleBytes = size_t(g.states + 1) * g.letters * 8;
+		plan.singleInLds = singleBytes <= kSlowSingleLdsMax ? 1 : 0;
+		plan.masksInLds = maskBytes + (plan.singleInLds ? singleBytes : 0) <= kSlowTablesLdsMax ? 1 : 0;
+		w.ldsBytes = uint32_t(272 + (plan.singleInLds ? singleBytes : 0) + (plan.masksInLds ? maskBytes : 0));
+		// big batches: 1024-thread blocks, as many per CU as the LDS copy of the masks allows (32 waves per CU at most);
+		// small ones: 256-thread blocks so that more CUs take part
+		w.threads = n >= kSlowScanBigBatch ? 1024 : 256;
+		w.blocks = GridBlocks(n, cus, w.threads, w.ldsBytes);
+		w.passes = GridPasses(n, uint64_t(w.blocks) * w.threads);
+		return plan;
+	}
+	// One wave per string.  LDS budget, in this order: the two sets of every wave (16 waves per block, fewer when the sets
+	// are large; device memory from the stream-ordered pool when not even one wave's fit), then jumpPos, then the jumps.
+	const size_t setBytes = size_t(g.words) * 8;   // cur + next of one wave
+	uint32_t waves = uint32_t(std::min<size_t>(kSlowWideWaves, kSlowWideLdsRoom / setBytes));
+	const bool inLds = waves >= 1 && !c.slow_sets_in_memory;   // (the knob: tests run the device-memory form at any size)
+	if (!inLds)
+		waves = kSlowWideWaves;
+	size_t room = kSlowWideLdsRoom - (inLds ? waves * setBytes : 0);
+	const size_t posBytes = (size_t(g.states) * g.letters + 1) * 4, jumpBytes = size_t(g.njumps) * 4;
+	plan.posInLds = posBytes <= room ? 1 : 0;
+	if (plan.posInLds)
+		room -= posBytes;
+	plan.jumpsInLds = plan.posInLds && jumpBytes <= room ? 1 : 0;
+	plan.setsInLds = inLds ? 1 : 0;
+	plan.waves = waves;
+	w.threads = waves * 64;
+	w.blocks = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((n + waves - 1) / waves, uint64_t(cus))));
+	w.ldsBytes = uint32_t(272 + (inLds ? waves * setBytes : 0) + (plan.posInLds ? posBytes : 0) + (plan.jumpsInLds ? jumpBytes : 0));
+	w.passes = GridPasses(n, uint64_t(w.blocks) * waves);
+	return plan;
+}
+
+SlowGeometry GeometryOf(const SlowHost& h)
+{
+	return SlowGeometry{h.states, h.letters, h.words, uint32_t(h.jumps.size()), !h.pair16.empty()};
+}
+
+template <int K>
+int LaunchSlowK(const SlowParams& p0, const SlowPlan& plan, hipStream_t stream)
 {
 	SlowParams p = p0;
-	int cus = 0;
-	if (int rc = DeviceCUs(&cus))
-		return rc;
-	const size_t setBytes = size_t(p.words) * 8;   // cur + next of one wave
-	const size_t ldsRoom = 158 * 1024 - 272;
-	uint32_t waves = uint32_t(std::min<size_t>(16, ldsRoom / setBytes));
-	const bool inLds = waves >= 1 && !GetConfig().slow_sets_in_memory;   // (the knob: tests run the device-memory form at any size)
-	if (!inLds)
-		waves = 16;
-	size_t room = ldsRoom - (inLds ? waves * setBytes : 0);
-	const size_t posBytes = (size_t(p.states) * p.letters + 1) * 4, jumpBytes = size_t(njumps) * 4;
-	const uint32_t posInLds = posBytes <= room ? 1 : 0;
-	if (posInLds)
-		room -= posBytes;
-	const uint32_t jumpsInLds = posInLds && jumpBytes <= room ? 1 : 0;
-	const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((p.n + waves - 1) / waves, uint64_t(cus)));
+	p.singleInLds = plan.singleInLds;
+	p.masksInLds = plan.masksInLds;
+	return Launch(SlowScanKernel<K>, plan.walk.blocks, plan.walk.threads, plan.walk.ldsBytes, stream, "slow kernel launch", p);
+}
+
+int LaunchSlowWide(const SlowParams& p0, const SlowPlan& plan, uint32_t njumps, hipStream_t stream)
+{
+	SlowParams p = p0;
 	StreamScratch scratch(stream);
-	if (!inLds) {
-		if (int rc = scratch.Alloc(blocks * waves * setBytes, "hipMallocAsync(slow scanner sets)"))
+	if (!plan.setsInLds) {
+		if (int rc = scratch.Alloc(uint64_t(plan.walk.blocks) * plan.waves * p.words * 8, "hipMallocAsync(slow scanner sets)"))
 			return rc;
 		p.scratch = scratch.as<uint32_t>();
 	}
-	const uint32_t ldsBytes = uint32_t(272 + (inLds ? waves * setBytes : 0) + (posInLds ? posBytes : 0) + (jumpsInLds ? jumpBytes : 0));
-	return Launch(inLds ? SlowWideKernel<true> : SlowWideKernel<false>, unsigned(blocks), waves * 64, ldsBytes, stream,
-	              "slow kernel launch", p, waves, posInLds, jumpsInLds, njumps);
+	return Launch(plan.setsInLds ? SlowWideKernel<true> : SlowWideKernel<false>, plan.walk.blocks, plan.walk.threads, plan.walk.ldsBytes,
+	              stream, "slow kernel launch", p, plan.waves, plan.posInLds, plan.jumpsInLds, njumps);
 }
 
 // List form first: SlowListKernel over the whole batch, then `fallback` -- the bitset kernel (<= 256 states) or the
 // wave-per-string kernel (more) -- over the strings whose sets outgrew the list (usually none; the count stays on the
 // device, an empty second launch costs a few microseconds).  The overflow list lives in stream-ordered scratch.
 template <class Fallback>
-int LaunchSlowListThen(const SlowParams& p0, hipStream_t stream, Fallback fallback)
+int LaunchSlowListThen(const SlowParams& p0, const SlowPlan& plan, hipStream_t stream, Fallback fallback)
 {
 	SlowParams p = p0;
-	int cus = 0;
-	if (int rc = DeviceCUs(&cus))
-		return rc;
 	StreamScratch list(stream);
 	if (int rc = OverflowList(list, p.n, stream, "hipMallocAsync(slow scanner overflow list)", &p.overflow))
 		return rc;
-	// ragged batches: the strings by length class (order.hip) -- this kernel is all VALU, a wave waiting for its longest
-	// string is its one avoidable cost
 	StreamScratch orderScratch(stream);
 	p.order = nullptr;
-	if (p.offsets)
+	if (plan.byLength)
 		if (int rc = OrderByLength(p.offsets, p.n, stream, orderScratch, &p.order, &p.serpentine))
 			return rc;
-	const uint32_t ldsBytes = uint32_t(1056 + 16 + size_t(p.states + 1) * p.letters * 4);
-	// one string per lane and ~100 VALU instructions per byte: spread the waves over every SIMD of the chip before
-	// stacking them (65 536 strings are 1 024 waves = one per SIMD: 256-thread blocks, one per CU)
-	const unsigned threads = p.n >= uint64_t(cus) * 2048 ? 1024 : p.n >= uint64_t(cus) * 512 ? 512 : 256;
-	if (int rc = Launch(SlowListKernel, GridBlocks(p.n, cus, threads, ldsBytes), threads, ldsBytes, stream, "slow kernel launch", p))
+	if (int rc = Launch(SlowListKernel, plan.list.blocks, plan.list.threads, plan.list.ldsBytes, stream, "slow kernel launch", p))
 		return rc;
 	if (GetConfig().slow_stats) {   // measurements: how many strings the 16-slot list could not hold
 		uint32_t over = 0;
@@ -1078,28 +1142,29 @@ int RunSlow(pire_hip_slow_table* t, const void* text, const uint64_t* offsets, u
 	p.stride = stride;
 	if (n == 0)
 		return PIRE_HIP_OK;
-	const int K = DeviceK(h.words);
-	const bool listFirst = image.pair16 && n < (1ull << 32) - 1 && !GetConfig().slow_no_list;
+	int cus = 0;
+	if (int rc = DeviceCUs(&cus))
+		return rc;
+	const SlowPlan plan = PlanSlow(GeometryOf(h), n, offsets != nullptr, cus, GetConfig());
 	auto plain = [&](const SlowParams& q) {
-		if (h.wide)
-			return LaunchSlowWide(q, uint32_t(h.jumps.size()), stream);
-		switch (K) {
-		case 1: return LaunchSlowK<1>(q, stream);
-		case 2: return LaunchSlowK<2>(q, stream);
-		case 4: return LaunchSlowK<4>(q, stream);
-		default: return LaunchSlowK<8>(q, stream);
+		switch (plan.K) {
+		case 0: return LaunchSlowWide(q, plan, uint32_t(h.jumps.size()), stream);
+		case 1: return LaunchSlowK<1>(q, plan, stream);
+		case 2: return LaunchSlowK<2>(q, plan, stream);
+		case 4: return LaunchSlowK<4>(q, plan, stream);
+		default: return LaunchSlowK<8>(q, plan, stream);
 		}
 	};
 	auto launch = [&](const SlowParams& q) {
-		if (listFirst) {
+		if (plan.first == kSlowFirstList) {
 			NoteKernel("slow_list", "pirehip::SlowListKernel");
-			return LaunchSlowListThen(q, stream, plain);
+			return LaunchSlowListThen(q, plan, stream, plain);
 		}
-		if (h.wide)
+		if (plan.first == kSlowFirstWide)
 			NoteKernel("slow_wide", "pirehip::SlowWideKernel");
 		else
-			NoteKernel("slow", K == 1 ? "pirehip::SlowScanKernel<1>" : K == 2 ? "pirehip::SlowScanKernel<2>" :
-			                    K == 4 ? "pirehip::SlowScanKernel<4>" : "pirehip::SlowScanKernel<8>");
+			NoteKernel("slow", plan.K == 1 ? "pirehip::SlowScanKernel<1>" : plan.K == 2 ? "pirehip::SlowScanKernel<2>" :
+			                    plan.K == 4 ? "pirehip::SlowScanKernel<4>" : "pirehip::SlowScanKernel<8>");
 		return plain(q);
 	};
 	BatchIO io(stream, (flags & PIRE_HIP_RUN_ON_DEVICE) != 0);
@@ -1175,6 +1240,49 @@ try {
 	out->words = t->host.words;
 	out->empty = t->host.empty ? 1 : 0;
 	out->mask_bytes = uint64_t(t->host.masks.size()) * 4;
+	return PIRE_HIP_OK;
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_slow_table_plan(const pire_hip_slow_table* t, uint64_t n, uint32_t ragged, uint32_t cus, uint32_t out[24])
+try {
+	if (!t || !out) {
+		SetError("null argument");
+		return PIRE_HIP_EINVAL;
+	}
+	int units = int(cus);
+	if (cus == 0)
+		if (int rc = DeviceCUs(&units))
+			return rc;
+	if (units <= 0) {
+		SetError("bad CU count");
+		return PIRE_HIP_EINVAL;
+	}
+	const SlowPlan plan = PlanSlow(GeometryOf(t->host), n, ragged != 0, units, GetConfig());
+	const SlowGrid& first = plan.first == kSlowFirstList ? plan.list : plan.walk;
+	const auto sat = [](uint64_t v) { return uint32_t(std::min<uint64_t>(v, 0xFFFFFFFFu)); };
+	memset(out, 0, 24 * sizeof(uint32_t));
+	out[0] = plan.first;
+	out[1] = plan.walker;
+	out[2] = plan.K;
+	out[3] = plan.listTable;
+	out[4] = plan.singleInLds;
+	out[5] = plan.masksInLds;
+	out[6] = first.threads;
+	out[7] = first.blocks;
+	out[8] = first.ldsBytes;
+	out[9] = sat(first.passes);
+	out[10] = plan.waves;
+	out[11] = plan.posInLds;
+	out[12] = plan.jumpsInLds;
+	out[13] = plan.setsInLds;
+	out[14] = plan.byLength;
+	out[15] = plan.walk.threads;
+	out[16] = plan.walk.blocks;
+	out[17] = plan.walk.ldsBytes;
+	out[18] = sat(plan.walk.passes);
+	out[19] = uint32_t(units);
 	return PIRE_HIP_OK;
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
