@@ -846,6 +846,66 @@ int pire_hip_slow_run_strided(pire_hip_slow_table* t, const void* text, uint64_t
                               uint32_t flags, uint8_t* out_final, uint32_t* out_state_bits, uint64_t* out_counts,
                               void* stream);
 
+/*
+ * From Final flags to the strings that matched -- or did not: a compacted, ascending list of their indices.  It takes no
+ * table and no text: it reads one flag byte per string, what pire_hip_slow_run wrote (out_final), and a flag counts as set
+ * when it is not 0 -- so the pass also works behind out_final of pire_hip_run and pire_hip_run_pair.
+ *   selected(i) <=> (final[i] != 0) != (mode == PIRE_HIP_FINAL_SELECT_ZERO)
+ * mode: 0 selects the strings whose flag is set, PIRE_HIP_FINAL_SELECT_ZERO those whose flag is not (grep -v).
+ * out_hits[hit_cap] (nullable), hit_cap, *out_hit_count (required): exactly pire_hip_select's -- ascending, the full count
+ * also when it exceeds hit_cap, only the first min(count, hit_cap) entries written and nothing behind them; n == 0 writes
+ * a count of 0.  n < 2^32.
+ * flags: PIRE_HIP_RUN_ON_DEVICE -> every pointer is a device pointer and the call only enqueues on `stream`: classify per
+ *        tile of 1 024 strings, the one-block scan of pire_hip_select, scatter; no atomics, no block waits for another: the
+ *        same input gives the same bits.  Scratch (n / 8 + n / 256 bytes) comes from the stream-ordered allocator: the rule
+ *        and the capture-mode caveat stated at pire_hip_select.  `final` may have any alignment.  Otherwise host pointers:
+ *        staged, synchronises, the list comes back only as far as it was written.
+ * PIRE_HIP_EINVAL before any device is touched: a mode other than the two; null out_hit_count; n > 0 with null final;
+ * hit_cap > 0 with null out_hits; n >= 2^32.
+ * pire_hip_last_kernel() is not changed by the pass.  No first-use self-test (it takes no table, as pire_hip_split).
+ */
+#define PIRE_HIP_FINAL_SELECT_ZERO 1u   /* `mode` */
+int pire_hip_final_select(const uint8_t* final, uint64_t n, uint32_t mode, uint32_t flags, uint64_t* out_hits, uint64_t hit_cap,
+                          uint64_t* out_hit_count, void* stream);
+
+/*
+ * pire_hip_slow_run[_strided] followed by pire_hip_final_select on the same stream, behind whichever launch form the scan
+ * takes (list kernel, bitset kernel, wave-per-string kernel, list then hand-on).  t .. flags, out_final, out_state_bits,
+ * out_counts: as the run call; out_final is nullable here: the flags then live in stream-ordered scratch of the library's
+ * own.  mode, out_hits, hit_cap, out_hit_count: as pire_hip_final_select.  With host pointers the text is staged once, and
+ * scan and pass run on the staged copy before anything comes back.  Hit indices are relative to the whole batch.  They
+ * refuse what the run call refuses and what pire_hip_final_select refuses.  pire_hip_last_kernel() names the scan's kernel.
+ */
+int pire_hip_slow_run_select(pire_hip_slow_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
+                             uint32_t mode, uint8_t* out_final, uint32_t* out_state_bits, uint64_t* out_counts,
+                             uint64_t* out_hits, uint64_t hit_cap, uint64_t* out_hit_count, void* stream);
+int pire_hip_slow_run_select_strided(pire_hip_slow_table* t, const void* text, uint64_t n, uint64_t len, uint64_t stride,
+                                     uint32_t flags, uint32_t mode, uint8_t* out_final, uint32_t* out_state_bits,
+                                     uint64_t* out_counts, uint64_t* out_hits, uint64_t hit_cap, uint64_t* out_hit_count,
+                                     void* stream);
+
+/*
+ * Raw bytes in, the lines a SlowScanner matches -- or, with mode = PIRE_HIP_FINAL_SELECT_ZERO, does not match -- out: the
+ * split into scratch, the slow scan on the lines with the flags in scratch, the pass.  out_line_count (required), delim,
+ * out_hits (the numbers of the lines), out_hit_spans[hit_cap][2] (nullable, needs out_hits: the whole line of hit k as a
+ * byte range of raw, delimiter not included), hit_cap, out_hit_count, flags (BEGIN | END | ON_DEVICE), the one
+ * synchronisation of `stream` (reading n back; the call adds none) and the refusal of 2^32 lines: as
+ * pire_hip_run_lines_select, which has `want` and masks where this has `mode`.  pire_hip_slow_lines_gather adds the gather
+ * of the selected lines from raw: tail, out_hits (nullable: the library keeps the hit list to itself), out_text, text_cap,
+ * out_offsets (hit_cap + 1 entries), out_bytes as pire_hip_run_lines_gather.  With mode = PIRE_HIP_FINAL_SELECT_ZERO and
+ * tail = delim the bytes in out_text are what `grep -v` prints for the buffer.  Host pointers with size == 0: zeros, no
+ * device is touched.  PIRE_HIP_EINVAL before any device is touched: null table, what pire_hip_final_select refuses (in the
+ * gather form hit_cap > 0 with null out_hits excepted), out_hit_spans without out_hits, delim > 255, null out_line_count,
+ * size > 0 with null raw, and what pire_hip_gather refuses of its outputs.  pire_hip_last_kernel() names the scan's kernel.
+ */
+int pire_hip_slow_lines_select(pire_hip_slow_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
+                               uint32_t mode, uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_hit_spans,
+                               uint64_t hit_cap, uint64_t* out_hit_count, void* stream);
+int pire_hip_slow_lines_gather(pire_hip_slow_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
+                               uint32_t mode, uint32_t tail, uint64_t* out_line_count, uint64_t* out_hits, uint64_t hit_cap,
+                               uint64_t* out_hit_count, void* out_text, uint64_t text_cap, uint64_t* out_offsets,
+                               uint64_t* out_bytes, void* stream);
+
 /* ---- one process, several GPUs (BASELINE config C4) --------------------------- */
 /*
  * The path shards by string: a string's walk depends on nothing but the table and its own bytes (run.h:271-275),

@@ -24,9 +24,10 @@
  *     OwnedStrings      a std::vector<ystring> as one text and offsets; OffsetsOr(): the {0} that stands in for the offsets of no
  *                       strings                                                      every Run(vector), every call that takes offsets
  *     GrowAndRetry()    one call at a first capacity, one more where the answer did not fit       BatchRunner's lines, text and route
- *                       forms, CountedBatchRunner, CaptureBatchRunner
+ *                       forms, CountedBatchRunner, CaptureBatchRunner, SlowBatchRunner
  *     Table             the device table, State <-> StateIndex (ToStates), Regexps()              BatchRunner, Multi-, PairBatchRunner
  *     CountedBatchRunner   all of HalfFinalBatchRunner and CountingBatchRunner but their table and their three C calls
+ *     LineMatcher       easy.h's choice between Scanner and SlowScanner, one lines surface over BatchRunner and SlowBatchRunner
  * Which C calls these make, in which order and with which arguments, is recorded: tests/cpp/shim_calls_test.cpp,
  * tests/cpp/shim_calls.expected.txt.
  */
@@ -1411,11 +1412,25 @@ private:
 /*
  * Batched Runner over a Pire::SlowScanner (scanners/slow.h): Matches(sc, str) per string, i.e.
  * Final(Runner(sc).Begin().Run(str).End().State()).
+ *
+ * Which strings matched -- or, inverted, did not -- answered on the device (pire_hip_slow_run_select): the scan and the hit
+ * list behind one call, Begin() and End() around every string as in Matches():
+ *     run.Run(text, offsets, n).Select();          run.Run(strings).Select(true);      // true: grep -v
+ *     run.Hits()       ascending indices of the selected strings          run.HitCount()  how many
+ * A buffer as it was read, cut into lines, scanned and selected on the device (pire_hip_slow_lines_select / _gather; getline's
+ * semantics, as BatchRunner::RunLines()):
+ *     run.RunLines(raw, size);                     run.RunLines(raw, size, '\n', true);
+ *     run.HitSpans()   [2 * k], [2 * k + 1]: hit k is raw[begin, end)      run.LineCount()  lines in the buffer
+ *     run.HitText()    the selected lines back to back, '\n' (or the byte given) behind each: grep's output -- inverted: grep
+ *                      -v's --, gathered on the device               run.HitTextOffsets()  hit k is HitText()[o[k], o[k + 1])
+ * The caller's arrays are read when an accessor first asks: they live until then.  HitText() is a call of its own, as in
+ * BatchRunner: after Hits() / HitSpans() it scans the buffer a second time.
  */
 class SlowBatchRunner {
 public:
 	explicit SlowBatchRunner(const Pire::SlowScanner& sc)
-	    : m_table(nullptr)
+	    : m_table(nullptr), m_form(kNone), m_text(nullptr), m_offsets(nullptr), m_n(0), m_len(0), m_delim('\n'), m_invert(false),
+	      m_listed(false), m_haveText(false), m_textTail('\n'), m_hitCount(0), m_lineCount(0)
 	{
 		const std::string blob = SavedBlob(sc);
 		Check(pire_hip_slow_table_create(blob.data(), blob.size(), &m_table));
@@ -1431,10 +1446,169 @@ public:
 		return std::vector<char>(fin.begin(), fin.end());
 	}
 
+	/* The batch of the hit forms: string i = text[offsets[i], offsets[i+1]).  Host pointers. */
+	SlowBatchRunner& Run(const char* text, const uint64_t* offsets, size_t n) { return SetBatch(kStrings, text, offsets, n, 0, '\n', false); }
+	SlowBatchRunner& Run(const std::vector<ystring>& strings)
+	{
+		m_ownStrings.Assign(strings);
+		return Run(m_ownStrings.Text(), m_ownStrings.Offsets(), strings.size());
+	}
+	SlowBatchRunner& Select(bool invert = false)
+	{
+		m_invert = invert;
+		m_listed = m_haveText = false;
+		return *this;
+	}
+	SlowBatchRunner& RunLines(const char* raw, size_t size, char delim = '\n', bool invert = false)
+	{
+		return SetBatch(kLines, raw, nullptr, 0, size, delim, invert);
+	}
+	uint64_t HitCount() { FetchHits(); return m_hitCount; }
+	const std::vector<uint64_t>& Hits() { FetchHits(); return m_hits; }
+	uint64_t LineCount() { NeedLines("LineCount()"); FetchHits(); return m_lineCount; }
+	const std::vector<uint64_t>& HitSpans() { NeedLines("HitSpans()"); FetchHits(); return m_hitSpans; }
+	const std::string& HitText(char tail = '\n') { FetchHitText(tail); return m_hitText; }
+	const std::vector<uint64_t>& HitTextOffsets()
+	{
+		if (!m_haveText)
+			FetchHitText('\n');
+		return m_hitTextOffsets;
+	}
+
 private:
 	SlowBatchRunner(const SlowBatchRunner&);
 	SlowBatchRunner& operator=(const SlowBatchRunner&);
+
+	enum Form { kNone, kStrings, kLines };
+	SlowBatchRunner& SetBatch(Form form, const char* text, const uint64_t* offsets, size_t n, size_t len, char delim, bool invert)
+	{
+		m_form = form, m_text = text, m_offsets = offsets, m_n = n, m_len = len, m_delim = uint8_t(delim), m_invert = invert;
+		m_listed = m_haveText = false;
+		return *this;
+	}
+	uint32_t Mode() const { return m_invert ? PIRE_HIP_FINAL_SELECT_ZERO : 0; }
+	void NeedLines(const char* what) const
+	{
+		if (m_form != kLines)
+			throw Pire::Error(std::string("pire_hip: ") + what + " follows RunLines()");
+	}
+
+	/* One call with room for every string -- RunLines(): for a hit on every line of 64 bytes or more, BatchRunner's first
+	 * capacity --, and a second one where there are more */
+	void FetchHits()
+	{
+		if (m_listed)
+			return;
+		if (m_form == kNone)
+			throw Pire::Error("pire_hip: Hits() follows Run() or RunLines()");
+		const uint32_t flags = PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END;
+		GrowAndRetry(m_form == kLines ? m_len / 64 + 1024 : m_n, [&](size_t cap) {
+			m_hits.resize(cap);
+			m_hitSpans.resize(m_form == kLines ? cap * 2 : 0);
+			Check(m_form == kLines
+			          ? pire_hip_slow_lines_select(m_table, m_text, m_len, m_delim, flags, Mode(), &m_lineCount, m_hits.data(),
+			                                       m_hitSpans.data(), cap, &m_hitCount, nullptr)
+			          : pire_hip_slow_run_select(m_table, m_text, OwnedStrings::OffsetsOr(m_offsets, m_n), m_n, flags, Mode(), nullptr, nullptr,
+			                                     nullptr, m_hits.data(), cap, &m_hitCount, nullptr));
+			return size_t(m_hitCount);
+		});
+		m_hits.resize(m_hitCount);
+		m_hitSpans.resize(m_form == kLines ? m_hitCount * 2 : 0);
+		m_listed = true;
+	}
+
+	/* RunLines(): the selected lines as bytes; room for every byte they can have, and for the hits that are known, or else
+	 * FetchHits()'s */
+	void FetchHitText(char tail)
+	{
+		NeedLines("HitText()");
+		if (m_haveText && m_textTail == tail)
+			return;
+		uint64_t count = 0, bytes = 0;
+		GrowAndRetry(m_listed ? size_t(m_hitCount) : m_len / 64 + 1024, [&](size_t cap) {
+			m_hitTextOffsets.resize(cap + 1);
+			m_hitText.resize(m_len + cap + 1);
+			Check(pire_hip_slow_lines_gather(m_table, m_text, m_len, m_delim, PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END, Mode(), uint8_t(tail),
+			                                 &m_lineCount, nullptr, cap, &count, &m_hitText[0], m_hitText.size(), m_hitTextOffsets.data(),
+			                                 &bytes, nullptr));
+			return size_t(count);   // (the text has room for the whole buffer and a tail per hit: where the hits fit, the bytes do)
+		});
+		m_hitText.resize(bytes);
+		m_hitTextOffsets.resize(count + 1);
+		m_textTail = tail;
+		m_haveText = true;
+	}
+
 	pire_hip_slow_table* m_table;
+	Form m_form;
+	const char* m_text;           // Run(): the strings' text; RunLines(): the raw buffer of m_len bytes
+	const uint64_t* m_offsets;
+	size_t m_n, m_len;
+	uint8_t m_delim;
+	bool m_invert;
+	bool m_listed, m_haveText;    // m_hits (and m_hitSpans, m_lineCount) / m_hitText are the batch's, with the tail m_textTail
+	char m_textTail;
+	OwnedStrings m_ownStrings;
+	uint64_t m_hitCount, m_lineCount;
+	std::vector<uint64_t> m_hits, m_hitSpans, m_hitTextOffsets;
+	std::string m_hitText;
+};
+
+/*
+ * easy.h's choice, made for the caller: Pire::Regexp (easy.h:211-214) compiles a Scanner where Fsm::Determine() succeeds and
+ * falls back to a SlowScanner where it gives up (fsm.cpp: more than 200 000 states -- a pattern like x.{40}$), and its user
+ * never learns which.  LineMatcher does the same for a buffer of lines: constructed from the Fsm as the caller built it
+ * (surrounded or not: PrependAnything() / AppendAnything() are the caller's), it offers one surface over
+ * BatchRunner<Scanner>::RunLines() and SlowBatchRunner::RunLines():
+ *     Pire::Hip::LineMatcher grep(fsm);
+ *     grep.RunLines(raw, size);                    grep.RunLines(raw, size, '\n', true);     // true: grep -v, slow form only
+ *     grep.HitText()   grep.HitSpans()   grep.Hits()   grep.HitCount()   grep.LineCount()   grep.IsSlow()
+ * Begin() and End() are stepped around every line, as Matches() does.  The inverted selection exists for the SlowScanner
+ * alone (the library has none behind pire_hip_select): RunLines(.., true) on a determinised pattern throws.
+ */
+class LineMatcher {
+public:
+	explicit LineMatcher(Pire::Fsm fsm)
+	    : m_fast(nullptr), m_slow(nullptr)
+	{
+		if (fsm.Determine()) {
+			m_scanner = fsm.Compile<Pire::Scanner>();
+			m_fast = new BatchRunner<Pire::Scanner>(m_scanner);
+		} else {
+			m_slowScanner = fsm.Compile<Pire::SlowScanner>();
+			m_slow = new SlowBatchRunner(m_slowScanner);
+		}
+	}
+	~LineMatcher()
+	{
+		delete m_fast;
+		delete m_slow;
+	}
+	bool IsSlow() const { return m_slow != nullptr; }
+	LineMatcher& RunLines(const char* raw, size_t size, char delim = '\n', bool invert = false)
+	{
+		if (m_slow)
+			m_slow->RunLines(raw, size, delim, invert);
+		else if (invert)
+			throw Pire::Error("pire_hip: LineMatcher::RunLines(): the inverted selection follows a SlowScanner only");
+		else
+			m_fast->Begin().RunLines(raw, size, delim).End();
+		return *this;
+	}
+	uint64_t LineCount() { return m_slow ? m_slow->LineCount() : m_fast->LineCount(); }
+	uint64_t HitCount() { return m_slow ? m_slow->HitCount() : m_fast->HitCount(); }
+	const std::vector<uint64_t>& Hits() { return m_slow ? m_slow->Hits() : m_fast->Hits(); }
+	const std::vector<uint64_t>& HitSpans() { return m_slow ? m_slow->HitSpans() : m_fast->HitSpans(); }
+	const std::string& HitText(char tail = '\n') { return m_slow ? m_slow->HitText(tail) : m_fast->HitText(tail); }
+	const std::vector<uint64_t>& HitTextOffsets() { return m_slow ? m_slow->HitTextOffsets() : m_fast->HitTextOffsets(); }
+
+private:
+	LineMatcher(const LineMatcher&);
+	LineMatcher& operator=(const LineMatcher&);
+	Pire::Scanner m_scanner;           // the one the pattern compiled to; the runners read it
+	Pire::SlowScanner m_slowScanner;
+	BatchRunner<Pire::Scanner>* m_fast;
+	SlowBatchRunner* m_slow;
 };
 
 }  // namespace Hip

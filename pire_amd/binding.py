@@ -138,6 +138,7 @@ GATHER_TILE = 16384   # include/pire_hip.h PIRE_HIP_GATHER_TILE_BYTES: the gathe
 NO_TAIL = (1 << 32) - 1   # include/pire_hip.h PIRE_HIP_GATHER_NO_TAIL: no byte behind the gathered strings
 FIELDS_TILE = 16384   # include/pire_hip.h PIRE_HIP_FIELDS_TILE_BYTES: the fields pass cuts text into tiles of this many bytes
 COUNT_ALL = 1   # include/pire_hip.h PIRE_HIP_COUNT_ALL (in `mode`): every wanted regexp reaches its threshold
+FINAL_SELECT_ZERO = 1   # include/pire_hip.h PIRE_HIP_FINAL_SELECT_ZERO (`mode`): the strings whose Final flag is NOT set
 FIELDS_REST = 1   # include/pire_hip.h PIRE_HIP_FIELDS_REST (in `mode`): the span runs to the end of the string, `cut -f k-`
 
 # every symbol include/pire_hip.h declares: (name, restype, argtypes)
@@ -244,6 +245,11 @@ ABI = [
     ("pire_hip_run_half_final_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_counting_lines_select", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_half_final_lines_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_final_select", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_slow_run_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_slow_run_select_strided", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_slow_lines_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_slow_lines_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_multi_create", C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
     ("pire_hip_multi_destroy", None, [C.c_void_p]),
     ("pire_hip_multi_device_count", C.c_int, [C.c_void_p]),
@@ -511,6 +517,30 @@ def count_select_device(results_ptr: int, n: int, regexps: int, out_hit_count_pt
 
 
 # --- from capture positions to byte ranges (pire_hip_capture_select)
+# --- from Final flags to the strings that matched, or did not (pire_hip_final_select)
+def _final_mode(invert) -> int:
+    return FINAL_SELECT_ZERO if invert else 0
+
+
+def final_select_host(final, invert=False, hit_cap: Optional[int] = None):
+    """pire_hip_final_select on a host array final[n]: {"hits" u64[k], "count"}, k = min(count, hit_cap); hit_cap None = room
+    for every string."""
+    final = np.ascontiguousarray(final, dtype=np.uint8)
+    n = final.size
+    cap = n if hit_cap is None else int(hit_cap)
+    hits = np.zeros(cap, dtype=np.uint64)
+    cnt = C.c_uint64(0)
+    _check(lib().pire_hip_final_select(final.ctypes.data if n else None, n, _final_mode(invert), 0, hits.ctypes.data if cap else None, cap,
+                                       C.byref(cnt), None))
+    return {"hits": hits[:min(int(cnt.value), cap)], "count": int(cnt.value)}
+
+
+def final_select_device(final_ptr: int, n: int, out_hit_count_ptr: int, invert=False, out_hits_ptr=0, hit_cap=0, stream: int = 0):
+    """pire_hip_final_select with PIRE_HIP_RUN_ON_DEVICE: raw device addresses, only enqueues on `stream`."""
+    _check(lib().pire_hip_final_select(final_ptr or None, n, _final_mode(invert), FLAG_ON_DEVICE, out_hits_ptr or None, hit_cap,
+                                       out_hit_count_ptr or None, stream or None))
+
+
 def capture_select_host(offsets, begin, end, final=None, flags=FLAG_BEGIN, need_final=False, hit_cap: Optional[int] = None,
                         want_hits=True, want_spans=True):
     """pire_hip_capture_select on host arrays: (hits u64[k] or None, spans u64[k, 2] or None, count), k = min(count, hit_cap).
@@ -1301,6 +1331,97 @@ class SlowTable:
         _check(lib().pire_hip_slow_run_strided(self._h, text_ptr or None, n, length, stride, flags | FLAG_ON_DEVICE,
                                                out_final_ptr or None, out_bits_ptr or None, out_counts_ptr or None,
                                                stream or None))
+
+    # --- the scan and the hit list behind one call (pire_hip_slow_run_select); invert: the strings that did NOT match
+    def run_select(self, text, offsets, flags=FLAG_BEGIN | FLAG_END, invert=False, hit_cap: Optional[int] = None, results=True):
+        """pire_hip_slow_run_select on host strings: what final_select_host returns and, with results, {"final", "bits"};
+        without, the library keeps the flags to itself."""
+        text = _raw_bytes(text)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        fin = np.empty(n, dtype=np.uint8) if results else None
+        bits = np.empty((n, self.words), dtype=np.uint32) if results else None
+        cap = n if hit_cap is None else int(hit_cap)
+        hits = np.zeros(cap, dtype=np.uint64)
+        cnt = C.c_uint64(0)
+        _check(lib().pire_hip_slow_run_select(self._h, text.ctypes.data if text.size else None, offsets.ctypes.data, n,
+                                              flags & ~FLAG_ON_DEVICE, _final_mode(invert), _np_ptr(fin), _np_ptr(bits), None,
+                                              hits.ctypes.data if cap else None, cap, C.byref(cnt), None))
+        got = {"hits": hits[:min(int(cnt.value), cap)], "count": int(cnt.value)}
+        if results:
+            got.update(final=fin, bits=bits)
+        return got
+
+    def run_select_strings(self, strings, **kw):
+        offs = np.zeros(len(strings) + 1, dtype=np.uint64)
+        if strings:
+            offs[1:] = np.cumsum([len(s) for s in strings], dtype=np.uint64)
+        return self.run_select(np.frombuffer(b"".join(strings), dtype=np.uint8), offs, **kw)
+
+    def run_select_device(self, text_ptr: int, offsets_ptr: int, n: int, flags, out_hit_count_ptr: int, invert=False, out_final_ptr=0,
+                          out_bits_ptr=0, out_counts_ptr=0, out_hits_ptr=0, hit_cap=0, stream: int = 0):
+        """pire_hip_slow_run_select on device pointers: only enqueues on `stream`."""
+        _check(lib().pire_hip_slow_run_select(self._h, text_ptr or None, offsets_ptr or None, n, flags | FLAG_ON_DEVICE, _final_mode(invert),
+                                              out_final_ptr or None, out_bits_ptr or None, out_counts_ptr or None, out_hits_ptr or None,
+                                              hit_cap, out_hit_count_ptr or None, stream or None))
+
+    def run_select_strided_device(self, text_ptr: int, n: int, length: int, stride: int, flags, out_hit_count_ptr: int, invert=False,
+                                  out_final_ptr=0, out_bits_ptr=0, out_counts_ptr=0, out_hits_ptr=0, hit_cap=0, stream: int = 0):
+        """pire_hip_slow_run_select_strided on device pointers: only enqueues on `stream`."""
+        _check(lib().pire_hip_slow_run_select_strided(self._h, text_ptr or None, n, length, stride, flags | FLAG_ON_DEVICE,
+                                                      _final_mode(invert), out_final_ptr or None, out_bits_ptr or None,
+                                                      out_counts_ptr or None, out_hits_ptr or None, hit_cap, out_hit_count_ptr or None,
+                                                      stream or None))
+
+    # --- raw bytes in, the lines that match (or, inverted, do not) out (pire_hip_slow_lines_select / _gather)
+    def lines_select_host(self, raw, delim: int = 10, flags=FLAG_BEGIN | FLAG_END, invert=False, hit_cap=None):
+        """pire_hip_slow_lines_select on a host buffer: {"lines", "hits", "spans", "count"}; hit_cap None = room for a hit on
+        every line (no more lines than bytes)."""
+        raw = _raw_bytes(raw)
+        cap = raw.size if hit_cap is None else int(hit_cap)
+        hits = np.zeros(cap, dtype=np.uint64)
+        spans = np.zeros((cap, 2), dtype=np.uint64)
+        lines, cnt = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().pire_hip_slow_lines_select(self._h, raw.ctypes.data if raw.size else None, raw.size, delim, flags & ~FLAG_ON_DEVICE,
+                                                _final_mode(invert), C.byref(lines), hits.ctypes.data if cap else None,
+                                                spans.ctypes.data if cap else None, cap, C.byref(cnt), None))
+        k = min(int(cnt.value), cap)
+        return {"lines": int(lines.value), "hits": hits[:k], "spans": spans[:k], "count": int(cnt.value)}
+
+    def lines_select_device(self, raw_ptr: int, size: int, flags, out_line_count_ptr: int, out_hit_count_ptr: int, delim: int = 10,
+                            invert=False, out_hits_ptr=0, out_hit_spans_ptr=0, hit_cap=0, stream: int = 0):
+        """pire_hip_slow_lines_select on device pointers (synchronises `stream` once, as Table.run_lines_select_device does)."""
+        _check(lib().pire_hip_slow_lines_select(self._h, raw_ptr or None, size, delim, flags | FLAG_ON_DEVICE, _final_mode(invert),
+                                                out_line_count_ptr or None, out_hits_ptr or None, out_hit_spans_ptr or None, hit_cap,
+                                                out_hit_count_ptr or None, stream or None))
+
+    def lines_gather_host(self, raw, delim: int = 10, flags=FLAG_BEGIN | FLAG_END, invert=False, tail=-1, hit_cap=None, text_cap=None):
+        """pire_hip_slow_lines_gather on a host buffer: {"lines", "hits", "count", "text", "offsets", "bytes"}.  tail -1 = the
+        delimiter (grep's output; inverted: grep -v's), None = none; hit_cap None = room for a hit on every line, text_cap None =
+        for all of them."""
+        raw = _raw_bytes(raw)
+        cap = raw.size if hit_cap is None else int(hit_cap)
+        room = raw.size + cap if text_cap is None else int(text_cap)
+        hits = np.zeros(cap, dtype=np.uint64)
+        text = np.zeros(max(room, 1), dtype=np.uint8)
+        offsets = np.zeros(cap + 1, dtype=np.uint64)
+        lines, cnt, total = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().pire_hip_slow_lines_gather(self._h, raw.ctypes.data if raw.size else None, raw.size, delim, flags & ~FLAG_ON_DEVICE,
+                                                _final_mode(invert), _tail(delim if tail == -1 else tail), C.byref(lines),
+                                                hits.ctypes.data if cap else None, cap, C.byref(cnt), text.ctypes.data if room else None,
+                                                room, offsets.ctypes.data, C.byref(total), None))
+        k = min(int(cnt.value), cap)
+        return {"lines": int(lines.value), "hits": hits[:k], "count": int(cnt.value), "text": text[:min(int(total.value), room)],
+                "offsets": offsets[:k + 1], "bytes": int(total.value)}
+
+    def lines_gather_device(self, raw_ptr: int, size: int, flags, out_line_count_ptr: int, out_hit_count_ptr: int, out_bytes_ptr: int,
+                            delim: int = 10, invert=False, tail=-1, out_hits_ptr=0, hit_cap=0, out_text_ptr=0, text_cap=0,
+                            out_offsets_ptr=0, stream: int = 0):
+        """pire_hip_slow_lines_gather on device pointers (synchronises `stream` once, as Table.run_lines_select_device does)."""
+        _check(lib().pire_hip_slow_lines_gather(self._h, raw_ptr or None, size, delim, flags | FLAG_ON_DEVICE, _final_mode(invert),
+                                                _tail(delim if tail == -1 else tail), out_line_count_ptr or None, out_hits_ptr or None,
+                                                hit_cap, out_hit_count_ptr or None, out_text_ptr or None, text_cap,
+                                                out_offsets_ptr or None, out_bytes_ptr or None, stream or None))
 
 
 class CountingTable:

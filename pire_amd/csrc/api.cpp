@@ -3007,6 +3007,81 @@ try {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
 
+// ---- raw bytes in, the lines a SlowScanner matches -- or does not -- out (split.hip, slow.hip, slow_hits.hip) ----------------
+// The frame around a SlowScanner's scan: the scan on the lines with the Final flags in scratch, the pass, the whole lines of
+// the hits as byte ranges of raw and, in the gather form, their bytes.  The frame itself takes no table: the scan is the
+// entry point's own call.
+namespace {
+
+int SlowLinesImpl(const char* who, pire_hip_slow_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags, uint32_t mode,
+                  uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_hit_spans, uint64_t hit_cap, uint64_t* out_hit_count,
+                  void* streamPtr, const LinesGather* gather)
+{
+	if (!t)
+		return GatherRefuse(who, "null table");
+	// (the gather form keeps the hit list to itself where the caller has no array for it)
+	const FinalSelectOut o = {mode, out_hits, gather && !out_hits ? 0 : hit_cap, out_hit_count};
+	if (int rc = FinalSelectArgsInvalid(who, 0, true, o))
+		return rc;
+	if (int rc = SplitArgsInvalid(who, raw, size, delim, out_line_count, "out_line_count"))
+		return rc;
+	if (out_hit_spans && !out_hits)
+		return GatherRefuse(who, "out_hit_spans without out_hits");
+	if (gather) {
+		if (int rc = GatherOutputsInvalid(who, "hit_cap", hit_cap, gather->tail, gather->outText, gather->textCap, gather->outOffsets,
+		                                  gather->outBytes))
+			return rc;
+		if (int rc = GatherOverlaps(who, raw, size, gather->outText, gather->textCap))
+			return rc;
+	}
+	LinesFrame f(who, raw, size, delim, flags, gather, streamPtr);
+	if (f.HostEdge(out_line_count)) {
+		*out_hit_count = 0;
+		return PIRE_HIP_OK;
+	}
+	if (int rc = f.Open())
+		return rc;
+	if (int rc = f.Split(out_line_count, out_hit_count, 1, hit_cap, true))
+		return rc;
+	if (int rc = f.Lists(out_hits, out_hit_spans))
+		return rc;
+	if (f.n == 0) {
+		if (int rc = f.ZeroCounts("hipMemsetAsync(hit count)"))
+			return rc;
+	} else {
+		if (int rc = pire_hip_slow_run_select(t, f.Text(), f.Offsets(), f.n, f.RunFlags(), mode, nullptr, nullptr, nullptr, f.dHits,
+		                                      f.dHits ? f.cap : 0, f.dCounts, f.stream))
+			return rc;
+		if (f.dSpans)   // (the whole line)
+			if (int rc = LaunchHitSpans(f.dHits, f.dCounts, 1, f.cap, f.cap, f.LineOffsets(), f.dSpans, f.stream, "split spans launch"))
+				return rc;
+	}
+	return f.Close("hipMemcpy(hits)");
+}
+
+}  // namespace
+
+int pire_hip_slow_lines_select(pire_hip_slow_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags, uint32_t mode,
+                               uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_hit_spans, uint64_t hit_cap,
+                               uint64_t* out_hit_count, void* stream)
+try {
+	return SlowLinesImpl("pire_hip_slow_lines_select", t, raw, size, delim, flags, mode, out_line_count, out_hits, out_hit_spans, hit_cap,
+	                     out_hit_count, stream, nullptr);
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_slow_lines_gather(pire_hip_slow_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags, uint32_t mode,
+                               uint32_t tail, uint64_t* out_line_count, uint64_t* out_hits, uint64_t hit_cap, uint64_t* out_hit_count,
+                               void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes, void* stream)
+try {
+	const LinesGather gather = {tail, out_text, text_cap, out_offsets, out_bytes, true, "hipMallocAsync(hit spans)"};
+	return SlowLinesImpl("pire_hip_slow_lines_gather", t, raw, size, delim, flags, mode, out_line_count, out_hits, nullptr, hit_cap,
+	                     out_hit_count, stream, &gather);
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
 int pire_hip_prefix(pire_hip_table* t, const void* text, const uint64_t* offsets, uint64_t n, int longest,
                     int through_begin, int through_end, uint32_t flags, int64_t* out_len, void* streamPtr)
 try {

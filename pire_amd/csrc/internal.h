@@ -1142,6 +1142,34 @@ struct CaptureSelectOut {
 int CaptureRunImpl(pire_hip_counting_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
                    uint32_t* outIdx, uint8_t* outFinal, int64_t* outBegin, int64_t* outEnd, const CaptureSelectOut* sel,
                    hipStream_t stream);
+// slow_hits.hip: from Final flags to a compacted, ascending list of the strings whose flag is set -- or, with
+// PIRE_HIP_FINAL_SELECT_ZERO, of those whose flag is not (pire_hip_final_select).  Device pointers only, three kernels enqueued
+// on `stream`, the compaction's scratch from the stream-ordered allocator.  n == 0: the count zeroed on the stream.
+int LaunchFinalSelect(const uint8_t* fin, uint64_t n, uint32_t mode, uint64_t* outHits, uint64_t hitCap, uint64_t* outHitCount,
+                      hipStream_t stream);
+// The pass's own arguments, as the caller of an entry point gave them
+struct FinalSelectOut {
+	uint32_t mode;
+	uint64_t* outHits;
+	uint64_t hitCap;
+	uint64_t* outHitCount;
+};
+// What pire_hip_final_select refuses before any device is touched, in `who`'s name (haveFinal: there are flags to read)
+int FinalSelectArgsInvalid(const char* who, uint64_t n, bool haveFinal, const FinalSelectOut& o);
+// The pass inside ONE call of an entry point (pire_hip_final_select itself, and the slow scan it follows on its stream), on
+// whichever side the caller's pointers live.  Order: Empty() instead of everything where there is nothing to read; else
+// Results() with its result arrays, io.Ready(), the scan, Launch(), io.Finish(), Back().
+struct FinalSelectStage {
+	const FinalSelectOut o;
+	const bool onDevice;
+	uint64_t *dCount = nullptr, *dHits = nullptr;
+	uint64_t cap = 0, count = 0;   // host pointers: no list is staged longer than the strings are many; the count comes back here first
+	FinalSelectStage(const FinalSelectOut& o_, bool onDevice_) : o(o_), onDevice(onDevice_) {}
+	int Empty(hipStream_t stream);   // no strings: a count of 0 -- host pointers: no device is touched
+	int Results(BatchIO& io, uint64_t n);
+	int Launch(const uint8_t* fin, uint64_t n, hipStream_t stream);
+	int Back();                      // host pointers: the count, and the list only as far as it was written
+};
 // split.hip: raw text into strings (pire_hip_split).  Device pointers only, everything enqueued on `stream`.  The pass
 // comes in two halves because a caller may want the number of strings before it has room for their offsets:
 // LaunchSplitCount counts and scans (*outN = n; the tile prefixes stay in `scratch`, the caller's owner, which has to live

@@ -1111,12 +1111,23 @@ int LaunchSlowListThen(const SlowParams& p0, const SlowPlan& plan, hipStream_t s
 	return fallback(p);   // p.overflow set: only the strings on the list
 }
 
-int RunSlow(pire_hip_slow_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint64_t len, uint64_t stride,
-            uint32_t flags, uint8_t* outFinal, uint32_t* outBits, uint64_t* outCounts, void* streamPtr)
+// sel == nullptr: pire_hip_slow_run[_strided].  Else outFinal may be null, and the pass of slow_hits.hip follows the scan on
+// the same stream, behind whichever launch form the plan picks (pire_hip_slow_run_select[_strided], the lines forms).
+int RunSlow(const char* who, pire_hip_slow_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint64_t len, uint64_t stride,
+            uint32_t flags, uint8_t* outFinal, uint32_t* outBits, uint64_t* outCounts, const FinalSelectOut* sel, void* streamPtr)
 {
 	if (!t) {
-		SetError("null table");
+		SetError(sel ? std::string(who) + ": null table" : std::string("null table"));
 		return PIRE_HIP_EINVAL;
+	}
+	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
+	std::optional<FinalSelectStage> pass;
+	if (sel) {
+		if (int rc = FinalSelectArgsInvalid(who, n, true, *sel))
+			return rc;
+		pass.emplace(*sel, onDevice);
+		if (n == 0)
+			return pass->Empty(static_cast<hipStream_t>(streamPtr));
 	}
 	SlowDevice image;
 	if (int rc = UploadSlow(t, &image))
@@ -1167,21 +1178,36 @@ int RunSlow(pire_hip_slow_table* t, const void* text, const uint64_t* offsets, u
 			                    plan.K == 4 ? "pirehip::SlowScanKernel<4>" : "pirehip::SlowScanKernel<8>");
 		return plain(q);
 	};
-	BatchIO io(stream, (flags & PIRE_HIP_RUN_ON_DEVICE) != 0);
+	BatchIO io(stream, onDevice);
 	const unsigned long long* dCnt = nullptr;   // accumulated into: an input as well as a result
 	int rc = io.Text(text, offsets, n, len, stride, &p.text, &p.offsets);
 	if (!rc && outCounts) {
 		rc = io.In(reinterpret_cast<const unsigned long long*>(outCounts), 2, &dCnt);
 		p.outCounts = const_cast<unsigned long long*>(dCnt);
 	}
-	if (!rc && outFinal)
+	if (!rc && (outFinal || pass))
 		rc = io.Result(outFinal, n, n, &p.outFinal);
 	if (!rc && outBits)
 		rc = io.Result(outBits, n * h.words, n * h.words, &p.outBits);
 	io.CopyBack(outCounts, dCnt, 16);
+	// the pass behind the scan: the flags it reads and the caller has no array for live in scratch (a host-pointer call's
+	// Result() has allocated them already)
+	StreamScratch ownFinal(stream);
+	if (!rc && pass) {
+		if (!p.outFinal) {
+			if ((rc = ownFinal.Alloc(size_t(n), "hipMallocAsync(slow scanner final flags)")))
+				return rc;
+			p.outFinal = ownFinal.as<uint8_t>();
+		}
+		rc = pass->Results(io, n);
+	}
 	if (rc || (rc = io.Ready()) || (rc = launch(p)))
 		return rc;
-	return io.Finish();
+	if (pass && (rc = pass->Launch(p.outFinal, n, stream)))
+		return rc;
+	if ((rc = io.Finish()))
+		return rc;
+	return pass ? pass->Back() : PIRE_HIP_OK;
 }
 
 }  // namespace
@@ -1295,7 +1321,7 @@ try {
 		SetError("null offsets");
 		return PIRE_HIP_EINVAL;
 	}
-	return RunSlow(t, text, offsets, n, 0, 0, flags, out_final, out_state_bits, out_counts, stream);
+	return RunSlow("pire_hip_slow_run", t, text, offsets, n, 0, 0, flags, out_final, out_state_bits, out_counts, nullptr, stream);
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
@@ -1308,7 +1334,36 @@ try {
 		SetError("stride smaller than len");
 		return PIRE_HIP_EINVAL;
 	}
-	return RunSlow(t, text, nullptr, n, len, stride, flags, out_final, out_state_bits, out_counts, stream);
+	return RunSlow("pire_hip_slow_run_strided", t, text, nullptr, n, len, stride, flags, out_final, out_state_bits, out_counts, nullptr, stream);
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_slow_run_select(pire_hip_slow_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags, uint32_t mode,
+                             uint8_t* out_final, uint32_t* out_state_bits, uint64_t* out_counts, uint64_t* out_hits, uint64_t hit_cap,
+                             uint64_t* out_hit_count, void* stream)
+try {
+	if (n && !offsets) {
+		SetError("pire_hip_slow_run_select: null offsets");
+		return PIRE_HIP_EINVAL;
+	}
+	const FinalSelectOut sel = {mode, out_hits, hit_cap, out_hit_count};
+	return RunSlow("pire_hip_slow_run_select", t, text, offsets, n, 0, 0, flags, out_final, out_state_bits, out_counts, &sel, stream);
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_slow_run_select_strided(pire_hip_slow_table* t, const void* text, uint64_t n, uint64_t len, uint64_t stride, uint32_t flags,
+                                     uint32_t mode, uint8_t* out_final, uint32_t* out_state_bits, uint64_t* out_counts, uint64_t* out_hits,
+                                     uint64_t hit_cap, uint64_t* out_hit_count, void* stream)
+try {
+	if (stride < len) {
+		SetError("pire_hip_slow_run_select_strided: stride smaller than len");
+		return PIRE_HIP_EINVAL;
+	}
+	const FinalSelectOut sel = {mode, out_hits, hit_cap, out_hit_count};
+	return RunSlow("pire_hip_slow_run_select_strided", t, text, nullptr, n, len, stride, flags, out_final, out_state_bits, out_counts, &sel,
+	               stream);
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
