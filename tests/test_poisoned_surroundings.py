@@ -48,6 +48,30 @@ class Embedded:
             self.dev_offs = torch.as_tensor(self.offs.astype(np.int64), device="cuda")
 
 
+class EmbeddedAt(Embedded):
+    """The same two addressings inside a buffer the caller owns (tests/test_past_4gib.py: one of more than 4 GiB, filled with
+    0xA5): the batch's first byte is byte `lead` behind big[skew], the bytes around it are poisoned anew, nothing else is
+    touched.  shifted_offsets: pointer = &big[skew], offsets[0] = lead; else pointer = &big[skew + lead], offsets from 0."""
+
+    GUARD = 1 << 16
+
+    def __init__(self, big, strings, lead, shifted_offsets, skew=0):
+        import torch
+
+        text, offs = H.pack(strings)
+        text = np.asarray(text, dtype=np.uint8)
+        self.text, self.offs, self.n, self.lead = text, np.asarray(offs, dtype=np.uint64), len(strings), lead
+        at = skew + lead
+        assert at >= self.GUARD and at + text.size + self.GUARD <= big.numel()
+        big[at - self.GUARD:at + text.size + self.GUARD].fill_(0xA5)
+        big[at:at + text.size].copy_(torch.as_tensor(text))
+        self.buf = big
+        self.shift = lead if shifted_offsets else 0          # what a byte position in the caller's terms is ahead of the batch's own
+        self.ptr = big.data_ptr() + skew + (0 if shifted_offsets else lead)
+        self.host_offs = self.offs + np.uint64(self.shift)
+        self.dev_offs = torch.as_tensor(self.host_offs.astype(np.int64), device="cuda")
+
+
 def poisoned(shape, dtype):
     import torch
 
