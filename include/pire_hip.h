@@ -1147,6 +1147,84 @@ int pire_hip_capture_lines_gather(pire_hip_counting_table* t, const void* raw, u
                                   void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes,
                                   void* stream);
 
+/* ---- the matched heads and tails, on the device ------------------------------------------------------------------ */
+
+#define PIRE_HIP_AFFIX_HEAD 0u   /* the matched prefix */
+#define PIRE_HIP_AFFIX_TAIL 1u   /* the matched suffix */
+#define PIRE_HIP_AFFIX_REST 2u   /* what the head and the tail leave */
+
+/*
+ * From prefix and suffix lengths to byte ranges: the strings that matched, as a compacted, ascending list, and where the
+ * matched head, the matched tail, or what lies between them is -- the input of pire_hip_gather_spans.  It takes no table
+ * and no text: it reads what pire_hip_prefix and pire_hip_suffix wrote for the same n strings (head_len, tail_len; either
+ * may be null, not both), plus offsets[n + 1].
+ *   len_i       = offsets[i+1] >= offsets[i] ? offsets[i+1] - offsets[i] : 0
+ *   selected(i) = (head_len == NULL || head_len[i] >= 0) && (tail_len == NULL || tail_len[i] >= 0)
+ *   h_i         = head_len ? min(head_len[i], len_i)       : 0
+ *   t_i         = tail_len ? min(tail_len[i], len_i)       : 0
+ *   r_i         = tail_len ? min(tail_len[i], len_i - h_i) : 0     (REST: the tail gives way to the head where they overlap)
+ *   HEAD: [offsets[i],              offsets[i] + h_i)              needs head_len
+ *   TAIL: [offsets[i] + len_i - t_i, offsets[i] + len_i)           needs tail_len
+ *   REST: [offsets[i] + h_i,         offsets[i] + len_i - r_i)     needs at least one of them
+ * A length of 0 is a match -- the scanner accepts the empty prefix --: the string is selected and its span is empty.  A
+ * length of -1 is the reference's null pointer: the string is not selected.  A span never leaves
+ * [offsets[i], offsets[i + 1]], whatever int64 the ON_DEVICE form is given (as pire_hip_capture_select, for the same reason).
+ * out_hits[hit_cap] (nullable): the indices of the selected strings, ascending.  out_spans[hit_cap][2] (nullable, and it
+ * does not need out_hits): their spans.  *out_hit_count (required): the number of selected strings, also when it exceeds
+ * hit_cap; only the first min(count, hit_cap) entries are written, nothing behind them.  n == 0 writes a count of 0.
+ * n < 2^32.
+ * flags: PIRE_HIP_RUN_ON_DEVICE -> every pointer is a device pointer and the call only enqueues on `stream`: three kernels
+ *        (classify per tile of 1 024 strings, the one-block scan of pire_hip_select, scatter), no atomics -- the same input
+ *        gives the same bits.  Scratch (n / 8 + n / 256 bytes) comes from the stream-ordered allocator: the rule and the
+ *        capture-mode caveat stated at pire_hip_select.  Otherwise host pointers: staged, synchronises.
+ * PIRE_HIP_EINVAL before any device is touched: unknown part; n > 0 with null head_len and null tail_len; HEAD without
+ * head_len, TAIL without tail_len; n > 0 with null offsets; null out_hit_count; hit_cap > 0 with null out_hits and null
+ * out_spans; n >= 2^32.
+ * pire_hip_last_kernel() is not changed by the pass.  No first-use self-test (as pire_hip_select).
+ */
+int pire_hip_affix_select(const uint64_t* offsets, uint64_t n, uint32_t part, uint32_t flags,
+                          const int64_t* head_len, const int64_t* tail_len,
+                          uint64_t* out_hits, uint64_t* out_spans, uint64_t hit_cap,
+                          uint64_t* out_hit_count, void* stream);
+
+#define PIRE_HIP_AFFIX_LONGEST 1u         /* LongestPrefix / LongestSuffix; without it the Shortest forms */
+#define PIRE_HIP_AFFIX_THROUGH_BEGIN 2u   /* the reference's throughBeginMark */
+#define PIRE_HIP_AFFIX_THROUGH_END 4u     /* the reference's throughEndMark */
+
+/*
+ * pire_hip_prefix on `head`, pire_hip_suffix on `tail` and pire_hip_affix_select, on one stream.  head and tail may each be
+ * NULL (that scan is skipped and the pass gets no such array), not both; they may be the same table.  head_opts / tail_opts:
+ * PIRE_HIP_AFFIX_* bits, the scans' longest, through_begin and through_end.  flags: PIRE_HIP_RUN_ON_DEVICE as above;
+ * PIRE_HIP_RUN_GENERIC is handed to the prefix scan.  out_head_len[n], out_tail_len[n] (nullable): what the scans wrote;
+ * what the caller has no array for lives in stream-ordered scratch of the library's own.  part, out_hits, out_spans, hit_cap,
+ * out_hit_count: as pire_hip_affix_select.  With host pointers the text is staged once, and both scans and the pass run on
+ * the staged copy before anything comes back.  Each scan keeps its first-use self-test and its kernel choice;
+ * pire_hip_last_kernel() names the scan that ran last.  It refuses what the three calls it stands for refuse (a part that
+ * needs the table that is NULL; unknown bits in head_opts or tail_opts).
+ */
+int pire_hip_affix_run_select(pire_hip_table* head, uint32_t head_opts, pire_hip_table* tail, uint32_t tail_opts,
+                              const void* text, const uint64_t* offsets, uint64_t n, uint32_t part, uint32_t flags,
+                              int64_t* out_head_len, int64_t* out_tail_len,
+                              uint64_t* out_hits, uint64_t* out_spans, uint64_t hit_cap, uint64_t* out_hit_count, void* stream);
+
+/*
+ * Raw bytes in, the matched head or tail of every line that matched -- or the line without them -- out: `grep -o '^re'`,
+ * `sed 's/^re//'` on the lines that match, a trim of both ends in one call.  The split into scratch, the scans on the lines,
+ * the pass -- its spans counted in raw: line i of the split buffer lies i bytes further into raw --, the gather from raw
+ * through them.  head .. tail_opts, part: as pire_hip_affix_run_select.  Everything else as pire_hip_capture_lines_gather:
+ * out_line_count, delim, the one synchronisation of `stream`, the refusal of 2^32 lines (PIRE_HIP_EUNSUPPORTED); out_hits
+ * (nullable): the numbers of the lines that matched; out_spans (nullable): byte ranges of raw; tail_byte (the gather's
+ * `tail`), out_text, text_cap, out_offsets (hit_cap + 1 entries), out_bytes: as pire_hip_gather_spans.  All four gather outputs null (text_cap == 0):
+ * spans only, the gather is skipped.  Host pointers with size == 0: zeros (out_offsets[0] = 0 where it is not null), no
+ * device is touched.
+ */
+int pire_hip_affix_lines_gather(pire_hip_table* head, uint32_t head_opts, pire_hip_table* tail, uint32_t tail_opts,
+                                const void* raw, uint64_t size, uint32_t delim, uint32_t part, uint32_t flags, uint32_t tail_byte,
+                                uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_spans,
+                                uint64_t hit_cap, uint64_t* out_hit_count,
+                                void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes,
+                                void* stream);
+
 /* ---- the strings that count, on the device ---------------------------------------------------------------------- */
 
 /*

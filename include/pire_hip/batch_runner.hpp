@@ -24,8 +24,8 @@
  *     OwnedStrings      a std::vector<ystring> as one text and offsets; OffsetsOr(): the {0} that stands in for the offsets of no
  *                       strings                                                      every Run(vector), every call that takes offsets
  *     GrowAndRetry()    one call at a first capacity, one more where the answer did not fit       BatchRunner's lines, text and route
- *                       forms, CountedBatchRunner, CaptureBatchRunner, SlowBatchRunner
- *     Table             the device table, State <-> StateIndex (ToStates), Regexps()              BatchRunner, Multi-, PairBatchRunner
+ *                       forms, CountedBatchRunner, CaptureBatchRunner, SlowBatchRunner, AffixBatchRunner
+ *     Table             the device table, State <-> StateIndex (ToStates), Regexps()              BatchRunner, Multi-, Pair-, AffixBatchRunner
  *     CountedBatchRunner   all of HalfFinalBatchRunner and CountingBatchRunner but their table and their three C calls
  *     LineMatcher       easy.h's choice between Scanner and SlowScanner, one lines surface over BatchRunner and SlowBatchRunner
  * Which C calls these make, in which order and with which arguments, is recorded: tests/cpp/shim_calls_test.cpp,
@@ -1609,6 +1609,158 @@ private:
 	Pire::SlowScanner m_slowScanner;
 	BatchRunner<Pire::Scanner>* m_fast;
 	SlowBatchRunner* m_slow;
+};
+
+/*
+ * Where the text lies: Pire::LongestPrefix / ShortestPrefix of a head scanner and Pire::LongestSuffix / ShortestSuffix of a tail
+ * scanner (run.h:277-362; the tail scanner compiled from Fsm::Reverse(), pire_ut.cpp:283) over n strings, and the byte ranges
+ * they mean, on the device (include/pire_hip.h, "the matched heads and tails, on the device").  Either scanner may be absent
+ * (a null pointer), not both; the options are PIRE_HIP_AFFIX_* bits.  A string is selected when every scanner that is given
+ * accepts a prefix (suffix) of it -- the empty one counts.
+ *     Pire::Hip::AffixBatchRunner<Pire::Scanner> trim(&blanks, &blanksReversed);
+ *     trim.Run(text, offsets, n).Select(PIRE_HIP_AFFIX_REST);      trim.Run(strings).Select(PIRE_HIP_AFFIX_HEAD);
+ *     trim.Hits()      ascending indices of the selected strings           trim.HitCount()  how many
+ *     trim.Spans()     [2 * k], [2 * k + 1]: the part of hit k is text[begin, end)
+ * A buffer as it was read, cut into lines on the device (pire_hip_affix_lines_gather; getline's semantics, as
+ * BatchRunner::RunLines()): `grep -o '^re'` (HEAD), `sed 's/^re//'` on the lines that match (REST), a trim of both ends (REST
+ * with both scanners):
+ *     trim.RunLines(raw, size, '\n', PIRE_HIP_AFFIX_REST);
+ *     trim.Spans()     byte ranges of raw                                  trim.LineCount()  lines in the buffer
+ *     trim.HitText()   the parts back to back, '\n' (or the byte given) behind each, gathered on the device
+ *     trim.HitTextOffsets()   part k is HitText()[o[k], o[k + 1])
+ * The caller's arrays are read when an accessor first asks: they live until then.  HitText() is a call of its own, as in
+ * BatchRunner: after Hits() / Spans() it scans the buffer a second time.
+ */
+template <class Scanner>
+class AffixBatchRunner {
+public:
+	AffixBatchRunner(const Scanner* head, const Scanner* tail, uint32_t headOpts = PIRE_HIP_AFFIX_LONGEST,
+	                 uint32_t tailOpts = PIRE_HIP_AFFIX_LONGEST)
+	    : m_head(head ? new Table<Scanner>(*head) : nullptr), m_tail(nullptr), m_headOpts(headOpts), m_tailOpts(tailOpts), m_form(kNone),
+	      m_text(nullptr), m_offsets(nullptr), m_n(0), m_len(0), m_delim('\n'), m_part(PIRE_HIP_AFFIX_HEAD), m_listed(false), m_haveText(false),
+	      m_textTail('\n'), m_hitCount(0), m_lineCount(0)
+	{
+		try {
+			m_tail = tail ? new Table<Scanner>(*tail) : nullptr;
+		} catch (...) {
+			delete m_head;
+			throw;
+		}
+	}
+	~AffixBatchRunner()
+	{
+		delete m_head;
+		delete m_tail;
+	}
+
+	/* The batch: string i = text[offsets[i], offsets[i+1]).  Host pointers. */
+	AffixBatchRunner& Run(const char* text, const uint64_t* offsets, size_t n) { return SetBatch(kStrings, text, offsets, n, 0, '\n', m_part); }
+	AffixBatchRunner& Run(const std::vector<ystring>& strings)
+	{
+		m_ownStrings.Assign(strings);
+		return Run(m_ownStrings.Text(), m_ownStrings.Offsets(), strings.size());
+	}
+	AffixBatchRunner& Select(uint32_t part)
+	{
+		m_part = part;
+		m_listed = m_haveText = false;
+		return *this;
+	}
+	AffixBatchRunner& RunLines(const char* raw, size_t size, char delim = '\n', uint32_t part = PIRE_HIP_AFFIX_HEAD)
+	{
+		return SetBatch(kLines, raw, nullptr, 0, size, delim, part);
+	}
+	uint64_t HitCount() { FetchHits(); return m_hitCount; }
+	const std::vector<uint64_t>& Hits() { FetchHits(); return m_hits; }
+	const std::vector<uint64_t>& Spans() { FetchHits(); return m_spans; }
+	uint64_t LineCount() { NeedLines("LineCount()"); FetchHits(); return m_lineCount; }
+	const std::string& HitText(char tail = '\n') { FetchHitText(tail); return m_hitText; }
+	const std::vector<uint64_t>& HitTextOffsets()
+	{
+		if (!m_haveText)
+			FetchHitText('\n');
+		return m_hitTextOffsets;
+	}
+
+private:
+	AffixBatchRunner(const AffixBatchRunner&);
+	AffixBatchRunner& operator=(const AffixBatchRunner&);
+
+	enum Form { kNone, kStrings, kLines };
+	AffixBatchRunner& SetBatch(Form form, const char* text, const uint64_t* offsets, size_t n, size_t len, char delim, uint32_t part)
+	{
+		m_form = form, m_text = text, m_offsets = offsets, m_n = n, m_len = len, m_delim = uint8_t(delim), m_part = part;
+		m_listed = m_haveText = false;
+		return *this;
+	}
+	pire_hip_table* Head() const { return m_head ? m_head->Handle() : nullptr; }
+	pire_hip_table* Tail() const { return m_tail ? m_tail->Handle() : nullptr; }
+	void NeedLines(const char* what) const
+	{
+		if (m_form != kLines)
+			throw Pire::Error(std::string("pire_hip: ") + what + " follows RunLines()");
+	}
+
+	/* One call with room for every string -- RunLines(): for a hit on every line of 64 bytes or more, BatchRunner's first
+	 * capacity --, and a second one where there are more */
+	void FetchHits()
+	{
+		if (m_listed)
+			return;
+		if (m_form == kNone)
+			throw Pire::Error("pire_hip: Hits() follows Run() or RunLines()");
+		GrowAndRetry(m_form == kLines ? m_len / 64 + 1024 : m_n, [&](size_t cap) {
+			m_hits.resize(cap);
+			m_spans.resize(cap * 2);
+			Check(m_form == kLines
+			          ? pire_hip_affix_lines_gather(Head(), m_headOpts, Tail(), m_tailOpts, m_text, m_len, m_delim, m_part, 0,
+			                                        PIRE_HIP_GATHER_NO_TAIL, &m_lineCount, m_hits.data(), m_spans.data(), cap, &m_hitCount,
+			                                        nullptr, 0, nullptr, nullptr, nullptr)
+			          : pire_hip_affix_run_select(Head(), m_headOpts, Tail(), m_tailOpts, m_text, OwnedStrings::OffsetsOr(m_offsets, m_n), m_n,
+			                                      m_part, 0, nullptr, nullptr, m_hits.data(), m_spans.data(), cap, &m_hitCount, nullptr));
+			return size_t(m_hitCount);
+		});
+		m_hits.resize(m_hitCount);
+		m_spans.resize(m_hitCount * 2);
+		m_listed = true;
+	}
+
+	/* RunLines(): the parts as bytes; room for every byte they can have, and for the hits that are known, or else FetchHits()'s */
+	void FetchHitText(char tail)
+	{
+		NeedLines("HitText()");
+		if (m_haveText && m_textTail == tail)
+			return;
+		uint64_t count = 0, bytes = 0;
+		GrowAndRetry(m_listed ? size_t(m_hitCount) : m_len / 64 + 1024, [&](size_t cap) {
+			m_hitTextOffsets.resize(cap + 1);
+			m_hitText.resize(m_len + cap + 1);
+			Check(pire_hip_affix_lines_gather(Head(), m_headOpts, Tail(), m_tailOpts, m_text, m_len, m_delim, m_part, 0, uint8_t(tail),
+			                                  &m_lineCount, nullptr, nullptr, cap, &count, &m_hitText[0], m_hitText.size(),
+			                                  m_hitTextOffsets.data(), &bytes, nullptr));
+			return size_t(count);   // (the text has room for the whole buffer and a tail per hit: where the hits fit, the bytes do)
+		});
+		m_hitText.resize(bytes);
+		m_hitTextOffsets.resize(count + 1);
+		m_textTail = tail;
+		m_haveText = true;
+	}
+
+	Table<Scanner>* m_head;       // nullable: no head is looked for
+	Table<Scanner>* m_tail;       // nullable
+	uint32_t m_headOpts, m_tailOpts;
+	Form m_form;
+	const char* m_text;           // Run(): the strings' text; RunLines(): the raw buffer of m_len bytes
+	const uint64_t* m_offsets;
+	size_t m_n, m_len;
+	uint8_t m_delim;
+	uint32_t m_part;
+	bool m_listed, m_haveText;    // m_hits, m_spans (and m_lineCount) / m_hitText are the batch's, with the tail m_textTail
+	char m_textTail;
+	OwnedStrings m_ownStrings;
+	uint64_t m_hitCount, m_lineCount;
+	std::vector<uint64_t> m_hits, m_spans, m_hitTextOffsets;
+	std::string m_hitText;
 };
 
 }  // namespace Hip

@@ -140,6 +140,8 @@ FIELDS_TILE = 16384   # include/pire_hip.h PIRE_HIP_FIELDS_TILE_BYTES: the field
 COUNT_ALL = 1   # include/pire_hip.h PIRE_HIP_COUNT_ALL (in `mode`): every wanted regexp reaches its threshold
 FINAL_SELECT_ZERO = 1   # include/pire_hip.h PIRE_HIP_FINAL_SELECT_ZERO (`mode`): the strings whose Final flag is NOT set
 FIELDS_REST = 1   # include/pire_hip.h PIRE_HIP_FIELDS_REST (in `mode`): the span runs to the end of the string, `cut -f k-`
+AFFIX_HEAD, AFFIX_TAIL, AFFIX_REST = 0, 1, 2   # include/pire_hip.h PIRE_HIP_AFFIX_HEAD / _TAIL / _REST (`part`)
+AFFIX_LONGEST, AFFIX_THROUGH_BEGIN, AFFIX_THROUGH_END = 1, 2, 4   # include/pire_hip.h PIRE_HIP_AFFIX_* (`head_opts`, `tail_opts`)
 
 # every symbol include/pire_hip.h declares: (name, restype, argtypes)
 ABI = [
@@ -250,6 +252,9 @@ ABI = [
     ("pire_hip_slow_run_select_strided", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_slow_lines_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_slow_lines_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_affix_select", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_affix_run_select", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_affix_lines_gather", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_multi_create", C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
     ("pire_hip_multi_destroy", None, [C.c_void_p]),
     ("pire_hip_multi_device_count", C.c_int, [C.c_void_p]),
@@ -539,6 +544,109 @@ def final_select_device(final_ptr: int, n: int, out_hit_count_ptr: int, invert=F
     """pire_hip_final_select with PIRE_HIP_RUN_ON_DEVICE: raw device addresses, only enqueues on `stream`."""
     _check(lib().pire_hip_final_select(final_ptr or None, n, _final_mode(invert), FLAG_ON_DEVICE, out_hits_ptr or None, hit_cap,
                                        out_hit_count_ptr or None, stream or None))
+
+
+# --- from prefix and suffix lengths to matched heads and tails (pire_hip_affix_select and the forms on top of it)
+def affix_opts(longest=True, through_begin=False, through_end=False) -> int:
+    """the PIRE_HIP_AFFIX_* bits of one scan"""
+    return (AFFIX_LONGEST if longest else 0) | (AFFIX_THROUGH_BEGIN if through_begin else 0) | (AFFIX_THROUGH_END if through_end else 0)
+
+
+def _table_ptr(t):
+    return None if t is None else t._h
+
+
+def affix_select_host(offsets, head_len=None, tail_len=None, part=AFFIX_HEAD, hit_cap: Optional[int] = None, want_hits=True,
+                      want_spans=True):
+    """pire_hip_affix_select on host arrays: {"hits" u64[k] or None, "spans" u64[k, 2] or None, "count"}, k = min(count,
+    hit_cap); hit_cap None = room for every string."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    head_len = None if head_len is None else np.ascontiguousarray(head_len, dtype=np.int64)
+    tail_len = None if tail_len is None else np.ascontiguousarray(tail_len, dtype=np.int64)
+    n = len(offsets) - 1
+    cap = n if hit_cap is None else int(hit_cap)
+    hits = np.zeros(cap, dtype=np.uint64) if want_hits else None
+    spans = np.zeros((cap, 2), dtype=np.uint64) if want_spans else None
+    cnt = C.c_uint64(0)
+    _check(lib().pire_hip_affix_select(offsets.ctypes.data, n, part, 0, _np_ptr(head_len), _np_ptr(tail_len),
+                                       _np_ptr(hits) if cap else None, _np_ptr(spans) if cap else None, cap, C.byref(cnt), None))
+    k = min(int(cnt.value), cap)
+    return {"hits": None if hits is None else hits[:k], "spans": None if spans is None else spans[:k], "count": int(cnt.value)}
+
+
+def affix_select_device(offsets_ptr: int, n: int, out_hit_count_ptr: int, head_len_ptr=0, tail_len_ptr=0, part=AFFIX_HEAD,
+                        out_hits_ptr=0, out_spans_ptr=0, hit_cap=0, stream: int = 0):
+    """pire_hip_affix_select with PIRE_HIP_RUN_ON_DEVICE: raw device addresses, only enqueues on `stream`."""
+    _check(lib().pire_hip_affix_select(offsets_ptr or None, n, part, FLAG_ON_DEVICE, head_len_ptr or None, tail_len_ptr or None,
+                                       out_hits_ptr or None, out_spans_ptr or None, hit_cap, out_hit_count_ptr or None, stream or None))
+
+
+def affix_run_select(head, tail, text, offsets, part=AFFIX_HEAD, head_opts=AFFIX_LONGEST, tail_opts=AFFIX_LONGEST,
+                     hit_cap: Optional[int] = None, lengths=True, generic=False):
+    """pire_hip_affix_run_select on host strings; head, tail: Table or None.  {"hits", "spans", "count"} and, with lengths,
+    {"head_len", "tail_len"} (None for the table that is not given); without, the library keeps those arrays to itself."""
+    text = _raw_bytes(text)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    cap = n if hit_cap is None else int(hit_cap)
+    hl = np.empty(n, dtype=np.int64) if lengths and head is not None else None
+    tl = np.empty(n, dtype=np.int64) if lengths and tail is not None else None
+    hits = np.zeros(cap, dtype=np.uint64)
+    spans = np.zeros((cap, 2), dtype=np.uint64)
+    cnt = C.c_uint64(0)
+    _check(lib().pire_hip_affix_run_select(_table_ptr(head), head_opts, _table_ptr(tail), tail_opts, text.ctypes.data if text.size else None,
+                                           offsets.ctypes.data, n, part, FLAG_GENERIC if generic else 0, _np_ptr(hl), _np_ptr(tl),
+                                           hits.ctypes.data if cap else None, spans.ctypes.data if cap else None, cap, C.byref(cnt), None))
+    k = min(int(cnt.value), cap)
+    out = {"hits": hits[:k], "spans": spans[:k], "count": int(cnt.value)}
+    if lengths:
+        out.update(head_len=hl, tail_len=tl)
+    return out
+
+
+def affix_run_select_device(head, tail, text_ptr: int, offsets_ptr: int, n: int, out_hit_count_ptr: int, part=AFFIX_HEAD,
+                            head_opts=AFFIX_LONGEST, tail_opts=AFFIX_LONGEST, out_head_len_ptr=0, out_tail_len_ptr=0, out_hits_ptr=0,
+                            out_spans_ptr=0, hit_cap=0, stream: int = 0, generic=False):
+    """pire_hip_affix_run_select on device pointers: only enqueues on `stream`."""
+    _check(lib().pire_hip_affix_run_select(_table_ptr(head), head_opts, _table_ptr(tail), tail_opts, text_ptr or None, offsets_ptr or None, n,
+                                           part, FLAG_ON_DEVICE | (FLAG_GENERIC if generic else 0), out_head_len_ptr or None,
+                                           out_tail_len_ptr or None, out_hits_ptr or None, out_spans_ptr or None, hit_cap,
+                                           out_hit_count_ptr or None, stream or None))
+
+
+def affix_lines_gather_host(head, tail, raw, part=AFFIX_HEAD, delim: int = 10, head_opts=AFFIX_LONGEST, tail_opts=AFFIX_LONGEST,
+                            tail_byte=-1, hit_cap=None, text_cap=None, gather=True):
+    """pire_hip_affix_lines_gather on a host buffer: {"lines", "hits", "spans", "count"} and, with gather, {"text", "offsets",
+    "bytes"}.  tail_byte -1 = the delimiter, None = none; hit_cap None = room for a hit on every line, text_cap None = for all
+    of them."""
+    raw = _raw_bytes(raw)
+    cap = raw.size if hit_cap is None else int(hit_cap)
+    room = (raw.size + cap if text_cap is None else int(text_cap)) if gather else 0
+    hits = np.zeros(cap, dtype=np.uint64)
+    spans = np.zeros((cap, 2), dtype=np.uint64)
+    text = np.zeros(max(room, 1), dtype=np.uint8)
+    offsets = np.zeros(cap + 1, dtype=np.uint64)
+    lines, cnt, total = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    _check(lib().pire_hip_affix_lines_gather(_table_ptr(head), head_opts, _table_ptr(tail), tail_opts, raw.ctypes.data if raw.size else None,
+                                             raw.size, delim, part, 0, _tail(delim if tail_byte == -1 else tail_byte), C.byref(lines),
+                                             hits.ctypes.data if cap else None, spans.ctypes.data if cap else None, cap, C.byref(cnt),
+                                             text.ctypes.data if room else None, room, offsets.ctypes.data if gather else None,
+                                             C.byref(total) if gather else None, None))
+    k = min(int(cnt.value), cap)
+    out = {"lines": int(lines.value), "hits": hits[:k], "spans": spans[:k], "count": int(cnt.value)}
+    if gather:
+        out.update(text=text[:min(int(total.value), room)], offsets=offsets[:k + 1], bytes=int(total.value))
+    return out
+
+
+def affix_lines_gather_device(head, tail, raw_ptr: int, size: int, out_line_count_ptr: int, out_hit_count_ptr: int, part=AFFIX_HEAD,
+                              out_bytes_ptr=0, delim: int = 10, head_opts=AFFIX_LONGEST, tail_opts=AFFIX_LONGEST, tail_byte=-1,
+                              out_hits_ptr=0, out_spans_ptr=0, hit_cap=0, out_text_ptr=0, text_cap=0, out_offsets_ptr=0, stream: int = 0):
+    """pire_hip_affix_lines_gather on device pointers (synchronises `stream` once, as run_lines_select_device does)."""
+    _check(lib().pire_hip_affix_lines_gather(_table_ptr(head), head_opts, _table_ptr(tail), tail_opts, raw_ptr or None, size, delim, part,
+                                             FLAG_ON_DEVICE, _tail(delim if tail_byte == -1 else tail_byte), out_line_count_ptr or None,
+                                             out_hits_ptr or None, out_spans_ptr or None, hit_cap, out_hit_count_ptr or None,
+                                             out_text_ptr or None, text_cap, out_offsets_ptr or None, out_bytes_ptr or None, stream or None))
 
 
 def capture_select_host(offsets, begin, end, final=None, flags=FLAG_BEGIN, need_final=False, hit_cap: Optional[int] = None,

@@ -3082,6 +3082,26 @@ try {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
 
+// The scan parameters of the prefix and the suffix searches (the caller holds the table: TableUse), for pire_hip_prefix /
+// pire_hip_suffix and for the calls that run both (pire_hip_affix_run_select)
+static int PrefixParams(pire_hip_table* t, ScanParams* p, bool throughBegin)
+{
+	if (int rc = FillParams(t, p, throughBegin ? PIRE_HIP_RUN_BEGIN : 0, /*wantDist=*/true))   // startPerm = Initialize [+ BeginMark]
+		return rc;
+	p->actDist = p->distFlaggedPerm;
+	return PIRE_HIP_OK;
+}
+static int SuffixParams(pire_hip_table* t, ScanParams* p, bool throughEnd)
+{
+	if (int rc = FillParams(t, p, 0))
+		return rc;
+	if (throughEnd) {   // Initialize, then Step(EndMark): run.h:319-320 / 349-350
+		const HostTable& h = t->host;
+		p->startPerm = p->hostPermOfOrig[h.next[size_t(h.initial) * h.letters + h.cls[kEndMark]]];
+	}
+	return PIRE_HIP_OK;
+}
+
 int pire_hip_prefix(pire_hip_table* t, const void* text, const uint64_t* offsets, uint64_t n, int longest,
                     int through_begin, int through_end, uint32_t flags, int64_t* out_len, void* streamPtr)
 try {
@@ -3095,12 +3115,11 @@ try {
 			return rc;
 	ScanParams p;
 	TableUse use(t, (flags & PIRE_HIP_RUN_ON_DEVICE) != 0);
-	if (int rc = FillParams(t, &p, through_begin ? PIRE_HIP_RUN_BEGIN : 0, /*wantDist=*/true))   // startPerm = Initialize [+ BeginMark]
+	if (int rc = PrefixParams(t, &p, through_begin != 0))
 		return rc;
 	p.n = n;
 	if (n == 0)
 		return PIRE_HIP_OK;
-	p.actDist = p.distFlaggedPerm;
 	BatchIO io(stream, (flags & PIRE_HIP_RUN_ON_DEVICE) != 0);
 	long long* dOut = nullptr;
 	if (int rc = io.Text(text, offsets, n, 0, 0, &p.text, &p.offsets))
@@ -3219,12 +3238,8 @@ try {
 			return rc;
 	ScanParams p;
 	TableUse use(t, (flags & PIRE_HIP_RUN_ON_DEVICE) != 0);
-	if (int rc = FillParams(t, &p, 0))
+	if (int rc = SuffixParams(t, &p, through_end != 0))
 		return rc;
-	if (through_end) {   // Initialize, then Step(EndMark): run.h:319-320 / 349-350
-		const HostTable& h = t->host;
-		p.startPerm = p.hostPermOfOrig[h.next[size_t(h.initial) * h.letters + h.cls[kEndMark]]];
-	}
 	p.n = n;
 	if (n == 0)
 		return PIRE_HIP_OK;
@@ -3241,6 +3256,206 @@ try {
 	return io.Finish();
 } catch (...) {
 	return pirehip::HandleException();
+}
+
+// ---- the matched heads and tails of a batch (exact.hip, affix.hip) and of the lines of a buffer ------------------------------
+namespace {
+
+// The two scans of the affix forms, as the caller of an entry point gave them (either table may be null, not both)
+struct AffixScans {
+	pire_hip_table* head;
+	uint32_t headOpts;
+	pire_hip_table* tail;
+	uint32_t tailOpts;
+};
+
+int AffixScansInvalid(const char* who, const AffixScans& s)
+{
+	const uint32_t known = PIRE_HIP_AFFIX_LONGEST | PIRE_HIP_AFFIX_THROUGH_BEGIN | PIRE_HIP_AFFIX_THROUGH_END;
+	const char* what = !s.head && !s.tail      ? "null head and null tail"
+	                   : s.headOpts & ~known   ? "unknown bits in head_opts"
+	                   : s.tailOpts & ~known   ? "unknown bits in tail_opts"
+	                                           : nullptr;
+	if (!what)
+		return PIRE_HIP_OK;
+	SetError(std::string(who) + ": " + what);
+	return PIRE_HIP_EINVAL;
+}
+
+// Both tables held still for one entry point, and their scan parameters.  Prepare (n > 0): each scan's first-use self-test
+// (it calls the scan's own entry point: before the tables are held), then the tables in address order -- two calls with the
+// tables swapped must not wait for each other (RunPairImpl) --, then the parameters.
+struct AffixTables {
+	TableUse use1, use2;
+	ScanParams ph, pt;
+	int Prepare(const AffixScans& s, bool enqueueOnly, hipStream_t stream)
+	{
+		if (s.head)
+			if (int rc = SelfTestPrefix(s.head, false, (s.headOpts & PIRE_HIP_AFFIX_THROUGH_BEGIN) != 0, (s.headOpts & PIRE_HIP_AFFIX_THROUGH_END) != 0,
+			                            stream))
+				return rc;
+		if (s.tail)
+			if (int rc = SelfTestPrefix(s.tail, true, (s.tailOpts & PIRE_HIP_AFFIX_THROUGH_END) != 0, (s.tailOpts & PIRE_HIP_AFFIX_THROUGH_BEGIN) != 0,
+			                            stream))
+				return rc;
+		pire_hip_table* first = !s.head ? s.tail : !s.tail ? s.head : std::min(s.head, s.tail);
+		pire_hip_table* second = s.head && s.tail && s.head != s.tail ? std::max(s.head, s.tail) : nullptr;
+		use1.Acquire(first, enqueueOnly);
+		if (second)
+			use2.Acquire(second, enqueueOnly);
+		if (s.head)
+			if (int rc = PrefixParams(s.head, &ph, (s.headOpts & PIRE_HIP_AFFIX_THROUGH_BEGIN) != 0))
+				return rc;
+		if (s.tail)
+			if (int rc = SuffixParams(s.tail, &pt, (s.tailOpts & PIRE_HIP_AFFIX_THROUGH_END) != 0))
+				return rc;
+		return PIRE_HIP_OK;
+	}
+};
+
+// The scans and the pass enqueued on `stream`, device pointers only (n > 0).  dHeadLen / dTailLen: nullable -- what the caller
+// has no array for lives in stream-ordered scratch.  shift: as LaunchAffixSelect's.
+int AffixEnqueue(const AffixScans& s, AffixTables& tabs, const void* dText, const uint64_t* dOffsets, uint64_t n, uint32_t flags,
+                 int64_t* dHeadLen, int64_t* dTailLen, uint32_t part, uint64_t shift, uint64_t* dHits, uint64_t* dSpans, uint64_t cap,
+                 uint64_t* dCount, hipStream_t stream)
+{
+	StreamScratch ownHead(stream), ownTail(stream);
+	long long* headLen = reinterpret_cast<long long*>(dHeadLen);
+	long long* tailLen = reinterpret_cast<long long*>(dTailLen);
+	if (s.head && !headLen) {
+		if (int rc = ownHead.Alloc(size_t(n) * 8, "hipMallocAsync(head lengths)"))
+			return rc;
+		headLen = ownHead.as<long long>();
+	}
+	if (s.tail && !tailLen) {
+		if (int rc = ownTail.Alloc(size_t(n) * 8, "hipMallocAsync(tail lengths)"))
+			return rc;
+		tailLen = ownTail.as<long long>();
+	}
+	if (s.head) {
+		ScanParams& p = tabs.ph;
+		p.n = n;
+		p.text = static_cast<const uint8_t*>(dText);
+		p.offsets = dOffsets;
+		if (int rc = LaunchPrefix(p, (s.headOpts & PIRE_HIP_AFFIX_LONGEST) != 0, (s.headOpts & PIRE_HIP_AFFIX_THROUGH_END) != 0, headLen, stream,
+		                          (flags & PIRE_HIP_RUN_GENERIC) ? nullptr : NextWorkSlot(s.head, p)))
+			return rc;
+	}
+	if (s.tail) {
+		ScanParams& p = tabs.pt;
+		p.n = n;
+		p.text = static_cast<const uint8_t*>(dText);
+		p.offsets = dOffsets;
+		if (int rc = LaunchSuffix(p, (s.tailOpts & PIRE_HIP_AFFIX_LONGEST) != 0, (s.tailOpts & PIRE_HIP_AFFIX_THROUGH_BEGIN) != 0, tailLen, stream))
+			return rc;
+	}
+	return LaunchAffixSelect(dOffsets, n, part, s.head ? headLen : nullptr, s.tail ? tailLen : nullptr, shift, dHits, dSpans, cap, dCount, stream);
+}
+
+}  // namespace
+
+int pire_hip_affix_run_select(pire_hip_table* head, uint32_t head_opts, pire_hip_table* tail, uint32_t tail_opts, const void* text,
+                              const uint64_t* offsets, uint64_t n, uint32_t part, uint32_t flags, int64_t* out_head_len,
+                              int64_t* out_tail_len, uint64_t* out_hits, uint64_t* out_spans, uint64_t hit_cap, uint64_t* out_hit_count,
+                              void* streamPtr)
+try {
+	const char* who = "pire_hip_affix_run_select";
+	const AffixScans scans = {head, head_opts, tail, tail_opts};
+	if (int rc = AffixScansInvalid(who, scans))
+		return rc;
+	const AffixSelectOut o = {part, out_hits, out_spans, hit_cap, out_hit_count};
+	if (int rc = AffixSelectArgsInvalid(who, n, offsets != nullptr, head != nullptr, tail != nullptr, o))
+		return rc;
+	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
+	AffixSelectStage pass(o, onDevice);
+	if (n == 0)
+		return pass.Empty(stream);
+	if (!onDevice) {   // what the scans refuse of a host batch, before their self-tests touch a device
+		uint64_t textBytes = 0;
+		if (int rc = CheckHostBatch(text, offsets, n, 0, 0, &textBytes))
+			return rc;
+	}
+	AffixTables tabs;
+	if (int rc = tabs.Prepare(scans, onDevice, stream))
+		return rc;
+	// host pointers: the text staged once, both scans and the pass on the staged copy, then everything back
+	BatchIO io(stream, onDevice);
+	const uint8_t* dText = nullptr;
+	const uint64_t* dOffsets = nullptr;
+	int64_t *dHeadLen = nullptr, *dTailLen = nullptr;
+	if (int rc = io.Text(text, offsets, n, 0, 0, &dText, &dOffsets))
+		return rc;
+	if (head && out_head_len)
+		if (int rc = io.Result(out_head_len, size_t(n), size_t(n), &dHeadLen))
+			return rc;
+	if (tail && out_tail_len)
+		if (int rc = io.Result(out_tail_len, size_t(n), size_t(n), &dTailLen))
+			return rc;
+	if (int rc = pass.Results(io, n))
+		return rc;
+	if (int rc = io.Ready())
+		return rc;
+	if (int rc = AffixEnqueue(scans, tabs, dText, dOffsets, n, flags, dHeadLen, dTailLen, part, 0, pass.dHits, pass.dSpans, pass.cap, pass.dCount,
+	                          stream))
+		return rc;
+	if (int rc = io.Finish())
+		return rc;
+	return pass.Back();
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+// The frame around the two searches: the scans on the lines, the pass with shift = 1 (string i of the split buffer lies i bytes
+// further into raw), the gather from raw through its spans.
+int pire_hip_affix_lines_gather(pire_hip_table* head, uint32_t head_opts, pire_hip_table* tail, uint32_t tail_opts, const void* raw,
+                                uint64_t size, uint32_t delim, uint32_t part, uint32_t flags, uint32_t tail_byte, uint64_t* out_line_count,
+                                uint64_t* out_hits, uint64_t* out_spans, uint64_t hit_cap, uint64_t* out_hit_count, void* out_text,
+                                uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes, void* streamPtr)
+try {
+	const char* who = "pire_hip_affix_lines_gather";
+	const AffixScans scans = {head, head_opts, tail, tail_opts};
+	if (int rc = AffixScansInvalid(who, scans))
+		return rc;
+	if (int rc = SplitArgsInvalid(who, raw, size, delim, out_line_count, "out_line_count"))
+		return rc;
+	// no gather output at all: spans only.  (The gather form keeps the span list to itself where the caller has no array for it.)
+	const bool gathers = out_text || text_cap || out_offsets || out_bytes;
+	const AffixSelectOut o = {part, out_hits, out_spans, hit_cap, out_hit_count};
+	if (int rc = AffixSelectArgsInvalid(who, 0, true, head != nullptr, tail != nullptr, o, gathers))
+		return rc;
+	if (gathers) {
+		if (int rc = GatherOutputsInvalid(who, "hit_cap", hit_cap, tail_byte, out_text, text_cap, out_offsets, out_bytes))
+			return rc;
+		if (int rc = GatherOverlaps(who, raw, size, out_text, text_cap))
+			return rc;
+	}
+	const LinesGather gather = {tail_byte, out_text, text_cap, out_offsets, out_bytes, false, "hipMallocAsync(affix spans)"};
+	LinesFrame f(who, raw, size, delim, flags, gathers ? &gather : nullptr, streamPtr);
+	if (f.HostEdge(out_line_count)) {
+		*out_hit_count = 0;
+		return PIRE_HIP_OK;
+	}
+	if (int rc = f.Open())
+		return rc;
+	if (int rc = f.Split(out_line_count, out_hit_count, 1, hit_cap, true))
+		return rc;
+	if (int rc = f.Lists(out_hits, out_spans))
+		return rc;
+	if (f.n == 0) {
+		if (int rc = f.ZeroCounts("hipMemsetAsync(hit count)"))
+			return rc;
+	} else {
+		AffixTables tabs;
+		if (int rc = tabs.Prepare(scans, f.onDevice, f.stream))
+			return rc;
+		if (int rc = AffixEnqueue(scans, tabs, f.Text(), f.Offsets(), f.n, f.RunFlags(), nullptr, nullptr, part, 1, f.dHits, f.dSpans, f.cap,
+		                          f.dCounts, f.stream))
+			return rc;
+	}
+	return f.Close("hipMemcpy(affix spans)");
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
 
 int pire_hip_step(pire_hip_table* t, uint32_t* state_idx, uint64_t n, uint32_t ch, void* stream)

@@ -1170,6 +1170,38 @@ struct FinalSelectStage {
 	int Launch(const uint8_t* fin, uint64_t n, hipStream_t stream);
 	int Back();                      // host pointers: the count, and the list only as far as it was written
 };
+// affix.hip: from prefix and suffix lengths to a compacted, ascending list of the strings that matched and the byte range of
+// the matched head, the matched tail or what they leave (pire_hip_affix_select).  Device pointers only, three kernels enqueued
+// on `stream`, the compaction's scratch from the stream-ordered allocator.  headLen / tailLen: nullable, not both where n > 0.
+// shift: as LaunchCaptureSelect's.  n == 0: the count zeroed on the stream.
+int LaunchAffixSelect(const uint64_t* offsets, uint64_t n, uint32_t part, const long long* headLen, const long long* tailLen,
+                      uint64_t shift, uint64_t* outHits, uint64_t* outSpans, uint64_t hitCap, uint64_t* outHitCount, hipStream_t stream);
+// The pass's own arguments, as the caller of an entry point gave them
+struct AffixSelectOut {
+	uint32_t part;
+	uint64_t* outHits;
+	uint64_t* outSpans;
+	uint64_t hitCap;
+	uint64_t* outHitCount;
+};
+// What pire_hip_affix_select refuses before any device is touched, in `who`'s name (have*: there is such an array to read;
+// ownList: the entry point keeps the span list to itself where the caller has no array for it)
+int AffixSelectArgsInvalid(const char* who, uint64_t n, bool haveOffsets, bool haveHead, bool haveTail, const AffixSelectOut& o,
+                           bool ownList = false);
+// The pass inside ONE call of an entry point (pire_hip_affix_select itself, and the two scans it follows on their stream), on
+// whichever side the caller's pointers live.  Order: Empty() instead of everything where there is nothing to read; else
+// Results() with its result arrays, io.Ready(), the scans, Launch(), io.Finish(), Back().
+struct AffixSelectStage {
+	const AffixSelectOut o;
+	const bool onDevice;
+	uint64_t *dCount = nullptr, *dHits = nullptr, *dSpans = nullptr;
+	uint64_t cap = 0, count = 0;   // host pointers: no list is staged longer than the strings are many; the count comes back here first
+	AffixSelectStage(const AffixSelectOut& o_, bool onDevice_) : o(o_), onDevice(onDevice_) {}
+	int Empty(hipStream_t stream);   // no strings: a count of 0 -- host pointers: no device is touched
+	int Results(BatchIO& io, uint64_t n);
+	int Launch(const uint64_t* offsets, uint64_t n, const int64_t* headLen, const int64_t* tailLen, hipStream_t stream);
+	int Back();                      // host pointers: the count, and the lists only as far as they were written
+};
 // split.hip: raw text into strings (pire_hip_split).  Device pointers only, everything enqueued on `stream`.  The pass
 // comes in two halves because a caller may want the number of strings before it has room for their offsets:
 // LaunchSplitCount counts and scans (*outN = n; the tile prefixes stay in `scratch`, the caller's owner, which has to live
