@@ -1293,6 +1293,85 @@ int pire_hip_half_final_lines_select(pire_hip_table* t, const void* raw, uint64_
                                      uint64_t* out_totals, uint64_t* out_hits, uint64_t* out_hit_spans,
                                      uint32_t* out_hit_results, uint64_t hit_cap, uint64_t* out_hit_count, void* stream);
 
+/* ---- the lines around a match, on the device (grep -A / -B / -C) -------------------------------------------------- */
+
+/*
+ * From a hit list to the hits and their neighbours: the ascending list of the lines that lie within `after` lines behind or
+ * `before` lines in front of a hit, and two bits a line.  It takes no table and no text: it reads line numbers, whoever wrote
+ * them -- every hit pass of the library writes such a list.  With k = min(hit_count ? *hit_count : hit_cap, hit_cap) (as
+ * pire_hip_gather) and hits[0, k) strictly ascending, every entry < n:
+ *   selected(i) <=> 0 <= i < n and there is j < k with hits[j] - before <= i <= hits[j] + after
+ * over the integers: nothing wraps, every value of before and after is legal, 2^64 - 1 included; before = after = 0 gives the
+ * hit list back.  out_lines[line_cap] (nullable): the selected i, ascending.  out_line_flags[line_cap] (nullable, needs
+ * out_lines): for out_lines[r],
+ *   PIRE_HIP_CONTEXT_HIT    the line is itself in the hit list (grep -n prints ':' behind its number, else '-')
+ *   PIRE_HIP_CONTEXT_GROUP  i == 0 or line i - 1 is not selected: the first line of a run (where grep prints "--" in front,
+ *                           the first run excepted)
+ * *out_line_count (required): the number of selected lines, also when it exceeds line_cap; only the first
+ * min(count, line_cap) entries of the two lists are written, nothing behind them.  *out_group_count (nullable): the number of
+ * selected lines that carry PIRE_HIP_CONTEXT_GROUP.  n == 0 or k == 0: both counts are 0, nothing else is written.
+ * flags: PIRE_HIP_RUN_ON_DEVICE -> every pointer (hit_count included) is a device pointer and the call only enqueues on
+ *        `stream`: classify per tile of 1 024 LINES -- a hit with after = 10^6 costs what any other costs --, the one-block
+ *        scan of pire_hip_select (a second launch of it for out_group_count), scatter; no atomics, no block waits for
+ *        another: the same input gives the same bits.  Scratch (3 * n / 8 + n / 128 bytes) comes from the stream-ordered
+ *        allocator: the rule and the capture-mode caveat stated at pire_hip_select.  `hits` and out_line_flags may have any
+ *        alignment.  A list that is not ascending, or that names lines >= n, gives an unspecified selection; even then the
+ *        call reads nothing outside hits[0, k) and writes nothing outside what is stated above.  Otherwise host pointers:
+ *        staged, synchronises, the lists come back only as far as they were written; a list that is not strictly ascending or
+ *        that names a line >= n is PIRE_HIP_EINVAL, and nothing is written.
+ * PIRE_HIP_EINVAL before any device is touched: null out_line_count; hit_cap > 0 with null hits; line_cap > 0 with null
+ * out_lines; out_line_flags without out_lines; n >= 2^32; hit_cap >= 2^32.
+ * pire_hip_last_kernel() is not changed by the pass.  No first-use self-test: it takes no table (as pire_hip_split).
+ *
+ * The chain that serves every lines form with device pointers and no read-back: pire_hip_split with out_text == NULL (the
+ * offsets of the lines in raw), any hit list over those lines, pire_hip_context, pire_hip_gather over raw and the split's
+ * offsets with idx = out_lines, idx_count = out_line_count and PIRE_HIP_GATHER_NO_TAIL (an offset range of the split with
+ * out_text == NULL includes the line's delimiter).
+ */
+#define PIRE_HIP_CONTEXT_HIT   1u   /* out_line_flags: the line is itself in the hit list */
+#define PIRE_HIP_CONTEXT_GROUP 2u   /* out_line_flags: line 0, or line i - 1 is not selected: the first line of a run */
+int pire_hip_context(const uint64_t* hits, const uint64_t* hit_count, uint64_t hit_cap, uint64_t n,
+                     uint64_t before, uint64_t after, uint32_t flags,
+                     uint64_t* out_lines, uint8_t* out_line_flags, uint64_t line_cap,
+                     uint64_t* out_line_count, uint64_t* out_group_count, void* stream);
+
+/*
+ * Raw bytes in, the lines that match and their neighbours out: `grep -A after -B before`.  The split into scratch, the scan
+ * on the lines with its hit list in stream-ordered scratch (8 bytes a line at most), pire_hip_context on that list; the
+ * context list takes the place the hit list has in pire_hip_run_lines_select / _gather and pire_hip_slow_lines_select /
+ * _gather, whose t, raw, size, delim, flags, want / mode, out_line_count, one synchronisation of `stream` and refusal of 2^32
+ * lines these forms keep (mode PIRE_HIP_FINAL_SELECT_ZERO: `grep -v -C`).  out_lines[line_cap], out_line_flags[line_cap],
+ * *out_group_count: as pire_hip_context.  out_line_spans[line_cap][2] (nullable, needs out_lines): the whole line of
+ * out_lines[r] as a byte range of raw, delimiter not included.  *out_sel_count (required): the number of selected lines,
+ * pire_hip_context's out_line_count.  *out_hit_count (nullable): the number of lines that matched (`grep -c`).
+ * The gather forms: out_lines is nullable (the list then lives in scratch of the library's own); tail, out_text, text_cap,
+ * out_offsets (line_cap + 1 entries), out_bytes: as pire_hip_gather_spans.  With tail = delim out_text holds what
+ * `grep -A after -B before --no-group-separator` prints; the "--" lines are the caller's to insert, PIRE_HIP_CONTEXT_GROUP
+ * says where.  They refuse what the form they extend refuses, what pire_hip_context refuses and, of their outputs, what
+ * pire_hip_gather_spans refuses.  Host pointers with size == 0: zeros (out_offsets[0] = 0 where it is not null), no device
+ * is touched.
+ */
+int pire_hip_run_lines_context_select(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
+                                      const uint64_t* want, uint64_t before, uint64_t after, uint64_t* out_line_count,
+                                      uint64_t* out_lines, uint8_t* out_line_flags, uint64_t* out_line_spans, uint64_t line_cap,
+                                      uint64_t* out_sel_count, uint64_t* out_group_count, uint64_t* out_hit_count, void* stream);
+int pire_hip_run_lines_context_gather(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
+                                      const uint64_t* want, uint64_t before, uint64_t after, uint64_t* out_line_count,
+                                      uint64_t* out_lines, uint8_t* out_line_flags, uint64_t* out_line_spans, uint64_t line_cap,
+                                      uint64_t* out_sel_count, uint64_t* out_group_count, uint64_t* out_hit_count,
+                                      uint32_t tail, void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes,
+                                      void* stream);
+int pire_hip_slow_lines_context_select(pire_hip_slow_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
+                                       uint32_t mode, uint64_t before, uint64_t after, uint64_t* out_line_count,
+                                       uint64_t* out_lines, uint8_t* out_line_flags, uint64_t* out_line_spans, uint64_t line_cap,
+                                       uint64_t* out_sel_count, uint64_t* out_group_count, uint64_t* out_hit_count, void* stream);
+int pire_hip_slow_lines_context_gather(pire_hip_slow_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
+                                       uint32_t mode, uint64_t before, uint64_t after, uint64_t* out_line_count,
+                                       uint64_t* out_lines, uint8_t* out_line_flags, uint64_t* out_line_spans, uint64_t line_cap,
+                                       uint64_t* out_sel_count, uint64_t* out_group_count, uint64_t* out_hit_count,
+                                       uint32_t tail, void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes,
+                                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@
  *     Table             the device table, State <-> StateIndex (ToStates), Regexps()              BatchRunner, Multi-, Pair-, AffixBatchRunner
  *     CountedBatchRunner   all of HalfFinalBatchRunner and CountingBatchRunner but their table and their three C calls
  *     LineMatcher       easy.h's choice between Scanner and SlowScanner, one lines surface over BatchRunner and SlowBatchRunner
+ *     LineContext       a Context(before, after) and what was fetched for it                      BatchRunner, SlowBatchRunner
  * Which C calls these make, in which order and with which arguments, is recorded: tests/cpp/shim_calls_test.cpp,
  * tests/cpp/shim_calls.expected.txt.
  */
@@ -104,6 +105,111 @@ size_t GrowAndRetry(size_t first, Call call)
 		cap = needed;
 	}
 }
+
+/*
+ * The lines around the hits of a RunLines(): grep -A / -B / -C on the device (include/pire_hip.h, "the lines around a match").
+ * What BatchRunner and SlowBatchRunner keep of a Context(before, after): the request, and what was fetched for it -- lazily,
+ * under a Has / Stale scheme of its own: the lists with the first accessor that asks (the select form), the text with
+ * ContextText() (the gather form, a call of its own as HitText() is).  The runner makes the C call: call(Call) fills in its
+ * table, buffer, flags and selection.
+ */
+class LineContext {
+public:
+	struct Call {
+		uint64_t before, after;
+		uint64_t* lineCount;
+		uint64_t* lines;       // null in the gather form
+		uint8_t* flags;
+		uint64_t* spans;
+		uint64_t cap;
+		uint64_t *selCount, *groupCount, *hitCount;
+		bool gather;
+		uint32_t tail;
+		char* text;
+		uint64_t textCap;
+		uint64_t* offsets;
+		uint64_t* bytes;
+	};
+	LineContext() : m_before(0), m_after(0), m_asked(false), m_current(0), m_textTail('\n'), m_lineCount(0), m_selCount(0), m_groupCount(0), m_hitCount(0) {}
+	void Ask(uint64_t before, uint64_t after)
+	{
+		m_before = before, m_after = after, m_asked = true;
+		Stale(kLists | kText);
+	}
+	void NewSelection() { Stale(kLists | kText); }   // the request stays
+	void NewBatch()                                  // the request goes with the batch it was made for
+	{
+		m_asked = false;
+		Stale(kLists | kText);
+	}
+	/* One call with room for a selected line per 64 bytes of the buffer, and a second one where there are more */
+	template <class Fn>
+	void FetchLists(const char* what, size_t len, Fn call)
+	{
+		Need(what);
+		if (Has(kLists))
+			return;
+		GrowAndRetry(len / 64 + 1024, [&](size_t cap) {
+			m_lines.resize(cap);
+			m_flags.resize(cap);
+			m_spans.resize(cap * 2);
+			const Call c = {m_before, m_after, &m_lineCount, m_lines.data(), m_flags.data(), m_spans.data(), cap, &m_selCount, &m_groupCount,
+			                &m_hitCount, false, 0, nullptr, 0, nullptr, nullptr};
+			call(c);
+			return size_t(m_selCount);
+		});
+		m_lines.resize(m_selCount);
+		m_flags.resize(m_selCount);
+		m_spans.resize(m_selCount * 2);
+		m_current |= kLists;
+	}
+	/* The selected lines as bytes; room for every byte they can have, and for the lines that are known, or else FetchLists()'s */
+	template <class Fn>
+	void FetchText(const char* what, size_t len, char tail, Fn call)
+	{
+		Need(what);
+		if (Has(kText) && m_textTail == tail)
+			return;
+		uint64_t count = 0, groups = 0, hits = 0, bytes = 0;
+		GrowAndRetry(Has(kLists) ? size_t(m_selCount) : len / 64 + 1024, [&](size_t cap) {
+			m_textOffsets.resize(cap + 1);
+			m_text.resize(len + cap + 1);
+			const Call c = {m_before, m_after, &m_lineCount, nullptr, nullptr, nullptr, cap, &count, &groups, &hits, true, uint8_t(tail),
+			                &m_text[0], m_text.size(), m_textOffsets.data(), &bytes};
+			call(c);
+			return size_t(count);   // (the text has room for the whole buffer and a tail per line: where the lines fit, the bytes do)
+		});
+		m_text.resize(bytes);
+		m_textOffsets.resize(count + 1);
+		m_textTail = tail;
+		m_current |= kText;
+	}
+	bool HasText() const { return Has(kText); }
+	const std::vector<uint64_t>& Lines() const { return m_lines; }
+	const std::vector<uint8_t>& Flags() const { return m_flags; }
+	const std::vector<uint64_t>& Spans() const { return m_spans; }
+	uint64_t GroupCount() const { return m_groupCount; }
+	const std::string& Text() const { return m_text; }
+	const std::vector<uint64_t>& TextOffsets() const { return m_textOffsets; }
+
+private:
+	enum Result { kLists = 1 << 0, kText = 1 << 1 };   // m_lines .. m_hitCount / m_text, m_textOffsets are the request's, with the tail m_textTail
+	bool Has(unsigned results) const { return (m_current & results) == results; }
+	void Stale(unsigned results) { m_current &= ~results; }
+	void Need(const char* what) const
+	{
+		if (!m_asked)
+			throw Pire::Error(std::string("pire_hip: ") + what + " follows Context()");
+	}
+	uint64_t m_before, m_after;
+	bool m_asked;
+	unsigned m_current;
+	char m_textTail;
+	uint64_t m_lineCount, m_selCount, m_groupCount, m_hitCount;
+	std::vector<uint64_t> m_lines, m_spans, m_textOffsets;
+	std::vector<uint8_t> m_flags;
+	std::string m_text;
+};
 
 /* Bytes between the State values of consecutive StateIndex numbers, from public API only. */
 template <class Scanner>
@@ -320,6 +426,35 @@ public:
 		return m_hitTextOffsets;
 	}
 
+	/*
+	 * The hits of RunLines() and the lines around them: grep -A after -B before (pire_hip_run_lines_context_select / _gather).
+	 *     run.Begin().RunLines(raw, size).End().Context(2, 2);      Select({..}) in front of it chooses regexps
+	 *     run.ContextLines()   the numbers of the selected lines, ascending      run.ContextSpans()  line k is raw[begin, end)
+	 *     run.ContextFlags()   PIRE_HIP_CONTEXT_HIT | PIRE_HIP_CONTEXT_GROUP per line     run.ContextGroupCount()  the runs
+	 *     run.ContextText()    the lines back to back, '\n' (or the byte given) behind each: grep --no-group-separator's output
+	 *     run.ContextTextOffsets()   line k is ContextText()[o[k], o[k + 1])
+	 * Fetched lazily; the text is a call of its own, as HitText() is.  A new batch ends the request, a new selection keeps it.
+	 * After anything but RunLines() it throws.
+	 */
+	BatchRunner& Context(uint64_t before, uint64_t after)
+	{
+		if (m_form != kLines)
+			throw Pire::Error("pire_hip: Context() follows RunLines()");
+		m_context.Ask(before, after);
+		return *this;
+	}
+	const std::vector<uint64_t>& ContextLines() { FetchContext("ContextLines()"); return m_context.Lines(); }
+	const std::vector<uint8_t>& ContextFlags() { FetchContext("ContextFlags()"); return m_context.Flags(); }
+	const std::vector<uint64_t>& ContextSpans() { FetchContext("ContextSpans()"); return m_context.Spans(); }
+	uint64_t ContextGroupCount() { FetchContext("ContextGroupCount()"); return m_context.GroupCount(); }
+	const std::string& ContextText(char tail = '\n') { FetchContextText("ContextText()", tail); return m_context.Text(); }
+	const std::vector<uint64_t>& ContextTextOffsets()
+	{
+		if (!m_context.HasText())
+			FetchContextText("ContextTextOffsets()", '\n');
+		return m_context.TextOffsets();
+	}
+
 	/* RunHelper::State() per string (run.h:378). */
 	const std::vector<State>& States()
 	{
@@ -369,6 +504,7 @@ public:
 			if (want[i] < m_want.size() * 64)
 				m_want[want[i] / 64] |= uint64_t(1) << (want[i] % 64);
 		Stale(kSelection | kHits | kHitText);
+		m_context.NewSelection();
 		return *this;
 	}
 	size_t MaskWords() const { return pire_hip_table_mask_words(m_table->Handle()); }
@@ -454,6 +590,7 @@ private:
 		// (a selection outlives a new batch of strings, as it always has here: SelectionCurrent() looks at the scan first, so Hits()
 		// right after Run*() select anew, and Hits() after its States() are those of the batch before -- tests/cpp/shim_calls_test.cpp)
 		Stale(Lines() ? kEverything : kEverything & ~(kSelection | kHits | kHitText));
+		m_context.NewBatch();
 		return *this;
 	}
 
@@ -570,6 +707,27 @@ private:
 		m_hitTextOffsets.resize(count + 1);
 		m_textTail = tail;
 		m_current |= kHitText;
+	}
+
+	/* Context(): the C call of a LineContext::Call, on this runner's table, buffer, flags and selection */
+	void ContextCall(const LineContext::Call& c)
+	{
+		Check(c.gather ? pire_hip_run_lines_context_gather(m_table->Handle(), m_text, m_len, m_delim, m_flags, Want(), c.before, c.after,
+		                                                   c.lineCount, c.lines, c.flags, c.spans, c.cap, c.selCount, c.groupCount, c.hitCount,
+		                                                   c.tail, c.text, c.textCap, c.offsets, c.bytes, nullptr)
+		               : pire_hip_run_lines_context_select(m_table->Handle(), m_text, m_len, m_delim, m_flags, Want(), c.before, c.after,
+		                                                   c.lineCount, c.lines, c.flags, c.spans, c.cap, c.selCount, c.groupCount, c.hitCount,
+		                                                   nullptr));
+	}
+	void FetchContext(const char* what)
+	{
+		SelectFinalsByDefault();
+		m_context.FetchLists(what, m_len, [&](const LineContext::Call& c) { ContextCall(c); });
+	}
+	void FetchContextText(const char* what, char tail)
+	{
+		SelectFinalsByDefault();
+		m_context.FetchText(what, m_len, tail, [&](const LineContext::Call& c) { ContextCall(c); });
 	}
 
 	void ExecuteSelect()
@@ -748,6 +906,7 @@ private:
 	std::vector<std::vector<uint64_t> > m_routeHits, m_routeSpans;
 	DeviceBuffer m_devRouteHits, m_devRouteCounts;
 	OwnedStrings m_ownStrings;
+	LineContext m_context;        // Context(): the request and what was fetched for it
 };
 
 template <class Scanner>
@@ -1457,6 +1616,7 @@ public:
 	{
 		m_invert = invert;
 		m_listed = m_haveText = false;
+		m_context.NewSelection();
 		return *this;
 	}
 	SlowBatchRunner& RunLines(const char* raw, size_t size, char delim = '\n', bool invert = false)
@@ -1474,6 +1634,25 @@ public:
 			FetchHitText('\n');
 		return m_hitTextOffsets;
 	}
+	/* The hits of RunLines() -- inverted: the lines that did not match, grep -v -C -- and the lines around them
+	 * (pire_hip_slow_lines_context_select / _gather): BatchRunner::Context() and its accessors.  It honours Select(invert). */
+	SlowBatchRunner& Context(uint64_t before, uint64_t after)
+	{
+		NeedLines("Context()");
+		m_context.Ask(before, after);
+		return *this;
+	}
+	const std::vector<uint64_t>& ContextLines() { FetchContext("ContextLines()"); return m_context.Lines(); }
+	const std::vector<uint8_t>& ContextFlags() { FetchContext("ContextFlags()"); return m_context.Flags(); }
+	const std::vector<uint64_t>& ContextSpans() { FetchContext("ContextSpans()"); return m_context.Spans(); }
+	uint64_t ContextGroupCount() { FetchContext("ContextGroupCount()"); return m_context.GroupCount(); }
+	const std::string& ContextText(char tail = '\n') { FetchContextText("ContextText()", tail); return m_context.Text(); }
+	const std::vector<uint64_t>& ContextTextOffsets()
+	{
+		if (!m_context.HasText())
+			FetchContextText("ContextTextOffsets()", '\n');
+		return m_context.TextOffsets();
+	}
 
 private:
 	SlowBatchRunner(const SlowBatchRunner&);
@@ -1484,6 +1663,7 @@ private:
 	{
 		m_form = form, m_text = text, m_offsets = offsets, m_n = n, m_len = len, m_delim = uint8_t(delim), m_invert = invert;
 		m_listed = m_haveText = false;
+		m_context.NewBatch();
 		return *this;
 	}
 	uint32_t Mode() const { return m_invert ? PIRE_HIP_FINAL_SELECT_ZERO : 0; }
@@ -1539,6 +1719,22 @@ private:
 		m_haveText = true;
 	}
 
+	/* Context(): the C call of a LineContext::Call, on this runner's table, buffer and selection */
+	void ContextCall(const LineContext::Call& c)
+	{
+		const uint32_t flags = PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END;
+		Check(c.gather ? pire_hip_slow_lines_context_gather(m_table, m_text, m_len, m_delim, flags, Mode(), c.before, c.after, c.lineCount, c.lines,
+		                                                    c.flags, c.spans, c.cap, c.selCount, c.groupCount, c.hitCount, c.tail, c.text,
+		                                                    c.textCap, c.offsets, c.bytes, nullptr)
+		               : pire_hip_slow_lines_context_select(m_table, m_text, m_len, m_delim, flags, Mode(), c.before, c.after, c.lineCount, c.lines,
+		                                                    c.flags, c.spans, c.cap, c.selCount, c.groupCount, c.hitCount, nullptr));
+	}
+	void FetchContext(const char* what) { m_context.FetchLists(what, m_len, [&](const LineContext::Call& c) { ContextCall(c); }); }
+	void FetchContextText(const char* what, char tail)
+	{
+		m_context.FetchText(what, m_len, tail, [&](const LineContext::Call& c) { ContextCall(c); });
+	}
+
 	pire_hip_slow_table* m_table;
 	Form m_form;
 	const char* m_text;           // Run(): the strings' text; RunLines(): the raw buffer of m_len bytes
@@ -1552,6 +1748,7 @@ private:
 	uint64_t m_hitCount, m_lineCount;
 	std::vector<uint64_t> m_hits, m_hitSpans, m_hitTextOffsets;
 	std::string m_hitText;
+	LineContext m_context;        // Context(): the request and what was fetched for it
 };
 
 /*
@@ -1601,6 +1798,21 @@ public:
 	const std::vector<uint64_t>& HitSpans() { return m_slow ? m_slow->HitSpans() : m_fast->HitSpans(); }
 	const std::string& HitText(char tail = '\n') { return m_slow ? m_slow->HitText(tail) : m_fast->HitText(tail); }
 	const std::vector<uint64_t>& HitTextOffsets() { return m_slow ? m_slow->HitTextOffsets() : m_fast->HitTextOffsets(); }
+	/* Context() and its accessors, forwarded to whichever runner the pattern picked */
+	LineMatcher& Context(uint64_t before, uint64_t after)
+	{
+		if (m_slow)
+			m_slow->Context(before, after);
+		else
+			m_fast->Context(before, after);
+		return *this;
+	}
+	const std::vector<uint64_t>& ContextLines() { return m_slow ? m_slow->ContextLines() : m_fast->ContextLines(); }
+	const std::vector<uint8_t>& ContextFlags() { return m_slow ? m_slow->ContextFlags() : m_fast->ContextFlags(); }
+	const std::vector<uint64_t>& ContextSpans() { return m_slow ? m_slow->ContextSpans() : m_fast->ContextSpans(); }
+	uint64_t ContextGroupCount() { return m_slow ? m_slow->ContextGroupCount() : m_fast->ContextGroupCount(); }
+	const std::string& ContextText(char tail = '\n') { return m_slow ? m_slow->ContextText(tail) : m_fast->ContextText(tail); }
+	const std::vector<uint64_t>& ContextTextOffsets() { return m_slow ? m_slow->ContextTextOffsets() : m_fast->ContextTextOffsets(); }
 
 private:
 	LineMatcher(const LineMatcher&);

@@ -139,6 +139,8 @@ NO_TAIL = (1 << 32) - 1   # include/pire_hip.h PIRE_HIP_GATHER_NO_TAIL: no byte 
 FIELDS_TILE = 16384   # include/pire_hip.h PIRE_HIP_FIELDS_TILE_BYTES: the fields pass cuts text into tiles of this many bytes
 COUNT_ALL = 1   # include/pire_hip.h PIRE_HIP_COUNT_ALL (in `mode`): every wanted regexp reaches its threshold
 FINAL_SELECT_ZERO = 1   # include/pire_hip.h PIRE_HIP_FINAL_SELECT_ZERO (`mode`): the strings whose Final flag is NOT set
+CONTEXT_HIT = 1   # include/pire_hip.h PIRE_HIP_CONTEXT_HIT (out_line_flags): the line is itself in the hit list
+CONTEXT_GROUP = 2   # include/pire_hip.h PIRE_HIP_CONTEXT_GROUP (out_line_flags): the first line of a run of selected lines
 FIELDS_REST = 1   # include/pire_hip.h PIRE_HIP_FIELDS_REST (in `mode`): the span runs to the end of the string, `cut -f k-`
 AFFIX_HEAD, AFFIX_TAIL, AFFIX_REST = 0, 1, 2   # include/pire_hip.h PIRE_HIP_AFFIX_HEAD / _TAIL / _REST (`part`)
 AFFIX_LONGEST, AFFIX_THROUGH_BEGIN, AFFIX_THROUGH_END = 1, 2, 4   # include/pire_hip.h PIRE_HIP_AFFIX_* (`head_opts`, `tail_opts`)
@@ -255,6 +257,11 @@ ABI = [
     ("pire_hip_affix_select", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_affix_run_select", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_affix_lines_gather", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_context", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_run_lines_context_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_run_lines_context_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_slow_lines_context_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_slow_lines_context_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_multi_create", C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
     ("pire_hip_multi_destroy", None, [C.c_void_p]),
     ("pire_hip_multi_device_count", C.c_int, [C.c_void_p]),
@@ -544,6 +551,73 @@ def final_select_device(final_ptr: int, n: int, out_hit_count_ptr: int, invert=F
     """pire_hip_final_select with PIRE_HIP_RUN_ON_DEVICE: raw device addresses, only enqueues on `stream`."""
     _check(lib().pire_hip_final_select(final_ptr or None, n, _final_mode(invert), FLAG_ON_DEVICE, out_hits_ptr or None, hit_cap,
                                        out_hit_count_ptr or None, stream or None))
+
+
+# --- from a hit list to the hits and their neighbours (pire_hip_context and the lines forms on top of it)
+def context_host(hits, n: int, before: int = 0, after: int = 0, hit_count: Optional[int] = None, line_cap: Optional[int] = None,
+                 want_lines=True, want_flags=True, want_groups=True):
+    """pire_hip_context on a host list hits[k]: {"lines" u64[m] or None, "flags" u8[m] or None, "count", "groups" or None},
+    m = min(count, line_cap); line_cap None = room for every line; hit_count None = no hit_count pointer (k = hits.size)."""
+    hits = np.ascontiguousarray(hits, dtype=np.uint64)
+    cap = int(n) if line_cap is None else int(line_cap)
+    lines = np.zeros(cap, dtype=np.uint64) if want_lines else None
+    flags = np.zeros(cap, dtype=np.uint8) if want_flags else None
+    k = None if hit_count is None else C.c_uint64(int(hit_count))
+    cnt, groups = C.c_uint64(0), C.c_uint64(0)
+    _check(lib().pire_hip_context(hits.ctypes.data if hits.size else None, None if k is None else C.byref(k), hits.size, n, before, after, 0,
+                                  lines.ctypes.data if want_lines and cap else None, flags.ctypes.data if want_flags and cap else None,
+                                  cap, C.byref(cnt), C.byref(groups) if want_groups else None, None))
+    m = min(int(cnt.value), cap)
+    return {"lines": lines[:m] if want_lines else None, "flags": flags[:m] if want_flags else None, "count": int(cnt.value),
+            "groups": int(groups.value) if want_groups else None}
+
+
+def context_device(hits_ptr: int, hit_cap: int, n: int, out_line_count_ptr: int, before: int = 0, after: int = 0, hit_count_ptr=0,
+                   out_lines_ptr=0, out_line_flags_ptr=0, line_cap=0, out_group_count_ptr=0, stream: int = 0):
+    """pire_hip_context with PIRE_HIP_RUN_ON_DEVICE: raw device addresses, only enqueues on `stream`."""
+    _check(lib().pire_hip_context(hits_ptr or None, hit_count_ptr or None, hit_cap, n, before, after, FLAG_ON_DEVICE, out_lines_ptr or None,
+                                  out_line_flags_ptr or None, line_cap, out_line_count_ptr or None, out_group_count_ptr or None,
+                                  stream or None))
+
+
+def _lines_context_host(select, gather, front, raw, delim, before, after, tail, line_cap, text_cap, with_text):
+    """the host form of the four lines forms: front = the arguments between flags and before (want / mode)"""
+    raw = _raw_bytes(raw)
+    cap = raw.size if line_cap is None else int(line_cap)
+    lines = np.zeros(cap, dtype=np.uint64)
+    flags = np.zeros(cap, dtype=np.uint8)
+    spans = np.zeros((cap, 2), dtype=np.uint64)
+    n, sel, groups, hit = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    args = front + [before, after, C.byref(n), lines.ctypes.data if cap else None, flags.ctypes.data if cap else None,
+                    spans.ctypes.data if cap else None, cap, C.byref(sel), C.byref(groups), C.byref(hit)]
+    if not with_text:
+        _check(select(*args, None))
+    else:
+        room = raw.size + cap if text_cap is None else int(text_cap)
+        text = np.zeros(max(room, 1), dtype=np.uint8)
+        offsets = np.zeros(cap + 1, dtype=np.uint64)
+        total = C.c_uint64(0)
+        _check(gather(*args, _tail(delim if tail == -1 else tail), text.ctypes.data if room else None, room, offsets.ctypes.data,
+                      C.byref(total), None))
+    k = min(int(sel.value), cap)
+    out = {"lines": int(n.value), "context": lines[:k], "flags": flags[:k], "spans": spans[:k], "count": int(sel.value),
+           "groups": int(groups.value), "hits": int(hit.value)}
+    if with_text:
+        out.update({"text": text[:min(int(total.value), room)], "offsets": offsets[:k + 1], "bytes": int(total.value)})
+    return out
+
+
+def _lines_context_device(select, gather, front, before, after, delim, tail, out_line_count_ptr, out_sel_count_ptr, out_lines_ptr,
+                          out_line_flags_ptr, out_line_spans_ptr, line_cap, out_group_count_ptr, out_hit_count_ptr, out_bytes_ptr,
+                          out_text_ptr, text_cap, out_offsets_ptr, stream):
+    args = front + [before, after, out_line_count_ptr or None, out_lines_ptr or None, out_line_flags_ptr or None,
+                    out_line_spans_ptr or None, line_cap, out_sel_count_ptr or None, out_group_count_ptr or None,
+                    out_hit_count_ptr or None]
+    if out_bytes_ptr is None:
+        _check(select(*args, stream or None))
+    else:
+        _check(gather(*args, _tail(delim if tail == -1 else tail), out_text_ptr or None, text_cap, out_offsets_ptr or None,
+                      out_bytes_ptr or None, stream or None))
 
 
 # --- from prefix and suffix lengths to matched heads and tails (pire_hip_affix_select and the forms on top of it)
@@ -1185,6 +1259,30 @@ class Table:
                                                hit_cap, out_hit_count_ptr or None, out_text_ptr or None, text_cap,
                                                out_offsets_ptr or None, out_bytes_ptr or None, stream or None))
 
+    # --- raw bytes in, the lines that match and their neighbours out (pire_hip_run_lines_context_select / _gather)
+    def run_lines_context_host(self, raw, before: int = 0, after: int = 0, delim: int = 10, flags=FLAG_BEGIN | FLAG_END, want=None,
+                               gather=False, tail=-1, line_cap=None, text_cap=None):
+        """pire_hip_run_lines_context_select (gather=True: _gather) on a host buffer: {"lines", "context" u64[k], "flags" u8[k],
+        "spans" u64[k, 2], "count", "groups", "hits"} and, with gather, {"text", "offsets", "bytes"}.  tail -1 = the delimiter
+        (grep -A -B --no-group-separator), None = none; line_cap None = room for every line."""
+        raw = _raw_bytes(raw)
+        wm = self.want_mask(want)
+        front = [self._h, raw.ctypes.data if raw.size else None, raw.size, delim, flags & ~FLAG_ON_DEVICE, _np_ptr(wm)]
+        return _lines_context_host(lib().pire_hip_run_lines_context_select, lib().pire_hip_run_lines_context_gather, front, raw, delim,
+                                   before, after, tail, line_cap, text_cap, gather)
+
+    def run_lines_context_device(self, raw_ptr: int, size: int, flags, out_line_count_ptr: int, out_sel_count_ptr: int, before: int = 0,
+                                 after: int = 0, delim: int = 10, want_ptr=0, out_lines_ptr=0, out_line_flags_ptr=0,
+                                 out_line_spans_ptr=0, line_cap=0, out_group_count_ptr=0, out_hit_count_ptr=0, out_bytes_ptr=None,
+                                 tail=-1, out_text_ptr=0, text_cap=0, out_offsets_ptr=0, stream: int = 0):
+        """pire_hip_run_lines_context_select on device pointers -- out_bytes_ptr not None: _gather -- (synchronises `stream`
+        once, as run_lines_select_device does)."""
+        front = [self._h, raw_ptr or None, size, delim, flags | FLAG_ON_DEVICE, want_ptr or None]
+        _lines_context_device(lib().pire_hip_run_lines_context_select, lib().pire_hip_run_lines_context_gather, front, before, after,
+                              delim, tail, out_line_count_ptr, out_sel_count_ptr, out_lines_ptr, out_line_flags_ptr, out_line_spans_ptr,
+                              line_cap, out_group_count_ptr, out_hit_count_ptr, out_bytes_ptr, out_text_ptr, text_cap, out_offsets_ptr,
+                              stream)
+
     # --- raw bytes in, the lines whose column matches out (pire_hip_run_lines_field_select / _gather): the results of the two
     # methods above, hits and spans being whole lines
     def run_lines_field_select_host(self, raw, field: int, sep: int = 9, delim: int = 10, rest: bool = False,
@@ -1530,6 +1628,28 @@ class SlowTable:
                                                 _tail(delim if tail == -1 else tail), out_line_count_ptr or None, out_hits_ptr or None,
                                                 hit_cap, out_hit_count_ptr or None, out_text_ptr or None, text_cap,
                                                 out_offsets_ptr or None, out_bytes_ptr or None, stream or None))
+
+    # --- raw bytes in, the lines that match (or, inverted, do not) and their neighbours out (pire_hip_slow_lines_context_*)
+    def lines_context_host(self, raw, before: int = 0, after: int = 0, delim: int = 10, flags=FLAG_BEGIN | FLAG_END, invert=False,
+                           gather=False, tail=-1, line_cap=None, text_cap=None):
+        """pire_hip_slow_lines_context_select (gather=True: _gather) on a host buffer: what Table.run_lines_context_host returns;
+        invert: grep -v -C."""
+        raw = _raw_bytes(raw)
+        front = [self._h, raw.ctypes.data if raw.size else None, raw.size, delim, flags & ~FLAG_ON_DEVICE, _final_mode(invert)]
+        return _lines_context_host(lib().pire_hip_slow_lines_context_select, lib().pire_hip_slow_lines_context_gather, front, raw, delim,
+                                   before, after, tail, line_cap, text_cap, gather)
+
+    def lines_context_device(self, raw_ptr: int, size: int, flags, out_line_count_ptr: int, out_sel_count_ptr: int, before: int = 0,
+                             after: int = 0, delim: int = 10, invert=False, out_lines_ptr=0, out_line_flags_ptr=0, out_line_spans_ptr=0,
+                             line_cap=0, out_group_count_ptr=0, out_hit_count_ptr=0, out_bytes_ptr=None, tail=-1, out_text_ptr=0,
+                             text_cap=0, out_offsets_ptr=0, stream: int = 0):
+        """pire_hip_slow_lines_context_select on device pointers -- out_bytes_ptr not None: _gather -- (synchronises `stream`
+        once, as Table.run_lines_select_device does)."""
+        front = [self._h, raw_ptr or None, size, delim, flags | FLAG_ON_DEVICE, _final_mode(invert)]
+        _lines_context_device(lib().pire_hip_slow_lines_context_select, lib().pire_hip_slow_lines_context_gather, front, before, after,
+                              delim, tail, out_line_count_ptr, out_sel_count_ptr, out_lines_ptr, out_line_flags_ptr, out_line_spans_ptr,
+                              line_cap, out_group_count_ptr, out_hit_count_ptr, out_bytes_ptr, out_text_ptr, text_cap, out_offsets_ptr,
+                              stream)
 
 
 class CountingTable:

@@ -3082,6 +3082,181 @@ try {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
 
+// ---- raw bytes in, the lines that match and their neighbours out (split.hip, context.hip) ----------------------------------
+// The frame around scan + hit list + pire_hip_context: the hit list of the scan lives in scratch, the context list takes the
+// place the hit list has in the forms above -- lines, spans, the gather through the spans.  The frame takes no table: the
+// scan is the entry point's own call (Scanner: with `want` staged in; SlowScanner: with `mode`).
+namespace {
+
+struct ContextLines {
+	uint64_t before, after;
+	uint64_t* outLines;
+	uint8_t* outFlags;
+	uint64_t* outSpans;
+	uint64_t lineCap;
+	uint64_t *outSelCount, *outGroupCount, *outHitCount;
+};
+
+// scan(f, dWant, dHits, dHitCount): the hit list of the lines f.Text() / f.Offsets() / f.n into dHits[f.n], their number into *dHitCount
+int ContextLinesImpl(const char* who, const char* refused, const void* raw, uint64_t size, uint32_t delim, uint32_t flags, const uint64_t* want,
+                     uint32_t wantWords, const ContextLines& c, uint64_t* out_line_count, const LinesGather* gather, void* streamPtr,
+                     const std::function<int(const LinesFrame&, const uint64_t*, uint64_t*, uint64_t*)>& scan)
+{
+	if (refused)
+		return GatherRefuse(who, refused);
+	if (int rc = SplitArgsInvalid(who, raw, size, delim, out_line_count, "out_line_count"))
+		return rc;
+	if (!c.outSelCount)
+		return GatherRefuse(who, "null out_sel_count");
+	// (the gather form keeps the line list to itself where the caller has no array for it)
+	const ContextOut o = {c.outLines, c.outFlags, c.lineCap, c.outSelCount, c.outGroupCount};
+	if (int rc = ContextArgsInvalid(who, true, 0, 0, o, gather != nullptr))
+		return rc;
+	if (c.outSpans && !c.outLines)
+		return GatherRefuse(who, "out_line_spans without out_lines");
+	if (gather) {
+		if (int rc = GatherOutputsInvalid(who, "line_cap", c.lineCap, gather->tail, gather->outText, gather->textCap, gather->outOffsets,
+		                                  gather->outBytes))
+			return rc;
+		if (int rc = GatherOverlaps(who, raw, size, gather->outText, gather->textCap))
+			return rc;
+	}
+	LinesFrame f(who, raw, size, delim, flags, gather, streamPtr);
+	if (f.HostEdge(out_line_count)) {
+		*c.outSelCount = 0;
+		if (c.outGroupCount)
+			*c.outGroupCount = 0;
+		if (c.outHitCount)
+			*c.outHitCount = 0;
+		return PIRE_HIP_OK;
+	}
+	const uint64_t* dWant = nullptr;
+	uint8_t* dFlags = nullptr;
+	uint64_t *dGroups = nullptr, *dHitCount = nullptr;
+	if (int rc = f.Open())
+		return rc;
+	if (want)
+		if (int rc = f.io.In(want, size_t(wantWords), &dWant))
+			return rc;
+	if (int rc = f.Split(out_line_count, c.outSelCount, 1, c.lineCap, true))
+		return rc;
+	if (int rc = f.Lists(c.outLines, c.outSpans))
+		return rc;
+	if (c.outFlags && f.cap)
+		if (int rc = f.io.Result(c.outFlags, size_t(f.cap), 0, &dFlags))
+			return rc;
+	if (c.outGroupCount)
+		if (int rc = f.io.Result(c.outGroupCount, 1, 1, &dGroups))
+			return rc;
+	if (c.outHitCount)
+		if (int rc = f.io.Result(c.outHitCount, 1, 1, &dHitCount))
+			return rc;
+	StreamScratch hitList(f.stream);   // (lives until the pass behind the scan is enqueued)
+	if (f.n == 0) {
+		if (int rc = f.ZeroCounts("hipMemsetAsync(line count)"))
+			return rc;
+		hipError_t e = dGroups ? hipMemsetAsync(dGroups, 0, 8, f.stream) : hipSuccess;
+		if (e == hipSuccess && dHitCount)
+			e = hipMemsetAsync(dHitCount, 0, 8, f.stream);
+		if (e != hipSuccess)
+			return HipFail(e, "hipMemsetAsync(line count)");
+	} else {
+		// the scan's hit list: 8 bytes a line at most, and its count where the caller has no place for it
+		if (int rc = hitList.Alloc((size_t(f.n) + 1) * 8, "hipMallocAsync(context hits)"))
+			return rc;
+		uint64_t* dScanHits = hitList.as<uint64_t>();
+		if (!dHitCount)
+			dHitCount = dScanHits + f.n;
+		if (int rc = scan(f, dWant, dScanHits, dHitCount))
+			return rc;
+		if (int rc = LaunchContext(dScanHits, dHitCount, f.n, f.n, c.before, c.after, f.dHits, dFlags, f.dHits ? f.cap : 0, f.dCounts, dGroups,
+		                           f.stream))
+			return rc;
+		if (f.dSpans)   // (the whole line)
+			if (int rc = LaunchHitSpans(f.dHits, f.dCounts, 1, f.cap, f.cap, f.LineOffsets(), f.dSpans, f.stream, "split spans launch"))
+				return rc;
+	}
+	if (int rc = f.Close("hipMemcpy(context lines)"))
+		return rc;
+	if (f.onDevice)
+		return PIRE_HIP_OK;
+	const uint64_t written = std::min(*c.outSelCount, f.cap);
+	const hipError_t e = written && dFlags ? hipMemcpy(c.outFlags, dFlags, size_t(written), hipMemcpyDeviceToHost) : hipSuccess;
+	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(context lines)");
+}
+
+int RunLinesContextImpl(const char* who, pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags, const uint64_t* want,
+                        const ContextLines& c, uint64_t* out_line_count, const LinesGather* gather, void* stream)
+{
+	return ContextLinesImpl(who, t ? nullptr : "null table", raw, size, delim, flags, want, t ? pire_hip_table_mask_words(t) : 0, c,
+	                        out_line_count, gather, stream,
+	                        [&](const LinesFrame& f, const uint64_t* dWant, uint64_t* dHits, uint64_t* dHitCount) {
+		                        return pire_hip_run_select(t, f.Text(), f.Offsets(), f.n, f.RunFlags(), nullptr, nullptr, nullptr, nullptr, dWant,
+		                                                   nullptr, dHits, nullptr, f.n, dHitCount, f.stream);
+	                        });
+}
+
+int SlowLinesContextImpl(const char* who, pire_hip_slow_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags, uint32_t mode,
+                         const ContextLines& c, uint64_t* out_line_count, const LinesGather* gather, void* stream)
+{
+	return ContextLinesImpl(who, !t ? "null table" : mode > PIRE_HIP_FINAL_SELECT_ZERO ? "unknown mode" : nullptr, raw, size, delim, flags,
+	                        nullptr, 0, c, out_line_count, gather, stream,
+	                        [&](const LinesFrame& f, const uint64_t*, uint64_t* dHits, uint64_t* dHitCount) {
+		                        return pire_hip_slow_run_select(t, f.Text(), f.Offsets(), f.n, f.RunFlags(), mode, nullptr, nullptr, nullptr, dHits,
+		                                                        f.n, dHitCount, f.stream);
+	                        });
+}
+
+}  // namespace
+
+int pire_hip_run_lines_context_select(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags, const uint64_t* want,
+                                      uint64_t before, uint64_t after, uint64_t* out_line_count, uint64_t* out_lines, uint8_t* out_line_flags,
+                                      uint64_t* out_line_spans, uint64_t line_cap, uint64_t* out_sel_count, uint64_t* out_group_count,
+                                      uint64_t* out_hit_count, void* stream)
+try {
+	const ContextLines c = {before, after, out_lines, out_line_flags, out_line_spans, line_cap, out_sel_count, out_group_count, out_hit_count};
+	return RunLinesContextImpl("pire_hip_run_lines_context_select", t, raw, size, delim, flags, want, c, out_line_count, nullptr, stream);
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_run_lines_context_gather(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags, const uint64_t* want,
+                                      uint64_t before, uint64_t after, uint64_t* out_line_count, uint64_t* out_lines, uint8_t* out_line_flags,
+                                      uint64_t* out_line_spans, uint64_t line_cap, uint64_t* out_sel_count, uint64_t* out_group_count,
+                                      uint64_t* out_hit_count, uint32_t tail, void* out_text, uint64_t text_cap, uint64_t* out_offsets,
+                                      uint64_t* out_bytes, void* stream)
+try {
+	const ContextLines c = {before, after, out_lines, out_line_flags, out_line_spans, line_cap, out_sel_count, out_group_count, out_hit_count};
+	const LinesGather gather = {tail, out_text, text_cap, out_offsets, out_bytes, true, "hipMallocAsync(line spans)"};
+	return RunLinesContextImpl("pire_hip_run_lines_context_gather", t, raw, size, delim, flags, want, c, out_line_count, &gather, stream);
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_slow_lines_context_select(pire_hip_slow_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags, uint32_t mode,
+                                       uint64_t before, uint64_t after, uint64_t* out_line_count, uint64_t* out_lines, uint8_t* out_line_flags,
+                                       uint64_t* out_line_spans, uint64_t line_cap, uint64_t* out_sel_count, uint64_t* out_group_count,
+                                       uint64_t* out_hit_count, void* stream)
+try {
+	const ContextLines c = {before, after, out_lines, out_line_flags, out_line_spans, line_cap, out_sel_count, out_group_count, out_hit_count};
+	return SlowLinesContextImpl("pire_hip_slow_lines_context_select", t, raw, size, delim, flags, mode, c, out_line_count, nullptr, stream);
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_slow_lines_context_gather(pire_hip_slow_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags, uint32_t mode,
+                                       uint64_t before, uint64_t after, uint64_t* out_line_count, uint64_t* out_lines, uint8_t* out_line_flags,
+                                       uint64_t* out_line_spans, uint64_t line_cap, uint64_t* out_sel_count, uint64_t* out_group_count,
+                                       uint64_t* out_hit_count, uint32_t tail, void* out_text, uint64_t text_cap, uint64_t* out_offsets,
+                                       uint64_t* out_bytes, void* stream)
+try {
+	const ContextLines c = {before, after, out_lines, out_line_flags, out_line_spans, line_cap, out_sel_count, out_group_count, out_hit_count};
+	const LinesGather gather = {tail, out_text, text_cap, out_offsets, out_bytes, true, "hipMallocAsync(line spans)"};
+	return SlowLinesContextImpl("pire_hip_slow_lines_context_gather", t, raw, size, delim, flags, mode, c, out_line_count, &gather, stream);
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
 // The scan parameters of the prefix and the suffix searches (the caller holds the table: TableUse), for pire_hip_prefix /
 // pire_hip_suffix and for the calls that run both (pire_hip_affix_run_select)
 static int PrefixParams(pire_hip_table* t, ScanParams* p, bool throughBegin)

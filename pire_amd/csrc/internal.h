@@ -1202,6 +1202,26 @@ struct AffixSelectStage {
 	int Launch(const uint64_t* offsets, uint64_t n, const int64_t* headLen, const int64_t* tailLen, hipStream_t stream);
 	int Back();                      // host pointers: the count, and the lists only as far as they were written
 };
+// context.hip: from an ascending hit list to the ascending list of the lines within `after` lines behind or `before` lines in
+// front of a hit, and two bits a line (pire_hip_context).  Device pointers only -- hitCount included, nullable: k = hitCap --,
+// three or four kernels enqueued on `stream`; scratch from the stream-ordered allocator: the compaction's and n / 4 bytes of
+// hit and run words.  outLines == nullptr: counts only.  n == 0 or hitCap == 0: the counts zeroed on the stream.
+int LaunchContext(const uint64_t* hits, const uint64_t* hitCount, uint64_t hitCap, uint64_t n, uint64_t before, uint64_t after,
+                  uint64_t* outLines, uint8_t* outFlags, uint64_t lineCap, uint64_t* outLineCount, uint64_t* outGroupCount,
+                  hipStream_t stream);
+// The pass's own outputs, as the caller of an entry point gave them
+struct ContextOut {
+	uint64_t* outLines;
+	uint8_t* outFlags;
+	uint64_t lineCap;
+	uint64_t* outLineCount;
+	uint64_t* outGroupCount;
+};
+// What pire_hip_context refuses before any device is touched, in `who`'s name (haveHits: there is a list to read; ownList: the
+// entry point keeps the line list to itself where the caller has no array for it)
+int ContextArgsInvalid(const char* who, bool haveHits, uint64_t hitCap, uint64_t n, const ContextOut& o, bool ownList = false);
+// What a host-pointer call refuses of its list: hits[0, k) -- any alignment -- strictly ascending, every entry < n
+int ContextHitsInvalid(const char* who, const void* hits, uint64_t k, uint64_t n);
 // split.hip: raw text into strings (pire_hip_split).  Device pointers only, everything enqueued on `stream`.  The pass
 // comes in two halves because a caller may want the number of strings before it has room for their offsets:
 // LaunchSplitCount counts and scans (*outN = n; the tile prefixes stay in `scratch`, the caller's owner, which has to live
