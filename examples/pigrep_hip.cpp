@@ -6,8 +6,9 @@
 //   pigrep_hip [-i] [-u] [-x] [-e pattern | pattern] [file [file2...]]
 //
 // Everything before the scan (lexer, features, Surround, Compile) is the reference library, unchanged; the scan goes
-// through include/pire_hip/batch_runner.hpp.  tests/test_examples.py builds the reference's own pigrep next to this
-// one and compares their outputs.
+// through include/pire_hip/batch_runner.hpp.  Several files are ONE call: they go into one buffer, and the device says which
+// file every hit belongs to (FileSet, Files()).  tests/test_examples.py builds the reference's own pigrep next to this one and
+// compares their outputs.
 #include <cstring>
 #include <fstream>
 #include <iostream>
@@ -39,6 +40,25 @@ void GrepStream(std::istream& in, const Pire::Hip::Table<Pire::Scanner>& table, 
 			std::cout << prefix;
 			std::cout.write(hits.data() + offsets[k], std::streamsize(offsets[k + 1] - offsets[k]));
 		}
+	}
+	std::cout.flush();
+}
+
+// Several inputs: all of them in one buffer (FileSet: a delimiter behind a file that lacks one, so no line runs from one file
+// into the next), ONE split + scan + hit list with the file of every hit (Files()), one gather of the hits' text.
+void GrepFiles(const Pire::Hip::FileSet& set, const Pire::Hip::Table<Pire::Scanner>& table)
+{
+	const std::string& raw = set.Raw();
+	if (raw.empty())
+		return;
+	Pire::Hip::BatchRunner<Pire::Scanner> run(table);
+	run.Begin().RunLines(raw.data(), raw.size()).End().Files(set.Bytes());
+	const std::string& hits = run.HitText();
+	const std::vector<uint64_t>& offsets = run.HitTextOffsets();
+	const std::vector<uint64_t>& files = run.HitFiles();
+	for (size_t k = 0; k + 1 < offsets.size() && k < files.size(); ++k) {
+		std::cout << set.Name(size_t(files[k])) << ": ";
+		std::cout.write(hits.data() + offsets[k], std::streamsize(offsets[k + 1] - offsets[k]));
 	}
 	std::cout.flush();
 }
@@ -98,17 +118,32 @@ int main(int argc, char** argv)
 		} else {
 			// pigrep.cpp:93-108: "-" is stdin; lines are prefixed with "name: " only when several files are given
 			const bool many = argc - arg > 1;
+			Pire::Hip::FileSet set;
 			for (; arg < argc; ++arg) {
 				const std::string name = argv[arg];
 				if (name == "-") {
-					GrepStream(std::cin, table, many ? "(stdin): " : "");
+					if (!many) {
+						GrepStream(std::cin, table, "");
+						continue;
+					}
+					const std::string raw((std::istreambuf_iterator<char>(std::cin)), std::istreambuf_iterator<char>());
+					set.Add("(stdin)", raw.data(), raw.size());
 					continue;
 				}
 				std::ifstream f(name.c_str());
-				if (!f)
+				if (!f) {
+					GrepFiles(set, table);   // (the hits of the files in front of it come out first, as they always did)
 					throw std::runtime_error("cannot open file " + name);
-				GrepStream(f, table, many ? name + ": " : std::string());
+				}
+				if (!many) {
+					GrepStream(f, table, std::string());
+					continue;
+				}
+				const std::string raw((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+				set.Add(name, raw.data(), raw.size());
 			}
+			if (many)
+				GrepFiles(set, table);
 		}
 		return 0;
 	} catch (const std::exception& e) {

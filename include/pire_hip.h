@@ -1372,6 +1372,85 @@ int pire_hip_slow_lines_context_gather(pire_hip_slow_table* t, const void* raw, 
                                        uint32_t tail, void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes,
                                        void* stream);
 
+/* ---- hits by file, on the device (grep -c / -l / -L / -H -n over many files in one buffer) ------------------------------ */
+
+/*
+ * From a hit list and the files' line boundaries to the hits of every file.  It takes no table and no text: it reads line
+ * numbers, whoever wrote them -- every hit pass of the library writes such a list.  With
+ * k = min(hit_count ? *hit_count : hit_cap, hit_cap) (as pire_hip_context and pire_hip_gather), hits[0, k) strictly ascending
+ * and every entry < n, and bounds[files + 1] non-decreasing with bounds[0] == 0 and bounds[files] == n: file f is the lines
+ * [bounds[f], bounds[f + 1]); repeated bounds are empty files, legal anywhere and in any number.
+ *   out_file_first[files + 1] (nullable): out_file_first[f] = the number of j < k with hits[j] < bounds[f].  The hits of file f
+ *       are hits[first[f], first[f + 1]), their number is `grep -c`.
+ *   out_hit_file[hit_cap], out_hit_line[hit_cap] (each nullable): for j < k the one f with bounds[f] <= hits[j] < bounds[f + 1],
+ *       and hits[j] - bounds[f]: the line number inside the file, 0-based (`grep -n` prints it plus one).  Nothing is written at
+ *       j >= k.
+ *   out_files[file_cap] (nullable when file_cap == 0): the ascending list of the f with a hit (`grep -l`); with file_mode
+ *       PIRE_HIP_FILES_WITHOUT the list of the f with none, empty files included (`grep -L`).
+ *   *out_file_count (required): the length of that list, also when it exceeds file_cap; only the first min(count, file_cap)
+ *       entries are written, nothing behind them.
+ * files == 0 (n must be 0 then): the count is 0, out_file_first[0] = 0 where it is not null.
+ * flags: PIRE_HIP_RUN_ON_DEVICE -> every pointer (hit_count included) is a device pointer and the call only enqueues on
+ *        `stream`: a lower bound in the list per file boundary (work is divided by files), classify per tile of 1 024 FILES, the
+ *        one-block scan of pire_hip_select, scatter, and -- only where out_hit_file or out_hit_line is asked for -- locate per
+ *        tile of 1 024 HITS: two wave-wide searches bound the slice of bounds a tile needs, so a tile inside one file costs
+ *        those two and no more; no atomics, no block waits for another: the same input gives the same bits.  Scratch
+ *        (files / 8 + files / 256 bytes, and 8 * (files + 1) where out_file_first is null) comes from the stream-ordered
+ *        allocator: the rule and the capture-mode caveat stated at pire_hip_select.  `hits` may have any alignment, the other
+ *        arrays are 8-byte aligned.  A list or bounds that break the preconditions give unspecified answers and nothing worse:
+ *        the call reads nothing outside hits[0, k) and bounds[0, files] and writes nothing outside what is stated above.
+ *        Otherwise host pointers: staged, synchronises, the file list comes back only as far as it was written; hits that are
+ *        not strictly ascending or name a line >= n, bounds that decrease, bounds[0] != 0 and bounds[files] != n are
+ *        PIRE_HIP_EINVAL, and nothing is written.
+ * PIRE_HIP_EINVAL before any device is touched: null out_file_count; hit_cap > 0 with null hits; files > 0 with null bounds;
+ * file_cap > 0 with null out_files; file_mode > 1; files == 0 with n > 0; n, hit_cap or files >= 2^32.
+ * pire_hip_last_kernel() is not changed by the pass.  No first-use self-test: it takes no table (as pire_hip_context).
+ *
+ * The chain that gives the text of one file's hits -- or of all files' -- with device pointers and no read-back: a lines form
+ * below (or any hit list with its spans), then pire_hip_gather_spans(raw, size, out_hit_spans + 2 * first[f], NULL,
+ * first[f + 1] - first[f], ...) for file f, where the caller knows first[] -- or, for every file at once,
+ * pire_hip_gather_spans(raw, size, out_hit_spans, out_hit_count, hit_cap, ...), whose out_offsets[first[f]] ..
+ * out_offsets[first[f + 1]] are then file f's bytes of out_text.
+ */
+#define PIRE_HIP_FILES_WITHOUT 1u   /* file_mode: list the files with NO hit (grep -L) instead of those with one (grep -l) */
+int pire_hip_files(const uint64_t* hits, const uint64_t* hit_count, uint64_t hit_cap, uint64_t n,
+                   const uint64_t* bounds, uint64_t files, uint32_t file_mode, uint32_t flags,
+                   uint64_t* out_file_first, uint64_t* out_hit_file, uint64_t* out_hit_line,
+                   uint64_t* out_files, uint64_t file_cap, uint64_t* out_file_count, void* stream);
+
+/*
+ * The bytes of many files laid end to end in, the matching lines by file out: one call for `grep -c / -l / -L / -H -n
+ * file...`.  file_bytes[files + 1], non-decreasing with file_bytes[0] == 0 and file_bytes[files] == size: file f is
+ * raw[file_bytes[f], file_bytes[f + 1]).  The split, the scan, the hit list, the one synchronisation of `stream`, the refusals
+ * and the refusal of 2^32 lines are those of pire_hip_run_lines_select / pire_hip_slow_lines_select (`want` chooses regexps;
+ * mode PIRE_HIP_FINAL_SELECT_ZERO: `grep -v -c`, `grep -v -l`), as are out_line_count, out_hits, out_hit_spans, hit_cap and
+ * out_hit_count.  On top of them:
+ *   out_file_lines[files + 1] (nullable): out_file_lines[f] = the number of lines whose first byte lies in front of
+ *       file_bytes[f] -- a line belongs to the file that holds its first byte.  These are the `bounds` of pire_hip_files.
+ *   *out_straddles (required): the number of f in [1, files) with 0 < file_bytes[f] < size and
+ *       raw[file_bytes[f] - 1] != delim: boundaries inside a line, because the file in front of them does not end in the
+ *       delimiter.  0 for well-formed input; otherwise the answers are still those of the rule above, and the caller knows.
+ *   out_hit_file[hit_cap], out_hit_line[hit_cap], out_file_first[files + 1], out_files[file_cap], *out_file_count: as
+ *       pire_hip_files on the whole hit list (hit_cap cuts what is written, not what is counted) and out_file_lines.
+ * They refuse what the form they extend refuses and, of the files, what pire_hip_files refuses (files == 0 with size > 0);
+ * host-pointer calls refuse a bad file_bytes with PIRE_HIP_EINVAL before any device is touched.  Host pointers with
+ * size == 0: zeros, out_file_first and out_file_lines all zero where not null, every file listed under
+ * PIRE_HIP_FILES_WITHOUT; no device is touched.
+ * There are no gather forms: out_hit_spans and out_file_first chain into pire_hip_gather_spans as stated at pire_hip_files.
+ */
+int pire_hip_run_lines_files_select(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
+                                    const uint64_t* want, const uint64_t* file_bytes, uint64_t files, uint32_t file_mode,
+                                    uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_hit_spans, uint64_t* out_hit_file,
+                                    uint64_t* out_hit_line, uint64_t hit_cap, uint64_t* out_hit_count, uint64_t* out_file_lines,
+                                    uint64_t* out_file_first, uint64_t* out_files, uint64_t file_cap, uint64_t* out_file_count,
+                                    uint64_t* out_straddles, void* stream);
+int pire_hip_slow_lines_files_select(pire_hip_slow_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
+                                     uint32_t mode, const uint64_t* file_bytes, uint64_t files, uint32_t file_mode,
+                                     uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_hit_spans, uint64_t* out_hit_file,
+                                     uint64_t* out_hit_line, uint64_t hit_cap, uint64_t* out_hit_count, uint64_t* out_file_lines,
+                                     uint64_t* out_file_first, uint64_t* out_files, uint64_t file_cap, uint64_t* out_file_count,
+                                     uint64_t* out_straddles, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@
  *     CountedBatchRunner   all of HalfFinalBatchRunner and CountingBatchRunner but their table and their three C calls
  *     LineMatcher       easy.h's choice between Scanner and SlowScanner, one lines surface over BatchRunner and SlowBatchRunner
  *     LineContext       a Context(before, after) and what was fetched for it                      BatchRunner, SlowBatchRunner
+ *     LineFiles         a Files(fileBytes) and what was fetched for it                            BatchRunner, SlowBatchRunner
  * Which C calls these make, in which order and with which arguments, is recorded: tests/cpp/shim_calls_test.cpp,
  * tests/cpp/shim_calls.expected.txt.
  */
@@ -209,6 +210,140 @@ private:
 	std::vector<uint64_t> m_lines, m_spans, m_textOffsets;
 	std::vector<uint8_t> m_flags;
 	std::string m_text;
+};
+
+/*
+ * The hits of a RunLines() by file: grep -c / -l / -L / -H -n over many files laid end to end in one buffer (include/pire_hip.h,
+ * "hits by file").  What BatchRunner and SlowBatchRunner keep of a Files(fileBytes): the request, and what was fetched for it
+ * -- lazily, as LineContext does: the lists with the first accessor that asks, the files WITHOUT a hit with a call of their
+ * own (the other file_mode, no room for hits).  The runner makes the C call: call(Call) fills in its table, buffer, flags and
+ * selection.
+ */
+class LineFiles {
+public:
+	struct Call {
+		const uint64_t* fileBytes;
+		uint64_t files;
+		uint32_t fileMode;
+		uint64_t* lineCount;
+		uint64_t *hits, *spans, *hitFile, *hitLine;
+		uint64_t cap;
+		uint64_t* hitCount;
+		uint64_t *fileLines, *fileFirst, *outFiles;
+		uint64_t fileCap;
+		uint64_t *fileCount, *straddles;
+	};
+	LineFiles() : m_asked(false), m_current(0), m_lineCount(0), m_hitCount(0), m_straddles(0) {}
+	void Ask(const std::vector<uint64_t>& fileBytes)
+	{
+		m_fileBytes = fileBytes, m_asked = true;
+		Stale(kLists | kWithout);
+	}
+	void NewSelection() { Stale(kLists | kWithout); }   // the request stays
+	void NewBatch()                                     // the request goes with the batch it was made for
+	{
+		m_asked = false;
+		Stale(kLists | kWithout);
+	}
+	/* One call with room for a hit per 64 bytes of the buffer, and a second one where there are more */
+	template <class Fn>
+	void FetchLists(const char* what, size_t len, Fn call)
+	{
+		Need(what);
+		if (Has(kLists))
+			return;
+		const size_t files = Files();
+		uint64_t listed = 0;
+		m_fileLines.assign(files + 1, 0);
+		m_first.assign(files + 1, 0);
+		m_with.assign(files, 0);
+		GrowAndRetry(len / 64 + 1024, [&](size_t cap) {
+			m_hits.resize(cap);
+			m_hitFile.resize(cap);
+			m_hitLine.resize(cap);
+			const Call c = {Bytes(), files, 0, &m_lineCount, m_hits.data(), nullptr, m_hitFile.data(), m_hitLine.data(), cap, &m_hitCount,
+			                m_fileLines.data(), m_first.data(), files ? m_with.data() : nullptr, files, &listed, &m_straddles};
+			call(c);
+			return size_t(m_hitCount);
+		});
+		m_hits.resize(m_hitCount);
+		m_hitFile.resize(m_hitCount);
+		m_hitLine.resize(m_hitCount);
+		m_with.resize(listed);
+		m_counts.resize(files);
+		for (size_t f = 0; f < files; ++f)
+			m_counts[f] = m_first[f + 1] - m_first[f];
+		m_current |= kLists;
+	}
+	/* The files without a hit: the other file_mode, no room for hits */
+	template <class Fn>
+	void FetchWithout(const char* what, Fn call)
+	{
+		Need(what);
+		if (Has(kWithout))
+			return;
+		const size_t files = Files();
+		uint64_t lines = 0, hits = 0, listed = 0, straddles = 0;
+		m_without.assign(files, 0);
+		const Call c = {Bytes(), files, PIRE_HIP_FILES_WITHOUT, &lines, nullptr, nullptr, nullptr, nullptr, 0, &hits, nullptr, nullptr,
+		                files ? m_without.data() : nullptr, files, &listed, &straddles};
+		call(c);
+		m_without.resize(listed);
+		m_current |= kWithout;
+	}
+	const std::vector<uint64_t>& Counts() const { return m_counts; }
+	const std::vector<uint64_t>& With() const { return m_with; }
+	const std::vector<uint64_t>& Without() const { return m_without; }
+	const std::vector<uint64_t>& HitFile() const { return m_hitFile; }
+	const std::vector<uint64_t>& HitLine() const { return m_hitLine; }
+	const std::vector<uint64_t>& FileLines() const { return m_fileLines; }
+	uint64_t Straddles() const { return m_straddles; }
+
+private:
+	enum Result { kLists = 1 << 0, kWithout = 1 << 1 };
+	bool Has(unsigned results) const { return (m_current & results) == results; }
+	void Stale(unsigned results) { m_current &= ~results; }
+	void Need(const char* what) const
+	{
+		if (!m_asked)
+			throw Pire::Error(std::string("pire_hip: ") + what + " follows Files()");
+	}
+	size_t Files() const { return m_fileBytes.empty() ? 0 : m_fileBytes.size() - 1; }
+	const uint64_t* Bytes() const { return m_fileBytes.empty() ? nullptr : m_fileBytes.data(); }
+	bool m_asked;
+	unsigned m_current;
+	uint64_t m_lineCount, m_hitCount, m_straddles;
+	std::vector<uint64_t> m_fileBytes, m_hits, m_hitFile, m_hitLine, m_fileLines, m_first, m_counts, m_with, m_without;
+};
+
+/*
+ * Many buffers as the one a Files() request takes: the files laid end to end, the delimiter appended behind a non-empty file
+ * that does not end in it -- so no boundary lies inside a line and Straddles() is 0 for what this builds.  Host only.
+ *     FileSet set;   set.Add("a.log", data, size);   ...   run.RunLines(set.Raw().data(), set.Raw().size()).Files(set.Bytes());
+ */
+class FileSet {
+public:
+	explicit FileSet(char delim = '\n') : m_delim(delim), m_bytes(1, 0) {}
+	void Add(const std::string& name, const char* data, size_t size)
+	{
+		m_names.push_back(name);
+		if (size) {
+			m_raw.append(data, size);
+			if (data[size - 1] != m_delim)
+				m_raw.push_back(m_delim);
+		}
+		m_bytes.push_back(m_raw.size());
+	}
+	const std::string& Raw() const { return m_raw; }
+	const std::vector<uint64_t>& Bytes() const { return m_bytes; }   // [Size() + 1]: file f is Raw()[Bytes()[f], Bytes()[f + 1])
+	const std::string& Name(size_t f) const { return m_names[f]; }
+	size_t Size() const { return m_names.size(); }
+
+private:
+	char m_delim;
+	std::string m_raw;
+	std::vector<uint64_t> m_bytes;
+	std::vector<std::string> m_names;
 };
 
 /* Bytes between the State values of consecutive StateIndex numbers, from public API only. */
@@ -455,6 +590,31 @@ public:
 		return m_context.TextOffsets();
 	}
 
+	/*
+	 * The hits of RunLines() by file, where the buffer is many files laid end to end (pire_hip_run_lines_files_select):
+	 * fileBytes[files + 1], from 0 to size, file f = raw[fileBytes[f], fileBytes[f + 1]) -- FileSet builds both.
+	 *     run.Begin().RunLines(raw, size).End().Files(set.Bytes());     Select({..}) in front of it chooses regexps
+	 *     run.FileHitCounts()     the matches of every file: grep -c          run.FileLines()   [files + 1]: file f is the lines [l[f], l[f + 1])
+	 *     run.FilesWithHits()     grep -l        run.FilesWithoutHits()  grep -L (a call of its own)
+	 *     run.HitFiles()          the file of every hit, in the order of Hits()       run.HitFileLines()  its line inside that file, from 0
+	 *     run.Straddles()         boundaries inside a line: 0 for a FileSet
+	 * Fetched lazily.  A new batch ends the request, a new selection keeps it.  After anything but RunLines() it throws.
+	 */
+	BatchRunner& Files(const std::vector<uint64_t>& fileBytes)
+	{
+		if (m_form != kLines)
+			throw Pire::Error("pire_hip: Files() follows RunLines()");
+		m_files.Ask(fileBytes);
+		return *this;
+	}
+	const std::vector<uint64_t>& FileHitCounts() { FetchFiles("FileHitCounts()"); return m_files.Counts(); }
+	const std::vector<uint64_t>& FilesWithHits() { FetchFiles("FilesWithHits()"); return m_files.With(); }
+	const std::vector<uint64_t>& FilesWithoutHits() { FetchFilesWithout("FilesWithoutHits()"); return m_files.Without(); }
+	const std::vector<uint64_t>& HitFiles() { FetchFiles("HitFiles()"); return m_files.HitFile(); }
+	const std::vector<uint64_t>& HitFileLines() { FetchFiles("HitFileLines()"); return m_files.HitLine(); }
+	const std::vector<uint64_t>& FileLines() { FetchFiles("FileLines()"); return m_files.FileLines(); }
+	uint64_t Straddles() { FetchFiles("Straddles()"); return m_files.Straddles(); }
+
 	/* RunHelper::State() per string (run.h:378). */
 	const std::vector<State>& States()
 	{
@@ -505,6 +665,7 @@ public:
 				m_want[want[i] / 64] |= uint64_t(1) << (want[i] % 64);
 		Stale(kSelection | kHits | kHitText);
 		m_context.NewSelection();
+		m_files.NewSelection();
 		return *this;
 	}
 	size_t MaskWords() const { return pire_hip_table_mask_words(m_table->Handle()); }
@@ -591,6 +752,7 @@ private:
 		// right after Run*() select anew, and Hits() after its States() are those of the batch before -- tests/cpp/shim_calls_test.cpp)
 		Stale(Lines() ? kEverything : kEverything & ~(kSelection | kHits | kHitText));
 		m_context.NewBatch();
+		m_files.NewBatch();
 		return *this;
 	}
 
@@ -728,6 +890,24 @@ private:
 	{
 		SelectFinalsByDefault();
 		m_context.FetchText(what, m_len, tail, [&](const LineContext::Call& c) { ContextCall(c); });
+	}
+
+	/* Files(): the C call of a LineFiles::Call, on this runner's table, buffer, flags and selection */
+	void FilesCall(const LineFiles::Call& c)
+	{
+		Check(pire_hip_run_lines_files_select(m_table->Handle(), m_text, m_len, m_delim, m_flags, Want(), c.fileBytes, c.files, c.fileMode,
+		                                      c.lineCount, c.hits, c.spans, c.hitFile, c.hitLine, c.cap, c.hitCount, c.fileLines, c.fileFirst,
+		                                      c.outFiles, c.fileCap, c.fileCount, c.straddles, nullptr));
+	}
+	void FetchFiles(const char* what)
+	{
+		SelectFinalsByDefault();
+		m_files.FetchLists(what, m_len, [&](const LineFiles::Call& c) { FilesCall(c); });
+	}
+	void FetchFilesWithout(const char* what)
+	{
+		SelectFinalsByDefault();
+		m_files.FetchWithout(what, [&](const LineFiles::Call& c) { FilesCall(c); });
 	}
 
 	void ExecuteSelect()
@@ -907,6 +1087,7 @@ private:
 	DeviceBuffer m_devRouteHits, m_devRouteCounts;
 	OwnedStrings m_ownStrings;
 	LineContext m_context;        // Context(): the request and what was fetched for it
+	LineFiles m_files;            // Files(): the request and what was fetched for it
 };
 
 template <class Scanner>
@@ -1617,6 +1798,7 @@ public:
 		m_invert = invert;
 		m_listed = m_haveText = false;
 		m_context.NewSelection();
+		m_files.NewSelection();
 		return *this;
 	}
 	SlowBatchRunner& RunLines(const char* raw, size_t size, char delim = '\n', bool invert = false)
@@ -1634,6 +1816,22 @@ public:
 			FetchHitText('\n');
 		return m_hitTextOffsets;
 	}
+	/* The hits of RunLines() by file (pire_hip_slow_lines_files_select): BatchRunner::Files() and its accessors.  It honours
+	 * Select(invert): grep -v -c, grep -v -l. */
+	SlowBatchRunner& Files(const std::vector<uint64_t>& fileBytes)
+	{
+		NeedLines("Files()");
+		m_files.Ask(fileBytes);
+		return *this;
+	}
+	const std::vector<uint64_t>& FileHitCounts() { FetchFiles("FileHitCounts()"); return m_files.Counts(); }
+	const std::vector<uint64_t>& FilesWithHits() { FetchFiles("FilesWithHits()"); return m_files.With(); }
+	const std::vector<uint64_t>& FilesWithoutHits() { FetchFilesWithout("FilesWithoutHits()"); return m_files.Without(); }
+	const std::vector<uint64_t>& HitFiles() { FetchFiles("HitFiles()"); return m_files.HitFile(); }
+	const std::vector<uint64_t>& HitFileLines() { FetchFiles("HitFileLines()"); return m_files.HitLine(); }
+	const std::vector<uint64_t>& FileLines() { FetchFiles("FileLines()"); return m_files.FileLines(); }
+	uint64_t Straddles() { FetchFiles("Straddles()"); return m_files.Straddles(); }
+
 	/* The hits of RunLines() -- inverted: the lines that did not match, grep -v -C -- and the lines around them
 	 * (pire_hip_slow_lines_context_select / _gather): BatchRunner::Context() and its accessors.  It honours Select(invert). */
 	SlowBatchRunner& Context(uint64_t before, uint64_t after)
@@ -1664,6 +1862,7 @@ private:
 		m_form = form, m_text = text, m_offsets = offsets, m_n = n, m_len = len, m_delim = uint8_t(delim), m_invert = invert;
 		m_listed = m_haveText = false;
 		m_context.NewBatch();
+		m_files.NewBatch();
 		return *this;
 	}
 	uint32_t Mode() const { return m_invert ? PIRE_HIP_FINAL_SELECT_ZERO : 0; }
@@ -1729,6 +1928,15 @@ private:
 		               : pire_hip_slow_lines_context_select(m_table, m_text, m_len, m_delim, flags, Mode(), c.before, c.after, c.lineCount, c.lines,
 		                                                    c.flags, c.spans, c.cap, c.selCount, c.groupCount, c.hitCount, nullptr));
 	}
+	/* Files(): the C call of a LineFiles::Call, on this runner's table, buffer and selection */
+	void FilesCall(const LineFiles::Call& c)
+	{
+		Check(pire_hip_slow_lines_files_select(m_table, m_text, m_len, m_delim, PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END, Mode(), c.fileBytes,
+		                                       c.files, c.fileMode, c.lineCount, c.hits, c.spans, c.hitFile, c.hitLine, c.cap, c.hitCount,
+		                                       c.fileLines, c.fileFirst, c.outFiles, c.fileCap, c.fileCount, c.straddles, nullptr));
+	}
+	void FetchFiles(const char* what) { m_files.FetchLists(what, m_len, [&](const LineFiles::Call& c) { FilesCall(c); }); }
+	void FetchFilesWithout(const char* what) { m_files.FetchWithout(what, [&](const LineFiles::Call& c) { FilesCall(c); }); }
 	void FetchContext(const char* what) { m_context.FetchLists(what, m_len, [&](const LineContext::Call& c) { ContextCall(c); }); }
 	void FetchContextText(const char* what, char tail)
 	{
@@ -1749,6 +1957,7 @@ private:
 	std::vector<uint64_t> m_hits, m_hitSpans, m_hitTextOffsets;
 	std::string m_hitText;
 	LineContext m_context;        // Context(): the request and what was fetched for it
+	LineFiles m_files;            // Files(): the request and what was fetched for it
 };
 
 /*
@@ -1813,6 +2022,22 @@ public:
 	uint64_t ContextGroupCount() { return m_slow ? m_slow->ContextGroupCount() : m_fast->ContextGroupCount(); }
 	const std::string& ContextText(char tail = '\n') { return m_slow ? m_slow->ContextText(tail) : m_fast->ContextText(tail); }
 	const std::vector<uint64_t>& ContextTextOffsets() { return m_slow ? m_slow->ContextTextOffsets() : m_fast->ContextTextOffsets(); }
+	/* Files() and its accessors, forwarded to whichever runner the pattern picked */
+	LineMatcher& Files(const std::vector<uint64_t>& fileBytes)
+	{
+		if (m_slow)
+			m_slow->Files(fileBytes);
+		else
+			m_fast->Files(fileBytes);
+		return *this;
+	}
+	const std::vector<uint64_t>& FileHitCounts() { return m_slow ? m_slow->FileHitCounts() : m_fast->FileHitCounts(); }
+	const std::vector<uint64_t>& FilesWithHits() { return m_slow ? m_slow->FilesWithHits() : m_fast->FilesWithHits(); }
+	const std::vector<uint64_t>& FilesWithoutHits() { return m_slow ? m_slow->FilesWithoutHits() : m_fast->FilesWithoutHits(); }
+	const std::vector<uint64_t>& HitFiles() { return m_slow ? m_slow->HitFiles() : m_fast->HitFiles(); }
+	const std::vector<uint64_t>& HitFileLines() { return m_slow ? m_slow->HitFileLines() : m_fast->HitFileLines(); }
+	const std::vector<uint64_t>& FileLines() { return m_slow ? m_slow->FileLines() : m_fast->FileLines(); }
+	uint64_t Straddles() { return m_slow ? m_slow->Straddles() : m_fast->Straddles(); }
 
 private:
 	LineMatcher(const LineMatcher&);

@@ -141,6 +141,7 @@ COUNT_ALL = 1   # include/pire_hip.h PIRE_HIP_COUNT_ALL (in `mode`): every wante
 FINAL_SELECT_ZERO = 1   # include/pire_hip.h PIRE_HIP_FINAL_SELECT_ZERO (`mode`): the strings whose Final flag is NOT set
 CONTEXT_HIT = 1   # include/pire_hip.h PIRE_HIP_CONTEXT_HIT (out_line_flags): the line is itself in the hit list
 CONTEXT_GROUP = 2   # include/pire_hip.h PIRE_HIP_CONTEXT_GROUP (out_line_flags): the first line of a run of selected lines
+FILES_WITHOUT = 1   # include/pire_hip.h PIRE_HIP_FILES_WITHOUT (`file_mode`): list the files with no hit (grep -L)
 FIELDS_REST = 1   # include/pire_hip.h PIRE_HIP_FIELDS_REST (in `mode`): the span runs to the end of the string, `cut -f k-`
 AFFIX_HEAD, AFFIX_TAIL, AFFIX_REST = 0, 1, 2   # include/pire_hip.h PIRE_HIP_AFFIX_HEAD / _TAIL / _REST (`part`)
 AFFIX_LONGEST, AFFIX_THROUGH_BEGIN, AFFIX_THROUGH_END = 1, 2, 4   # include/pire_hip.h PIRE_HIP_AFFIX_* (`head_opts`, `tail_opts`)
@@ -262,6 +263,9 @@ ABI = [
     ("pire_hip_run_lines_context_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_slow_lines_context_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_slow_lines_context_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_files", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_run_lines_files_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_slow_lines_files_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_multi_create", C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
     ("pire_hip_multi_destroy", None, [C.c_void_p]),
     ("pire_hip_multi_device_count", C.c_int, [C.c_void_p]),
@@ -618,6 +622,74 @@ def _lines_context_device(select, gather, front, before, after, delim, tail, out
     else:
         _check(gather(*args, _tail(delim if tail == -1 else tail), out_text_ptr or None, text_cap, out_offsets_ptr or None,
                       out_bytes_ptr or None, stream or None))
+
+
+# --- from a hit list and file boundaries to hits by file (pire_hip_files and the lines forms on top of it)
+def _file_mode(without) -> int:
+    return FILES_WITHOUT if without else 0
+
+
+def files_host(hits, n: int, bounds, without=False, hit_count: Optional[int] = None, file_cap: Optional[int] = None, want_first=True,
+               want_hit_file=True, want_hit_line=True):
+    """pire_hip_files on a host list hits[k] and bounds[files + 1]: {"first" u64[files + 1] or None, "hit_file" / "hit_line"
+    u64[k] or None, "files" u64[m], "count"}, m = min(count, file_cap); file_cap None = room for every file; hit_count None =
+    no hit_count pointer (k = hits.size)."""
+    hits = np.ascontiguousarray(hits, dtype=np.uint64)
+    bounds = np.ascontiguousarray(bounds, dtype=np.uint64)
+    files = max(bounds.size - 1, 0)
+    cap = files if file_cap is None else int(file_cap)
+    k = None if hit_count is None else C.c_uint64(int(hit_count))
+    kk = hits.size if hit_count is None else min(int(hit_count), hits.size)
+    first = np.zeros(files + 1, dtype=np.uint64) if want_first else None
+    hit_file = np.zeros(hits.size, dtype=np.uint64) if want_hit_file else None
+    hit_line = np.zeros(hits.size, dtype=np.uint64) if want_hit_line else None
+    listed = np.zeros(cap, dtype=np.uint64)
+    cnt = C.c_uint64(0)
+    _check(lib().pire_hip_files(hits.ctypes.data if hits.size else None, None if k is None else C.byref(k), hits.size, n,
+                                bounds.ctypes.data if bounds.size else None, files, _file_mode(without), 0, _np_ptr(first),
+                                hit_file.ctypes.data if want_hit_file and hits.size else None,
+                                hit_line.ctypes.data if want_hit_line and hits.size else None, listed.ctypes.data if cap else None, cap,
+                                C.byref(cnt), None))
+    return {"first": first, "hit_file": hit_file[:kk] if want_hit_file else None, "hit_line": hit_line[:kk] if want_hit_line else None,
+            "files": listed[:min(int(cnt.value), cap)], "count": int(cnt.value)}
+
+
+def files_device(hits_ptr: int, hit_cap: int, n: int, bounds_ptr: int, files: int, out_file_count_ptr: int, without=False, hit_count_ptr=0,
+                 out_file_first_ptr=0, out_hit_file_ptr=0, out_hit_line_ptr=0, out_files_ptr=0, file_cap=0, stream: int = 0):
+    """pire_hip_files with PIRE_HIP_RUN_ON_DEVICE: raw device addresses, only enqueues on `stream`."""
+    _check(lib().pire_hip_files(hits_ptr or None, hit_count_ptr or None, hit_cap, n, bounds_ptr or None, files, _file_mode(without),
+                                FLAG_ON_DEVICE, out_file_first_ptr or None, out_hit_file_ptr or None, out_hit_line_ptr or None,
+                                out_files_ptr or None, file_cap, out_file_count_ptr or None, stream or None))
+
+
+def _lines_files_host(call, front, raw, file_bytes, without, hit_cap, file_cap):
+    """the host form of the two lines forms: front = the arguments in front of file_bytes (table .. want / mode)"""
+    file_bytes = np.ascontiguousarray(file_bytes, dtype=np.uint64)
+    files = max(file_bytes.size - 1, 0)
+    cap = raw.size if hit_cap is None else int(hit_cap)
+    fcap = files if file_cap is None else int(file_cap)
+    hits, hit_file, hit_line = (np.zeros(cap, dtype=np.uint64) for _ in range(3))
+    spans = np.zeros((cap, 2), dtype=np.uint64)
+    file_lines, first = np.zeros(files + 1, dtype=np.uint64), np.zeros(files + 1, dtype=np.uint64)
+    listed = np.zeros(fcap, dtype=np.uint64)
+    n, cnt, fcnt, straddles = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    _check(call(*front, file_bytes.ctypes.data if file_bytes.size else None, files, _file_mode(without), C.byref(n),
+                hits.ctypes.data if cap else None, spans.ctypes.data if cap else None, hit_file.ctypes.data if cap else None,
+                hit_line.ctypes.data if cap else None, cap, C.byref(cnt), file_lines.ctypes.data, first.ctypes.data,
+                listed.ctypes.data if fcap else None, fcap, C.byref(fcnt), C.byref(straddles), None))
+    k = min(int(cnt.value), cap)
+    return {"lines": int(n.value), "hits": hits[:k], "spans": spans[:k], "hit_file": hit_file[:k], "hit_line": hit_line[:k],
+            "count": int(cnt.value), "file_lines": file_lines, "first": first, "files": listed[:min(int(fcnt.value), fcap)],
+            "file_count": int(fcnt.value), "straddles": int(straddles.value)}
+
+
+def _lines_files_device(call, front, file_bytes_ptr, files, without, out_line_count_ptr, out_hits_ptr, out_hit_spans_ptr, out_hit_file_ptr,
+                        out_hit_line_ptr, hit_cap, out_hit_count_ptr, out_file_lines_ptr, out_file_first_ptr, out_files_ptr, file_cap,
+                        out_file_count_ptr, out_straddles_ptr, stream):
+    _check(call(*front, file_bytes_ptr or None, files, _file_mode(without), out_line_count_ptr or None, out_hits_ptr or None,
+                out_hit_spans_ptr or None, out_hit_file_ptr or None, out_hit_line_ptr or None, hit_cap, out_hit_count_ptr or None,
+                out_file_lines_ptr or None, out_file_first_ptr or None, out_files_ptr or None, file_cap, out_file_count_ptr or None,
+                out_straddles_ptr or None, stream or None))
 
 
 # --- from prefix and suffix lengths to matched heads and tails (pire_hip_affix_select and the forms on top of it)
@@ -1283,6 +1355,27 @@ class Table:
                               line_cap, out_group_count_ptr, out_hit_count_ptr, out_bytes_ptr, out_text_ptr, text_cap, out_offsets_ptr,
                               stream)
 
+    # --- the bytes of many files in, the matching lines by file out (pire_hip_run_lines_files_select)
+    def run_lines_files_host(self, raw, file_bytes, delim: int = 10, flags=FLAG_BEGIN | FLAG_END, want=None, without=False, hit_cap=None,
+                             file_cap=None):
+        """pire_hip_run_lines_files_select on a host buffer and file_bytes[files + 1]: {"lines", "hits" u64[k], "spans" u64[k, 2],
+        "hit_file" u64[k], "hit_line" u64[k], "count", "file_lines" u64[files + 1], "first" u64[files + 1], "files" u64[m],
+        "file_count", "straddles"}; hit_cap None = room for a hit on every line, file_cap None = room for every file."""
+        raw = _raw_bytes(raw)
+        wm = self.want_mask(want)
+        front = [self._h, raw.ctypes.data if raw.size else None, raw.size, delim, flags & ~FLAG_ON_DEVICE, _np_ptr(wm)]
+        return _lines_files_host(lib().pire_hip_run_lines_files_select, front, raw, file_bytes, without, hit_cap, file_cap)
+
+    def run_lines_files_device(self, raw_ptr: int, size: int, flags, file_bytes_ptr: int, files: int, out_line_count_ptr: int,
+                               out_hit_count_ptr: int, out_file_count_ptr: int, out_straddles_ptr: int, delim: int = 10, want_ptr=0,
+                               without=False, out_hits_ptr=0, out_hit_spans_ptr=0, out_hit_file_ptr=0, out_hit_line_ptr=0, hit_cap=0,
+                               out_file_lines_ptr=0, out_file_first_ptr=0, out_files_ptr=0, file_cap=0, stream: int = 0):
+        """pire_hip_run_lines_files_select on device pointers (synchronises `stream` once, as run_lines_select_device does)."""
+        front = [self._h, raw_ptr or None, size, delim, flags | FLAG_ON_DEVICE, want_ptr or None]
+        _lines_files_device(lib().pire_hip_run_lines_files_select, front, file_bytes_ptr, files, without, out_line_count_ptr, out_hits_ptr,
+                            out_hit_spans_ptr, out_hit_file_ptr, out_hit_line_ptr, hit_cap, out_hit_count_ptr, out_file_lines_ptr,
+                            out_file_first_ptr, out_files_ptr, file_cap, out_file_count_ptr, out_straddles_ptr, stream)
+
     # --- raw bytes in, the lines whose column matches out (pire_hip_run_lines_field_select / _gather): the results of the two
     # methods above, hits and spans being whole lines
     def run_lines_field_select_host(self, raw, field: int, sep: int = 9, delim: int = 10, rest: bool = False,
@@ -1650,6 +1743,24 @@ class SlowTable:
                               delim, tail, out_line_count_ptr, out_sel_count_ptr, out_lines_ptr, out_line_flags_ptr, out_line_spans_ptr,
                               line_cap, out_group_count_ptr, out_hit_count_ptr, out_bytes_ptr, out_text_ptr, text_cap, out_offsets_ptr,
                               stream)
+
+    # --- the bytes of many files in, the lines that match (or, inverted, do not) by file out (pire_hip_slow_lines_files_select)
+    def lines_files_host(self, raw, file_bytes, delim: int = 10, flags=FLAG_BEGIN | FLAG_END, invert=False, without=False, hit_cap=None,
+                         file_cap=None):
+        """pire_hip_slow_lines_files_select on a host buffer: what Table.run_lines_files_host returns; invert: grep -v -c / -l."""
+        raw = _raw_bytes(raw)
+        front = [self._h, raw.ctypes.data if raw.size else None, raw.size, delim, flags & ~FLAG_ON_DEVICE, _final_mode(invert)]
+        return _lines_files_host(lib().pire_hip_slow_lines_files_select, front, raw, file_bytes, without, hit_cap, file_cap)
+
+    def lines_files_device(self, raw_ptr: int, size: int, flags, file_bytes_ptr: int, files: int, out_line_count_ptr: int,
+                           out_hit_count_ptr: int, out_file_count_ptr: int, out_straddles_ptr: int, delim: int = 10, invert=False,
+                           without=False, out_hits_ptr=0, out_hit_spans_ptr=0, out_hit_file_ptr=0, out_hit_line_ptr=0, hit_cap=0,
+                           out_file_lines_ptr=0, out_file_first_ptr=0, out_files_ptr=0, file_cap=0, stream: int = 0):
+        """pire_hip_slow_lines_files_select on device pointers (synchronises `stream` once, as Table.run_lines_select_device does)."""
+        front = [self._h, raw_ptr or None, size, delim, flags | FLAG_ON_DEVICE, _final_mode(invert)]
+        _lines_files_device(lib().pire_hip_slow_lines_files_select, front, file_bytes_ptr, files, without, out_line_count_ptr, out_hits_ptr,
+                            out_hit_spans_ptr, out_hit_file_ptr, out_hit_line_ptr, hit_cap, out_hit_count_ptr, out_file_lines_ptr,
+                            out_file_first_ptr, out_files_ptr, file_cap, out_file_count_ptr, out_straddles_ptr, stream)
 
 
 class CountingTable:

@@ -3257,6 +3257,174 @@ try {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
 
+// ---- the bytes of many files in, the matching lines by file out (split.hip, files.hip) ---------------------------------------
+// The frame around scan + hit list + pire_hip_files: the hit list of the scan lives in scratch, whole -- a file's count does not
+// depend on hit_cap --, the pass copies what the caller has room for.  The frame takes no table: the scan is the entry point's
+// own call (Scanner: with `want` staged in; SlowScanner: with `mode`).
+namespace {
+
+struct FilesLines {
+	const uint64_t* fileBytes;
+	uint64_t files;
+	uint32_t fileMode;
+	uint64_t *outHits, *outHitSpans, *outHitFile, *outHitLine;
+	uint64_t hitCap;
+	uint64_t *outHitCount, *outFileLines, *outFileFirst, *outFiles;
+	uint64_t fileCap;
+	uint64_t *outFileCount, *outStraddles;
+};
+
+// scan(f, dWant, dHits, dHitCount): the hit list of the lines f.Text() / f.Offsets() / f.n into dHits[f.n], their number into *dHitCount
+int FilesLinesImpl(const char* who, const char* refused, const void* raw, uint64_t size, uint32_t delim, uint32_t flags, const uint64_t* want,
+                   uint32_t wantWords, const FilesLines& c, uint64_t* out_line_count, void* streamPtr,
+                   const std::function<int(const LinesFrame&, const uint64_t*, uint64_t*, uint64_t*)>& scan)
+{
+	if (refused)
+		return GatherRefuse(who, refused);
+	if (!c.outHitCount)
+		return GatherRefuse(who, "null out_hit_count");
+	if (c.hitCap && !c.outHits)
+		return GatherRefuse(who, "hit_cap > 0 with null out_hits");
+	if (int rc = SplitArgsInvalid(who, raw, size, delim, out_line_count, "out_line_count"))
+		return rc;
+	if (c.outHitSpans && !c.outHits)
+		return GatherRefuse(who, "out_hit_spans without out_hits");
+	const FilesOut o = {c.outFiles, c.fileCap, c.outFileCount};
+	if (int rc = FilesArgsInvalid(who, c.fileBytes != nullptr, "file_bytes", c.files, c.fileMode, o))
+		return rc;
+	if (!c.outStraddles)
+		return GatherRefuse(who, "null out_straddles");
+	if (c.files == 0 && size)
+		return GatherRefuse(who, "files == 0 with size > 0");
+	LinesFrame f(who, raw, size, delim, flags, nullptr, streamPtr);
+	if (!f.onDevice)
+		if (int rc = FilesBoundsInvalid(who, "file_bytes", c.fileBytes, c.files, size, "size"))
+			return rc;
+	const uint64_t files = c.files;
+	if (f.HostEdge(out_line_count)) {
+		// no bytes: no line, no hit, every file empty
+		*c.outHitCount = 0;
+		*c.outStraddles = 0;
+		for (uint64_t k = 0; k <= files; ++k) {
+			if (c.outFileLines)
+				c.outFileLines[k] = 0;
+			if (c.outFileFirst)
+				c.outFileFirst[k] = 0;
+		}
+		*c.outFileCount = c.fileMode & PIRE_HIP_FILES_WITHOUT ? files : 0;
+		for (uint64_t k = 0; k < std::min(*c.outFileCount, c.fileCap); ++k)
+			c.outFiles[k] = k;
+		return PIRE_HIP_OK;
+	}
+	const uint64_t *dWant = nullptr, *dFileBytes = nullptr;
+	uint64_t *dHitFile = nullptr, *dHitLine = nullptr, *dFileLines = nullptr, *dFileFirst = nullptr, *dFiles = nullptr, *dFileCount = nullptr,
+	         *dStraddles = nullptr;
+	if (int rc = f.Open())
+		return rc;
+	if (want)
+		if (int rc = f.io.In(want, size_t(wantWords), &dWant))
+			return rc;
+	if (files)
+		if (int rc = f.io.In(c.fileBytes, size_t(files) + 1, &dFileBytes))
+			return rc;
+	if (int rc = f.Split(out_line_count, c.outHitCount, 1, c.hitCap, true))
+		return rc;
+	if (int rc = f.Lists(c.outHits, c.outHitSpans))
+		return rc;
+	const uint64_t listCap = std::min(c.fileCap, files);   // `files` files: no list is staged longer
+	if (c.outHitFile && f.cap)
+		if (int rc = f.io.Result(c.outHitFile, size_t(f.cap), 0, &dHitFile))
+			return rc;
+	if (c.outHitLine && f.cap)
+		if (int rc = f.io.Result(c.outHitLine, size_t(f.cap), 0, &dHitLine))
+			return rc;
+	if (c.outFileLines)
+		if (int rc = f.io.Result(c.outFileLines, size_t(files) + 1, size_t(files) + 1, &dFileLines))
+			return rc;
+	if (c.outFileFirst)
+		if (int rc = f.io.Result(c.outFileFirst, size_t(files) + 1, size_t(files) + 1, &dFileFirst))
+			return rc;
+	if (c.outFiles && listCap)
+		if (int rc = f.io.Result(c.outFiles, size_t(listCap), 0, &dFiles))
+			return rc;
+	if (int rc = f.io.Result(c.outFileCount, 1, 1, &dFileCount))
+		return rc;
+	if (int rc = f.io.Result(c.outStraddles, 1, 1, &dStraddles))
+		return rc;
+	StreamScratch hitList(f.stream), ownLines(f.stream);   // (live until the pass behind the scan is enqueued)
+	if (!dFileLines) {
+		if (int rc = ownLines.Alloc((size_t(files) + 1) * 8, "hipMallocAsync(file lines)"))
+			return rc;
+		dFileLines = ownLines.as<uint64_t>();
+	}
+	// the scan's hit list: 8 bytes a line at most
+	if (int rc = hitList.Alloc((size_t(f.n) + 1) * 8, "hipMallocAsync(files hits)"))
+		return rc;
+	uint64_t* dScanHits = hitList.as<uint64_t>();
+	if (f.n == 0) {
+		if (int rc = f.ZeroCounts("hipMemsetAsync(hit count)"))
+			return rc;
+	} else {
+		if (int rc = scan(f, dWant, dScanHits, f.dCounts))
+			return rc;
+	}
+	if (int rc = LaunchFileLines(f.LineOffsets(), f.n, dFileBytes, files, f.dRaw, size, delim, dFileLines, dStraddles, f.stream))
+		return rc;
+	if (int rc = LaunchFiles(dScanHits, f.dCounts, f.n, dFileLines, files, c.fileMode, dFileFirst, f.dHits, dHitFile, dHitLine, f.dHits ? f.cap : 0,
+	                         dFiles, listCap, dFileCount, f.stream))
+		return rc;
+	if (f.dSpans)   // (the whole line)
+		if (int rc = LaunchHitSpans(f.dHits, f.dCounts, 1, f.cap, f.cap, f.LineOffsets(), f.dSpans, f.stream, "split spans launch"))
+			return rc;
+	if (int rc = f.Close("hipMemcpy(hits)"))
+		return rc;
+	if (f.onDevice)
+		return PIRE_HIP_OK;
+	if (int rc = HitsBack(1, c.outHitCount, f.cap, f.cap, dHitFile, c.outHitFile, 1, "hipMemcpy(hit files)"))
+		return rc;
+	if (int rc = HitsBack(1, c.outHitCount, f.cap, f.cap, dHitLine, c.outHitLine, 1, "hipMemcpy(hit files)"))
+		return rc;
+	return HitsBack(1, c.outFileCount, listCap, listCap, dFiles, c.outFiles, 1, "hipMemcpy(files)");
+}
+
+}  // namespace
+
+int pire_hip_run_lines_files_select(pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags, const uint64_t* want,
+                                    const uint64_t* file_bytes, uint64_t files, uint32_t file_mode, uint64_t* out_line_count, uint64_t* out_hits,
+                                    uint64_t* out_hit_spans, uint64_t* out_hit_file, uint64_t* out_hit_line, uint64_t hit_cap,
+                                    uint64_t* out_hit_count, uint64_t* out_file_lines, uint64_t* out_file_first, uint64_t* out_files,
+                                    uint64_t file_cap, uint64_t* out_file_count, uint64_t* out_straddles, void* stream)
+try {
+	const FilesLines c = {file_bytes, files, file_mode, out_hits, out_hit_spans, out_hit_file, out_hit_line, hit_cap, out_hit_count,
+	                      out_file_lines, out_file_first, out_files, file_cap, out_file_count, out_straddles};
+	return FilesLinesImpl("pire_hip_run_lines_files_select", t ? nullptr : "null table", raw, size, delim, flags, want,
+	                      t ? pire_hip_table_mask_words(t) : 0, c, out_line_count, stream,
+	                      [&](const LinesFrame& f, const uint64_t* dWant, uint64_t* dHits, uint64_t* dHitCount) {
+		                      return pire_hip_run_select(t, f.Text(), f.Offsets(), f.n, f.RunFlags(), nullptr, nullptr, nullptr, nullptr, dWant,
+		                                                 nullptr, dHits, nullptr, f.n, dHitCount, f.stream);
+	                      });
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_slow_lines_files_select(pire_hip_slow_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags, uint32_t mode,
+                                     const uint64_t* file_bytes, uint64_t files, uint32_t file_mode, uint64_t* out_line_count, uint64_t* out_hits,
+                                     uint64_t* out_hit_spans, uint64_t* out_hit_file, uint64_t* out_hit_line, uint64_t hit_cap,
+                                     uint64_t* out_hit_count, uint64_t* out_file_lines, uint64_t* out_file_first, uint64_t* out_files,
+                                     uint64_t file_cap, uint64_t* out_file_count, uint64_t* out_straddles, void* stream)
+try {
+	const FilesLines c = {file_bytes, files, file_mode, out_hits, out_hit_spans, out_hit_file, out_hit_line, hit_cap, out_hit_count,
+	                      out_file_lines, out_file_first, out_files, file_cap, out_file_count, out_straddles};
+	return FilesLinesImpl("pire_hip_slow_lines_files_select", !t ? "null table" : mode > PIRE_HIP_FINAL_SELECT_ZERO ? "unknown mode" : nullptr,
+	                      raw, size, delim, flags, nullptr, 0, c, out_line_count, stream,
+	                      [&](const LinesFrame& f, const uint64_t*, uint64_t* dHits, uint64_t* dHitCount) {
+		                      return pire_hip_slow_run_select(t, f.Text(), f.Offsets(), f.n, f.RunFlags(), mode, nullptr, nullptr, nullptr, dHits,
+		                                                      f.n, dHitCount, f.stream);
+	                      });
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
 // The scan parameters of the prefix and the suffix searches (the caller holds the table: TableUse), for pire_hip_prefix /
 // pire_hip_suffix and for the calls that run both (pire_hip_affix_run_select)
 static int PrefixParams(pire_hip_table* t, ScanParams* p, bool throughBegin)

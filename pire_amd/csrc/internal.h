@@ -1222,6 +1222,30 @@ struct ContextOut {
 int ContextArgsInvalid(const char* who, bool haveHits, uint64_t hitCap, uint64_t n, const ContextOut& o, bool ownList = false);
 // What a host-pointer call refuses of its list: hits[0, k) -- any alignment -- strictly ascending, every entry < n
 int ContextHitsInvalid(const char* who, const void* hits, uint64_t k, uint64_t n);
+// files.hip: from an ascending hit list and the files' line boundaries to hits by file (pire_hip_files).  Device pointers only
+// -- hitCount included, nullable: k = hitCap --, four or five kernels enqueued on `stream`; scratch from the stream-ordered
+// allocator: the compaction's over `files`, and the first row where outFileFirst is null.  outHits (nullable): the first
+// min(k, outCap) entries of the list itself, for a caller whose list lives in scratch; outHitFile / outHitLine: outCap entries.
+// files == 0: the count and outFileFirst[0] zeroed on the stream.
+int LaunchFiles(const uint64_t* hits, const uint64_t* hitCount, uint64_t hitCap, const uint64_t* bounds, uint64_t files, uint32_t fileMode,
+                uint64_t* outFileFirst, uint64_t* outHits, uint64_t* outHitFile, uint64_t* outHitLine, uint64_t outCap, uint64_t* outFiles,
+                uint64_t fileCap, uint64_t* outFileCount, hipStream_t stream);
+// outFileLines[f] for f in [0, files] = how many of the split's n lines (line i begins at offsets[i] + i of raw) begin in front
+// of byte fileBytes[f]; *outStraddles = how many f in [1, files) have 0 < fileBytes[f] < size and raw[fileBytes[f] - 1] != delim.
+// Two kernels, files / 256 bytes of scratch.
+int LaunchFileLines(const uint64_t* offsets, uint64_t n, const uint64_t* fileBytes, uint64_t files, const void* raw, uint64_t size,
+                    uint32_t delim, uint64_t* outFileLines, uint64_t* outStraddles, hipStream_t stream);
+// The file list of the pass, as the caller of an entry point gave it
+struct FilesOut {
+	uint64_t* outFiles;
+	uint64_t fileCap;
+	uint64_t* outFileCount;
+};
+// What pire_hip_files and the lines forms refuse of the files before any device is touched, in `who`'s name (boundsName: what
+// the entry point calls its boundaries), and what a host-pointer call refuses of the boundaries themselves: bounds[files + 1]
+// non-decreasing from 0 to `total` (totalName: n or size)
+int FilesArgsInvalid(const char* who, bool haveBounds, const char* boundsName, uint64_t files, uint32_t fileMode, const FilesOut& o);
+int FilesBoundsInvalid(const char* who, const char* boundsName, const uint64_t* bounds, uint64_t files, uint64_t total, const char* totalName);
 // split.hip: raw text into strings (pire_hip_split).  Device pointers only, everything enqueued on `stream`.  The pass
 // comes in two halves because a caller may want the number of strings before it has room for their offsets:
 // LaunchSplitCount counts and scans (*outN = n; the tile prefixes stay in `scratch`, the caller's owner, which has to live
