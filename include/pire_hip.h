@@ -1451,6 +1451,95 @@ int pire_hip_slow_lines_files_select(pire_hip_slow_table* t, const void* raw, ui
                                      uint64_t* out_file_first, uint64_t* out_files, uint64_t file_cap, uint64_t* out_file_count,
                                      uint64_t* out_straddles, void* stream);
 
+/* ---- boolean queries over hit lists, on the device (grep a | grep -v b, two columns, two kinds of scanner) -------------- */
+
+/*
+ * From up to six hit lists to the lines that a boolean function of "is in list j" selects.  It takes no table and no text: it
+ * reads line numbers, whoever wrote them -- every hit pass of the library writes such a list, pire_hip_route one per regexp.
+ * List j has k_j = min(list_counts && list_counts[j] ? *list_counts[j] : list_caps[j], list_caps[j]) entries (as
+ * pire_hip_gather), lists[j][0, k_j) strictly ascending and every entry < n.  With
+ *   m(i) = sum over j < k_lists of [i is in list j] << j,      for 0 <= i < n
+ *   selected(i) <=> (truth >> m(i)) & 1
+ * bits of truth at or above 2^k_lists are never looked at; bit 0 -- the lines in no list -- is legal: k_lists = 1 with
+ * truth = 1 is the complement of a list (`grep -v` behind any pass), truth = 2 gives the list back, k_lists = 2 with
+ * truth = 0x2 is "in list 0 and not in list 1", 0x8 the intersection, 0xE the union.
+ *   out_hits[hit_cap] (nullable): the selected i, ascending.
+ *   out_hit_members[hit_cap] (nullable, needs out_hits): m(out_hits[r]), one byte.
+ *   *out_hit_count (required): the number of selected lines, also when it exceeds hit_cap; only the first
+ *       min(count, hit_cap) entries of the two lists are written, nothing behind them.
+ * n == 0: the count is 0, nothing else is written.  All lists empty: all n lines are selected if bit 0 of truth is set, none
+ * otherwise.  The same list may be passed twice.
+ * The arrays lists, list_counts (nullable as a whole: every k_j = list_caps[j]) and list_caps themselves, k_lists entries each,
+ * are always HOST memory: they are read during the call and travel to the kernels by value.
+ * flags: PIRE_HIP_RUN_ON_DEVICE -> their entries and all outputs are device pointers and the call only enqueues on `stream`
+ *        -- the rows of pire_hip_route pass as they are: out_hits + r * hit_cap, out_hit_counts + r --: classify per tile of
+ *        1 024 LINES (2 * k_lists wave-wide searches bound the lists' slices inside the tile, so a list of 10^6 entries costs
+ *        what any other costs), the one-block scan of pire_hip_select, scatter; no atomics, no block waits for another: the
+ *        same input gives the same bytes.  Scratch (n / 8 + n / 256 bytes, and n bytes more where out_hit_members is asked
+ *        for) comes from the stream-ordered allocator: the rule and the capture-mode caveat stated at pire_hip_select.  The
+ *        lists and out_hit_members may have any alignment.  A list that is not ascending, or that names lines >= n, gives an
+ *        unspecified selection; even then the call reads nothing outside lists[j][0, k_j) and writes nothing outside what is
+ *        stated above.  Otherwise host pointers: staged, synchronises, the lists come back only as far as they were written;
+ *        a list that is not strictly ascending or that names a line >= n is PIRE_HIP_EINVAL, and nothing is written.
+ * PIRE_HIP_EINVAL before any device is touched: k_lists == 0 or > PIRE_HIP_COMBINE_MAX_LISTS; null lists or list_caps;
+ * list_caps[j] > 0 with null lists[j]; null out_hit_count; hit_cap > 0 with null out_hits; out_hit_members without out_hits;
+ * n >= 2^32; a list_caps[j] >= 2^32.
+ * pire_hip_last_kernel() is not changed by the pass.  No first-use self-test: it takes no table (as pire_hip_context).
+ * The result is a hit list like any other: it chains into pire_hip_context, pire_hip_files, pire_hip_gather and into
+ * pire_hip_combine again.
+ */
+#define PIRE_HIP_COMBINE_MAX_LISTS 6u
+int pire_hip_combine(const uint64_t* const* lists, const uint64_t* const* list_counts, const uint64_t* list_caps,
+                     uint32_t k_lists, uint64_t n, uint64_t truth, uint32_t flags,
+                     uint64_t* out_hits, uint8_t* out_hit_members, uint64_t hit_cap, uint64_t* out_hit_count, void* stream);
+
+/*
+ * Raw bytes in, the lines that a boolean function of up to six scans selects out, behind one call, one split and one wait:
+ * `grep a | grep -v b`, `awk -F'\t' '$3 ~ /a/ && $5 !~ /b/'`, a Scanner term and a SlowScanner term on the same lines.
+ * terms[k_terms] is a HOST array in both flag modes.  Term j scans the whole line (column == PIRE_HIP_TERM_LINE) or the
+ * field `column` of it, cut as pire_hip_fields cuts it with sep and field_mode (one cut per distinct column, sep and
+ * field_mode), with its own run_flags (PIRE_HIP_RUN_BEGIN | _END | _GENERIC):
+ *   table       the lines pire_hip_run_select lists under `want` (NULL: Final; host or device memory like the call's other
+ *               pointers, pire_hip_table_mask_words(table) words)
+ *   slow_table  the lines pire_hip_slow_run_select lists under `mode` (0, or PIRE_HIP_FINAL_SELECT_ZERO: the lines it does
+ *               NOT match)
+ * exactly one of the two per term.  The k_terms lists live in stream-ordered scratch (8 bytes a line a term at most);
+ * pire_hip_combine with `truth` (bit j of the member mask: term j) gives out_hits, out_hit_members, hit_cap and
+ * *out_hit_count, as stated there.  out_hit_spans[hit_cap][2] (nullable, needs out_hits): the whole line of out_hits[r] as a
+ * byte range of raw, delimiter not included.  out_term_counts[k_terms] (nullable): the number of lines of every term's own
+ * list (`grep -c` of every term).  *out_line_count, raw, size, delim, the one synchronisation of `stream` EVEN WITH
+ * PIRE_HIP_RUN_ON_DEVICE and the refusal of 2^32 lines: as pire_hip_run_lines_select.  flags carries
+ * PIRE_HIP_RUN_ON_DEVICE and nothing else.
+ * The gather form: out_hits is nullable (the list then lives in scratch of the library's own); tail, out_text, text_cap,
+ * out_offsets (hit_cap + 1 entries), out_bytes: as pire_hip_gather_spans.
+ * PIRE_HIP_EINVAL before any device is touched: null terms, k_terms == 0 or > PIRE_HIP_COMBINE_MAX_LISTS; a term with both
+ * tables or neither; a slow term with a mode above PIRE_HIP_FINAL_SELECT_ZERO; a column term with sep > 255, sep == delim or
+ * unknown bits in field_mode; bits in flags other than PIRE_HIP_RUN_ON_DEVICE; what pire_hip_split refuses of raw, size and
+ * delim; what pire_hip_combine refuses of its outputs; out_hit_spans without out_hits; the gather form: what
+ * pire_hip_gather_spans refuses of its outputs.  Host pointers with size == 0: zeros (out_term_counts all zero,
+ * out_offsets[0] = 0 where not null), no device is touched.
+ */
+#define PIRE_HIP_TERM_LINE (~0u)
+typedef struct pire_hip_line_term {
+    pire_hip_table* table;            /* exactly one of table / slow_table */
+    pire_hip_slow_table* slow_table;
+    const uint64_t* want;             /* table terms: as pire_hip_select (NULL: Final); host or device like the call's other pointers */
+    uint32_t mode;                    /* slow terms: 0 or PIRE_HIP_FINAL_SELECT_ZERO */
+    uint32_t run_flags;               /* PIRE_HIP_RUN_BEGIN | _END | _GENERIC */
+    uint32_t column;                  /* PIRE_HIP_TERM_LINE: the whole line; else the field, as pire_hip_fields */
+    uint32_t sep, field_mode;         /* as pire_hip_fields; ignored for PIRE_HIP_TERM_LINE */
+} pire_hip_line_term;
+int pire_hip_lines_combine_select(const pire_hip_line_term* terms, uint32_t k_terms, uint64_t truth,
+                                  const void* raw, uint64_t size, uint32_t delim, uint32_t flags, uint64_t* out_line_count,
+                                  uint64_t* out_hits, uint64_t* out_hit_spans, uint8_t* out_hit_members, uint64_t hit_cap,
+                                  uint64_t* out_hit_count, uint64_t* out_term_counts, void* stream);
+int pire_hip_lines_combine_gather(const pire_hip_line_term* terms, uint32_t k_terms, uint64_t truth,
+                                  const void* raw, uint64_t size, uint32_t delim, uint32_t flags, uint64_t* out_line_count,
+                                  uint64_t* out_hits, uint64_t* out_hit_spans, uint8_t* out_hit_members, uint64_t hit_cap,
+                                  uint64_t* out_hit_count, uint64_t* out_term_counts,
+                                  uint32_t tail, void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes,
+                                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,7 @@
  *     LineMatcher       easy.h's choice between Scanner and SlowScanner, one lines surface over BatchRunner and SlowBatchRunner
  *     LineContext       a Context(before, after) and what was fetched for it                      BatchRunner, SlowBatchRunner
  *     LineFiles         a Files(fileBytes) and what was fetched for it                            BatchRunner, SlowBatchRunner
+ *     LineQuery, Truth  several scanners over the lines of one buffer and a boolean function of what they match; tables of its own
  * Which C calls these make, in which order and with which arguments, is recorded: tests/cpp/shim_calls_test.cpp,
  * tests/cpp/shim_calls.expected.txt.
  */
@@ -2046,6 +2047,175 @@ private:
 	Pire::SlowScanner m_slowScanner;
 	BatchRunner<Pire::Scanner>* m_fast;
 	SlowBatchRunner* m_slow;
+};
+
+/*
+ * Truth tables of a LineQuery over k terms (include/pire_hip.h, pire_hip_combine): bit m of the table says whether a line is
+ * selected whose member mask is m -- bit j of m: term j lists the line.  k is 1 .. PIRE_HIP_COMBINE_MAX_LISTS.
+ *     Truth::All(2)                                   both terms                     Truth::Any(3)   at least one of three
+ *     Truth::Of(2, [](unsigned m) { return m == 1; }) the first and not the second   (grep a | grep -v b)
+ */
+struct Truth {
+	template <class Predicate>
+	static uint64_t Of(unsigned k, Predicate selected)
+	{
+		if (k < 1 || k > PIRE_HIP_COMBINE_MAX_LISTS)
+			throw Pire::Error("pire_hip: Truth: 1 .. 6 terms");
+		uint64_t table = 0;
+		for (unsigned m = 0; m < (1u << k); ++m)
+			if (selected(m))
+				table |= uint64_t(1) << m;
+		return table;
+	}
+	static uint64_t All(unsigned k)
+	{
+		return Of(k, [k](unsigned m) { return m == (1u << k) - 1; });
+	}
+	static uint64_t Any(unsigned k)
+	{
+		return Of(k, [](unsigned m) { return m != 0; });
+	}
+};
+
+/*
+ * Several scanners over the lines of one buffer, and a boolean function of what they match: one call, one split, one wait
+ * (pire_hip_lines_combine_select / _gather).  Begin() and End() are stepped around every line -- or column -- of every term, as
+ * Matches() does.
+ *     Pire::Hip::LineQuery q;
+ *     q.Add(errors).AddSlow(noise, true);                              // term 0: a Scanner; term 1: the lines a SlowScanner does NOT match
+ *     q.AddField(user, 2);                                             // term 2: a Scanner on column 2 of the line (0-based, '\t' between)
+ *     q.Where(Pire::Hip::Truth::All(3)).RunLines(raw, size);           // Where() is optional: every term
+ *     q.Hits()  q.HitSpans()  q.HitMembers()  q.HitCount()  q.LineCount()  q.TermCounts()  q.HitText()  q.HitTextOffsets()
+ * HitMembers()[r] is the member mask of Hits()[r]; TermCounts()[j] is grep -c of term j alone.  The scanners are read when they
+ * are added; the buffer is read when an accessor first asks: it lives until then.  HitText() is a call of its own, as in
+ * BatchRunner: after Hits() it scans the buffer a second time.  A Scanner term lists the lines whose end state is Final.
+ */
+class LineQuery {
+public:
+	LineQuery() : m_truth(0), m_where(false), m_ran(false), m_raw(nullptr), m_len(0), m_delim('\n'), m_listed(false), m_haveText(false),
+	              m_textTail('\n'), m_lineCount(0), m_hitCount(0) {}
+	~LineQuery()
+	{
+		for (size_t j = 0; j < m_terms.size(); ++j) {
+			pire_hip_table_destroy(m_terms[j].table);
+			pire_hip_slow_table_destroy(m_terms[j].slow_table);
+		}
+	}
+	LineQuery& Add(const Pire::Scanner& sc) { return AddTerm(&sc, nullptr, false, PIRE_HIP_TERM_LINE, 0, false); }
+	LineQuery& AddField(const Pire::Scanner& sc, uint32_t field, char sep = '\t', bool rest = false)
+	{
+		return AddTerm(&sc, nullptr, false, field, uint8_t(sep), rest);
+	}
+	LineQuery& AddSlow(const Pire::SlowScanner& sc, bool invert = false) { return AddTerm(nullptr, &sc, invert, PIRE_HIP_TERM_LINE, 0, false); }
+	LineQuery& Where(uint64_t truth)
+	{
+		m_truth = truth, m_where = true;
+		m_listed = m_haveText = false;
+		return *this;
+	}
+	LineQuery& RunLines(const char* raw, size_t size, char delim = '\n')
+	{
+		m_raw = raw, m_len = size, m_delim = delim, m_ran = true;
+		m_listed = m_haveText = false;
+		return *this;
+	}
+	size_t Terms() const { return m_terms.size(); }
+	uint64_t LineCount() { FetchLists("LineCount()"); return m_lineCount; }
+	uint64_t HitCount() { FetchLists("HitCount()"); return m_hitCount; }
+	const std::vector<uint64_t>& Hits() { FetchLists("Hits()"); return m_hits; }
+	const std::vector<uint64_t>& HitSpans() { FetchLists("HitSpans()"); return m_hitSpans; }
+	const std::vector<uint8_t>& HitMembers() { FetchLists("HitMembers()"); return m_hitMembers; }
+	const std::vector<uint64_t>& TermCounts() { FetchLists("TermCounts()"); return m_termCounts; }
+	const std::string& HitText(char tail = '\n') { FetchText("HitText()", tail); return m_hitText; }
+	const std::vector<uint64_t>& HitTextOffsets()
+	{
+		if (!m_haveText)
+			FetchText("HitTextOffsets()", '\n');
+		return m_hitTextOffsets;
+	}
+
+private:
+	LineQuery(const LineQuery&);
+	LineQuery& operator=(const LineQuery&);
+	LineQuery& AddTerm(const Pire::Scanner* fast, const Pire::SlowScanner* slow, bool invert, uint32_t column, uint32_t sep, bool rest)
+	{
+		pire_hip_line_term t = {};
+		const std::string blob = fast ? SavedBlob(*fast) : SavedBlob(*slow);
+		if (fast)
+			Check(pire_hip_table_create(blob.data(), blob.size(), &t.table));
+		else
+			Check(pire_hip_slow_table_create(blob.data(), blob.size(), &t.slow_table));
+		t.mode = invert ? PIRE_HIP_FINAL_SELECT_ZERO : 0;
+		t.run_flags = PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END;
+		t.column = column, t.sep = sep, t.field_mode = rest ? PIRE_HIP_FIELDS_REST : 0;
+		m_terms.push_back(t);
+		m_listed = m_haveText = false;
+		return *this;
+	}
+	void Need(const char* what) const
+	{
+		if (!m_ran)
+			throw Pire::Error(std::string("pire_hip: ") + what + " follows RunLines()");
+	}
+	/* Where() was not called: every term.  (More terms than a table has bits for: the library refuses the call.) */
+	uint64_t TruthTable() const
+	{
+		const size_t k = m_terms.size();
+		return m_where ? m_truth : k >= 1 && k <= PIRE_HIP_COMBINE_MAX_LISTS ? Truth::All(unsigned(k)) : 0;
+	}
+	/* One call with room for a hit per 64 bytes of the buffer, and a second one where there are more */
+	void FetchLists(const char* what)
+	{
+		Need(what);
+		if (m_listed)
+			return;
+		m_termCounts.assign(m_terms.size(), 0);
+		GrowAndRetry(m_len / 64 + 1024, [&](size_t cap) {
+			m_hits.resize(cap);
+			m_hitSpans.resize(cap * 2);
+			m_hitMembers.resize(cap);
+			Check(pire_hip_lines_combine_select(m_terms.data(), uint32_t(m_terms.size()), TruthTable(), m_raw, m_len, uint8_t(m_delim), 0,
+			                                    &m_lineCount, m_hits.data(), m_hitSpans.data(), m_hitMembers.data(), cap, &m_hitCount,
+			                                    m_termCounts.data(), nullptr));
+			return size_t(m_hitCount);
+		});
+		m_hits.resize(m_hitCount);
+		m_hitSpans.resize(m_hitCount * 2);
+		m_hitMembers.resize(m_hitCount);
+		m_listed = true;
+	}
+	/* The selected lines as bytes; room for every byte they can have, and for the hits that are known, or else FetchLists()'s */
+	void FetchText(const char* what, char tail)
+	{
+		Need(what);
+		if (m_haveText && m_textTail == tail)
+			return;
+		uint64_t lines = 0, count = 0, bytes = 0;
+		GrowAndRetry(m_listed ? size_t(m_hitCount) : m_len / 64 + 1024, [&](size_t cap) {
+			m_hitTextOffsets.resize(cap + 1);
+			m_hitText.resize(m_len + cap + 1);
+			Check(pire_hip_lines_combine_gather(m_terms.data(), uint32_t(m_terms.size()), TruthTable(), m_raw, m_len, uint8_t(m_delim), 0, &lines,
+			                                    nullptr, nullptr, nullptr, cap, &count, nullptr, uint8_t(tail), &m_hitText[0], m_hitText.size(),
+			                                    m_hitTextOffsets.data(), &bytes, nullptr));
+			return size_t(count);   // (the text has room for the whole buffer and a tail per line: where the hits fit, the bytes do)
+		});
+		m_hitText.resize(bytes);
+		m_hitTextOffsets.resize(count + 1);
+		m_textTail = tail;
+		m_haveText = true;
+	}
+	std::vector<pire_hip_line_term> m_terms;
+	uint64_t m_truth;
+	bool m_where, m_ran;
+	const char* m_raw;
+	size_t m_len;
+	char m_delim;
+	bool m_listed, m_haveText;
+	char m_textTail;
+	uint64_t m_lineCount, m_hitCount;
+	std::vector<uint64_t> m_hits, m_hitSpans, m_termCounts, m_hitTextOffsets;
+	std::vector<uint8_t> m_hitMembers;
+	std::string m_hitText;
 };
 
 /*

@@ -266,6 +266,9 @@ ABI = [
     ("pire_hip_files", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_run_lines_files_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_slow_lines_files_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_combine", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_lines_combine_select", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_lines_combine_gather", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_multi_create", C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
     ("pire_hip_multi_destroy", None, [C.c_void_p]),
     ("pire_hip_multi_device_count", C.c_int, [C.c_void_p]),
@@ -622,6 +625,127 @@ def _lines_context_device(select, gather, front, before, after, delim, tail, out
     else:
         _check(gather(*args, _tail(delim if tail == -1 else tail), out_text_ptr or None, text_cap, out_offsets_ptr or None,
                       out_bytes_ptr or None, stream or None))
+
+
+# --- boolean queries over hit lists (pire_hip_combine and the lines forms on top of it)
+COMBINE_MAX_LISTS = 6   # include/pire_hip.h PIRE_HIP_COMBINE_MAX_LISTS
+TERM_LINE = 0xFFFFFFFF   # include/pire_hip.h PIRE_HIP_TERM_LINE (`column`): the term scans the whole line
+
+
+def truth(k: int, fn) -> int:
+    """The truth table of pire_hip_combine over k lists from a Python predicate over the member mask: bit m is set where
+    fn(m) holds, m = sum of 1 << j over the lists j a line is in.  truth(2, lambda m: m == 1): in list 0 and not in list 1."""
+    if not 1 <= int(k) <= COMBINE_MAX_LISTS:
+        raise ValueError(f"truth: k = {k}, 1 .. {COMBINE_MAX_LISTS} lists")
+    return sum(1 << m for m in range(1 << int(k)) if fn(m))
+
+
+def _combine_arrays(ptrs, count_ptrs, caps):
+    """the three host arrays of pire_hip_combine (count_ptrs None: a null list_counts)"""
+    k = len(ptrs)
+    lists = (C.c_void_p * max(k, 1))(*[p or None for p in ptrs])
+    counts = None if count_ptrs is None else (C.c_void_p * max(k, 1))(*[p or None for p in count_ptrs])
+    return lists, counts, (C.c_uint64 * max(k, 1))(*[int(c) for c in caps])
+
+
+def combine_host(lists, n: int, truth_bits: int, list_counts=None, hit_cap: Optional[int] = None, want_hits=True, want_members=True):
+    """pire_hip_combine on host lists (a sequence of uint64 arrays): {"hits" u64[m] or None, "members" u8[m] or None, "count"},
+    m = min(count, hit_cap); hit_cap None = room for every line; list_counts None = no list_counts array, else one entry per
+    list (an int, or None for a null pointer)."""
+    arrs = [np.ascontiguousarray(a, dtype=np.uint64) for a in lists]
+    cap = int(n) if hit_cap is None else int(hit_cap)
+    hits = np.zeros(cap, dtype=np.uint64) if want_hits else None
+    members = np.zeros(cap, dtype=np.uint8) if want_members else None
+    ks = None if list_counts is None else [None if c is None else C.c_uint64(int(c)) for c in list_counts]
+    pl, pc, caps = _combine_arrays([a.ctypes.data if a.size else 0 for a in arrs],
+                                   None if ks is None else [0 if c is None else C.addressof(c) for c in ks], [a.size for a in arrs])
+    cnt = C.c_uint64(0)
+    _check(lib().pire_hip_combine(pl, pc, caps, len(arrs), n, truth_bits, 0, hits.ctypes.data if want_hits and cap else None,
+                                  members.ctypes.data if want_members and cap else None, cap, C.byref(cnt), None))
+    m = min(int(cnt.value), cap)
+    return {"hits": hits[:m] if want_hits else None, "members": members[:m] if want_members else None, "count": int(cnt.value)}
+
+
+def combine_device(list_ptrs, list_caps, n: int, truth_bits: int, out_hit_count_ptr: int, list_count_ptrs=None, out_hits_ptr=0,
+                   out_hit_members_ptr=0, hit_cap=0, stream: int = 0):
+    """pire_hip_combine with PIRE_HIP_RUN_ON_DEVICE: raw device addresses (the sequences themselves are the host's), only
+    enqueues on `stream`."""
+    pl, pc, caps = _combine_arrays(list_ptrs, list_count_ptrs, list_caps)
+    _check(lib().pire_hip_combine(pl, pc, caps, len(list_ptrs), n, truth_bits, FLAG_ON_DEVICE, out_hits_ptr or None,
+                                  out_hit_members_ptr or None, hit_cap, out_hit_count_ptr or None, stream or None))
+
+
+class LineTerm(C.Structure):
+    """pire_hip_line_term (include/pire_hip.h)."""
+    _fields_ = [("table", C.c_void_p), ("slow_table", C.c_void_p), ("want", C.c_void_p), ("mode", C.c_uint32),
+                ("run_flags", C.c_uint32), ("column", C.c_uint32), ("sep", C.c_uint32), ("field_mode", C.c_uint32)]
+
+
+def line_term(table=None, slow_table=None, want_ptr=0, invert=False, flags=FLAG_BEGIN | FLAG_END, column: Optional[int] = None,
+              sep: int = 9, rest=False) -> LineTerm:
+    """One term of the lines forms: a Table (want_ptr: `want`, on the side the call's other pointers live) or a SlowTable
+    (invert: the lines it does not match), on the whole line (column None) or on one column."""
+    t = LineTerm()
+    t.table = None if table is None else table._h
+    t.slow_table = None if slow_table is None else slow_table._h
+    t.want = want_ptr or None
+    t.mode = _final_mode(invert)
+    t.run_flags = flags
+    t.column = TERM_LINE if column is None else int(column)
+    t.sep = sep
+    t.field_mode = FIELDS_REST if rest else 0
+    return t
+
+
+def _line_terms(terms):
+    return (LineTerm * max(len(terms), 1))(*terms)
+
+
+def lines_combine_host(terms, truth_bits: int, raw, delim: int = 10, hit_cap: Optional[int] = None, gather=False, tail=-1,
+                       text_cap: Optional[int] = None):
+    """pire_hip_lines_combine_select (gather=True: _gather) on a host buffer: {"lines", "hits" u64[k], "spans" u64[k, 2],
+    "members" u8[k], "count", "term_counts" u64[len(terms)]} and, gathered, "text", "offsets", "bytes"; k = min(count, hit_cap);
+    tail -1 = the delimiter.  A term's want_ptr is then a host address (keep the array alive)."""
+    raw = _raw_bytes(raw)
+    cap = raw.size if hit_cap is None else int(hit_cap)
+    hits = np.zeros(cap, dtype=np.uint64)
+    spans = np.zeros((cap, 2), dtype=np.uint64)
+    members = np.zeros(cap, dtype=np.uint8)
+    term_counts = np.zeros(max(len(terms), 1), dtype=np.uint64)
+    n, cnt = C.c_uint64(0), C.c_uint64(0)
+    args = [_line_terms(terms), len(terms), truth_bits, raw.ctypes.data if raw.size else None, raw.size, delim, 0, C.byref(n),
+            hits.ctypes.data if cap else None, spans.ctypes.data if cap else None, members.ctypes.data if cap else None, cap,
+            C.byref(cnt), term_counts.ctypes.data]
+    if not gather:
+        _check(lib().pire_hip_lines_combine_select(*args, None))
+    else:
+        room = raw.size + cap if text_cap is None else int(text_cap)
+        text = np.zeros(max(room, 1), dtype=np.uint8)
+        offsets = np.zeros(cap + 1, dtype=np.uint64)
+        total = C.c_uint64(0)
+        _check(lib().pire_hip_lines_combine_gather(*args, _tail(delim if tail == -1 else tail), text.ctypes.data if room else None, room,
+                                                   offsets.ctypes.data, C.byref(total), None))
+    k = min(int(cnt.value), cap)
+    out = {"lines": int(n.value), "hits": hits[:k], "spans": spans[:k], "members": members[:k], "count": int(cnt.value),
+           "term_counts": term_counts[:len(terms)]}
+    if gather:
+        out.update({"text": text[:min(int(total.value), room)], "offsets": offsets[:k + 1], "bytes": int(total.value)})
+    return out
+
+
+def lines_combine_device(terms, truth_bits: int, raw_ptr: int, size: int, out_line_count_ptr: int, out_hit_count_ptr: int, delim: int = 10,
+                         out_hits_ptr=0, out_hit_spans_ptr=0, out_hit_members_ptr=0, hit_cap=0, out_term_counts_ptr=0, tail=-1,
+                         out_bytes_ptr=None, out_text_ptr=0, text_cap=0, out_offsets_ptr=0, stream: int = 0):
+    """pire_hip_lines_combine_select on device pointers -- out_bytes_ptr not None: _gather -- (synchronises `stream` once, to
+    read the line count back).  A term's want_ptr is a device address."""
+    args = [_line_terms(terms), len(terms), truth_bits, raw_ptr or None, size, delim, FLAG_ON_DEVICE, out_line_count_ptr or None,
+            out_hits_ptr or None, out_hit_spans_ptr or None, out_hit_members_ptr or None, hit_cap, out_hit_count_ptr or None,
+            out_term_counts_ptr or None]
+    if out_bytes_ptr is None:
+        _check(lib().pire_hip_lines_combine_select(*args, stream or None))
+    else:
+        _check(lib().pire_hip_lines_combine_gather(*args, _tail(delim if tail == -1 else tail), out_text_ptr or None, text_cap,
+                                                   out_offsets_ptr or None, out_bytes_ptr or None, stream or None))
 
 
 # --- from a hit list and file boundaries to hits by file (pire_hip_files and the lines forms on top of it)

@@ -2145,13 +2145,16 @@ struct LinesFrame {
 		}
 		return gather->outOffsets ? io.Result(gather->outOffsets, size_t(cap) + 1, 0, &dOutOffsets) : PIRE_HIP_OK;
 	}
-	int Cut(const LinesField& c)
+	int Cut(const LinesField& c) { return Cut(c, cut); }
+	// (a form that scans several columns cuts once per column, each cut into an owner of its own that it keeps alive until its
+	// scans are enqueued; Text() and Offsets() are the latest cut)
+	int Cut(const LinesField& c, StreamScratch& owner)
 	{
 		// one block: spans[n][2], offsets[n + 1], the byte count, the text (no longer than the lines are)
 		const size_t words = size_t(n) * 3 + 2;
-		if (int rc = cut.Alloc(words * 8 + size_t(size) + 16, "hipMallocAsync(fields)"))
+		if (int rc = owner.Alloc(words * 8 + size_t(size) + 16, "hipMallocAsync(fields)"))
 			return rc;
-		uint64_t* spans = cut.as<uint64_t>();
+		uint64_t* spans = owner.as<uint64_t>();
 		uint64_t* offsets = spans + 2 * n;
 		uint64_t* bytes = offsets + n + 1;
 		uint8_t* text = reinterpret_cast<uint8_t*>(bytes + 1);
@@ -3421,6 +3424,178 @@ try {
 		                      return pire_hip_slow_run_select(t, f.Text(), f.Offsets(), f.n, f.RunFlags(), mode, nullptr, nullptr, nullptr, dHits,
 		                                                      f.n, dHitCount, f.stream);
 	                      });
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+// ---- raw bytes in, the lines a boolean function of several scans selects out (split.hip, fields.hip, combine.hip) ----------
+// The frame around k scans + their hit lists + pire_hip_combine: one split, one cut per distinct column, every term's list
+// in scratch (8 bytes a line a term at most), the combined list in the place the hit list has in the forms above -- hits,
+// spans, the gather through the spans.  Every term scans with its own table, `want` / mode and run flags.
+namespace {
+
+struct CombineLines {
+	uint64_t truth;
+	uint64_t* outHits;
+	uint64_t* outSpans;
+	uint8_t* outMembers;
+	uint64_t hitCap;
+	uint64_t *outHitCount, *outTermCounts;
+};
+
+int CombineLinesImpl(const char* who, const pire_hip_line_term* terms, uint32_t kTerms, const CombineLines& c, const void* raw, uint64_t size,
+                     uint32_t delim, uint32_t flags, uint64_t* out_line_count, const LinesGather* gather, void* streamPtr)
+{
+	if (!terms)
+		return GatherRefuse(who, "null terms");
+	if (kTerms == 0 || kTerms > PIRE_HIP_COMBINE_MAX_LISTS)
+		return GatherRefuse(who, kTerms ? "more than 6 terms" : "k_terms == 0");
+	if (flags & ~uint32_t(PIRE_HIP_RUN_ON_DEVICE))
+		return GatherRefuse(who, "flags other than PIRE_HIP_RUN_ON_DEVICE (BEGIN / END are each term's own)");
+	for (uint32_t j = 0; j < kTerms; ++j) {
+		const pire_hip_line_term& t = terms[j];
+		const std::string term = "term " + std::to_string(j) + ": ";
+		if (!t.table == !t.slow_table)
+			return GatherRefuse(who, (term + (t.table ? "both table and slow_table" : "neither table nor slow_table")).c_str());
+		if (t.slow_table && t.mode > PIRE_HIP_FINAL_SELECT_ZERO)
+			return GatherRefuse(who, (term + "unknown mode").c_str());
+		if (t.run_flags & ~uint32_t(PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END | PIRE_HIP_RUN_GENERIC))
+			return GatherRefuse(who, (term + "unknown bits in run_flags").c_str());
+		if (t.column != PIRE_HIP_TERM_LINE) {
+			if (int rc = FieldArgsInvalid(who, t.sep, t.field_mode))
+				return rc;
+			if (t.sep == delim)
+				return GatherRefuse(who, (term + "sep == delim").c_str());
+		}
+	}
+	if (int rc = SplitArgsInvalid(who, raw, size, delim, out_line_count, "out_line_count"))
+		return rc;
+	// (the gather form keeps the hit list to itself where the caller has no array for it)
+	const CombineOut o = {c.outHits, c.outMembers, c.hitCap, c.outHitCount};
+	if (int rc = CombineOutputsInvalid(who, 0, o, gather != nullptr))
+		return rc;
+	if (c.outSpans && !c.outHits)
+		return GatherRefuse(who, "out_hit_spans without out_hits");
+	if (gather) {
+		if (int rc = GatherOutputsInvalid(who, "hit_cap", c.hitCap, gather->tail, gather->outText, gather->textCap, gather->outOffsets,
+		                                  gather->outBytes))
+			return rc;
+		if (int rc = GatherOverlaps(who, raw, size, gather->outText, gather->textCap))
+			return rc;
+	}
+	LinesFrame f(who, raw, size, delim, flags, gather, streamPtr);
+	if (f.HostEdge(out_line_count)) {
+		*c.outHitCount = 0;
+		for (uint32_t j = 0; j < kTerms && c.outTermCounts; ++j)
+			c.outTermCounts[j] = 0;
+		return PIRE_HIP_OK;
+	}
+	const uint64_t* dWant[PIRE_HIP_COMBINE_MAX_LISTS] = {};
+	uint8_t* dMembers = nullptr;
+	uint64_t* dTermCounts = nullptr;
+	if (int rc = f.Open())
+		return rc;
+	for (uint32_t j = 0; j < kTerms; ++j)
+		if (terms[j].table && terms[j].want)
+			if (int rc = f.io.In(terms[j].want, size_t(pire_hip_table_mask_words(terms[j].table)), &dWant[j]))
+				return rc;
+	if (int rc = f.Split(out_line_count, c.outHitCount, 1, c.hitCap, true))
+		return rc;
+	if (int rc = f.Lists(c.outHits, c.outSpans))
+		return rc;
+	if (c.outHits && c.outMembers && f.cap)
+		if (int rc = f.io.Result(c.outMembers, size_t(f.cap), 0, &dMembers))
+			return rc;
+	if (c.outTermCounts)
+		if (int rc = f.io.Result(c.outTermCounts, size_t(kTerms), size_t(kTerms), &dTermCounts))
+			return rc;
+	StreamScratch termLists(f.stream);   // (lives until the pass behind the scans is enqueued)
+	std::vector<std::unique_ptr<StreamScratch>> cuts;   // one per distinct column, alive until the scans are enqueued
+	if (f.n == 0) {
+		if (int rc = f.ZeroCounts("hipMemsetAsync(hit count)"))
+			return rc;
+		const hipError_t e = dTermCounts ? hipMemsetAsync(dTermCounts, 0, size_t(kTerms) * 8, f.stream) : hipSuccess;
+		if (e != hipSuccess)
+			return HipFail(e, "hipMemsetAsync(term counts)");
+	} else {
+		// the terms' hit lists: 8 bytes a line a term at most, and their counts where the caller has no place for them
+		if (int rc = termLists.Alloc((size_t(f.n) + 1) * 8 * kTerms, "hipMallocAsync(term hits)"))
+			return rc;
+		uint64_t* base = termLists.as<uint64_t>();
+		if (!dTermCounts)
+			dTermCounts = base + size_t(f.n) * kTerms;
+		const void* text[PIRE_HIP_COMBINE_MAX_LISTS];
+		const uint64_t* offsets[PIRE_HIP_COMBINE_MAX_LISTS];
+		for (uint32_t j = 0; j < kTerms; ++j) {
+			const pire_hip_line_term& t = terms[j];
+			if (t.column == PIRE_HIP_TERM_LINE) {
+				text[j] = f.lines.text.get(), offsets[j] = f.LineOffsets();
+				continue;
+			}
+			uint32_t same = j;   // an earlier term with the same cut
+			for (uint32_t i = 0; i < j && same == j; ++i)
+				if (terms[i].column == t.column && terms[i].sep == t.sep && terms[i].field_mode == t.field_mode)
+					same = i;
+			if (same == j) {
+				cuts.push_back(std::make_unique<StreamScratch>(f.stream));
+				const LinesField column = {t.sep, t.column, t.field_mode};
+				if (int rc = f.Cut(column, *cuts.back()))
+					return rc;
+				text[j] = f.cutText, offsets[j] = f.cutOffsets;
+			} else {
+				text[j] = text[same], offsets[j] = offsets[same];
+			}
+		}
+		f.cutText = nullptr, f.cutOffsets = nullptr;   // (the frame itself goes on with the whole lines)
+		CombineLists in = {};
+		in.k = kTerms;
+		for (uint32_t j = 0; j < kTerms; ++j) {
+			const pire_hip_line_term& t = terms[j];
+			uint64_t* list = base + size_t(f.n) * j;
+			const uint32_t runFlags = t.run_flags | PIRE_HIP_RUN_ON_DEVICE;
+			const int rc = t.table ? pire_hip_run_select(t.table, text[j], offsets[j], f.n, runFlags, nullptr, nullptr, nullptr, nullptr, dWant[j],
+			                                             nullptr, list, nullptr, f.n, dTermCounts + j, f.stream)
+			                       : pire_hip_slow_run_select(t.slow_table, text[j], offsets[j], f.n, runFlags, t.mode, nullptr, nullptr, nullptr,
+			                                                  list, f.n, dTermCounts + j, f.stream);
+			if (rc)
+				return rc;
+			in.lists[j] = list, in.counts[j] = dTermCounts + j, in.caps[j] = f.n;
+		}
+		if (int rc = LaunchCombine(in, f.n, c.truth, f.dHits, dMembers, f.dHits ? f.cap : 0, f.dCounts, f.stream))
+			return rc;
+		if (f.dSpans)   // (the whole line, whatever part of it was scanned)
+			if (int rc = LaunchHitSpans(f.dHits, f.dCounts, 1, f.cap, f.cap, f.LineOffsets(), f.dSpans, f.stream, "split spans launch"))
+				return rc;
+	}
+	if (int rc = f.Close("hipMemcpy(combined hits)"))
+		return rc;
+	if (f.onDevice)
+		return PIRE_HIP_OK;
+	const uint64_t written = std::min(*c.outHitCount, f.cap);
+	const hipError_t e = written && dMembers ? hipMemcpy(c.outMembers, dMembers, size_t(written), hipMemcpyDeviceToHost) : hipSuccess;
+	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(combined hits)");
+}
+
+}  // namespace
+
+int pire_hip_lines_combine_select(const pire_hip_line_term* terms, uint32_t k_terms, uint64_t truth, const void* raw, uint64_t size,
+                                  uint32_t delim, uint32_t flags, uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_hit_spans,
+                                  uint8_t* out_hit_members, uint64_t hit_cap, uint64_t* out_hit_count, uint64_t* out_term_counts, void* stream)
+try {
+	const CombineLines c = {truth, out_hits, out_hit_spans, out_hit_members, hit_cap, out_hit_count, out_term_counts};
+	return CombineLinesImpl("pire_hip_lines_combine_select", terms, k_terms, c, raw, size, delim, flags, out_line_count, nullptr, stream);
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_lines_combine_gather(const pire_hip_line_term* terms, uint32_t k_terms, uint64_t truth, const void* raw, uint64_t size,
+                                  uint32_t delim, uint32_t flags, uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_hit_spans,
+                                  uint8_t* out_hit_members, uint64_t hit_cap, uint64_t* out_hit_count, uint64_t* out_term_counts, uint32_t tail,
+                                  void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes, void* stream)
+try {
+	const CombineLines c = {truth, out_hits, out_hit_spans, out_hit_members, hit_cap, out_hit_count, out_term_counts};
+	const LinesGather gather = {tail, out_text, text_cap, out_offsets, out_bytes, true, "hipMallocAsync(hit spans)"};
+	return CombineLinesImpl("pire_hip_lines_combine_gather", terms, k_terms, c, raw, size, delim, flags, out_line_count, &gather, stream);
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }

@@ -1222,6 +1222,29 @@ struct ContextOut {
 int ContextArgsInvalid(const char* who, bool haveHits, uint64_t hitCap, uint64_t n, const ContextOut& o, bool ownList = false);
 // What a host-pointer call refuses of its list: hits[0, k) -- any alignment -- strictly ascending, every entry < n
 int ContextHitsInvalid(const char* who, const void* hits, uint64_t k, uint64_t n);
+// combine.hip: from up to six ascending hit lists and a truth table over their member masks to the ascending list of the
+// selected lines and the mask of each (pire_hip_combine).  Device pointers only -- the counts included, each nullable:
+// k_j = caps[j] --, three kernels enqueued on `stream`; scratch from the stream-ordered allocator: the compaction's and,
+// where outMembers is asked for, n bytes of member masks.  outHits == nullptr: the count only.  n == 0: the count zeroed on
+// the stream.  The arrays of CombineLists are the host's and travel to the kernels by value.
+struct CombineLists {
+	const uint64_t* lists[PIRE_HIP_COMBINE_MAX_LISTS];
+	const uint64_t* counts[PIRE_HIP_COMBINE_MAX_LISTS];
+	uint64_t caps[PIRE_HIP_COMBINE_MAX_LISTS];
+	uint32_t k;
+};
+int LaunchCombine(const CombineLists& in, uint64_t n, uint64_t truth, uint64_t* outHits, uint8_t* outMembers, uint64_t hitCap,
+                  uint64_t* outHitCount, hipStream_t stream);
+// The pass's own outputs, as the caller of an entry point gave them
+struct CombineOut {
+	uint64_t* outHits;
+	uint8_t* outMembers;
+	uint64_t hitCap;
+	uint64_t* outHitCount;
+};
+// What pire_hip_combine refuses of its outputs and of n before any device is touched, in `who`'s name (ownList: the entry
+// point keeps the list to itself where the caller has no array for it)
+int CombineOutputsInvalid(const char* who, uint64_t n, const CombineOut& o, bool ownList = false);
 // files.hip: from an ascending hit list and the files' line boundaries to hits by file (pire_hip_files).  Device pointers only
 // -- hitCount included, nullable: k = hitCap --, four or five kernels enqueued on `stream`; scratch from the stream-ordered
 // allocator: the compaction's over `files`, and the first row where outFileFirst is null.  outHits (nullable): the first
