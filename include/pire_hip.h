@@ -1147,6 +1147,89 @@ int pire_hip_capture_lines_gather(pire_hip_counting_table* t, const void* raw, u
                                   void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes,
                                   void* stream);
 
+/* ---- SlowCapturingScanner: exact and non-greedy captures ----------------------------------------------------------- */
+/*
+ * Pire::SlowCapturingScanner (pire/extra/capture.h:170-581): the NFA walk with priorities, the one scanner of the reference
+ * that tells .*?(re) from .*(re) and (A)|A from A|(A) -- the DFA behind pire_hip_capture_run records the first BeginCapture
+ * and EndCapture it meets.  Ingests SlowScanner::Save() bytes WITH the action area (scanner_io.cpp:71-110); the blob does not
+ * say whether it has one, so a blob that ends where a plain SlowScanner's does is PIRE_HIP_EFORMAT.  Header checks as
+ * pire_hip_slow_table_create.  Up to 1 024 states; a larger scanner is PIRE_HIP_EUNSUPPORTED at create.  An empty scanner
+ * loads, as it does there: one state with nowhere to go -- no string matches or captures.
+ * The table holds the flat form of the reference's walk, built on the host at create in O(states^2 *
+ * letters): for every (state, letter) the ordered list NextAndGetToGroups leaves, per state whether it matches at the end of
+ * the string, and what Initialize() leaves.  The library has no host walk: pire_hip_slow_capture_table_image exports that
+ * form, as pire_hip_table_layout does for the fast scanner's.
+ */
+typedef struct pire_hip_slow_capture_table pire_hip_slow_capture_table;
+
+typedef struct pire_hip_slow_capture_info {
+	uint32_t states;        /* SlowScanner::Size() */
+	uint32_t letters;       /* SlowScanner::GetLettersCount() */
+	uint32_t start;         /* m.start */
+	uint32_t entries;       /* of all lists together */
+	uint32_t longest_list;  /* entries of the longest list(state, letter) */
+	uint32_t init_len;      /* states Initialize() leaves on the list */
+	uint32_t init_matched;  /* 1 if Initialize() leaves a match */
+	uint32_t empty;         /* SlowScanner::Empty() */
+	uint32_t reserved[4];
+} pire_hip_slow_capture_info;
+
+int pire_hip_slow_capture_table_create(const void* save_blob, size_t len, pire_hip_slow_capture_table** out);
+void pire_hip_slow_capture_table_destroy(pire_hip_slow_capture_table* t);
+int pire_hip_slow_capture_table_get_info(const pire_hip_slow_capture_table* t, pire_hip_slow_capture_info* out);
+/*
+ * The table's image.  list_pos[states * letters + 1]: list(s, l) is entries[list_pos[s * letters + l] .. list_pos[s * letters
+ * + l + 1]).  entries[entries_cap] (entries_cap >= info.entries): bits 0-15 the target state, bit 16 the path from s to it
+ * carries a BeginCapture, bit 17 an EndCapture; the targets of one list are distinct.  state_flags[states]: bit 0 the state
+ * matches at the end of the string (Captured()'s `matched`), bit 1 Captured()'s return for that state without a begin.
+ * init[init_len][3]: (state, begin, end) of Initialize()'s list, positions 0 or -1 (not set); init_match[3]: the match it
+ * leaves where info.init_matched.  letters[260]: the letter of every Char (256 bytes, then Epsilon = 257, BeginMark = 258,
+ * EndMark = 259).  A step on a byte and GetCapture() over these arrays: DESIGN.md 4.23, restated in tests/test_slow_capture.py.
+ */
+int pire_hip_slow_capture_table_image(const pire_hip_slow_capture_table* t, uint32_t* list_pos, uint32_t* entries,
+                                      uint64_t entries_cap, uint8_t* state_flags, int64_t* init, int64_t* init_match,
+                                      uint8_t* letters);
+
+/*
+ * For each string: Initialize, Run, GetCapture (capture_ut.cpp:77-83, 259-272) -- the scanner takes the begin and end marks
+ * itself.  out_captured[i] = GetCapture()'s return.  out_begin[i] / out_end[i] = final.GetBegin() / GetEnd() where GetCapture
+ * assigned `final`, -1 for npos and where it assigned nothing: 0-based byte offsets into the string, the captured text is
+ * [begin, end).  out_matched (nullable): 1 where `final` was assigned (the string matched, captured or not).
+ * flags: PIRE_HIP_RUN_ON_DEVICE as pire_hip_slow_run (device pointers, the call only enqueues); every other flag but BEGIN /
+ * END is ignored, as there.  One wave per string: the ordered state list (state, begin, end) lives in LDS, 24 bytes per
+ * state and wave; the image stays in LDS up to 48 KB and in device memory beyond.
+ * PIRE_HIP_EINVAL before any device is touched: null table; PIRE_HIP_RUN_BEGIN or PIRE_HIP_RUN_END; n > 0 with null offsets,
+ * out_captured, out_begin or out_end; with host pointers what pire_hip_run refuses of a batch, and a string of 2^32 - 1 bytes
+ * or more (positions are 32 bits wide on the device; with ON_DEVICE this is the caller's precondition).  n == 0 and empty
+ * strings are legal.  pire_hip_last_kernel() names "slow_capture".  No first-use self-test, as pire_hip_slow_run.
+ */
+int pire_hip_slow_capture_run(pire_hip_slow_capture_table* t, const void* text, const uint64_t* offsets, uint64_t n,
+                              uint32_t flags, uint8_t* out_captured, int64_t* out_begin, int64_t* out_end,
+                              uint8_t* out_matched, void* stream);
+
+/*
+ * pire_hip_slow_capture_run followed by pire_hip_capture_select on the same stream: the pass gets no PIRE_HIP_RUN_BEGIN,
+ * final = the captured flags and need_final = 1, so hit k is a string that captured and its span is [offsets[i] + begin,
+ * offsets[i] + end), clamped as that pass clamps.  out_captured, out_begin, out_end and out_matched are all nullable here:
+ * what the pass needs and the caller has no array for lives in stream-ordered scratch.  out_hits, out_spans, hit_cap,
+ * out_hit_count: as pire_hip_capture_select.  It refuses what the run call refuses (the null result arrays excepted) and
+ * what pire_hip_capture_select refuses.
+ */
+int pire_hip_slow_capture_run_select(pire_hip_slow_capture_table* t, const void* text, const uint64_t* offsets, uint64_t n,
+                                     uint32_t flags, uint8_t* out_captured, int64_t* out_begin, int64_t* out_end,
+                                     uint8_t* out_matched, uint64_t* out_hits, uint64_t* out_spans, uint64_t hit_cap,
+                                     uint64_t* out_hit_count, void* stream);
+
+/*
+ * Raw bytes in, the captured field of every line that captured out -- `grep -o` with lazy quantifiers.  Arguments, nulls,
+ * refusals and the one synchronisation of `stream` as pire_hip_capture_lines_gather, which has need_final where this has
+ * none (a line is listed when GetCapture() returned true); flags: PIRE_HIP_RUN_ON_DEVICE only, BEGIN / END are refused.
+ */
+int pire_hip_slow_capture_lines_gather(pire_hip_slow_capture_table* t, const void* raw, uint64_t size, uint32_t delim,
+                                       uint32_t flags, uint32_t tail, uint64_t* out_line_count, uint64_t* out_hits,
+                                       uint64_t* out_spans, uint64_t hit_cap, uint64_t* out_hit_count, void* out_text,
+                                       uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes, void* stream);
+
 /* ---- the matched heads and tails, on the device ------------------------------------------------------------------ */
 
 #define PIRE_HIP_AFFIX_HEAD 0u   /* the matched prefix */

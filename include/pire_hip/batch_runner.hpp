@@ -1748,6 +1748,167 @@ private:
 	std::vector<uint64_t> m_hits, m_spans, m_capturedOffsets;
 	std::string m_capturedText;
 };
+
+/*
+ * Batched runs of a Pire::SlowCapturingScanner (extra/capture.h:170-581): Initialize, Run, GetCapture per string -- the
+ * scanner that tells .*?(re) from .*(re).  It takes the begin and end marks itself: there is no Begin() / End() here.
+ *     Pire::Hip::SlowCaptureBatchRunner run(sc);            // Save() -> pire_hip_slow_capture_table_create()
+ *     run.Run(text, offsets, n);   run.Run(strings);
+ *     run.Captured(i)   GetCapture()'s return        run.Matched(i)   whether it assigned `final`
+ *     run.Begin(i)  run.End(i)                       final.GetBegin() / GetEnd(): the captured text is string i [begin, end)
+ *     run.Select();     run.Hits()      the strings that captured, ascending        run.HitCount()
+ *                       run.HitSpans()  [2 * k], [2 * k + 1]: the capture of hit k as a byte range of the text (Run()) or of raw
+ *     run.RunLines(raw, size);          one raw buffer cut into lines on the device (pire_hip_slow_capture_lines_gather)
+ *     run.LineCount()   run.HitText()   the captured fields back to back, '\n' (or the byte given) behind each: `grep -o` with
+ *                       lazy quantifiers                 run.HitTextOffsets()  field k is HitText()[o[k], o[k + 1])
+ * The caller's arrays are read when an accessor first asks: they live until then.  What the library refuses comes back as
+ * Pire::Error.
+ */
+class SlowCaptureBatchRunner {
+public:
+	explicit SlowCaptureBatchRunner(const Pire::SlowCapturingScanner& sc)
+	    : m_table(nullptr), m_form(kNone), m_text(nullptr), m_offsets(nullptr), m_n(0), m_len(0), m_delim('\n'), m_ran(false),
+	      m_listed(false), m_haveText(false), m_textTail('\n'), m_hitCount(0), m_lineCount(0)
+	{
+		const std::string blob = SavedBlob(sc);
+		Check(pire_hip_slow_capture_table_create(blob.data(), blob.size(), &m_table));
+	}
+	~SlowCaptureBatchRunner() { pire_hip_slow_capture_table_destroy(m_table); }
+
+	SlowCaptureBatchRunner& Run(const char* text, const uint64_t* offsets, size_t n) { return SetBatch(kStrings, text, offsets, n, 0, '\n'); }
+	SlowCaptureBatchRunner& Run(const std::vector<ystring>& strings)
+	{
+		m_ownStrings.Assign(strings);
+		return Run(m_ownStrings.Text(), m_ownStrings.Offsets(), strings.size());
+	}
+	SlowCaptureBatchRunner& RunLines(const char* raw, size_t size, char delim = '\n') { return SetBatch(kLines, raw, nullptr, 0, size, delim); }
+	/* The list of the strings (lines) that captured: fetched with the first accessor that asks */
+	SlowCaptureBatchRunner& Select()
+	{
+		m_listed = m_haveText = false;
+		return *this;
+	}
+
+	bool Captured(size_t i) { Execute(); return m_captured[i] != 0; }
+	bool Matched(size_t i) { Execute(); return m_matched[i] != 0; }
+	size_t Begin(size_t i) { Execute(); return size_t(m_begin[i]); }      // (npos if unset)
+	size_t End(size_t i) { Execute(); return size_t(m_end[i]); }
+
+	uint64_t HitCount() { FetchHits(); return m_hitCount; }
+	const std::vector<uint64_t>& Hits() { FetchHits(); return m_hits; }
+	const std::vector<uint64_t>& HitSpans() { FetchHits(); return m_hitSpans; }
+	uint64_t LineCount() { NeedLines("LineCount()"); FetchHits(); return m_lineCount; }
+	const std::string& HitText(char tail = '\n') { FetchHitText(tail); return m_hitText; }
+	const std::vector<uint64_t>& HitTextOffsets()
+	{
+		if (!m_haveText)
+			FetchHitText('\n');
+		return m_hitTextOffsets;
+	}
+
+private:
+	SlowCaptureBatchRunner(const SlowCaptureBatchRunner&);
+	SlowCaptureBatchRunner& operator=(const SlowCaptureBatchRunner&);
+
+	enum Form { kNone, kStrings, kLines };
+	SlowCaptureBatchRunner& SetBatch(Form form, const char* text, const uint64_t* offsets, size_t n, size_t len, char delim)
+	{
+		m_form = form, m_text = text, m_offsets = offsets, m_n = n, m_len = len, m_delim = uint8_t(delim);
+		m_ran = m_listed = m_haveText = false;
+		return *this;
+	}
+	void NeedLines(const char* what) const
+	{
+		if (m_form != kLines)
+			throw Pire::Error(std::string("pire_hip: ") + what + " follows RunLines()");
+	}
+	void ResultsPerString()
+	{
+		m_captured.assign(m_n, 0);
+		m_matched.assign(m_n, 0);
+		m_begin.assign(m_n, -1);
+		m_end.assign(m_n, -1);
+	}
+	void Execute()
+	{
+		if (m_form != kStrings)
+			throw Pire::Error("pire_hip: the accessors per string follow Run()");
+		if (m_ran)
+			return;
+		ResultsPerString();
+		Check(pire_hip_slow_capture_run(m_table, m_text, OwnedStrings::OffsetsOr(m_offsets, m_n), m_n, 0, m_captured.data(), m_begin.data(),
+		                                m_end.data(), m_matched.data(), nullptr));
+		m_ran = true;
+	}
+	/* Run(): one call with room for every string, which leaves the answers per string as well.  RunLines(): room for a capture
+	 * on every line of 64 bytes or more, and a second call where there are more */
+	void FetchHits()
+	{
+		if (m_listed)
+			return;
+		if (m_form == kNone)
+			throw Pire::Error("pire_hip: Hits() follows Run() or RunLines()");
+		if (m_form == kStrings) {
+			ResultsPerString();
+			m_hits.resize(m_n);
+			m_hitSpans.resize(m_n * 2);
+			Check(pire_hip_slow_capture_run_select(m_table, m_text, OwnedStrings::OffsetsOr(m_offsets, m_n), m_n, 0, m_captured.data(),
+			                                       m_begin.data(), m_end.data(), m_matched.data(), m_hits.data(), m_hitSpans.data(), m_n,
+			                                       &m_hitCount, nullptr));
+			m_ran = true;
+		} else {
+			GrowAndRetry(m_len / 64 + 1024, [&](size_t cap) {
+				m_hits.resize(cap);
+				m_hitSpans.resize(cap * 2);
+				Check(pire_hip_slow_capture_lines_gather(m_table, m_text, m_len, m_delim, 0, PIRE_HIP_GATHER_NO_TAIL, &m_lineCount, m_hits.data(),
+				                                         m_hitSpans.data(), cap, &m_hitCount, nullptr, 0, nullptr, nullptr, nullptr));
+				return size_t(m_hitCount);
+			});
+		}
+		m_hits.resize(m_hitCount);
+		m_hitSpans.resize(m_hitCount * 2);
+		m_listed = true;
+	}
+	/* RunLines(): the captured fields as bytes (and the list with them) */
+	void FetchHitText(char tail)
+	{
+		NeedLines("HitText()");
+		if (m_haveText && m_textTail == tail)
+			return;
+		uint64_t bytes = 0;
+		GrowAndRetry(m_listed ? size_t(m_hitCount) : m_len / 64 + 1024, [&](size_t cap) {
+			m_hits.resize(cap);
+			m_hitSpans.resize(cap * 2);
+			m_hitTextOffsets.resize(cap + 1);
+			m_hitText.resize(m_len + cap + 1);
+			Check(pire_hip_slow_capture_lines_gather(m_table, m_text, m_len, m_delim, 0, uint8_t(tail), &m_lineCount, m_hits.data(),
+			                                         m_hitSpans.data(), cap, &m_hitCount, &m_hitText[0], m_hitText.size(),
+			                                         m_hitTextOffsets.data(), &bytes, nullptr));
+			return size_t(m_hitCount);   // (the bytes fit where the hits do, as in BatchRunner::FetchHitText())
+		});
+		m_hits.resize(m_hitCount);
+		m_hitSpans.resize(m_hitCount * 2);
+		m_hitText.resize(bytes);
+		m_hitTextOffsets.resize(m_hitCount + 1);
+		m_textTail = tail;
+		m_listed = m_haveText = true;
+	}
+
+	pire_hip_slow_capture_table* m_table;
+	Form m_form;
+	const char* m_text;           // Run(): the strings' text; RunLines(): the raw buffer of m_len bytes
+	const uint64_t* m_offsets;
+	size_t m_n, m_len;
+	uint8_t m_delim;
+	bool m_ran, m_listed, m_haveText;
+	char m_textTail;
+	OwnedStrings m_ownStrings;
+	uint64_t m_hitCount, m_lineCount;
+	std::vector<uint8_t> m_captured, m_matched;
+	std::vector<int64_t> m_begin, m_end;
+	std::vector<uint64_t> m_hits, m_hitSpans, m_hitTextOffsets;
+	std::string m_hitText;
+};
 #endif  // PIRE_EXTRA_CAPTURE_H
 
 /*

@@ -13,6 +13,7 @@ from .binding import (  # noqa: F401
     PireHipError,
     Table,
     SlowTable,
+    SlowCaptureTable,
     CountingTable,
     BatchRunner,
     MultiRunner,

@@ -73,6 +73,12 @@ class SlowInfo(C.Structure):
                 ("empty", C.c_uint32), ("reserved", C.c_uint32), ("mask_bytes", C.c_uint64)]
 
 
+class SlowCaptureInfo(C.Structure):
+    _fields_ = [("states", C.c_uint32), ("letters", C.c_uint32), ("start", C.c_uint32), ("entries", C.c_uint32),
+                ("longest_list", C.c_uint32), ("init_len", C.c_uint32), ("init_matched", C.c_uint32), ("empty", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
 def lib_path() -> str:
     return _LIB_PATH
 
@@ -255,6 +261,13 @@ ABI = [
     ("pire_hip_slow_run_select_strided", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_slow_lines_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_slow_lines_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_slow_capture_table_create", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    ("pire_hip_slow_capture_table_destroy", None, [C.c_void_p]),
+    ("pire_hip_slow_capture_table_get_info", C.c_int, [C.c_void_p, C.POINTER(SlowCaptureInfo)]),
+    ("pire_hip_slow_capture_table_image", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_slow_capture_run", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_slow_capture_run_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_slow_capture_lines_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_affix_select", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_affix_run_select", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_affix_lines_gather", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1885,6 +1898,133 @@ class SlowTable:
         _lines_files_device(lib().pire_hip_slow_lines_files_select, front, file_bytes_ptr, files, without, out_line_count_ptr, out_hits_ptr,
                             out_hit_spans_ptr, out_hit_file_ptr, out_hit_line_ptr, hit_cap, out_hit_count_ptr, out_file_lines_ptr,
                             out_file_first_ptr, out_files_ptr, file_cap, out_file_count_ptr, out_straddles_ptr, stream)
+
+
+class SlowCaptureTable:
+    """An ingested Pire::SlowCapturingScanner (from its Save() bytes, which carry the actions): exact captures, greedy and lazy."""
+
+    def __init__(self, blob: bytes):
+        L = lib()
+        h = C.c_void_p()
+        blob = bytes(blob)
+        _check(L.pire_hip_slow_capture_table_create(blob, len(blob), C.byref(h)))
+        self._h = h
+        self.info = SlowCaptureInfo()
+        _check(L.pire_hip_slow_capture_table_get_info(h, C.byref(self.info)))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _lib is not None:
+            try:
+                _lib.pire_hip_slow_capture_table_destroy(h)
+            except Exception:
+                pass
+            self._h = None
+
+    Size = property(lambda s: s.info.states)
+    LettersCount = property(lambda s: s.info.letters)
+    Empty = property(lambda s: bool(s.info.empty))
+
+    def image(self) -> dict:
+        """pire_hip_slow_capture_table_image: {"list_pos", "entries", "state_flags", "init" [init_len][3], "init_match" (or None),
+        "letters" [260]} -- the flat form of the reference's walk."""
+        i = self.info
+        pos = np.zeros(i.states * i.letters + 1, dtype=np.uint32)
+        entries = np.zeros(max(i.entries, 1), dtype=np.uint32)
+        flags = np.zeros(i.states, dtype=np.uint8)
+        init = np.zeros((max(i.init_len, 1), 3), dtype=np.int64)
+        match = np.zeros(3, dtype=np.int64)
+        letters = np.zeros(260, dtype=np.uint8)
+        _check(lib().pire_hip_slow_capture_table_image(self._h, pos.ctypes.data, entries.ctypes.data, entries.size, flags.ctypes.data,
+                                                       init.ctypes.data, match.ctypes.data, letters.ctypes.data))
+        return {"list_pos": pos, "entries": entries[:i.entries], "state_flags": flags, "init": init[:i.init_len],
+                "init_match": match if i.init_matched else None, "letters": letters}
+
+    def run(self, text, offsets, flags=0):
+        """pire_hip_slow_capture_run on host strings: (captured, begin, end, matched)"""
+        text = _raw_bytes(text)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        cap, mat = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        b, e = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        _check(lib().pire_hip_slow_capture_run(self._h, text.ctypes.data if text.size else None, offsets.ctypes.data, n,
+                                               flags & ~FLAG_ON_DEVICE, cap.ctypes.data, b.ctypes.data, e.ctypes.data, mat.ctypes.data, None))
+        return cap, b, e, mat
+
+    def run_strings(self, strings, **kw):
+        offs = np.zeros(len(strings) + 1, dtype=np.uint64)
+        if strings:
+            offs[1:] = np.cumsum([len(s) for s in strings], dtype=np.uint64)
+        return self.run(np.frombuffer(b"".join(strings), dtype=np.uint8), offs, **kw)
+
+    def run_device(self, text_ptr, offsets_ptr, n, out_captured_ptr, out_begin_ptr, out_end_ptr, out_matched_ptr=0, flags=0, stream=0):
+        """pire_hip_slow_capture_run with every pointer on the device (offsets: n + 1 uint64): only enqueues on `stream`."""
+        _check(lib().pire_hip_slow_capture_run(self._h, text_ptr or None, offsets_ptr or None, n, flags | FLAG_ON_DEVICE,
+                                               out_captured_ptr or None, out_begin_ptr or None, out_end_ptr or None,
+                                               out_matched_ptr or None, stream or None))
+
+    def run_select(self, text, offsets, hit_cap: Optional[int] = None, positions=True, lists=True, flags=0):
+        """pire_hip_slow_capture_run_select on host strings: {"hits", "spans", "count"} and, with positions, {"captured", "begin",
+        "end", "matched"}; without, the library keeps those arrays to itself.  hit_cap None = room for every string."""
+        text = _raw_bytes(text)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        cap = (n if hit_cap is None else int(hit_cap)) if lists else 0
+        c, m = (np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)) if positions else (None, None)
+        b, e = (np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)) if positions else (None, None)
+        hits = np.zeros(cap, dtype=np.uint64)
+        spans = np.zeros((cap, 2), dtype=np.uint64)
+        cnt = C.c_uint64(0)
+        _check(lib().pire_hip_slow_capture_run_select(self._h, text.ctypes.data if text.size else None, offsets.ctypes.data, n,
+                                                      flags & ~FLAG_ON_DEVICE, _np_ptr(c), _np_ptr(b), _np_ptr(e), _np_ptr(m),
+                                                      hits.ctypes.data if cap else None, spans.ctypes.data if cap else None, cap,
+                                                      C.byref(cnt), None))
+        k = min(int(cnt.value), cap)
+        out = {"hits": hits[:k], "spans": spans[:k], "count": int(cnt.value)}
+        if positions:
+            out.update(captured=c, begin=b, end=e, matched=m)
+        return out
+
+    def run_select_device(self, text_ptr: int, offsets_ptr: int, n: int, out_hit_count_ptr: int, out_captured_ptr=0, out_begin_ptr=0,
+                          out_end_ptr=0, out_matched_ptr=0, out_hits_ptr=0, out_spans_ptr=0, hit_cap=0, flags=0, stream: int = 0):
+        """pire_hip_slow_capture_run_select on device pointers: only enqueues on `stream`."""
+        _check(lib().pire_hip_slow_capture_run_select(self._h, text_ptr or None, offsets_ptr or None, n, flags | FLAG_ON_DEVICE,
+                                                      out_captured_ptr or None, out_begin_ptr or None, out_end_ptr or None,
+                                                      out_matched_ptr or None, out_hits_ptr or None, out_spans_ptr or None, hit_cap,
+                                                      out_hit_count_ptr or None, stream or None))
+
+    def lines_gather_host(self, raw, delim: int = 10, tail=-1, hit_cap=None, text_cap=None, gather=True, flags=0):
+        """pire_hip_slow_capture_lines_gather on a host buffer: {"lines", "hits", "spans", "count"} and, with gather, {"text",
+        "offsets", "bytes"}.  tail -1 = the delimiter, None = none; hit_cap None = room for a hit on every line, text_cap None
+        = for all of them."""
+        raw = _raw_bytes(raw)
+        cap = raw.size if hit_cap is None else int(hit_cap)
+        room = (raw.size + cap if text_cap is None else int(text_cap)) if gather else 0
+        hits = np.zeros(cap, dtype=np.uint64)
+        spans = np.zeros((cap, 2), dtype=np.uint64)
+        text = np.zeros(max(room, 1), dtype=np.uint8)
+        offsets = np.zeros(cap + 1, dtype=np.uint64)
+        lines, cnt, total = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().pire_hip_slow_capture_lines_gather(self._h, raw.ctypes.data if raw.size else None, raw.size, delim,
+                                                        flags & ~FLAG_ON_DEVICE, _tail(delim if tail == -1 else tail), C.byref(lines),
+                                                        hits.ctypes.data if cap else None, spans.ctypes.data if cap else None, cap,
+                                                        C.byref(cnt), text.ctypes.data if room else None, room,
+                                                        offsets.ctypes.data if gather else None, C.byref(total) if gather else None, None))
+        k = min(int(cnt.value), cap)
+        out = {"lines": int(lines.value), "hits": hits[:k], "spans": spans[:k], "count": int(cnt.value)}
+        if gather:
+            out.update(text=text[:min(int(total.value), room)], offsets=offsets[:k + 1], bytes=int(total.value))
+        return out
+
+    def lines_gather_device(self, raw_ptr: int, size: int, out_line_count_ptr: int, out_hit_count_ptr: int, out_bytes_ptr=0,
+                            delim: int = 10, tail=-1, out_hits_ptr=0, out_spans_ptr=0, hit_cap=0, out_text_ptr=0, text_cap=0,
+                            out_offsets_ptr=0, flags=0, stream: int = 0):
+        """pire_hip_slow_capture_lines_gather on device pointers (synchronises `stream` once, as Table.run_lines_select_device does)."""
+        _check(lib().pire_hip_slow_capture_lines_gather(self._h, raw_ptr or None, size, delim, flags | FLAG_ON_DEVICE,
+                                                        _tail(delim if tail == -1 else tail), out_line_count_ptr or None,
+                                                        out_hits_ptr or None, out_spans_ptr or None, hit_cap, out_hit_count_ptr or None,
+                                                        out_text_ptr or None, text_cap, out_offsets_ptr or None, out_bytes_ptr or None,
+                                                        stream or None))
 
 
 class CountingTable:

@@ -2551,6 +2551,63 @@ try {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
 
+// ---- the same two forms around a SlowCapturingScanner (slow_capture.hip): the pass reads the captured flags as Final ------
+int pire_hip_slow_capture_run_select(pire_hip_slow_capture_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
+                                     uint8_t* out_captured, int64_t* out_begin, int64_t* out_end, uint8_t* out_matched, uint64_t* out_hits,
+                                     uint64_t* out_spans, uint64_t hit_cap, uint64_t* out_hit_count, void* stream)
+try {
+	const char* who = "pire_hip_slow_capture_run_select";
+	if (int rc = CaptureSelectOutputsInvalid(who, n, 1, true, out_hits || out_spans, hit_cap, out_hit_count))
+		return rc;
+	const CaptureSelectOut sel = {1, 0, out_hits, out_spans, hit_cap, out_hit_count};
+	return SlowCaptureRunImpl(who, t, text, offsets, n, flags, out_captured, out_begin, out_end, out_matched, &sel, static_cast<hipStream_t>(stream));
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_slow_capture_lines_gather(pire_hip_slow_capture_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
+                                       uint32_t tail, uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_spans, uint64_t hit_cap,
+                                       uint64_t* out_hit_count, void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes,
+                                       void* streamPtr)
+try {
+	const char* who = "pire_hip_slow_capture_lines_gather";
+	if (!t)
+		return GatherRefuse(who, "null table");
+	if (flags & (PIRE_HIP_RUN_BEGIN | PIRE_HIP_RUN_END))
+		return GatherRefuse(who, "PIRE_HIP_RUN_BEGIN / PIRE_HIP_RUN_END: the scanner takes both marks itself");
+	if (int rc = SplitArgsInvalid(who, raw, size, delim, out_line_count, "out_line_count"))
+		return rc;
+	const bool gathers = out_text || text_cap || out_offsets || out_bytes;
+	if (int rc = CaptureSelectOutputsInvalid(who, 0, 1, true, out_hits || out_spans || gathers, hit_cap, out_hit_count))
+		return rc;
+	if (gathers) {
+		if (int rc = GatherOutputsInvalid(who, "hit_cap", hit_cap, tail, out_text, text_cap, out_offsets, out_bytes))
+			return rc;
+		if (int rc = GatherOverlaps(who, raw, size, out_text, text_cap))
+			return rc;
+	}
+	const LinesGather gather = {tail, out_text, text_cap, out_offsets, out_bytes, false, "hipMallocAsync(capture spans)"};
+	LinesFrame f(who, raw, size, delim, flags, gathers ? &gather : nullptr, streamPtr);
+	if (f.HostEdge(out_line_count)) {
+		*out_hit_count = 0;
+		return PIRE_HIP_OK;
+	}
+	if (int rc = f.Open())
+		return rc;
+	if (int rc = f.Split(out_line_count, out_hit_count, 1, hit_cap, true))
+		return rc;
+	if (int rc = f.Lists(out_hits, out_spans))
+		return rc;
+	// (no lines: the pass itself zeroes the count.  A line is a string of fewer than 2^32 - 1 bytes where the buffer is: the
+	// split refuses 2^32 lines, not long ones -- a longer line is the precondition of the device form of the run call.)
+	const CaptureSelectOut sel = {1, 1, f.dHits, f.dSpans, f.cap, f.dCounts};
+	if (int rc = SlowCaptureRunImpl(who, t, f.Text(), f.Offsets(), f.n, f.RunFlags(), nullptr, nullptr, nullptr, nullptr, &sel, f.stream))
+		return rc;
+	return f.Close("hipMemcpy(captures)");
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
 // ---- first-use self-tests of the entry points with actions (selftest.h) -------------------------------------------------
 namespace {
 

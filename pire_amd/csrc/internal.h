@@ -1142,6 +1142,11 @@ struct CaptureSelectOut {
 int CaptureRunImpl(pire_hip_counting_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
                    uint32_t* outIdx, uint8_t* outFinal, int64_t* outBegin, int64_t* outEnd, const CaptureSelectOut* sel,
                    hipStream_t stream);
+// slow_capture.hip: pire_hip_slow_capture_run, and behind it -- where sel is not null -- the same pass with final = the captured
+// flags; the result arrays may then be null.  `who` names the entry point in what is refused.
+int SlowCaptureRunImpl(const char* who, pire_hip_slow_capture_table* t, const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
+                       uint8_t* outCaptured, int64_t* outBegin, int64_t* outEnd, uint8_t* outMatched, const CaptureSelectOut* sel,
+                       hipStream_t stream);
 // slow_hits.hip: from Final flags to a compacted, ascending list of the strings whose flag is set -- or, with
 // PIRE_HIP_FINAL_SELECT_ZERO, of those whose flag is not (pire_hip_final_select).  Device pointers only, three kernels enqueued
 // on `stream`, the compaction's scratch from the stream-ordered allocator.  n == 0: the count zeroed on the stream.
