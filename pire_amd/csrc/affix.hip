@@ -13,109 +13,67 @@
 //   scatter   rank of a selected string = tile offset + the popcounts of the waves in front + mbcnt of its own wave's
 //             ballot word; the lane computes its span from offsets and lengths, clamped into the string.
 //
-// The classify tail, the scatter head and the launcher's front are the select pass's (compact.h TileBallot / TileRank,
-// select.hip TileCompaction); this unit keeps its predicate and what a selected lane writes.  Three launches on the caller's
-// stream, the shape of select.hip: no block waits for another block, no atomics (the same input gives the same bits).
+// Both kernels and the launcher are tile_pass.h's, the staging of the count and the lists is internal.h's HitStage; this
+// unit keeps its predicate and what a selected lane writes (AffixPass).  Three launches on the caller's stream, the shape
+// of select.hip: no block waits for another block, no atomics (the same input gives the same bits).
 // Plain HIP with compiler-placed waits: nothing here keeps data on its way in registers.
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "compact.h"
-#include "internal.h"
+#include "tile_pass.h"
 
 namespace pirehip {
 
 namespace {
 
-constexpr uint32_t kAffixThreads = kBlockThreads;   // one tile = 1 024 strings = 16 ballot words
-constexpr uint32_t kAffixWaves = kBlockWaves;
-constexpr uint32_t kAffixMaxBlocks = 8192;
-
-struct AffixSelectParams {
+struct AffixPass {
 	const uint64_t* offsets;
 	const long long* headLen;   // nullable: no head was looked for
 	const long long* tailLen;   // nullable: no tail was looked for
-	uint64_t n;
 	uint32_t part;              // PIRE_HIP_AFFIX_HEAD / _TAIL / _REST
 	uint64_t shift;             // string i lies shift * i bytes further into the buffer of the spans
 	uint64_t* outHits;          // nullable
 	uint64_t* outSpans;         // nullable
-	uint64_t hitCap;
-	uint64_t* ballots;          // [tiles * 16] selected bits, one word per wave
-	uint32_t* tileCounts;       // [tiles] selected strings per tile; after the scan: selected strings in front of the tile
-	uint32_t tiles;
-};
 
-__global__ __launch_bounds__(kAffixThreads) void AffixClassifyKernel(AffixSelectParams p)
-{
-	__shared__ uint32_t waveCount[kAffixWaves];
-	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
-		const uint64_t i = uint64_t(tile) * kAffixThreads + threadIdx.x;
-		bool sel = false;
-		if (i < p.n)
-			sel = (!p.headLen || p.headLen[i] >= 0) && (!p.tailLen || p.tailLen[i] >= 0);
-		TileBallot(sel, tile, p.ballots, p.tileCounts, waveCount);
-	}
-}
-
-__global__ __launch_bounds__(kAffixThreads) void AffixScatterKernel(AffixSelectParams p)
-{
-	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
-		bool selected;
-		const uint64_t rank = TileRank(tile, p.ballots, p.tileCounts, &selected);
-		if (selected && rank < p.hitCap) {   // (a selected bit: i < n, and the lengths that are given are >= 0)
-			const uint64_t i = uint64_t(tile) * kAffixThreads + threadIdx.x;
-			if (p.outHits)
-				p.outHits[rank] = i;
-			if (p.outSpans) {
-				const uint64_t o0 = p.offsets[i], o1 = p.offsets[i + 1];
-				const uint64_t len = o1 >= o0 ? o1 - o0 : 0;   // (offsets that decrease: an empty string)
-				const uint64_t h = p.headLen ? std::min<uint64_t>(uint64_t(p.headLen[i]), len) : 0;
-				const uint64_t base = o0 + p.shift * i;
-				uint64_t b, e;
-				if (p.part == PIRE_HIP_AFFIX_HEAD) {
-					b = 0, e = h;
-				} else if (p.part == PIRE_HIP_AFFIX_TAIL) {
-					b = len - std::min<uint64_t>(uint64_t(p.tailLen[i]), len), e = len;
-				} else {   // REST: the tail gives way to the head where they overlap
-					b = h, e = len - (p.tailLen ? std::min<uint64_t>(uint64_t(p.tailLen[i]), len - h) : 0);
-				}
-				p.outSpans[2 * rank] = base + b;
-				p.outSpans[2 * rank + 1] = base + e;
+	__device__ __forceinline__ bool Selected(uint64_t i) const { return (!headLen || headLen[i] >= 0) && (!tailLen || tailLen[i] >= 0); }
+	// (a selected bit: the lengths that are given are >= 0)
+	__device__ __forceinline__ void Write(uint64_t rank, uint64_t i) const
+	{
+		if (outHits)
+			outHits[rank] = i;
+		if (outSpans) {
+			const uint64_t o0 = offsets[i], o1 = offsets[i + 1];
+			const uint64_t len = o1 >= o0 ? o1 - o0 : 0;   // (offsets that decrease: an empty string)
+			const uint64_t h = headLen ? std::min<uint64_t>(uint64_t(headLen[i]), len) : 0;
+			const uint64_t base = o0 + shift * i;
+			uint64_t b, e;
+			if (part == PIRE_HIP_AFFIX_HEAD) {
+				b = 0, e = h;
+			} else if (part == PIRE_HIP_AFFIX_TAIL) {
+				b = len - std::min<uint64_t>(uint64_t(tailLen[i]), len), e = len;
+			} else {   // REST: the tail gives way to the head where they overlap
+				b = h, e = len - (tailLen ? std::min<uint64_t>(uint64_t(tailLen[i]), len - h) : 0);
 			}
+			outSpans[2 * rank] = base + b;
+			outSpans[2 * rank + 1] = base + e;
 		}
 	}
-}
+};
 
 }  // namespace
 
 int LaunchAffixSelect(const uint64_t* offsets, uint64_t n, uint32_t part, const long long* headLen, const long long* tailLen,
                       uint64_t shift, uint64_t* outHits, uint64_t* outSpans, uint64_t hitCap, uint64_t* outHitCount, hipStream_t stream)
 {
-	AffixSelectParams p;
-	StreamScratch scratch(stream);
-	const int rc = TileCompaction("pire_hip_affix_select", "hipMallocAsync(affix select scratch)", n, outHitCount, stream, scratch, &p.tiles,
-	                              &p.ballots, &p.tileCounts);
-	if (rc || !p.tiles)
+	TilePass t(stream);
+	const int rc = t.Front("pire_hip_affix_select", "hipMallocAsync(affix select scratch)", n, outHitCount);
+	if (rc || !t.s.tiles)
 		return rc;
-	p.offsets = offsets;
-	p.headLen = headLen;
-	p.tailLen = tailLen;
-	p.n = n;
-	p.part = part;
-	p.shift = shift;
-	p.outHits = outHits;
-	p.outSpans = outSpans;
-	p.hitCap = outHits || outSpans ? hitCap : 0;
-	const dim3 grid(std::min(p.tiles, kAffixMaxBlocks));
-	hipLaunchKernelGGL(AffixClassifyKernel, grid, dim3(kAffixThreads), 0, stream, p);
-	LaunchTileScan(p.tileCounts, 1, p.tiles, outHitCount, stream);
-	if (p.hitCap)
-		hipLaunchKernelGGL(AffixScatterKernel, grid, dim3(kAffixThreads), 0, stream, p);
-	const hipError_t e = hipGetLastError();
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "affix select launch");
+	const AffixPass p = {offsets, headLen, tailLen, part, shift, outHits, outSpans};
+	t.Classify(p, n);
+	return t.Tail(p, outHits || outSpans ? hitCap : 0, outHitCount, "affix select launch");
 }
 
 int AffixSelectArgsInvalid(const char* who, uint64_t n, bool haveOffsets, bool haveHead, bool haveTail, const AffixSelectOut& o, bool ownList)
@@ -137,7 +95,7 @@ int AffixSelectArgsInvalid(const char* who, uint64_t n, bool haveOffsets, bool h
 
 int AffixSelectStage::Empty(hipStream_t stream)
 {
-	if (onDevice)
+	if (list.onDevice)
 		return LaunchAffixSelect(nullptr, 0, o.part, nullptr, nullptr, 0, nullptr, nullptr, 0, o.outHitCount, stream);
 	*o.outHitCount = 0;
 	return PIRE_HIP_OK;
@@ -145,36 +103,16 @@ int AffixSelectStage::Empty(hipStream_t stream)
 
 int AffixSelectStage::Results(BatchIO& io, uint64_t n)
 {
-	cap = onDevice ? o.hitCap : std::min<uint64_t>(o.hitCap, n);   // n strings have at most n hits: a host call stages no more
-	if (int rc = io.Result(onDevice ? o.outHitCount : &count, 1, 1, &dCount))   // (host pointers: the count comes back here first)
+	int rc;
+	if ((rc = list.Count(io, o.hitCap, n)) || (rc = list.List(io, o.outHits, 1, &dHits)))
 		return rc;
-	if (o.outHits && cap)
-		if (int rc = io.Result(o.outHits, size_t(cap), 0, &dHits))
-			return rc;
-	if (o.outSpans && cap)
-		if (int rc = io.Result(o.outSpans, size_t(cap) * 2, 0, &dSpans))
-			return rc;
-	return PIRE_HIP_OK;
+	return list.List(io, o.outSpans, 2, &dSpans);
 }
 
 int AffixSelectStage::Launch(const uint64_t* offsets, uint64_t n, const int64_t* headLen, const int64_t* tailLen, hipStream_t stream)
 {
 	return LaunchAffixSelect(offsets, n, o.part, reinterpret_cast<const long long*>(headLen), reinterpret_cast<const long long*>(tailLen), 0,
-	                         dHits, dSpans, cap, dCount, stream);
-}
-
-int AffixSelectStage::Back()
-{
-	if (onDevice)
-		return PIRE_HIP_OK;
-	*o.outHitCount = count;
-	const uint64_t written = std::min<uint64_t>(count, cap);
-	hipError_t e = hipSuccess;
-	if (written && dHits)
-		e = hipMemcpy(o.outHits, dHits, size_t(written) * 8, hipMemcpyDeviceToHost);
-	if (e == hipSuccess && written && dSpans)
-		e = hipMemcpy(o.outSpans, dSpans, size_t(written) * 16, hipMemcpyDeviceToHost);
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(hits)");
+	                         dHits, dSpans, list.cap, list.dCount, stream);
 }
 
 }  // namespace pirehip

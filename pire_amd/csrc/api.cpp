@@ -1607,14 +1607,14 @@ int SelectImageFor(const char* who, pire_hip_table* t, const uint32_t* stateIdx,
 }
 
 // Host pointers: the lists of a pass come back only as far as they were written -- row r of dev[rows][staged] (entries of
-// `width` words) into row r of out[rows][pitch], its first min(counts[r], staged) entries.  dev == nullptr: nothing.
-int HitsBack(uint32_t rows, const uint64_t* counts, uint64_t staged, uint64_t pitch, const uint64_t* dev, uint64_t* out, size_t width,
-             const char* what)
+// `width` bytes) into row r of out[rows][pitch], its first min(counts[r], staged) entries.  dev == nullptr: nothing.  (The
+// row-pitch form of HitStage::Back, for the lists that a LinesFrame stages and the rows of a route.)
+int HitsBack(uint32_t rows, const uint64_t* counts, uint64_t staged, uint64_t pitch, const void* dev, void* out, size_t width, const char* what)
 {
 	for (uint32_t r = 0; r < rows && dev; ++r)
 		if (const uint64_t written = std::min(counts[r], staged)) {
-			const hipError_t e = hipMemcpy(out + uint64_t(r) * pitch * width, dev + uint64_t(r) * staged * width, size_t(written) * width * 8,
-			                               hipMemcpyDeviceToHost);
+			const hipError_t e = hipMemcpy(static_cast<uint8_t*>(out) + uint64_t(r) * pitch * width,
+			                               static_cast<const uint8_t*>(dev) + uint64_t(r) * staged * width, size_t(written) * width, hipMemcpyDeviceToHost);
 			if (e != hipSuccess)
 				return HipFail(e, what);
 		}
@@ -1665,9 +1665,9 @@ int SelectImpl(pire_hip_table* t, const uint32_t* stateIdx, uint64_t n, const ui
 		return rc;
 	if (onDevice)
 		return PIRE_HIP_OK;
-	if (int rc = HitsBack(1, outHitCount, cap, cap, dHits, outHits, 1, "hipMemcpy(hits)"))
+	if (int rc = HitsBack(1, outHitCount, cap, cap, dHits, outHits, 8, "hipMemcpy(hits)"))
 		return rc;
-	return HitsBack(1, outHitCount, cap, cap, dHits ? dHitMasks : nullptr, outHitMasks, words, "hipMemcpy(hits)");
+	return HitsBack(1, outHitCount, cap, cap, dHits ? dHitMasks : nullptr, outHitMasks, size_t(words) * 8, "hipMemcpy(hits)");
 }
 
 // pire_hip_run[_strided] followed by a pass over its state indices on the same stream: the one owner of the state-index
@@ -1765,7 +1765,7 @@ int RouteImpl(pire_hip_table* t, const uint32_t* stateIdx, uint64_t n, uint32_t 
 	if (int rc = io.Finish())
 		return rc;
 	// (the caller's pitch stays hitCap)
-	return onDevice ? PIRE_HIP_OK : HitsBack(regexps, outHitCounts, cap, hitCap, dHits, outHits, 1, "hipMemcpy(route hits)");
+	return onDevice ? PIRE_HIP_OK : HitsBack(regexps, outHitCounts, cap, hitCap, dHits, outHits, 8, "hipMemcpy(route hits)");
 }
 
 int RunRouteImpl(const char* who, pire_hip_table* t, uint64_t n, uint32_t flags, uint32_t* outIdx, uint64_t* outHits, uint64_t hitCap,
@@ -2186,9 +2186,9 @@ struct LinesFrame {
 			return PIRE_HIP_OK;
 		*outLineCount = n;
 		// (the caller's pitch stays hit_cap where the staged rows are cap long)
-		if (int rc = HitsBack(rows, outCounts, cap, hitCap, outHits ? dHits : nullptr, outHits, 1, backLabel))
+		if (int rc = HitsBack(rows, outCounts, cap, hitCap, outHits ? dHits : nullptr, outHits, 8, backLabel))
 			return rc;
-		if (int rc = HitsBack(rows, outCounts, cap, hitCap, outSpans ? dSpans : nullptr, outSpans, 2, backLabel))
+		if (int rc = HitsBack(rows, outCounts, cap, hitCap, outSpans ? dSpans : nullptr, outSpans, 16, backLabel))
 			return rc;
 		if (!gather)
 			return PIRE_HIP_OK;
@@ -2266,7 +2266,7 @@ int RunLinesImpl(pire_hip_table* t, const void* raw, uint64_t size, uint32_t del
 	}
 	if (int rc = f.Close("hipMemcpy(hits)"))
 		return rc;
-	return f.onDevice ? PIRE_HIP_OK : HitsBack(1, out_hit_count, f.cap, f.cap, dHitMasks, out_hit_masks, words, "hipMemcpy(hits)");
+	return f.onDevice ? PIRE_HIP_OK : HitsBack(1, out_hit_count, f.cap, f.cap, dHitMasks, out_hit_masks, size_t(words) * 8, "hipMemcpy(hits)");
 }
 
 // Both gather entry points behind their checks.  spans == nullptr: text + offsets[n + 1] + idx; else raw = text, `size` bytes.
@@ -3023,11 +3023,7 @@ int CountLinesImpl(const char* who, uint32_t regexps, const void* raw, uint64_t 
 			return rc;
 	if (int rc = f.Close("hipMemcpy(hits)"))
 		return rc;
-	if (f.onDevice || !dHitResults)
-		return PIRE_HIP_OK;
-	const uint64_t written = std::min(*o.outHitCount, f.cap);
-	const hipError_t e = written ? hipMemcpy(o.outHitResults, dHitResults, size_t(written) * regexps * 4, hipMemcpyDeviceToHost) : hipSuccess;
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(hits)");
+	return f.onDevice ? PIRE_HIP_OK : HitsBack(1, o.outHitCount, f.cap, f.cap, dHitResults, o.outHitResults, size_t(regexps) * 4, "hipMemcpy(hits)");
 }
 
 }  // namespace
@@ -3238,11 +3234,7 @@ int ContextLinesImpl(const char* who, const char* refused, const void* raw, uint
 	}
 	if (int rc = f.Close("hipMemcpy(context lines)"))
 		return rc;
-	if (f.onDevice)
-		return PIRE_HIP_OK;
-	const uint64_t written = std::min(*c.outSelCount, f.cap);
-	const hipError_t e = written && dFlags ? hipMemcpy(c.outFlags, dFlags, size_t(written), hipMemcpyDeviceToHost) : hipSuccess;
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(context lines)");
+	return f.onDevice ? PIRE_HIP_OK : HitsBack(1, c.outSelCount, f.cap, f.cap, dFlags, c.outFlags, 1, "hipMemcpy(context lines)");
 }
 
 int RunLinesContextImpl(const char* who, pire_hip_table* t, const void* raw, uint64_t size, uint32_t delim, uint32_t flags, const uint64_t* want,
@@ -3440,11 +3432,11 @@ int FilesLinesImpl(const char* who, const char* refused, const void* raw, uint64
 		return rc;
 	if (f.onDevice)
 		return PIRE_HIP_OK;
-	if (int rc = HitsBack(1, c.outHitCount, f.cap, f.cap, dHitFile, c.outHitFile, 1, "hipMemcpy(hit files)"))
+	if (int rc = HitsBack(1, c.outHitCount, f.cap, f.cap, dHitFile, c.outHitFile, 8, "hipMemcpy(hit files)"))
 		return rc;
-	if (int rc = HitsBack(1, c.outHitCount, f.cap, f.cap, dHitLine, c.outHitLine, 1, "hipMemcpy(hit files)"))
+	if (int rc = HitsBack(1, c.outHitCount, f.cap, f.cap, dHitLine, c.outHitLine, 8, "hipMemcpy(hit files)"))
 		return rc;
-	return HitsBack(1, c.outFileCount, listCap, listCap, dFiles, c.outFiles, 1, "hipMemcpy(files)");
+	return HitsBack(1, c.outFileCount, listCap, listCap, dFiles, c.outFiles, 8, "hipMemcpy(files)");
 }
 
 }  // namespace
@@ -3626,11 +3618,7 @@ int CombineLinesImpl(const char* who, const pire_hip_line_term* terms, uint32_t 
 	}
 	if (int rc = f.Close("hipMemcpy(combined hits)"))
 		return rc;
-	if (f.onDevice)
-		return PIRE_HIP_OK;
-	const uint64_t written = std::min(*c.outHitCount, f.cap);
-	const hipError_t e = written && dMembers ? hipMemcpy(c.outMembers, dMembers, size_t(written), hipMemcpyDeviceToHost) : hipSuccess;
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(combined hits)");
+	return f.onDevice ? PIRE_HIP_OK : HitsBack(1, c.outHitCount, f.cap, f.cap, dMembers, c.outMembers, 1, "hipMemcpy(combined hits)");
 }
 
 }  // namespace
@@ -3971,7 +3959,7 @@ try {
 		return rc;
 	if (int rc = io.Ready())
 		return rc;
-	if (int rc = AffixEnqueue(scans, tabs, dText, dOffsets, n, flags, dHeadLen, dTailLen, part, 0, pass.dHits, pass.dSpans, pass.cap, pass.dCount,
+	if (int rc = AffixEnqueue(scans, tabs, dText, dOffsets, n, flags, dHeadLen, dTailLen, part, 0, pass.dHits, pass.dSpans, pass.list.cap, pass.list.dCount,
 	                          stream))
 		return rc;
 	if (int rc = io.Finish())

@@ -11,77 +11,50 @@
 //   scatter   rank of a selected string = tile offset + the popcounts of the waves in front + mbcnt of its own wave's
 //             ballot word; the lane computes its span again from offsets and positions, clamped into the string.
 //
-// The classify tail, the scatter head and the launcher's front are the select pass's too (compact.h TileBallot / TileRank,
-// select.hip TileCompaction).  Three launches on the caller's stream, the shape of select.hip: no block waits for another
-// block, no atomics (the same input gives the same bits).  Plain HIP with compiler-placed waits: nothing here keeps data on
-// its way in registers.
+// Both kernels and the launcher are tile_pass.h's, the staging of the count and the lists is internal.h's HitStage; this
+// unit keeps its predicate and what a selected lane writes (CapturePass).  Three launches on the caller's stream, the shape
+// of select.hip: no block waits for another block, no atomics (the same input gives the same bits).  Plain HIP with
+// compiler-placed waits: nothing here keeps data on its way in registers.
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "compact.h"
-#include "internal.h"
+#include "tile_pass.h"
 
 namespace pirehip {
 
 namespace {
 
-constexpr uint32_t kCapThreads = kBlockThreads;   // one tile = 1 024 strings = 16 ballot words
-constexpr uint32_t kCapWaves = kBlockWaves;
-constexpr uint32_t kCapMaxBlocks = 8192;
-
-struct CaptureSelectParams {
+struct CapturePass {
 	const uint64_t* offsets;
 	const long long* begin;
 	const long long* end;
 	const uint8_t* fin;      // nullable: Final is not asked for
-	uint64_t n;
 	long long beginMark;     // B: 1 where the BeginMark step was counted
 	uint64_t shift;          // string i lies shift * i bytes further into the buffer of the spans
 	uint64_t* outHits;       // nullable
 	uint64_t* outSpans;      // nullable
-	uint64_t hitCap;
-	uint64_t* ballots;       // [tiles * 16] selected bits, one word per wave
-	uint32_t* tileCounts;    // [tiles] selected strings per tile; after the scan: selected strings in front of the tile
-	uint32_t tiles;
-};
 
-__global__ __launch_bounds__(kCapThreads) void CaptureClassifyKernel(CaptureSelectParams p)
-{
-	__shared__ uint32_t waveCount[kCapWaves];
-	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
-		const uint64_t i = uint64_t(tile) * kCapThreads + threadIdx.x;
-		bool sel = false;
-		if (i < p.n)
-			sel = p.begin[i] >= 0 && p.end[i] >= 0 && (!p.fin || p.fin[i] != 0);
-		TileBallot(sel, tile, p.ballots, p.tileCounts, waveCount);
-	}
-}
-
-__global__ __launch_bounds__(kCapThreads) void CaptureScatterKernel(CaptureSelectParams p)
-{
-	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
-		bool selected;
-		const uint64_t rank = TileRank(tile, p.ballots, p.tileCounts, &selected);
-		if (selected && rank < p.hitCap) {   // (a selected bit: i < n, begin >= 0 and end >= 0)
-			const uint64_t i = uint64_t(tile) * kCapThreads + threadIdx.x;
-			if (p.outHits)
-				p.outHits[rank] = i;
-			if (p.outSpans) {
-				const uint64_t o0 = p.offsets[i], o1 = p.offsets[i + 1];
-				const uint64_t len = o1 >= o0 ? o1 - o0 : 0;   // (offsets that decrease: an empty string)
-				// begin >= 0 and B <= 1: the differences cannot wrap
-				const long long bb = p.begin[i] - p.beginMark, ee = p.end[i] - p.beginMark;
-				const uint64_t b = bb < 0 ? 0 : std::min<uint64_t>(uint64_t(bb), len);
-				const uint64_t e = ee < 0 ? b : std::min<uint64_t>(std::max<uint64_t>(uint64_t(ee), b), len);
-				const uint64_t base = o0 + p.shift * i;
-				p.outSpans[2 * rank] = base + b;
-				p.outSpans[2 * rank + 1] = base + e;
-			}
+	__device__ __forceinline__ bool Selected(uint64_t i) const { return begin[i] >= 0 && end[i] >= 0 && (!fin || fin[i] != 0); }
+	// (a selected bit: begin >= 0 and end >= 0)
+	__device__ __forceinline__ void Write(uint64_t rank, uint64_t i) const
+	{
+		if (outHits)
+			outHits[rank] = i;
+		if (outSpans) {
+			const uint64_t o0 = offsets[i], o1 = offsets[i + 1];
+			const uint64_t len = o1 >= o0 ? o1 - o0 : 0;   // (offsets that decrease: an empty string)
+			// begin >= 0 and B <= 1: the differences cannot wrap
+			const long long bb = begin[i] - beginMark, ee = end[i] - beginMark;
+			const uint64_t b = bb < 0 ? 0 : std::min<uint64_t>(uint64_t(bb), len);
+			const uint64_t e = ee < 0 ? b : std::min<uint64_t>(std::max<uint64_t>(uint64_t(ee), b), len);
+			const uint64_t base = o0 + shift * i;
+			outSpans[2 * rank] = base + b;
+			outSpans[2 * rank + 1] = base + e;
 		}
 	}
-}
+};
 
 }  // namespace
 
@@ -89,29 +62,13 @@ int LaunchCaptureSelect(const uint64_t* offsets, uint64_t n, bool beginMark, con
                         const uint8_t* fin, uint64_t shift, uint64_t* outHits, uint64_t* outSpans, uint64_t hitCap,
                         uint64_t* outHitCount, hipStream_t stream)
 {
-	CaptureSelectParams p;
-	StreamScratch scratch(stream);
-	const int rc = TileCompaction("pire_hip_capture_select", "hipMallocAsync(capture select scratch)", n, outHitCount, stream, scratch,
-	                              &p.tiles, &p.ballots, &p.tileCounts);
-	if (rc || !p.tiles)
+	TilePass t(stream);
+	const int rc = t.Front("pire_hip_capture_select", "hipMallocAsync(capture select scratch)", n, outHitCount);
+	if (rc || !t.s.tiles)
 		return rc;
-	p.offsets = offsets;
-	p.begin = begin;
-	p.end = end;
-	p.fin = fin;
-	p.n = n;
-	p.beginMark = beginMark ? 1 : 0;
-	p.shift = shift;
-	p.outHits = outHits;
-	p.outSpans = outSpans;
-	p.hitCap = outHits || outSpans ? hitCap : 0;
-	const dim3 grid(std::min(p.tiles, kCapMaxBlocks));
-	hipLaunchKernelGGL(CaptureClassifyKernel, grid, dim3(kCapThreads), 0, stream, p);
-	LaunchTileScan(p.tileCounts, 1, p.tiles, outHitCount, stream);
-	if (p.hitCap)
-		hipLaunchKernelGGL(CaptureScatterKernel, grid, dim3(kCapThreads), 0, stream, p);
-	const hipError_t e = hipGetLastError();
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "capture select launch");
+	const CapturePass p = {offsets, begin, end, fin, beginMark ? 1 : 0, shift, outHits, outSpans};
+	t.Classify(p, n);
+	return t.Tail(p, outHits || outSpans ? hitCap : 0, outHitCount, "capture select launch");
 }
 
 int CaptureSelectOutputsInvalid(const char* who, uint64_t n, int needFinal, bool haveFinal, bool haveList, uint64_t hitCap,
@@ -168,32 +125,17 @@ try {
 	if (fin)
 		if ((rc = io.In(fin, size_t(n), &dFin)))
 			return rc;
-	const uint64_t cap = std::min<uint64_t>(hit_cap, n);   // n strings have at most n hits: a host call stages no more
-	uint64_t count = 0;   // the count comes back here first
-	uint64_t *dCount = nullptr, *dHits = nullptr, *dSpans = nullptr;
-	if ((rc = io.Result(&count, 1, 1, &dCount)))
-		return rc;
-	if (out_hits && cap)
-		if ((rc = io.Result(out_hits, size_t(cap), 0, &dHits)))
-			return rc;
-	if (out_spans && cap)
-		if ((rc = io.Result(out_spans, size_t(cap) * 2, 0, &dSpans)))
-			return rc;
-	if ((rc = io.Ready()))
+	HitStage list(false, out_hit_count, "hipMemcpy(hits)");
+	uint64_t *dHits = nullptr, *dSpans = nullptr;
+	if ((rc = list.Count(io, hit_cap, n)) || (rc = list.List(io, out_hits, 1, &dHits)) || (rc = list.List(io, out_spans, 2, &dSpans)) ||
+	    (rc = io.Ready()))
 		return rc;
 	if ((rc = LaunchCaptureSelect(dOffsets, n, beginMark, reinterpret_cast<const long long*>(dBegin), reinterpret_cast<const long long*>(dEnd),
-	                              dFin, 0, dHits, dSpans, cap, dCount, stream)))
+	                              dFin, 0, dHits, dSpans, list.cap, list.dCount, stream)))
 		return rc;
 	if ((rc = io.Finish()))
 		return rc;
-	*out_hit_count = count;
-	const uint64_t written = std::min<uint64_t>(count, cap);
-	hipError_t e = hipSuccess;
-	if (written && dHits)
-		e = hipMemcpy(out_hits, dHits, size_t(written) * 8, hipMemcpyDeviceToHost);
-	if (e == hipSuccess && written && dSpans)
-		e = hipMemcpy(out_spans, dSpans, size_t(written) * 16, hipMemcpyDeviceToHost);
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(hits)");
+	return list.Back();
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }

@@ -19,10 +19,10 @@
 // Scratch, stream-ordered: n / 8 + n / 256 bytes of ballot words and tile counts, and n bytes of member masks where
 // out_hit_members is asked for.
 //
-// The classify tail, the scatter head and the launcher's front are the select pass's (compact.h TileBallot / TileRank,
-// select.hip TileCompaction).  The wave-wide lower bound and the packed entry type are copies of context.hip's: that unit
-// and files.hip stay as they are.  Launches on the caller's stream: no block waits for another block,
-// no atomics (the same input gives the same bytes).  Plain HIP with compiler-placed waits.  Lists may have any alignment.
+// The scatter kernel and the launcher are tile_pass.h's, the wave-wide search and the load of a list entry compact.h's
+// (WaveBound, LoadU64), the staging of the count and the lists internal.h's HitStage; this unit keeps its classify kernel
+// -- it ends in compact.h's TileBallot -- and what a selected lane writes (CombinePass).  Launches on the caller's stream:
+// no block waits for another block, no atomics (the same input gives the same bytes).  Plain HIP with compiler-placed waits.  Lists may have any alignment.
 // A list that is not ascending or names lines >= n gives an unspecified selection and nothing worse: every index into a
 // list is clamped into [0, k_j), every index into the tile's bytes is checked against the tile.
 
@@ -30,24 +30,16 @@
 
 #include <algorithm>
 
-#include "compact.h"
-#include "internal.h"
+#include "tile_pass.h"
 
 namespace pirehip {
 
 namespace {
 
-constexpr uint32_t kCmbThreads = kBlockThreads;   // one tile = 1 024 lines = 16 ballot words
-constexpr uint32_t kCmbWaves = kBlockWaves;
-constexpr uint32_t kCmbMaxBlocks = 8192;
 constexpr uint32_t kCmbLists = PIRE_HIP_COMBINE_MAX_LISTS;
-static_assert(2 * kCmbLists <= kCmbWaves, "one wave per bound of every list");
+static_assert(2 * kCmbLists <= kBlockWaves, "one wave per bound of every list");
 
-struct __attribute__((packed, aligned(1))) UnalignedU64 {
-	uint64_t v;
-};
-
-struct CombineParams {
+struct CombinePass {
 	const uint64_t* lists[kCmbLists];    // any alignment
 	const uint64_t* counts[kCmbLists];   // nullable: k_j = caps[j]
 	uint64_t caps[kCmbLists];
@@ -56,49 +48,31 @@ struct CombineParams {
 	uint64_t truth;
 	uint64_t* outHits;       // nullable
 	uint8_t* outMembers;     // nullable
-	uint64_t hitCap;
-	uint64_t* ballots;       // [tiles * 16] selected bits, one word per wave
-	uint32_t* tileCounts;    // [tiles] selected lines per tile; after the scan: selected lines in front of the tile
 	uint8_t* members;        // [tiles * 1024] member masks, or null
-	uint32_t tiles;
+
+	__device__ __forceinline__ void Write(uint64_t rank, uint64_t i) const
+	{
+		outHits[rank] = i;
+		if (outMembers)
+			outMembers[rank] = members[i];
+	}
 };
 
-__device__ __forceinline__ uint64_t EntryAt(const uint64_t* list, uint64_t j)
+__global__ __launch_bounds__(kBlockThreads) void CombineClassifyKernel(CombinePass p, TileScratch t)
 {
-	return reinterpret_cast<const UnalignedU64*>(list)[j].v;
-}
-
-// How many of list[0, k) are < x (the list ascends), found by one wave: 64 probes a step, every probe inside [0, k)
-__device__ __forceinline__ uint64_t WaveLowerBound(const uint64_t* list, uint64_t k, uint64_t x)
-{
-	const uint32_t lane = threadIdx.x & 63;
-	uint64_t lo = 0, hi = k;   // the answer is in [lo, hi]
-	while (hi > lo) {
-		const uint64_t step = (hi - lo + 63) / 64;
-		const uint64_t q = lo + (lane + 1) * step - 1;
-		const bool lt = q < hi && EntryAt(list, q) < x;   // true in the first c lanes, false behind them
-		const uint64_t c = uint64_t(__popcll(__ballot(lt)));
-		hi = std::min(hi, lo + (c + 1) * step - 1);
-		lo = std::min(lo + c * step, hi);   // (the min: a list that does not ascend)
-	}
-	return lo;
-}
-
-__global__ __launch_bounds__(kCmbThreads) void CombineClassifyKernel(CombineParams p)
-{
-	__shared__ uint32_t waveCount[kCmbWaves];
+	__shared__ uint32_t waveCount[kBlockWaves];
 	__shared__ uint64_t slice[2 * kCmbLists];
-	__shared__ uint8_t mark[kCmbThreads];
+	__shared__ uint8_t mark[kBlockThreads];
 	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
-		const uint64_t t0 = uint64_t(tile) * kCmbThreads, t1 = std::min(t0 + kCmbThreads, p.n);
+	for (uint32_t tile = blockIdx.x; tile < t.tiles; tile += gridDim.x) {
+		const uint64_t t0 = uint64_t(tile) * kBlockThreads, t1 = std::min(t0 + kBlockThreads, p.n);
 		const uint64_t i = t0 + threadIdx.x;
 		// the slices of the lists inside the tile: wave 2j finds where list j's begins, wave 2j + 1 where it ends
 #pragma unroll
 		for (uint32_t j = 0; j < kCmbLists; ++j)
 			if (j < p.kLists && (wave >> 1) == j) {
 				const uint64_t k = std::min(p.counts[j] ? *p.counts[j] : p.caps[j], p.caps[j]);
-				const uint64_t at = WaveLowerBound(p.lists[j], k, wave & 1 ? t1 : t0);
+				const uint64_t at = WaveBound<false>(p.lists[j], k, wave & 1 ? t1 : t0);
 				if (lane == 0)
 					slice[wave] = at;
 			}
@@ -110,7 +84,7 @@ __global__ __launch_bounds__(kCmbThreads) void CombineClassifyKernel(CombinePara
 			if (j < p.kLists) {
 				const uint64_t lo = slice[2 * j], hi = std::max(slice[2 * j + 1], lo);
 				if (threadIdx.x < hi - lo) {
-					const uint64_t h = EntryAt(p.lists[j], lo + threadIdx.x);
+					const uint64_t h = LoadU64(p.lists[j], lo + threadIdx.x);
 					if (h >= t0 && h < t1)
 						mark[h - t0] |= uint8_t(1u << j);
 				}
@@ -119,21 +93,8 @@ __global__ __launch_bounds__(kCmbThreads) void CombineClassifyKernel(CombinePara
 		const uint32_t m = mark[threadIdx.x];
 		const bool sel = i < p.n && ((p.truth >> m) & 1);
 		if (p.members)
-			p.members[size_t(tile) * kCmbThreads + threadIdx.x] = uint8_t(m);
-		TileBallot(sel, tile, p.ballots, p.tileCounts, waveCount);   // (two barriers: slice and mark are free again)
-	}
-}
-
-__global__ __launch_bounds__(kCmbThreads) void CombineScatterKernel(CombineParams p)
-{
-	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
-		bool selected;
-		const uint64_t rank = TileRank(tile, p.ballots, p.tileCounts, &selected);
-		if (selected && rank < p.hitCap) {   // (a selected bit: i < n)
-			p.outHits[rank] = uint64_t(tile) * kCmbThreads + threadIdx.x;
-			if (p.outMembers)
-				p.outMembers[rank] = p.members[size_t(tile) * kCmbThreads + threadIdx.x];
-		}
+			p.members[size_t(tile) * kBlockThreads + threadIdx.x] = uint8_t(m);
+		TileBallot(sel, tile, t.ballots, t.tileCounts, waveCount);   // (two barriers: slice and mark are free again)
 	}
 }
 
@@ -142,18 +103,18 @@ __global__ __launch_bounds__(kCmbThreads) void CombineScatterKernel(CombineParam
 int LaunchCombine(const CombineLists& in, uint64_t n, uint64_t truth, uint64_t* outHits, uint8_t* outMembers, uint64_t hitCap,
                   uint64_t* outHitCount, hipStream_t stream)
 {
-	CombineParams p;
-	StreamScratch scratch(stream), members(stream);
-	const int rc = TileCompaction("pire_hip_combine", "hipMallocAsync(combine scratch)", n, outHitCount, stream, scratch, &p.tiles, &p.ballots,
-	                              &p.tileCounts);
-	if (rc || !p.tiles)
+	TilePass t(stream);
+	StreamScratch members(stream);
+	const int rc = t.Front("pire_hip_combine", "hipMallocAsync(combine scratch)", n, outHitCount);
+	if (rc || !t.s.tiles)
 		return rc;
+	CombinePass p;
+	const uint64_t cap = outHits ? hitCap : 0;
 	p.outHits = outHits;
 	p.outMembers = outHits ? outMembers : nullptr;
-	p.hitCap = outHits ? hitCap : 0;
 	p.members = nullptr;
-	if (p.outMembers && p.hitCap) {   // n bytes of member masks, rounded up to whole tiles
-		if (int rc2 = members.Alloc(size_t(p.tiles) * kCmbThreads, "hipMallocAsync(combine members)"))
+	if (p.outMembers && cap) {   // n bytes of member masks, rounded up to whole tiles
+		if (int rc2 = members.Alloc(size_t(t.s.tiles) * kBlockThreads, "hipMallocAsync(combine members)"))
 			return rc2;
 		p.members = members.as<uint8_t>();
 	}
@@ -166,13 +127,8 @@ int LaunchCombine(const CombineLists& in, uint64_t n, uint64_t truth, uint64_t* 
 	p.kLists = in.k;
 	p.n = n;
 	p.truth = truth;
-	const dim3 grid(std::min(p.tiles, kCmbMaxBlocks));
-	hipLaunchKernelGGL(CombineClassifyKernel, grid, dim3(kCmbThreads), 0, stream, p);
-	LaunchTileScan(p.tileCounts, 1, p.tiles, outHitCount, stream);
-	if (p.hitCap)
-		hipLaunchKernelGGL(CombineScatterKernel, grid, dim3(kCmbThreads), 0, stream, p);
-	const hipError_t e = hipGetLastError();
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "combine launch");
+	hipLaunchKernelGGL(CombineClassifyKernel, t.Grid(), dim3(kBlockThreads), 0, stream, p, t.s);
+	return t.Tail(p, cap, outHitCount, "combine launch");
 }
 
 int CombineOutputsInvalid(const char* who, uint64_t n, const CombineOut& o, bool ownList)
@@ -251,10 +207,9 @@ try {
 		return PIRE_HIP_OK;
 	}
 	BatchIO io(stream, false);
-	uint64_t count = 0;   // the count comes back here first
-	uint64_t *dCount = nullptr, *dHits = nullptr;
+	HitStage list(false, out_hit_count, "hipMemcpy(combined hits)");   // n lines: no list is staged longer
+	uint64_t* dHits = nullptr;
 	uint8_t* dMembers = nullptr;
-	const uint64_t cap = std::min(hit_cap, n);   // n lines: no list is staged longer
 	int rc;
 	for (uint32_t j = 0; j < k_lists; ++j) {
 		const uint8_t* d = nullptr;
@@ -264,28 +219,14 @@ try {
 		in.counts[j] = nullptr;
 		in.caps[j] = k[j];
 	}
-	if ((rc = io.Result(&count, 1, 1, &dCount)))
+	if ((rc = list.Count(io, hit_cap, n)) || (rc = list.List(io, out_hits, 1, &dHits)) || (rc = list.List(io, out_hit_members, 1, &dMembers)) ||
+	    (rc = io.Ready()))
 		return rc;
-	if (out_hits && cap)
-		if ((rc = io.Result(out_hits, size_t(cap), 0, &dHits)))
-			return rc;
-	if (out_hit_members && cap)
-		if ((rc = io.Result(out_hit_members, size_t(cap), 0, &dMembers)))
-			return rc;
-	if ((rc = io.Ready()))
-		return rc;
-	if ((rc = LaunchCombine(in, n, truth, dHits, dMembers, dHits ? cap : 0, dCount, stream)))
+	if ((rc = LaunchCombine(in, n, truth, dHits, dMembers, dHits ? list.cap : 0, list.dCount, stream)))
 		return rc;
 	if ((rc = io.Finish()))
 		return rc;
-	*out_hit_count = count;
-	const uint64_t written = std::min(count, cap);
-	hipError_t e = hipSuccess;
-	if (written && dHits)
-		e = hipMemcpy(out_hits, dHits, size_t(written) * 8, hipMemcpyDeviceToHost);
-	if (e == hipSuccess && written && dMembers)
-		e = hipMemcpy(out_hit_members, dMembers, size_t(written), hipMemcpyDeviceToHost);
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(combined hits)");
+	return list.Back();
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }

@@ -1,7 +1,8 @@
-// The pieces the hit passes share on the device (select.hip, capture_select.hip, route.hip, split.hip, gather.hip,
+// The pieces the hit passes share on the device (the eight ballot compactions, route.hip, split.hip, gather.hip,
 // fields.hip): the prefix sum over a block of 1 024 threads, the ballot compaction of a tile of 1 024 strings, the 16-byte
-// lane load of the byte-rate passes and the wave-wide search in an offsets array.  Device only, force-inlined into the
-// kernels that use them; DESIGN.md section 4.15 says who owns what.
+// lane load of the byte-rate passes, the wave-wide searches in an offsets array and in a hit list, and the load of a list
+// entry of any alignment.  Device only, force-inlined into the kernels that use them; tile_pass.h builds the kernel pair and
+// the launcher of the ballot compactions on them; DESIGN.md section 4.15 says who owns what.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -14,6 +15,14 @@ namespace pirehip {
 
 constexpr uint32_t kBlockThreads = 1024;   // every kernel that uses these pieces is launched with this many threads ...
 constexpr uint32_t kBlockWaves = kBlockThreads / 64;   // ... one tile of the compaction = 1 024 strings = 16 ballot words
+constexpr uint32_t kTileMaxBlocks = 8192;  // the grid of a kernel that walks tiles: no larger, tiles in a grid-stride loop
+
+// The scratch of one ballot compaction (select.hip TileCompaction carves it out of one allocation)
+struct TileScratch {
+	uint64_t* ballots;      // [tiles * 16] selected bits, one word per wave
+	uint32_t* tileCounts;   // [tiles] selected strings per tile; after the scan: selected strings in front of the tile
+	uint32_t tiles;
+};
 
 __device__ __forceinline__ uint32_t ShuffleUp(uint32_t v, uint32_t d) { return uint32_t(__shfl_up(int(v), int(d), 64)); }
 __device__ __forceinline__ uint64_t ShuffleUp(uint64_t v, uint32_t d) { return __shfl_up(static_cast<unsigned long long>(v), d, 64); }
@@ -130,6 +139,34 @@ __device__ __forceinline__ uint64_t WaveOwner(const uint64_t* off, uint64_t k, u
 		const uint64_t c = uint64_t(__popcll(__ballot(le)));
 		hi = std::min(hi, lo + (c + 1) * step);
 		lo += c * step;
+	}
+	return lo;
+}
+
+// Entry j of a hit list: `list` may have any alignment, the entry is read through a packed type
+struct __attribute__((packed, aligned(1))) UnalignedU64 {
+	uint64_t v;
+};
+
+__device__ __forceinline__ uint64_t LoadU64(const uint64_t* list, uint64_t j)
+{
+	return reinterpret_cast<const UnalignedU64*>(list)[j].v;
+}
+
+// How many of a[0, m) are < x -- kInclusive: <= x -- (the array does not decrease; any alignment), found by one wave: 64
+// probes a step, every probe inside [0, m)
+template <bool kInclusive>
+__device__ __forceinline__ uint64_t WaveBound(const uint64_t* a, uint64_t m, uint64_t x)
+{
+	const uint32_t lane = threadIdx.x & 63;
+	uint64_t lo = 0, hi = m;   // the answer is in [lo, hi]
+	while (hi > lo) {
+		const uint64_t step = (hi - lo + 63) / 64;
+		const uint64_t q = lo + (lane + 1) * step - 1;
+		const bool in = q < hi && (kInclusive ? LoadU64(a, q) <= x : LoadU64(a, q) < x);   // true in the first c lanes, false behind them
+		const uint64_t c = uint64_t(__popcll(__ballot(in)));
+		hi = std::min(hi, lo + (c + 1) * step - 1);
+		lo = std::min(lo + c * step, hi);   // (the min: an array that decreases)
 	}
 	return lo;
 }

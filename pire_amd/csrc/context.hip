@@ -19,33 +19,24 @@
 //   scatter   rank of a selected line = tile offset + the popcounts of the waves in front + mbcnt of its own wave's ballot
 //             word; the lane writes its index and its flag byte.
 //
-// The classify tail, the scatter head and the launcher's front are the select pass's (compact.h TileBallot / TileRank,
-// select.hip TileCompaction); this unit keeps its predicate and what a selected lane writes.  Launches on the caller's
-// stream: no block waits for another block, no atomics (the same input gives the same bits).  Plain HIP with
-// compiler-placed waits: nothing here keeps data on its way in registers.  `hits` may have any alignment: an entry is read
-// through a packed type.  A list that is not ascending or names lines >= n gives an unspecified selection and nothing worse:
+// The scatter kernel and the launcher are tile_pass.h's, the wave-wide search and the load of a list entry compact.h's
+// (WaveBound, LoadU64), the staging of the count and the lists internal.h's HitStage; this unit keeps its classify kernel --
+// it ends in compact.h's TileBallot -- and what a selected lane writes (ContextPass).  Launches on the caller's stream: no
+// block waits for another block, no atomics (the same input gives the same bits).  Plain HIP with compiler-placed waits:
+// nothing here keeps data on its way in registers.  `hits` may have any alignment: an entry is read through a packed type.  A list that is not ascending or names lines >= n gives an unspecified selection and nothing worse:
 // every index into `hits` is clamped into [0, k), every index into the tile's bytes is checked against the tile.
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "compact.h"
-#include "internal.h"
+#include "tile_pass.h"
 
 namespace pirehip {
 
 namespace {
 
-constexpr uint32_t kCtxThreads = kBlockThreads;   // one tile = 1 024 lines = 16 ballot words
-constexpr uint32_t kCtxWaves = kBlockWaves;
-constexpr uint32_t kCtxMaxBlocks = 8192;
-
-struct __attribute__((packed, aligned(1))) UnalignedU64 {
-	uint64_t v;
-};
-
-struct ContextParams {
+struct ContextPass {
 	const uint64_t* hits;       // [k], any alignment
 	const uint64_t* hitCount;   // nullable: k = hitCap
 	uint64_t hitCap;
@@ -53,51 +44,36 @@ struct ContextParams {
 	uint64_t before, after;
 	uint64_t* outLines;         // nullable
 	uint8_t* outFlags;          // nullable
-	uint64_t lineCap;
-	uint64_t* ballots;          // [tiles * 16] selected bits, one word per wave
-	uint32_t* tileCounts;       // [tiles] selected lines per tile; after the scan: selected lines in front of the tile
 	uint64_t* marks;            // [tiles * 16][2] hit bits and run bits of the wave
 	uint32_t* groupCounts;      // [tiles] runs that begin in the tile
-	uint32_t tiles;
+
+	__device__ __forceinline__ void Write(uint64_t rank, uint64_t i) const
+	{
+		outLines[rank] = i;
+		if (outFlags) {
+			const uint32_t lane = threadIdx.x & 63;
+			const uint64_t* m = marks + (i >> 6) * 2;   // (line i: wave i / 64 of the batch)
+			outFlags[rank] = uint8_t(((m[0] >> lane) & 1 ? PIRE_HIP_CONTEXT_HIT : 0) | ((m[1] >> lane) & 1 ? PIRE_HIP_CONTEXT_GROUP : 0));
+		}
+	}
 };
 
-__device__ __forceinline__ uint64_t HitAt(const uint64_t* hits, uint64_t j)
+__global__ __launch_bounds__(kBlockThreads) void ContextClassifyKernel(ContextPass p, TileScratch t)
 {
-	return reinterpret_cast<const UnalignedU64*>(hits)[j].v;
-}
-
-// How many of hits[0, k) are < x (the list ascends), found by one wave: 64 probes a step, every probe inside [0, k)
-__device__ __forceinline__ uint64_t WaveLowerBound(const uint64_t* hits, uint64_t k, uint64_t x)
-{
-	const uint32_t lane = threadIdx.x & 63;
-	uint64_t lo = 0, hi = k;   // the answer is in [lo, hi]
-	while (hi > lo) {
-		const uint64_t step = (hi - lo + 63) / 64;
-		const uint64_t q = lo + (lane + 1) * step - 1;
-		const bool lt = q < hi && HitAt(hits, q) < x;   // true in the first c lanes, false behind them
-		const uint64_t c = uint64_t(__popcll(__ballot(lt)));
-		hi = std::min(hi, lo + (c + 1) * step - 1);
-		lo = std::min(lo + c * step, hi);   // (the min: a list that does not ascend)
-	}
-	return lo;
-}
-
-__global__ __launch_bounds__(kCtxThreads) void ContextClassifyKernel(ContextParams p)
-{
-	__shared__ uint32_t waveCount[kCtxWaves];
-	__shared__ uint32_t groupWave[kCtxWaves];
-	__shared__ uint64_t hitWords[kCtxWaves];
-	__shared__ uint64_t selWords[kCtxWaves];
+	__shared__ uint32_t waveCount[kBlockWaves];
+	__shared__ uint32_t groupWave[kBlockWaves];
+	__shared__ uint64_t hitWords[kBlockWaves];
+	__shared__ uint64_t selWords[kBlockWaves];
 	__shared__ uint64_t slice[2];
-	__shared__ uint8_t mark[kCtxThreads];
+	__shared__ uint8_t mark[kBlockThreads];
 	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	const uint64_t k = std::min(p.hitCount ? *p.hitCount : p.hitCap, p.hitCap);
-	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
-		const uint64_t t0 = uint64_t(tile) * kCtxThreads, t1 = std::min(t0 + kCtxThreads, p.n);
+	for (uint32_t tile = blockIdx.x; tile < t.tiles; tile += gridDim.x) {
+		const uint64_t t0 = uint64_t(tile) * kBlockThreads, t1 = std::min(t0 + kBlockThreads, p.n);
 		const uint64_t i = t0 + threadIdx.x;
 		// the slice of the list inside the tile: hits[lo, hi)
 		if (wave < 2) {
-			const uint64_t at = WaveLowerBound(p.hits, k, wave ? t1 : t0);
+			const uint64_t at = WaveBound<false>(p.hits, k, wave ? t1 : t0);
 			if (lane == 0)
 				slice[wave] = at;
 		}
@@ -105,7 +81,7 @@ __global__ __launch_bounds__(kCtxThreads) void ContextClassifyKernel(ContextPara
 		__syncthreads();
 		const uint64_t lo = slice[0], hi = std::max(slice[1], lo);
 		if (threadIdx.x < hi - lo) {
-			const uint64_t h = HitAt(p.hits, lo + threadIdx.x);
+			const uint64_t h = LoadU64(p.hits, lo + threadIdx.x);
 			if (h >= t0 && h < t1)
 				mark[h - t0] = 1;
 		}
@@ -116,9 +92,9 @@ __global__ __launch_bounds__(kCtxThreads) void ContextClassifyKernel(ContextPara
 			hitWords[wave] = hitBallot;
 		// the one entry outside the slice on either side, and the first entry not in front of the tile
 		const bool havePrev = lo > 0, haveNext = hi < k, haveFirst = lo < k;
-		const uint64_t prev = havePrev ? HitAt(p.hits, lo - 1) : 0;
-		const uint64_t next = haveNext ? HitAt(p.hits, hi) : 0;
-		const uint64_t first = haveFirst ? HitAt(p.hits, lo) : 0;
+		const uint64_t prev = havePrev ? LoadU64(p.hits, lo - 1) : 0;
+		const uint64_t next = haveNext ? LoadU64(p.hits, hi) : 0;
+		const uint64_t first = haveFirst ? LoadU64(p.hits, lo) : 0;
 		__syncthreads();
 		// the nearest hit at or before the line, the nearest at or after it
 		bool havePred = false, haveSucc = false;
@@ -137,7 +113,7 @@ __global__ __launch_bounds__(kCtxThreads) void ContextClassifyKernel(ContextPara
 		{
 			uint64_t w = hitBallot & (~0ull << lane);
 			uint32_t at = wave;
-			for (uint32_t v = wave + 1; v < kCtxWaves && !w; ++v)
+			for (uint32_t v = wave + 1; v < kBlockWaves && !w; ++v)
 				if (hitWords[v])
 					w = hitWords[v], at = v;
 			if (w)
@@ -161,32 +137,16 @@ __global__ __launch_bounds__(kCtxThreads) void ContextClassifyKernel(ContextPara
 		const uint64_t groupBallot = __ballot(sel && !front);
 		if (lane == 0) {
 			groupWave[wave] = uint32_t(__popcll(groupBallot));
-			uint64_t* m = p.marks + (size_t(tile) * kCtxWaves + wave) * 2;
+			uint64_t* m = p.marks + (size_t(tile) * kBlockWaves + wave) * 2;
 			m[0] = hitBallot;
 			m[1] = groupBallot;
 		}
-		TileBallot(sel, tile, p.ballots, p.tileCounts, waveCount);   // (two barriers: groupWave is whole)
+		TileBallot(sel, tile, t.ballots, t.tileCounts, waveCount);   // (two barriers: groupWave is whole)
 		if (threadIdx.x == 0) {
 			uint32_t sum = 0;
-			for (uint32_t w = 0; w < kCtxWaves; ++w)
+			for (uint32_t w = 0; w < kBlockWaves; ++w)
 				sum += groupWave[w];
 			p.groupCounts[tile] = sum;
-		}
-	}
-}
-
-__global__ __launch_bounds__(kCtxThreads) void ContextScatterKernel(ContextParams p)
-{
-	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
-		bool selected;
-		const uint64_t rank = TileRank(tile, p.ballots, p.tileCounts, &selected);
-		if (selected && rank < p.lineCap) {   // (a selected bit: i < n)
-			p.outLines[rank] = uint64_t(tile) * kCtxThreads + threadIdx.x;
-			if (p.outFlags) {
-				const uint64_t* m = p.marks + (size_t(tile) * kCtxWaves + wave) * 2;
-				p.outFlags[rank] = uint8_t(((m[0] >> lane) & 1 ? PIRE_HIP_CONTEXT_HIT : 0) | ((m[1] >> lane) & 1 ? PIRE_HIP_CONTEXT_GROUP : 0));
-			}
 		}
 	}
 }
@@ -207,15 +167,15 @@ int LaunchContext(const uint64_t* hits, const uint64_t* hitCount, uint64_t hitCa
 {
 	if (n == 0 || hitCap == 0)
 		return ZeroCounts(outLineCount, outGroupCount, stream);
-	ContextParams p;
-	StreamScratch scratch(stream), marks(stream);
-	const int rc = TileCompaction("pire_hip_context", "hipMallocAsync(context scratch)", n, outLineCount, stream, scratch, &p.tiles, &p.ballots,
-	                              &p.tileCounts);
-	if (rc || !p.tiles)
+	TilePass t(stream);
+	StreamScratch marks(stream);
+	const int rc = t.Front("pire_hip_context", "hipMallocAsync(context scratch)", n, outLineCount);
+	if (rc || !t.s.tiles)
 		return rc;
+	ContextPass p;
 	// 2 * n / 8 bytes of hit and run words + n / 256 bytes of run counts
-	const size_t markBytes = size_t(p.tiles) * kCtxWaves * 16;
-	if (int rc2 = marks.Alloc(markBytes + size_t(p.tiles) * 4, "hipMallocAsync(context marks)"))
+	const size_t markBytes = size_t(t.s.tiles) * kBlockWaves * 16;
+	if (int rc2 = marks.Alloc(markBytes + size_t(t.s.tiles) * 4, "hipMallocAsync(context marks)"))
 		return rc2;
 	p.marks = marks.as<uint64_t>();
 	p.groupCounts = reinterpret_cast<uint32_t*>(marks.as<uint8_t>() + markBytes);
@@ -227,16 +187,12 @@ int LaunchContext(const uint64_t* hits, const uint64_t* hitCount, uint64_t hitCa
 	p.after = after;
 	p.outLines = outLines;
 	p.outFlags = outLines ? outFlags : nullptr;
-	p.lineCap = outLines ? lineCap : 0;
-	const dim3 grid(std::min(p.tiles, kCtxMaxBlocks));
-	hipLaunchKernelGGL(ContextClassifyKernel, grid, dim3(kCtxThreads), 0, stream, p);
-	LaunchTileScan(p.tileCounts, 1, p.tiles, outLineCount, stream);
+	hipLaunchKernelGGL(ContextClassifyKernel, t.Grid(), dim3(kBlockThreads), 0, stream, p, t.s);
+	t.Scan(outLineCount);
 	if (outGroupCount)
-		LaunchTileScan(p.groupCounts, 1, p.tiles, outGroupCount, stream);
-	if (p.lineCap)
-		hipLaunchKernelGGL(ContextScatterKernel, grid, dim3(kCtxThreads), 0, stream, p);
-	const hipError_t e = hipGetLastError();
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "context launch");
+		LaunchTileScan(p.groupCounts, 1, t.s.tiles, outGroupCount, stream);
+	t.Scatter(p, outLines ? lineCap : 0);
+	return t.Done("context launch");
 }
 
 int ContextArgsInvalid(const char* who, bool haveHits, uint64_t hitCap, uint64_t n, const ContextOut& o, bool ownList)
@@ -298,36 +254,23 @@ try {
 	}
 	BatchIO io(stream, false);
 	const uint8_t* dHits = nullptr;
-	uint64_t count = 0;   // the count comes back here first
-	uint64_t *dCount = nullptr, *dGroups = nullptr, *dLines = nullptr;
+	HitStage list(false, out_line_count, "hipMemcpy(context lines)");   // n lines: no list is staged longer
+	uint64_t *dGroups = nullptr, *dLines = nullptr;
 	uint8_t* dFlags = nullptr;
-	const uint64_t cap = std::min(line_cap, n);   // n lines: no list is staged longer
 	int rc;
-	if ((rc = io.In(reinterpret_cast<const uint8_t*>(hits), size_t(k) * 8, &dHits)) || (rc = io.Result(&count, 1, 1, &dCount)))
+	if ((rc = io.In(reinterpret_cast<const uint8_t*>(hits), size_t(k) * 8, &dHits)) || (rc = list.Count(io, line_cap, n)))
 		return rc;
 	if (out_group_count)
 		if ((rc = io.Result(out_group_count, 1, 1, &dGroups)))
 			return rc;
-	if (out_lines && cap)
-		if ((rc = io.Result(out_lines, size_t(cap), 0, &dLines)))
-			return rc;
-	if (out_line_flags && cap)
-		if ((rc = io.Result(out_line_flags, size_t(cap), 0, &dFlags)))
-			return rc;
-	if ((rc = io.Ready()))
+	if ((rc = list.List(io, out_lines, 1, &dLines)) || (rc = list.List(io, out_line_flags, 1, &dFlags)) || (rc = io.Ready()))
 		return rc;
-	if ((rc = LaunchContext(reinterpret_cast<const uint64_t*>(dHits), nullptr, k, n, before, after, dLines, dFlags, cap, dCount, dGroups, stream)))
+	if ((rc = LaunchContext(reinterpret_cast<const uint64_t*>(dHits), nullptr, k, n, before, after, dLines, dFlags, list.cap, list.dCount, dGroups,
+	                        stream)))
 		return rc;
 	if ((rc = io.Finish()))
 		return rc;
-	*out_line_count = count;
-	const uint64_t written = std::min(count, cap);
-	hipError_t e = hipSuccess;
-	if (written && dLines)
-		e = hipMemcpy(out_lines, dLines, size_t(written) * 8, hipMemcpyDeviceToHost);
-	if (e == hipSuccess && written && dFlags)
-		e = hipMemcpy(out_line_flags, dFlags, size_t(written), hipMemcpyDeviceToHost);
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(context lines)");
+	return list.Back();
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }

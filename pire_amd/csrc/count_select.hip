@@ -15,30 +15,27 @@
 //   scatter   rank of a selected string = tile offset + the popcounts of the waves in front + mbcnt of its own wave's
 //             ballot word; the lane writes its index and copies its row.
 //
-// The classify tail, the scatter head and the launcher's front are the select pass's (compact.h TileBallot / TileRank,
-// select.hip TileCompaction); the sums are this unit's own.  Launches on the caller's stream, the shape of select.hip: no
-// block waits for another block, no atomics (the same input gives the same bits).  Plain HIP with compiler-placed waits:
-// nothing here keeps data on its way in registers.  A row is read with 4-byte loads: `results` is only 4-byte aligned.
+// The scatter kernel and the launcher are tile_pass.h's, the staging of the count and the lists is internal.h's HitStage; the
+// classify kernel -- it ends in compact.h's TileBallot -- and its sums are this unit's own.  Launches on the caller's stream,
+// the shape of select.hip: no block waits for another block, no atomics (the same input gives the same bits).  Plain HIP
+// with compiler-placed waits: nothing here keeps data on its way in registers.  A row is read with 4-byte loads: `results`
+// is only 4-byte aligned.
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "compact.h"
-#include "internal.h"
+#include "tile_pass.h"
 
 namespace pirehip {
 
 namespace {
 
-constexpr uint32_t kCntThreads = kBlockThreads;   // one tile = 1 024 strings = 16 ballot words
-constexpr uint32_t kCntWaves = kBlockWaves;
-constexpr uint32_t kCntMaxBlocks = 8192;
 constexpr uint32_t kCntChunk = 16;                // regexps summed between two barriers: 16 waves x 16 sums of LDS
 constexpr uint32_t kCntTotalBlocks = 1024;        // the totals' grid: a block per regexp, regexps in a grid-stride loop
 constexpr uint32_t kCntMaxRegexps = 1024;
 
-struct CountSelectParams {
+struct CountPass {
 	const uint32_t* results;   // [n][regexps]
 	uint64_t n;
 	uint32_t regexps;
@@ -46,21 +43,29 @@ struct CountSelectParams {
 	uint32_t all;              // PIRE_HIP_COUNT_ALL
 	uint64_t* outHits;         // nullable
 	uint32_t* outHitResults;   // nullable
-	uint64_t hitCap;
-	uint64_t* ballots;         // [tiles * 16] selected bits, one word per wave
-	uint32_t* tileCounts;      // [tiles] selected strings per tile; after the scan: selected strings in front of the tile
 	uint64_t* tileSums;        // [regexps][tiles] the counters of a tile added up (kSums)
-	uint32_t tiles;
+
+	__device__ __forceinline__ void Write(uint64_t rank, uint64_t i) const
+	{
+		if (outHits)
+			outHits[rank] = i;
+		if (outHitResults) {
+			const uint32_t* row = results + i * regexps;
+			uint32_t* out = outHitResults + rank * regexps;
+			for (uint32_t r = 0; r < regexps; ++r)
+				out[r] = row[r];
+		}
+	}
 };
 
 template <bool kSums>
-__global__ __launch_bounds__(kCntThreads) void CountClassifyKernel(CountSelectParams p)
+__global__ __launch_bounds__(kBlockThreads) void CountClassifyKernel(CountPass p, TileScratch t)
 {
-	__shared__ uint32_t waveCount[kCntWaves];
-	__shared__ uint64_t waveSum[kSums ? kCntWaves * kCntChunk : 1];
+	__shared__ uint32_t waveCount[kBlockWaves];
+	__shared__ uint64_t waveSum[kSums ? kBlockWaves * kCntChunk : 1];
 	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
-		const uint64_t i = uint64_t(tile) * kCntThreads + threadIdx.x;
+	for (uint32_t tile = blockIdx.x; tile < t.tiles; tile += gridDim.x) {
+		const uint64_t i = uint64_t(tile) * kBlockThreads + threadIdx.x;
 		const bool live = i < p.n;
 		const uint32_t* row = p.results + (live ? i : 0) * p.regexps;
 		bool wanted = false, any = false, every = true;
@@ -86,48 +91,29 @@ __global__ __launch_bounds__(kCntThreads) void CountClassifyKernel(CountSelectPa
 				__syncthreads();
 				if (threadIdx.x < cnt) {
 					uint64_t s = 0;
-					for (uint32_t w = 0; w < kCntWaves; ++w)
+					for (uint32_t w = 0; w < kBlockWaves; ++w)
 						s += waveSum[w * kCntChunk + threadIdx.x];
-					p.tileSums[size_t(r0 + threadIdx.x) * p.tiles + tile] = s;
+					p.tileSums[size_t(r0 + threadIdx.x) * t.tiles + tile] = s;
 				}
 				__syncthreads();   // (the next step writes waveSum again)
 			}
 		}
-		TileBallot(live && wanted && (p.all ? every : any), tile, p.ballots, p.tileCounts, waveCount);
+		TileBallot(live && wanted && (p.all ? every : any), tile, t.ballots, t.tileCounts, waveCount);
 	}
 }
 
-__global__ __launch_bounds__(kCntThreads) void CountTotalsKernel(const uint64_t* tileSums, uint32_t regexps, uint32_t tiles, uint64_t* outTotals)
+__global__ __launch_bounds__(kBlockThreads) void CountTotalsKernel(const uint64_t* tileSums, uint32_t regexps, uint32_t tiles, uint64_t* outTotals)
 {
-	__shared__ uint64_t waveSum[kCntWaves];
+	__shared__ uint64_t waveSum[kBlockWaves];
 	for (uint32_t r = blockIdx.x; r < regexps; r += gridDim.x) {
 		const uint64_t* row = tileSums + size_t(r) * tiles;
 		uint64_t s = 0;
-		for (uint32_t t = threadIdx.x; t < tiles; t += kCntThreads)
+		for (uint32_t t = threadIdx.x; t < tiles; t += kBlockThreads)
 			s += row[t];
 		uint64_t total;
 		(void)BlockExclusive(s, waveSum, &total);
 		if (threadIdx.x == 0)
 			outTotals[r] = total;   // n < 2^32 counters of 32 bits: the sum fits
-	}
-}
-
-__global__ __launch_bounds__(kCntThreads) void CountScatterKernel(CountSelectParams p)
-{
-	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
-		bool selected;
-		const uint64_t rank = TileRank(tile, p.ballots, p.tileCounts, &selected);
-		if (selected && rank < p.hitCap) {   // (a selected bit: i < n)
-			const uint64_t i = uint64_t(tile) * kCntThreads + threadIdx.x;
-			if (p.outHits)
-				p.outHits[rank] = i;
-			if (p.outHitResults) {
-				const uint32_t* row = p.results + i * p.regexps;
-				uint32_t* out = p.outHitResults + rank * p.regexps;
-				for (uint32_t r = 0; r < p.regexps; ++r)
-					out[r] = row[r];
-			}
-		}
 	}
 }
 
@@ -143,15 +129,15 @@ int LaunchCountSelect(const uint32_t* results, uint64_t n, uint32_t regexps, con
 		if (e != hipSuccess)
 			return HipFail(e, "hipMemsetAsync(totals)");
 	}
-	CountSelectParams p;
-	StreamScratch scratch(stream), sums(stream);
-	const int rc = TileCompaction("pire_hip_count_select", "hipMallocAsync(count select scratch)", n, outHitCount, stream, scratch, &p.tiles,
-	                              &p.ballots, &p.tileCounts);
-	if (rc || !p.tiles)
+	TilePass t(stream);
+	StreamScratch sums(stream);
+	const int rc = t.Front("pire_hip_count_select", "hipMallocAsync(count select scratch)", n, outHitCount);
+	if (rc || !t.s.tiles)
 		return rc;
+	CountPass p;
 	p.tileSums = nullptr;
 	if (outTotals) {
-		if (int src = sums.Alloc(size_t(regexps) * p.tiles * 8, "hipMallocAsync(count select sums)"))
+		if (int src = sums.Alloc(size_t(regexps) * t.s.tiles * 8, "hipMallocAsync(count select sums)"))
 			return src;
 		p.tileSums = sums.as<uint64_t>();
 	}
@@ -162,20 +148,14 @@ int LaunchCountSelect(const uint32_t* results, uint64_t n, uint32_t regexps, con
 	p.all = (mode & PIRE_HIP_COUNT_ALL) != 0;
 	p.outHits = outHits;
 	p.outHitResults = outHitResults;
-	p.hitCap = outHits || outHitResults ? hitCap : 0;
-	const dim3 grid(std::min(p.tiles, kCntMaxBlocks));
 	if (outTotals) {
-		hipLaunchKernelGGL(CountClassifyKernel<true>, grid, dim3(kCntThreads), 0, stream, p);
-		hipLaunchKernelGGL(CountTotalsKernel, dim3(std::min(regexps, kCntTotalBlocks)), dim3(kCntThreads), 0, stream, p.tileSums, regexps, p.tiles,
+		hipLaunchKernelGGL(CountClassifyKernel<true>, t.Grid(), dim3(kBlockThreads), 0, stream, p, t.s);
+		hipLaunchKernelGGL(CountTotalsKernel, dim3(std::min(regexps, kCntTotalBlocks)), dim3(kBlockThreads), 0, stream, p.tileSums, regexps, t.s.tiles,
 		                   outTotals);
 	} else {
-		hipLaunchKernelGGL(CountClassifyKernel<false>, grid, dim3(kCntThreads), 0, stream, p);
+		hipLaunchKernelGGL(CountClassifyKernel<false>, t.Grid(), dim3(kBlockThreads), 0, stream, p, t.s);
 	}
-	LaunchTileScan(p.tileCounts, 1, p.tiles, outHitCount, stream);
-	if (p.hitCap)
-		hipLaunchKernelGGL(CountScatterKernel, grid, dim3(kCntThreads), 0, stream, p);
-	const hipError_t e = hipGetLastError();
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "count select launch");
+	return t.Tail(p, outHits || outHitResults ? hitCap : 0, outHitCount, "count select launch");
 }
 
 int CountSelectArgsInvalid(const char* who, uint64_t n, uint32_t regexps, bool haveResults, const CountSelectOut& o)
@@ -196,7 +176,7 @@ int CountSelectArgsInvalid(const char* who, uint64_t n, uint32_t regexps, bool h
 
 int CountSelectStage::Empty(hipStream_t stream)
 {
-	if (onDevice)
+	if (list.onDevice)
 		return LaunchCountSelect(nullptr, 0, regexps, nullptr, 0, o.outTotals, nullptr, nullptr, 0, o.outHitCount, stream);
 	*o.outHitCount = 0;
 	if (o.outTotals)
@@ -211,38 +191,19 @@ int CountSelectStage::In(BatchIO& io)
 
 int CountSelectStage::Results(BatchIO& io, uint64_t n)
 {
-	cap = onDevice ? o.hitCap : std::min<uint64_t>(o.hitCap, n);   // n strings have at most n hits: a host call stages no more
-	if (int rc = io.Result(onDevice ? o.outHitCount : &count, 1, 1, &dCount))   // (host pointers: the count comes back here first)
+	if (int rc = list.Count(io, o.hitCap, n))
 		return rc;
 	if (o.outTotals && regexps)
 		if (int rc = io.Result(o.outTotals, size_t(regexps), size_t(regexps), &dTotals))
 			return rc;
-	if (o.outHits && cap)
-		if (int rc = io.Result(o.outHits, size_t(cap), 0, &dHits))
-			return rc;
-	if (o.outHitResults && cap && regexps)
-		if (int rc = io.Result(o.outHitResults, size_t(cap) * regexps, 0, &dHitResults))
-			return rc;
-	return PIRE_HIP_OK;
+	if (int rc = list.List(io, o.outHits, 1, &dHits))
+		return rc;
+	return list.List(io, o.outHitResults, regexps, &dHitResults);
 }
 
 int CountSelectStage::Launch(const uint32_t* results, uint64_t n, hipStream_t stream)
 {
-	return LaunchCountSelect(results, n, regexps, dMin, o.mode, dTotals, dHits, dHitResults, cap, dCount, stream);
-}
-
-int CountSelectStage::Back()
-{
-	if (onDevice)
-		return PIRE_HIP_OK;
-	*o.outHitCount = count;
-	const uint64_t written = std::min<uint64_t>(count, cap);
-	hipError_t e = hipSuccess;
-	if (written && dHits)
-		e = hipMemcpy(o.outHits, dHits, size_t(written) * 8, hipMemcpyDeviceToHost);
-	if (e == hipSuccess && written && dHitResults)
-		e = hipMemcpy(o.outHitResults, dHitResults, size_t(written) * regexps * 4, hipMemcpyDeviceToHost);
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(hits)");
+	return LaunchCountSelect(results, n, regexps, dMin, o.mode, dTotals, dHits, dHitResults, list.cap, list.dCount, stream);
 }
 
 }  // namespace pirehip

@@ -2350,9 +2350,8 @@ int CaptureRunImpl(pire_hip_counting_table* t, const void* text, const uint64_t*
 	// the pass behind the scan: what it reads and the caller has no array for lives in scratch (a host-pointer call's
 	// Result() has allocated it already), its lists are staged as far as n strings can fill them
 	StreamScratch ownPositions(stream), ownFinal(stream);
-	const uint64_t cap = sel ? std::min<uint64_t>(sel->hitCap, n) : 0;
-	uint64_t count = 0;   // host pointers: the count comes back here first
-	uint64_t *dCount = nullptr, *dHits = nullptr, *dSpans = nullptr;
+	HitStage list(onDevice, sel ? sel->outHitCount : nullptr, "hipMemcpy(hits)");
+	uint64_t *dHits = nullptr, *dSpans = nullptr;
 	if (sel) {
 		if (onDevice && (!p.outBegin || !p.outEnd)) {
 			if ((rc = ownPositions.Alloc(size_t(n) * 16, "hipMallocAsync(capture positions)")))
@@ -2367,14 +2366,8 @@ int CaptureRunImpl(pire_hip_counting_table* t, const void* text, const uint64_t*
 				return rc;
 			p.outFinal = ownFinal.as<uint8_t>();
 		}
-		if ((rc = io.Result(onDevice ? sel->outHitCount : &count, 1, 1, &dCount)))
+		if ((rc = list.Count(io, sel->hitCap, n)) || (rc = list.List(io, sel->outHits, 1, &dHits)) || (rc = list.List(io, sel->outSpans, 2, &dSpans)))
 			return rc;
-		if (sel->outHits && cap)
-			if ((rc = io.Result(sel->outHits, size_t(cap), 0, &dHits)))
-				return rc;
-		if (sel->outSpans && cap)
-			if ((rc = io.Result(sel->outSpans, size_t(cap) * 2, 0, &dSpans)))
-				return rc;
 	}
 	if ((rc = io.Ready()))
 		return rc;
@@ -2385,20 +2378,11 @@ int CaptureRunImpl(pire_hip_counting_table* t, const void* text, const uint64_t*
 		return rc;
 	if (sel)
 		if ((rc = LaunchCaptureSelect(p.offsets, n, (flags & PIRE_HIP_RUN_BEGIN) != 0, p.outBegin, p.outEnd,
-		                              sel->needFinal ? p.outFinal : nullptr, sel->shift, dHits, dSpans, cap, dCount, stream)))
+		                              sel->needFinal ? p.outFinal : nullptr, sel->shift, dHits, dSpans, list.cap, list.dCount, stream)))
 			return rc;
 	if ((rc = io.Finish()))
 		return rc;
-	if (!sel || onDevice)
-		return PIRE_HIP_OK;
-	*sel->outHitCount = count;
-	const uint64_t written = std::min<uint64_t>(count, cap);
-	hipError_t e = hipSuccess;
-	if (written && dHits)
-		e = hipMemcpy(sel->outHits, dHits, size_t(written) * 8, hipMemcpyDeviceToHost);
-	if (e == hipSuccess && written && dSpans)
-		e = hipMemcpy(sel->outSpans, dSpans, size_t(written) * 16, hipMemcpyDeviceToHost);
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(hits)");
+	return sel ? list.Back() : PIRE_HIP_OK;
 }
 
 }  // namespace pirehip

@@ -20,9 +20,10 @@
 //   lines     for the lines forms: out_file_lines[f] = how many lines begin in front of byte file_bytes[f], a lower bound in
 //             the split's offsets (line i begins at offsets[i] + i of raw), and which boundaries lie inside a line.
 //
-// The classify tail, the scatter head and the launcher's front are the select pass's (compact.h TileBallot / TileRank,
-// select.hip TileCompaction).  Launches on the caller's stream: no block waits for another block, no atomics (the same
-// input gives the same bits).  Plain HIP with compiler-placed waits: nothing here keeps data on its way in registers.
+// The classify and scatter kernels and the launcher are tile_pass.h's, the wave-wide search and the load of a list entry
+// compact.h's (WaveBound, LoadU64), the staging of the file count and list internal.h's HitStage; this unit keeps its
+// predicate and what a listed file writes (FilesPass), and the bounds, locate and lines kernels.  Launches on the caller's
+// stream: no block waits for another block, no atomics (the same input gives the same bits).  Plain HIP with compiler-placed waits: nothing here keeps data on its way in registers.
 // `hits` may have any alignment: an entry is read through a packed type.  A list or bounds that break the preconditions
 // give unspecified answers and nothing worse: every index into `hits` is clamped into [0, k), every index into `bounds`
 // into [0, files].
@@ -31,22 +32,14 @@
 
 #include <algorithm>
 
-#include "compact.h"
-#include "internal.h"
+#include "tile_pass.h"
 
 namespace pirehip {
 
 namespace {
 
-constexpr uint32_t kFilesThreads = kBlockThreads;   // one tile = 1 024 files, or 1 024 hits
-constexpr uint32_t kFilesWaves = kBlockWaves;
-constexpr uint32_t kFilesMaxBlocks = 8192;
-
-struct __attribute__((packed, aligned(1))) UnalignedU64 {
-	uint64_t v;
-};
-
-struct FilesParams {
+// (one tile = 1 024 files, or 1 024 hits)
+struct FilesPass {
 	const uint64_t* hits;       // [k], any alignment
 	const uint64_t* hitCount;   // nullable: k = hitCap
 	uint64_t hitCap;
@@ -59,48 +52,27 @@ struct FilesParams {
 	uint64_t* outHitLine;       // nullable
 	uint64_t outCap;            // entries of the three arrays above
 	uint64_t* outFiles;
-	uint64_t fileCap;
-	uint64_t* ballots;          // [tiles * 16] listed bits, one word per wave
-	uint32_t* tileCounts;       // [tiles] listed files per tile; after the scan: listed files in front of the tile
-	uint32_t tiles;             // of files
 	uint32_t hitTiles;
+
+	// listed: the file has hits, or -- `without` -- has none
+	__device__ __forceinline__ bool Selected(uint64_t f) const { return (first[f + 1] != first[f]) != (without != 0); }
+	__device__ __forceinline__ void Write(uint64_t rank, uint64_t f) const { outFiles[rank] = f; }
 };
 
-__device__ __forceinline__ uint64_t HitAt(const uint64_t* hits, uint64_t j)
-{
-	return reinterpret_cast<const UnalignedU64*>(hits)[j].v;
-}
-
-__device__ __forceinline__ uint64_t HitsInList(const FilesParams& p)
+__device__ __forceinline__ uint64_t HitsInList(const FilesPass& p)
 {
 	return std::min(p.hitCount ? *p.hitCount : p.hitCap, p.hitCap);
 }
 
-// How many of a[0, m) are <= x (the array does not decrease), found by one wave: 64 probes a step, every probe inside [0, m)
-__device__ __forceinline__ uint64_t WaveCountNotAbove(const uint64_t* a, uint64_t m, uint64_t x)
-{
-	const uint32_t lane = threadIdx.x & 63;
-	uint64_t lo = 0, hi = m;   // the answer is in [lo, hi]
-	while (hi > lo) {
-		const uint64_t step = (hi - lo + 63) / 64;
-		const uint64_t q = lo + (lane + 1) * step - 1;
-		const bool le = q < hi && a[q] <= x;   // true in the first c lanes, false behind them
-		const uint64_t c = uint64_t(__popcll(__ballot(le)));
-		hi = std::min(hi, lo + (c + 1) * step - 1);
-		lo = std::min(lo + c * step, hi);   // (the min: an array that decreases)
-	}
-	return lo;
-}
-
-__global__ __launch_bounds__(kFilesThreads) void FilesBoundsKernel(FilesParams p)
+__global__ __launch_bounds__(kBlockThreads) void FilesBoundsKernel(FilesPass p)
 {
 	const uint64_t k = HitsInList(p);
-	for (uint64_t f = uint64_t(blockIdx.x) * kFilesThreads + threadIdx.x; f <= p.files; f += uint64_t(gridDim.x) * kFilesThreads) {
+	for (uint64_t f = uint64_t(blockIdx.x) * kBlockThreads + threadIdx.x; f <= p.files; f += uint64_t(gridDim.x) * kBlockThreads) {
 		const uint64_t x = p.bounds[f];
 		uint64_t lo = 0, hi = k;   // how many hits are < x; every probe inside [0, k)
 		while (lo < hi) {
 			const uint64_t mid = lo + (hi - lo) / 2;
-			if (HitAt(p.hits, mid) < x)
+			if (LoadU64(p.hits, mid) < x)
 				lo = mid + 1;
 			else
 				hi = mid;
@@ -109,40 +81,20 @@ __global__ __launch_bounds__(kFilesThreads) void FilesBoundsKernel(FilesParams p
 	}
 }
 
-__global__ __launch_bounds__(kFilesThreads) void FilesClassifyKernel(FilesParams p)
-{
-	__shared__ uint32_t waveCount[kFilesWaves];
-	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
-		const uint64_t f = uint64_t(tile) * kFilesThreads + threadIdx.x;
-		const bool sel = f < p.files && ((p.first[f + 1] != p.first[f]) != (p.without != 0));
-		TileBallot(sel, tile, p.ballots, p.tileCounts, waveCount);
-	}
-}
-
-__global__ __launch_bounds__(kFilesThreads) void FilesScatterKernel(FilesParams p)
-{
-	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
-		bool selected;
-		const uint64_t rank = TileRank(tile, p.ballots, p.tileCounts, &selected);
-		if (selected && rank < p.fileCap)   // (a listed bit: f < files)
-			p.outFiles[rank] = uint64_t(tile) * kFilesThreads + threadIdx.x;
-	}
-}
-
 // files > 0
-__global__ __launch_bounds__(kFilesThreads) void FilesLocateKernel(FilesParams p)
+__global__ __launch_bounds__(kBlockThreads) void FilesLocateKernel(FilesPass p)
 {
 	__shared__ uint64_t slice[2];
 	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	const uint64_t k = HitsInList(p);
 	for (uint32_t tile = blockIdx.x; tile < p.hitTiles; tile += gridDim.x) {
-		const uint64_t t0 = uint64_t(tile) * kFilesThreads;
+		const uint64_t t0 = uint64_t(tile) * kBlockThreads;
 		if (t0 >= k)   // (the whole block, and every tile it would take behind this one)
 			break;
-		const uint64_t t1 = std::min(t0 + kFilesThreads, k);
+		const uint64_t t1 = std::min(t0 + kBlockThreads, k);
 		// the files of the tile's first and of its last hit: the last f with bounds[f] <= hit, inside [0, files)
 		if (wave < 2) {
-			const uint64_t c = WaveCountNotAbove(p.bounds, p.files + 1, HitAt(p.hits, wave ? t1 - 1 : t0));
+			const uint64_t c = WaveBound<true>(p.bounds, p.files + 1, LoadU64(p.hits, wave ? t1 - 1 : t0));
 			if (lane == 0)
 				slice[wave] = std::min(c ? c - 1 : 0, p.files - 1);
 		}
@@ -150,7 +102,7 @@ __global__ __launch_bounds__(kFilesThreads) void FilesLocateKernel(FilesParams p
 		const uint64_t fLo = slice[0], fHi = std::max(slice[1], fLo);
 		const uint64_t j = t0 + threadIdx.x;
 		if (j < t1 && j < p.outCap) {
-			const uint64_t h = HitAt(p.hits, j);
+			const uint64_t h = LoadU64(p.hits, j);
 			uint64_t lo = fLo, hi = fHi;   // the last f in [fLo, fHi] with bounds[f] <= h; every probe inside (fLo, fHi]
 			while (lo < hi) {
 				const uint64_t mid = lo + (hi - lo + 1) / 2;
@@ -183,12 +135,12 @@ struct FileLinesParams {
 	uint32_t tiles;              // of files + 1 entries
 };
 
-__global__ __launch_bounds__(kFilesThreads) void FileLinesKernel(FileLinesParams p)
+__global__ __launch_bounds__(kBlockThreads) void FileLinesKernel(FileLinesParams p)
 {
-	__shared__ uint32_t waveCount[kFilesWaves];
+	__shared__ uint32_t waveCount[kBlockWaves];
 	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
-		const uint64_t f = uint64_t(tile) * kFilesThreads + threadIdx.x;
+		const uint64_t f = uint64_t(tile) * kBlockThreads + threadIdx.x;
 		bool inside = false;
 		if (f <= p.files) {
 			const uint64_t x = p.fileBytes[f];
@@ -209,7 +161,7 @@ __global__ __launch_bounds__(kFilesThreads) void FileLinesKernel(FileLinesParams
 		__syncthreads();
 		if (threadIdx.x == 0) {
 			uint32_t sum = 0;
-			for (uint32_t w = 0; w < kFilesWaves; ++w)
+			for (uint32_t w = 0; w < kBlockWaves; ++w)
 				sum += waveCount[w];
 			p.straddles[tile] = sum;
 		}
@@ -235,12 +187,12 @@ int LaunchFiles(const uint64_t* hits, const uint64_t* hitCount, uint64_t hitCap,
 			e = hipMemsetAsync(outFileFirst, 0, 8, stream);
 		return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemsetAsync(file count)");
 	}
-	FilesParams p;
-	StreamScratch scratch(stream), ownFirst(stream);
-	const int rc = TileCompaction("pire_hip_files", "hipMallocAsync(files scratch)", files, outFileCount, stream, scratch, &p.tiles, &p.ballots,
-	                              &p.tileCounts);
-	if (rc || !p.tiles)
+	TilePass t(stream);
+	StreamScratch ownFirst(stream);
+	const int rc = t.Front("pire_hip_files", "hipMallocAsync(files scratch)", files, outFileCount);
+	if (rc || !t.s.tiles)
 		return rc;
+	FilesPass p;
 	if (!outFileFirst) {
 		if (int rc2 = ownFirst.Alloc((size_t(files) + 1) * 8, "hipMallocAsync(file first)"))
 			return rc2;
@@ -258,19 +210,15 @@ int LaunchFiles(const uint64_t* hits, const uint64_t* hitCount, uint64_t hitCap,
 	p.outHitLine = outHitLine;
 	p.outCap = std::min(outCap, hitCap);
 	p.outFiles = outFiles;
-	p.fileCap = outFiles ? fileCap : 0;
-	p.hitTiles = uint32_t((p.outCap + kFilesThreads - 1) / kFilesThreads);
-	const dim3 block(kFilesThreads);
-	hipLaunchKernelGGL(FilesBoundsKernel, dim3(std::min(uint32_t(files / kFilesThreads) + 1, kFilesMaxBlocks)), block, 0, stream, p);
-	const dim3 grid(std::min(p.tiles, kFilesMaxBlocks));
-	hipLaunchKernelGGL(FilesClassifyKernel, grid, block, 0, stream, p);
-	LaunchTileScan(p.tileCounts, 1, p.tiles, outFileCount, stream);
-	if (p.fileCap)
-		hipLaunchKernelGGL(FilesScatterKernel, grid, block, 0, stream, p);
+	p.hitTiles = uint32_t((p.outCap + kBlockThreads - 1) / kBlockThreads);
+	const dim3 block(kBlockThreads);
+	hipLaunchKernelGGL(FilesBoundsKernel, dim3(std::min(uint32_t(files / kBlockThreads) + 1, kTileMaxBlocks)), block, 0, stream, p);
+	t.Classify(p, files);
+	t.Scan(outFileCount);
+	t.Scatter(p, outFiles ? fileCap : 0);
 	if (p.hitTiles && (outHits || outHitFile || outHitLine))
-		hipLaunchKernelGGL(FilesLocateKernel, dim3(std::min(p.hitTiles, kFilesMaxBlocks)), block, 0, stream, p);
-	const hipError_t e = hipGetLastError();
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "files launch");
+		hipLaunchKernelGGL(FilesLocateKernel, dim3(std::min(p.hitTiles, kTileMaxBlocks)), block, 0, stream, p);
+	return t.Done("files launch");
 }
 
 int LaunchFileLines(const uint64_t* offsets, uint64_t n, const uint64_t* fileBytes, uint64_t files, const void* raw, uint64_t size,
@@ -284,7 +232,7 @@ int LaunchFileLines(const uint64_t* offsets, uint64_t n, const uint64_t* fileByt
 	}
 	FileLinesParams p;
 	StreamScratch counts(stream);
-	p.tiles = uint32_t(files / kFilesThreads) + 1;   // files + 1 entries
+	p.tiles = uint32_t(files / kBlockThreads) + 1;   // files + 1 entries
 	if (int rc = counts.Alloc(size_t(p.tiles) * 4, "hipMallocAsync(file lines scratch)"))
 		return rc;
 	p.offsets = offsets;
@@ -296,7 +244,7 @@ int LaunchFileLines(const uint64_t* offsets, uint64_t n, const uint64_t* fileByt
 	p.delim = delim;
 	p.outLines = outFileLines;
 	p.straddles = counts.as<uint32_t>();
-	hipLaunchKernelGGL(FileLinesKernel, dim3(std::min(p.tiles, kFilesMaxBlocks)), dim3(kFilesThreads), 0, stream, p);
+	hipLaunchKernelGGL(FileLinesKernel, dim3(std::min(p.tiles, kTileMaxBlocks)), dim3(kBlockThreads), 0, stream, p);
 	LaunchTileScan(p.straddles, 1, p.tiles, outStraddles, stream);
 	const hipError_t e = hipGetLastError();
 	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "file lines launch");
@@ -375,14 +323,13 @@ try {
 	BatchIO io(stream, false);
 	const uint8_t* dHits = nullptr;
 	const uint64_t* dBounds = nullptr;
-	uint64_t count = 0;   // the count comes back here first
-	uint64_t *dCount = nullptr, *dFirst = nullptr, *dHitFile = nullptr, *dHitLine = nullptr, *dFiles = nullptr;
-	const uint64_t cap = std::min(file_cap, files);   // `files` files: no list is staged longer
+	HitStage list(false, out_file_count, "hipMemcpy(files)");   // `files` files: no list is staged longer
+	uint64_t *dFirst = nullptr, *dHitFile = nullptr, *dHitLine = nullptr, *dFiles = nullptr;
 	int rc;
 	if (k)
 		if ((rc = io.In(reinterpret_cast<const uint8_t*>(hits), size_t(k) * 8, &dHits)))
 			return rc;
-	if ((rc = io.In(bounds, size_t(files) + 1, &dBounds)) || (rc = io.Result(&count, 1, 1, &dCount)))
+	if ((rc = io.In(bounds, size_t(files) + 1, &dBounds)) || (rc = list.Count(io, file_cap, files)))
 		return rc;
 	if (out_file_first)
 		if ((rc = io.Result(out_file_first, size_t(files) + 1, size_t(files) + 1, &dFirst)))
@@ -393,20 +340,14 @@ try {
 	if (out_hit_line && k)
 		if ((rc = io.Result(out_hit_line, size_t(k), size_t(k), &dHitLine)))
 			return rc;
-	if (out_files && cap)
-		if ((rc = io.Result(out_files, size_t(cap), 0, &dFiles)))
-			return rc;
-	if ((rc = io.Ready()))
+	if ((rc = list.List(io, out_files, 1, &dFiles)) || (rc = io.Ready()))
 		return rc;
 	if ((rc = LaunchFiles(reinterpret_cast<const uint64_t*>(dHits), nullptr, k, dBounds, files, file_mode, dFirst, nullptr, dHitFile, dHitLine, k,
-	                      dFiles, cap, dCount, stream)))
+	                      dFiles, list.cap, list.dCount, stream)))
 		return rc;
 	if ((rc = io.Finish()))
 		return rc;
-	*out_file_count = count;
-	const uint64_t written = std::min(count, cap);
-	const hipError_t e = written && dFiles ? hipMemcpy(out_files, dFiles, size_t(written) * 8, hipMemcpyDeviceToHost) : hipSuccess;
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(files)");
+	return list.Back();
 } catch (...) {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }

@@ -1072,11 +1072,45 @@ int LaunchSelect(const SelectDevice& image, uint32_t states, uint32_t words, con
 // counts[rows][entries] -- selected strings per tile of 1 024 -- in place, a block per row; outCounts[r] = the total of row r.
 // Enqueues; the caller asks hipGetLastError() behind its launches.
 void LaunchTileScan(uint32_t* counts, uint32_t rows, uint32_t entries, uint64_t* outCounts, hipStream_t stream);
-// The front of both ballot compactions' launchers (select.hip, capture_select.hip).  n == 0: *outHitCount is zeroed on the
-// stream and *tiles = 0 (nothing to launch); 2^32 strings or more: refused in `who`'s name; else *tiles = ceil(n / 1024) and
-// the one allocation of `scratch`, carved into ballots[tiles * 16] and tileCounts[tiles].
+// The front of every ballot compaction's launcher (tile_pass.h TilePass).  n == 0: *outHitCount is zeroed on the stream and
+// s->tiles = 0 (nothing to launch); 2^32 strings or more: refused in `who`'s name; else s->tiles = ceil(n / 1024) and the one
+// allocation of `scratch`, carved into s->ballots[tiles * 16] and s->tileCounts[tiles].
+struct TileScratch;   // compact.h
 int TileCompaction(const char* who, const char* scratchLabel, uint64_t n, uint64_t* outHitCount, hipStream_t stream, StreamScratch& scratch,
-                   uint32_t* tiles, uint64_t** ballots, uint32_t** tileCounts);
+                   TileScratch* s);
+// The count and the lists of a hit pass inside ONE call of an entry point, on whichever side the caller's pointers live: the
+// one home of "the count comes back first; host pointers stage no list longer than min(hit_cap, n); the lists come back only
+// as far as they were written".  Order: Count(), a List() for every list the pass writes (cap == 0 or a null array: no list,
+// *dev = nullptr) -- the pass's other result arrays between them, where it has any --, io.Ready(), the launches on dCount,
+// cap and the lists, io.Finish(), Back().  Device pointers pass through; Back() then does nothing.
+struct HitStage {
+	static constexpr uint32_t kMaxLists = 3;
+	const bool onDevice;
+	uint64_t* const outCount;    // the caller's
+	const char* const backLabel; // names the copies back where one fails
+	uint64_t cap = 0, count = 0; // host pointers: the count comes back in `count` first
+	uint64_t* dCount = nullptr;
+	struct Staged {
+		void* host;
+		const void* dev;
+		size_t width;   // bytes an entry
+	} lists[kMaxLists];
+	uint32_t nLists = 0;
+	HitStage(bool onDevice_, uint64_t* outCount_, const char* backLabel_) : onDevice(onDevice_), outCount(outCount_), backLabel(backLabel_) {}
+	int Count(BatchIO& io, uint64_t hitCap, uint64_t n);   // n strings have at most n hits
+	template <class T>
+	int List(BatchIO& io, T* host, size_t perEntry, T** dev)   // perEntry elements of T an entry
+	{
+		*dev = nullptr;
+		if (!host || !cap || !perEntry)
+			return PIRE_HIP_OK;
+		if (int rc = io.Result(host, size_t(cap) * perEntry, 0, dev))
+			return rc;
+		lists[nLists++] = Staged{host, *dev, perEntry * sizeof(T)};
+		return PIRE_HIP_OK;
+	}
+	int Back();   // host pointers: the count to the caller, and every list as far as it was written
+};
 // capture_select.hip: from capture positions to a compacted, ascending list of byte ranges (pire_hip_capture_select).
 // Device pointers only, three kernels enqueued on `stream`, scratch from the stream-ordered allocator.  fin == nullptr:
 // Final is not asked for.  shift: string i lies shift * i bytes further into the buffer the spans are counted in (1: the
@@ -1111,17 +1145,19 @@ int CountSelectArgsInvalid(const char* who, uint64_t n, uint32_t regexps, bool h
 struct CountSelectStage {
 	const CountSelectOut o;
 	const uint32_t regexps;
-	const bool onDevice;
+	HitStage list;   // the count, out_hits, out_hit_results
 	const uint32_t* dMin = nullptr;
-	uint64_t *dCount = nullptr, *dTotals = nullptr, *dHits = nullptr;
+	uint64_t *dTotals = nullptr, *dHits = nullptr;
 	uint32_t* dHitResults = nullptr;
-	uint64_t cap = 0, count = 0;   // host pointers: no list is staged longer than the strings are many; the count comes back here first
-	CountSelectStage(const CountSelectOut& o_, uint32_t regexps_, bool onDevice_) : o(o_), regexps(regexps_), onDevice(onDevice_) {}
+	CountSelectStage(const CountSelectOut& o_, uint32_t regexps_, bool onDevice_)
+		: o(o_), regexps(regexps_), list(onDevice_, o_.outHitCount, "hipMemcpy(hits)")
+	{
+	}
 	int Empty(hipStream_t stream);   // no strings or no regexps: zeros -- host pointers: no device is touched
 	int In(BatchIO& io);             // min_count
 	int Results(BatchIO& io, uint64_t n);
 	int Launch(const uint32_t* results, uint64_t n, hipStream_t stream);
-	int Back();                      // host pointers: the count, and the lists only as far as they were written
+	int Back() { return list.Back(); }
 };
 // counting.hip: pire_hip_counting_run, and behind it -- where sel is not null -- the pass above on the same stream, on the
 // staged copy of a host-pointer call; outResults may then be null (the rows live in stream-ordered scratch).  `who` names the
@@ -1166,14 +1202,13 @@ int FinalSelectArgsInvalid(const char* who, uint64_t n, bool haveFinal, const Fi
 // Results() with its result arrays, io.Ready(), the scan, Launch(), io.Finish(), Back().
 struct FinalSelectStage {
 	const FinalSelectOut o;
-	const bool onDevice;
-	uint64_t *dCount = nullptr, *dHits = nullptr;
-	uint64_t cap = 0, count = 0;   // host pointers: no list is staged longer than the strings are many; the count comes back here first
-	FinalSelectStage(const FinalSelectOut& o_, bool onDevice_) : o(o_), onDevice(onDevice_) {}
+	HitStage list;   // the count, out_hits
+	uint64_t* dHits = nullptr;
+	FinalSelectStage(const FinalSelectOut& o_, bool onDevice_) : o(o_), list(onDevice_, o_.outHitCount, "hipMemcpy(hits)") {}
 	int Empty(hipStream_t stream);   // no strings: a count of 0 -- host pointers: no device is touched
 	int Results(BatchIO& io, uint64_t n);
 	int Launch(const uint8_t* fin, uint64_t n, hipStream_t stream);
-	int Back();                      // host pointers: the count, and the list only as far as it was written
+	int Back() { return list.Back(); }
 };
 // affix.hip: from prefix and suffix lengths to a compacted, ascending list of the strings that matched and the byte range of
 // the matched head, the matched tail or what they leave (pire_hip_affix_select).  Device pointers only, three kernels enqueued
@@ -1198,14 +1233,13 @@ int AffixSelectArgsInvalid(const char* who, uint64_t n, bool haveOffsets, bool h
 // Results() with its result arrays, io.Ready(), the scans, Launch(), io.Finish(), Back().
 struct AffixSelectStage {
 	const AffixSelectOut o;
-	const bool onDevice;
-	uint64_t *dCount = nullptr, *dHits = nullptr, *dSpans = nullptr;
-	uint64_t cap = 0, count = 0;   // host pointers: no list is staged longer than the strings are many; the count comes back here first
-	AffixSelectStage(const AffixSelectOut& o_, bool onDevice_) : o(o_), onDevice(onDevice_) {}
+	HitStage list;   // the count, out_hits, out_spans
+	uint64_t *dHits = nullptr, *dSpans = nullptr;
+	AffixSelectStage(const AffixSelectOut& o_, bool onDevice_) : o(o_), list(onDevice_, o_.outHitCount, "hipMemcpy(hits)") {}
 	int Empty(hipStream_t stream);   // no strings: a count of 0 -- host pointers: no device is touched
 	int Results(BatchIO& io, uint64_t n);
 	int Launch(const uint64_t* offsets, uint64_t n, const int64_t* headLen, const int64_t* tailLen, hipStream_t stream);
-	int Back();                      // host pointers: the count, and the lists only as far as they were written
+	int Back() { return list.Back(); }
 };
 // context.hip: from an ascending hit list to the ascending list of the lines within `after` lines behind or `before` lines in
 // front of a hit, and two bits a line (pire_hip_context).  Device pointers only -- hitCount included, nullable: k = hitCap --,

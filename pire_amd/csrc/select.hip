@@ -14,7 +14,9 @@
 //   scatter   rank of a selected string = tile offset + the popcounts of the waves in front + mbcnt of its own wave's
 //             ballot word: the hits come out in ascending order, deterministically, with no atomics.
 //
-// The block scan, the classify tail and the scatter head are compact.h's (BlockExclusive, TileBallot, TileRank).
+// The block scan and the classify tail are compact.h's (BlockExclusive, TileBallot); the scatter kernel and the launcher are
+// tile_pass.h's, shared with the seven passes that came after this one.  This unit also defines what they all call on the
+// host: the tile scan (LaunchTileScan), the launcher's front (TileCompaction) and the staging of a count and its lists (HitStage).
 // Three launches on the caller's stream, the shape of order.hip.  No block ever waits for another block (no look-back,
 // no flags between blocks): the order of the three kernels on the stream is the only synchronisation.
 //
@@ -26,21 +28,17 @@
 
 #include <algorithm>
 
-#include "compact.h"
-#include "internal.h"
+#include "tile_pass.h"
 
 namespace pirehip {
 
 namespace {
 
-constexpr uint32_t kSelThreads = kBlockThreads;    // one tile = 1 024 strings = 16 ballot words
-constexpr uint32_t kSelWaves = kBlockWaves;
 constexpr uint32_t kSelScanBlocks = 1024;          // the tile scan's grid: a block per row, rows in a grid-stride loop
 constexpr uint32_t kSelLdsStates = 8192;           // x 8 bytes = 64 KiB: two blocks a CU
 constexpr uint32_t kSelLdsBlocks = 512;            // the LDS form's grid: 2 blocks on each of 256 CUs, tiles in a grid-stride loop
-constexpr uint32_t kSelMaxBlocks = 8192;
 
-struct SelectParams {
+struct SelectPass {
 	const uint64_t* masks;   // [states * words], reference numbering
 	const uint8_t* fin;      // [states]
 	uint32_t states, words;
@@ -51,27 +49,33 @@ struct SelectParams {
 	uint32_t store16;        // outMasks is 16-byte aligned and words is even: pairs of words in one store
 	uint64_t* outHits;
 	uint64_t* outHitMasks;   // nullable
-	uint64_t hitCap;
-	uint64_t* ballots;       // [tiles * 16] selected bits, one word per wave
-	uint32_t* tileCounts;    // [tiles] selected strings per tile; after the scan: selected strings in front of the tile
-	uint32_t tiles;
+
+	__device__ __forceinline__ void Write(uint64_t rank, uint64_t i) const
+	{
+		outHits[rank] = i;
+		if (outHitMasks) {
+			const uint32_t s = stateIdx[i];
+			for (uint32_t w = 0; w < words; ++w)
+				outHitMasks[rank * words + w] = s < states ? masks[size_t(s) * words + w] : 0;
+		}
+	}
 };
 
 // A state index beyond the table (undefined behaviour of the ON_DEVICE form; the host-pointer form refuses it) reads
 // nothing: an empty mask, not selected.
 template <bool kLds>
-__global__ __launch_bounds__(kSelThreads) void SelectClassifyKernel(SelectParams p)
+__global__ __launch_bounds__(kBlockThreads) void SelectClassifyKernel(SelectPass p, TileScratch t)
 {
 	extern __shared__ uint64_t ldsMasks[];
-	__shared__ uint32_t waveCount[kSelWaves];
+	__shared__ uint32_t waveCount[kBlockWaves];
 	if (kLds) {
-		for (uint32_t s = threadIdx.x; s < p.states; s += kSelThreads)
+		for (uint32_t s = threadIdx.x; s < p.states; s += kBlockThreads)
 			ldsMasks[s] = p.masks[s];
 		__syncthreads();
 	}
 	const bool needMask = p.want || p.outMasks;
-	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
-		const uint64_t i = uint64_t(tile) * kSelThreads + threadIdx.x;
+	for (uint32_t tile = blockIdx.x; tile < t.tiles; tile += gridDim.x) {
+		const uint64_t i = uint64_t(tile) * kBlockThreads + threadIdx.x;
 		bool sel = false;
 		if (i < p.n) {
 			const uint32_t s = p.stateIdx[i];
@@ -111,20 +115,20 @@ __global__ __launch_bounds__(kSelThreads) void SelectClassifyKernel(SelectParams
 				}
 			}
 		}
-		TileBallot(sel, tile, p.ballots, p.tileCounts, waveCount);
+		TileBallot(sel, tile, t.ballots, t.tileCounts, waveCount);
 	}
 }
 
-// The tile scan of every hit pass (this unit, capture_select.hip, route.hip): exclusive scan of every row of
+// The tile scan of every hit pass (the eight ballot compactions through tile_pass.h, route.hip): exclusive scan of every row of
 // counts[rows][entries] in place, a block per row (grid-stride): 1 024 entries (2^20 strings) a step, a carry between the
 // steps.  A batch of 2^20 strings is one step; 2^24 strings, sixteen.  outCounts[r] = the total of row r.
-__global__ __launch_bounds__(kSelThreads) void SelectScanKernel(uint32_t* counts, uint32_t rows, uint32_t entries, uint64_t* outCounts)
+__global__ __launch_bounds__(kBlockThreads) void SelectScanKernel(uint32_t* counts, uint32_t rows, uint32_t entries, uint64_t* outCounts)
 {
-	__shared__ uint32_t waveSum[kSelWaves];
+	__shared__ uint32_t waveSum[kBlockWaves];
 	for (uint32_t r = blockIdx.x; r < rows; r += gridDim.x) {
 		uint32_t* row = counts + size_t(r) * entries;
 		uint32_t carry = 0;
-		for (uint32_t base = 0; base < entries; base += kSelThreads) {
+		for (uint32_t base = 0; base < entries; base += kBlockThreads) {
 			const uint32_t i = base + threadIdx.x;
 			uint32_t total;
 			const uint32_t front = BlockExclusive(i < entries ? row[i] : 0, waveSum, &total);
@@ -134,23 +138,6 @@ __global__ __launch_bounds__(kSelThreads) void SelectScanKernel(uint32_t* counts
 		}
 		if (threadIdx.x == 0)
 			outCounts[r] = carry;
-	}
-}
-
-__global__ __launch_bounds__(kSelThreads) void SelectScatterKernel(SelectParams p)
-{
-	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
-		bool selected;
-		const uint64_t rank = TileRank(tile, p.ballots, p.tileCounts, &selected);
-		if (selected && rank < p.hitCap) {
-			const uint64_t i = uint64_t(tile) * kSelThreads + threadIdx.x;
-			p.outHits[rank] = i;
-			if (p.outHitMasks) {
-				const uint32_t s = p.stateIdx[i];
-				for (uint32_t w = 0; w < p.words; ++w)
-					p.outHitMasks[rank * p.words + w] = s < p.states ? p.masks[size_t(s) * p.words + w] : 0;
-			}
-		}
 	}
 }
 
@@ -235,13 +222,13 @@ int UploadSelect(pire_hip_table* t, SelectDevice* image)
 
 void LaunchTileScan(uint32_t* counts, uint32_t rows, uint32_t entries, uint64_t* outCounts, hipStream_t stream)
 {
-	hipLaunchKernelGGL(SelectScanKernel, dim3(std::min(rows, kSelScanBlocks)), dim3(kSelThreads), 0, stream, counts, rows, entries, outCounts);
+	hipLaunchKernelGGL(SelectScanKernel, dim3(std::min(rows, kSelScanBlocks)), dim3(kBlockThreads), 0, stream, counts, rows, entries, outCounts);
 }
 
 int TileCompaction(const char* who, const char* scratchLabel, uint64_t n, uint64_t* outHitCount, hipStream_t stream, StreamScratch& scratch,
-                   uint32_t* tiles, uint64_t** ballots, uint32_t** tileCounts)
+                   TileScratch* s)
 {
-	*tiles = 0;
+	*s = TileScratch();
 	if (n == 0) {
 		const hipError_t e = hipMemsetAsync(outHitCount, 0, 8, stream);
 		return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemsetAsync(hit count)");
@@ -250,27 +237,44 @@ int TileCompaction(const char* who, const char* scratchLabel, uint64_t n, uint64
 		SetError(std::string(who) + ": 2^32 strings or more in one call");   // tile offsets are 32 bits (as order.hip's indices)
 		return PIRE_HIP_EUNSUPPORTED;
 	}
-	const uint32_t t = uint32_t((n + kSelThreads - 1) / kSelThreads);
+	const uint32_t t = uint32_t((n + kBlockThreads - 1) / kBlockThreads);
 	// scratch: n / 8 bytes of ballot words + n / 256 bytes of tile counts, stream-ordered (the call only enqueues)
-	const size_t ballotBytes = size_t(t) * kSelWaves * 8;
+	const size_t ballotBytes = size_t(t) * kBlockWaves * 8;
 	if (int rc = scratch.Alloc(ballotBytes + size_t(t) * 4, scratchLabel))
 		return rc;
-	*ballots = scratch.as<uint64_t>();
-	*tileCounts = reinterpret_cast<uint32_t*>(scratch.as<uint8_t>() + ballotBytes);
-	*tiles = t;
+	s->ballots = scratch.as<uint64_t>();
+	s->tileCounts = reinterpret_cast<uint32_t*>(scratch.as<uint8_t>() + ballotBytes);
+	s->tiles = t;
 	return PIRE_HIP_OK;
+}
+
+int HitStage::Count(BatchIO& io, uint64_t hitCap, uint64_t n)
+{
+	cap = onDevice ? hitCap : std::min<uint64_t>(hitCap, n);   // a host call stages no more
+	return io.Result(onDevice ? outCount : &count, 1, 1, &dCount);
+}
+
+int HitStage::Back()
+{
+	if (onDevice)
+		return PIRE_HIP_OK;
+	*outCount = count;
+	const uint64_t written = std::min<uint64_t>(count, cap);
+	hipError_t e = hipSuccess;
+	for (uint32_t k = 0; k < nLists && written && e == hipSuccess; ++k)
+		e = hipMemcpy(lists[k].host, lists[k].dev, size_t(written) * lists[k].width, hipMemcpyDeviceToHost);
+	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, backLabel);
 }
 
 int LaunchSelect(const SelectDevice& image, uint32_t states, uint32_t words, const uint32_t* stateIdx, uint64_t n,
                  const uint64_t* want, uint64_t* outMasks, uint64_t* outHits, uint64_t* outHitMasks, uint64_t hitCap,
                  uint64_t* outHitCount, hipStream_t stream)
 {
-	SelectParams p;
-	StreamScratch scratch(stream);
-	const int rc = TileCompaction("pire_hip_select", "hipMallocAsync(select scratch)", n, outHitCount, stream, scratch, &p.tiles, &p.ballots,
-	                              &p.tileCounts);
-	if (rc || !p.tiles)
+	TilePass t(stream);
+	const int rc = t.Front("pire_hip_select", "hipMallocAsync(select scratch)", n, outHitCount);
+	if (rc || !t.s.tiles)
 		return rc;
+	SelectPass p;
 	p.masks = image.masks;
 	p.fin = image.fin;
 	p.states = states;
@@ -282,25 +286,20 @@ int LaunchSelect(const SelectDevice& image, uint32_t states, uint32_t words, con
 	p.store16 = outMasks && words % 2 == 0 && reinterpret_cast<uintptr_t>(outMasks) % 16 == 0;
 	p.outHits = outHits;
 	p.outHitMasks = outHitMasks;
-	p.hitCap = outHits ? hitCap : 0;
 	// The LDS form reads states * 8 bytes per BLOCK to save 8 bytes per STRING: only where a block of the small grid
 	// walks at least twice as many strings as the table has states
-	const uint32_t ldsGrid = std::min(p.tiles, kSelLdsBlocks);
-	const uint64_t ldsStrings = uint64_t((p.tiles + ldsGrid - 1) / ldsGrid) * kSelThreads;
+	const uint32_t ldsGrid = std::min(t.s.tiles, kSelLdsBlocks);
+	const uint64_t ldsStrings = uint64_t((t.s.tiles + ldsGrid - 1) / ldsGrid) * kBlockThreads;
 	const bool lds = words == 1 && (want || outMasks) && states <= kSelLdsStates && ldsStrings >= 2ull * states;
 	if (lds) {
 		const hipError_t e = SetDynamicLds(reinterpret_cast<const void*>(SelectClassifyKernel<true>), kSelLdsStates * 8);
 		if (e != hipSuccess)
 			return HipFail(e, "hipFuncSetAttribute(LDS)");
-		hipLaunchKernelGGL(SelectClassifyKernel<true>, dim3(ldsGrid), dim3(kSelThreads), size_t(states) * 8, stream, p);
+		hipLaunchKernelGGL(SelectClassifyKernel<true>, dim3(ldsGrid), dim3(kBlockThreads), size_t(states) * 8, stream, p, t.s);
 	} else {
-		hipLaunchKernelGGL(SelectClassifyKernel<false>, dim3(std::min(p.tiles, kSelMaxBlocks)), dim3(kSelThreads), 0, stream, p);
+		hipLaunchKernelGGL(SelectClassifyKernel<false>, t.Grid(), dim3(kBlockThreads), 0, stream, p, t.s);
 	}
-	LaunchTileScan(p.tileCounts, 1, p.tiles, outHitCount, stream);
-	if (p.hitCap)
-		hipLaunchKernelGGL(SelectScatterKernel, dim3(std::min(p.tiles, kSelMaxBlocks)), dim3(kSelThreads), 0, stream, p);
-	const hipError_t e = hipGetLastError();
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "select launch");
+	return t.Tail(p, outHits ? hitCap : 0, outHitCount, "select launch");
 }
 
 }  // namespace pirehip

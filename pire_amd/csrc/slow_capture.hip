@@ -686,9 +686,8 @@ int SlowCaptureRunImpl(const char* who, pire_hip_slow_capture_table* t, const vo
 	if (outMatched && (rc = io.Result(outMatched, n, n, &p.outMatched)))
 		return rc;
 	StreamScratch ownPositions(stream), ownCaptured(stream);
-	const uint64_t cap = sel ? std::min<uint64_t>(sel->hitCap, n) : 0;
-	uint64_t count = 0;   // host pointers: the count comes back here first
-	uint64_t *dCount = nullptr, *dHits = nullptr, *dSpans = nullptr;
+	HitStage list(onDevice, sel ? sel->outHitCount : nullptr, "hipMemcpy(hits)");
+	uint64_t *dHits = nullptr, *dSpans = nullptr;
 	if (sel) {
 		if (onDevice && (!p.outBegin || !p.outEnd)) {
 			if ((rc = ownPositions.Alloc(size_t(n) * 16, "hipMallocAsync(slow capture positions)")))
@@ -703,14 +702,8 @@ int SlowCaptureRunImpl(const char* who, pire_hip_slow_capture_table* t, const vo
 				return rc;
 			p.outCaptured = ownCaptured.as<uint8_t>();
 		}
-		if ((rc = io.Result(onDevice ? sel->outHitCount : &count, 1, 1, &dCount)))
+		if ((rc = list.Count(io, sel->hitCap, n)) || (rc = list.List(io, sel->outHits, 1, &dHits)) || (rc = list.List(io, sel->outSpans, 2, &dSpans)))
 			return rc;
-		if (sel->outHits && cap)
-			if ((rc = io.Result(sel->outHits, size_t(cap), 0, &dHits)))
-				return rc;
-		if (sel->outSpans && cap)
-			if ((rc = io.Result(sel->outSpans, size_t(cap) * 2, 0, &dSpans)))
-				return rc;
 	}
 	if ((rc = io.Ready()))
 		return rc;
@@ -718,20 +711,11 @@ int SlowCaptureRunImpl(const char* who, pire_hip_slow_capture_table* t, const vo
 	if ((rc = Launch(SlowCaptureKernel, blocks, p.waves * 64, ldsBytes, stream, "slow capture kernel launch", p)))
 		return rc;
 	if (sel)
-		if ((rc = LaunchCaptureSelect(p.offsets, n, false, p.outBegin, p.outEnd, p.outCaptured, sel->shift, dHits, dSpans, cap, dCount, stream)))
+		if ((rc = LaunchCaptureSelect(p.offsets, n, false, p.outBegin, p.outEnd, p.outCaptured, sel->shift, dHits, dSpans, list.cap, list.dCount, stream)))
 			return rc;
 	if ((rc = io.Finish()))
 		return rc;
-	if (!sel || onDevice)
-		return PIRE_HIP_OK;
-	*sel->outHitCount = count;
-	const uint64_t written = std::min<uint64_t>(count, cap);
-	hipError_t e = hipSuccess;
-	if (written && dHits)
-		e = hipMemcpy(sel->outHits, dHits, size_t(written) * 8, hipMemcpyDeviceToHost);
-	if (e == hipSuccess && written && dSpans)
-		e = hipMemcpy(sel->outSpans, dSpans, size_t(written) * 16, hipMemcpyDeviceToHost);
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(hits)");
+	return sel ? list.Back() : PIRE_HIP_OK;
 }
 
 }  // namespace pirehip

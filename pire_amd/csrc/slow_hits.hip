@@ -12,9 +12,9 @@
 //   scatter   rank of a selected string = tile offset + the popcounts of the waves in front + mbcnt of its own wave's
 //             ballot word; the lane writes its index.
 //
-// The classify tail, the scatter head and the launcher's front are the select pass's (compact.h TileBallot / TileRank,
-// select.hip TileCompaction); this unit keeps its predicate and what a selected lane writes.  Launches on the caller's
-// stream, the shape of select.hip: no block waits for another block, no atomics (the same input gives the same bits).
+// Both kernels and the launcher are tile_pass.h's, the staging of the count and the list is internal.h's HitStage; this
+// unit keeps its predicate and what a selected lane writes (FinalPass).  Launches on the caller's stream, the shape of
+// select.hip: no block waits for another block, no atomics (the same input gives the same bits).
 // Plain HIP with compiler-placed waits: nothing here keeps data on its way in registers.  A flag is read with a byte load
 // (a wave reads 64 consecutive bytes, a tile 1 KiB): `final` may have any alignment.
 
@@ -22,72 +22,33 @@
 
 #include <algorithm>
 
-#include "compact.h"
-#include "internal.h"
+#include "tile_pass.h"
 
 namespace pirehip {
 
 namespace {
 
-constexpr uint32_t kFinThreads = kBlockThreads;   // one tile = 1 024 strings = 16 ballot words
-constexpr uint32_t kFinWaves = kBlockWaves;
-constexpr uint32_t kFinMaxBlocks = 8192;
-
-struct FinalSelectParams {
-	const uint8_t* fin;     // [n]
-	uint64_t n;
-	uint32_t invert;        // PIRE_HIP_FINAL_SELECT_ZERO
+struct FinalPass {
+	const uint8_t* fin;   // [n]
+	uint32_t invert;      // PIRE_HIP_FINAL_SELECT_ZERO
 	uint64_t* outHits;
-	uint64_t hitCap;
-	uint64_t* ballots;      // [tiles * 16] selected bits, one word per wave
-	uint32_t* tileCounts;   // [tiles] selected strings per tile; after the scan: selected strings in front of the tile
-	uint32_t tiles;
+
+	__device__ __forceinline__ bool Selected(uint64_t i) const { return (fin[i] != 0) != (invert != 0); }
+	__device__ __forceinline__ void Write(uint64_t rank, uint64_t i) const { outHits[rank] = i; }
 };
-
-__global__ __launch_bounds__(kFinThreads) void FinalClassifyKernel(FinalSelectParams p)
-{
-	__shared__ uint32_t waveCount[kFinWaves];
-	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
-		const uint64_t i = uint64_t(tile) * kFinThreads + threadIdx.x;
-		const bool live = i < p.n;
-		const bool set = live && p.fin[i] != 0;
-		TileBallot(live && set != (p.invert != 0), tile, p.ballots, p.tileCounts, waveCount);
-	}
-}
-
-__global__ __launch_bounds__(kFinThreads) void FinalScatterKernel(FinalSelectParams p)
-{
-	for (uint32_t tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
-		bool selected;
-		const uint64_t rank = TileRank(tile, p.ballots, p.tileCounts, &selected);
-		if (selected && rank < p.hitCap)   // (a selected bit: i < n)
-			p.outHits[rank] = uint64_t(tile) * kFinThreads + threadIdx.x;
-	}
-}
 
 }  // namespace
 
 int LaunchFinalSelect(const uint8_t* fin, uint64_t n, uint32_t mode, uint64_t* outHits, uint64_t hitCap, uint64_t* outHitCount,
                       hipStream_t stream)
 {
-	FinalSelectParams p;
-	StreamScratch scratch(stream);
-	const int rc = TileCompaction("pire_hip_final_select", "hipMallocAsync(final select scratch)", n, outHitCount, stream, scratch, &p.tiles,
-	                              &p.ballots, &p.tileCounts);
-	if (rc || !p.tiles)
+	TilePass t(stream);
+	const int rc = t.Front("pire_hip_final_select", "hipMallocAsync(final select scratch)", n, outHitCount);
+	if (rc || !t.s.tiles)
 		return rc;
-	p.fin = fin;
-	p.n = n;
-	p.invert = mode == PIRE_HIP_FINAL_SELECT_ZERO;
-	p.outHits = outHits;
-	p.hitCap = outHits ? hitCap : 0;
-	const dim3 grid(std::min(p.tiles, kFinMaxBlocks));
-	hipLaunchKernelGGL(FinalClassifyKernel, grid, dim3(kFinThreads), 0, stream, p);
-	LaunchTileScan(p.tileCounts, 1, p.tiles, outHitCount, stream);
-	if (p.hitCap)
-		hipLaunchKernelGGL(FinalScatterKernel, grid, dim3(kFinThreads), 0, stream, p);
-	const hipError_t e = hipGetLastError();
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "final select launch");
+	const FinalPass p = {fin, mode == PIRE_HIP_FINAL_SELECT_ZERO, outHits};
+	t.Classify(p, n);
+	return t.Tail(p, outHits ? hitCap : 0, outHitCount, "final select launch");
 }
 
 int FinalSelectArgsInvalid(const char* who, uint64_t n, bool haveFinal, const FinalSelectOut& o)
@@ -106,7 +67,7 @@ int FinalSelectArgsInvalid(const char* who, uint64_t n, bool haveFinal, const Fi
 
 int FinalSelectStage::Empty(hipStream_t stream)
 {
-	if (onDevice)
+	if (list.onDevice)
 		return LaunchFinalSelect(nullptr, 0, o.mode, nullptr, 0, o.outHitCount, stream);
 	*o.outHitCount = 0;
 	return PIRE_HIP_OK;
@@ -114,28 +75,14 @@ int FinalSelectStage::Empty(hipStream_t stream)
 
 int FinalSelectStage::Results(BatchIO& io, uint64_t n)
 {
-	cap = onDevice ? o.hitCap : std::min<uint64_t>(o.hitCap, n);   // n strings have at most n hits: a host call stages no more
-	if (int rc = io.Result(onDevice ? o.outHitCount : &count, 1, 1, &dCount))   // (host pointers: the count comes back here first)
+	if (int rc = list.Count(io, o.hitCap, n))
 		return rc;
-	if (o.outHits && cap)
-		if (int rc = io.Result(o.outHits, size_t(cap), 0, &dHits))
-			return rc;
-	return PIRE_HIP_OK;
+	return list.List(io, o.outHits, 1, &dHits);
 }
 
 int FinalSelectStage::Launch(const uint8_t* fin, uint64_t n, hipStream_t stream)
 {
-	return LaunchFinalSelect(fin, n, o.mode, dHits, cap, dCount, stream);
-}
-
-int FinalSelectStage::Back()
-{
-	if (onDevice)
-		return PIRE_HIP_OK;
-	*o.outHitCount = count;
-	const uint64_t written = std::min<uint64_t>(count, cap);
-	const hipError_t e = written && dHits ? hipMemcpy(o.outHits, dHits, size_t(written) * 8, hipMemcpyDeviceToHost) : hipSuccess;
-	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "hipMemcpy(hits)");
+	return LaunchFinalSelect(fin, n, o.mode, dHits, list.cap, list.dCount, stream);
 }
 
 }  // namespace pirehip

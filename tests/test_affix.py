@@ -468,9 +468,12 @@ def test_the_pass_names_no_kernel_and_reads_no_environment():
     with open(os.path.join(ROOT, "pire_amd", "csrc", "affix.hip")) as f:
         src = f.read()
     assert "NoteKernel" not in src and "getenv" not in src and "atomic" not in src.lower().replace("no atomics", "")
-    for shared in ("TileCompaction(", "TileBallot(", "TileRank(", "LaunchTileScan("):
+    for shared in ('#include "tile_pass.h"', "TilePass t(", "t.Front(", "t.Classify(", "t.Tail(", "list.Count(", "list.List("):
         assert shared in src, shared
     assert "__shfl" not in src and "__ballot" not in src and "BlockExclusive" not in src   # (the scan is select.hip's, not a copy)
+    # both kernels, the launcher and the copies back are the shared ones: the unit has a predicate and a Write, nothing else of a pass
+    for copy in ("__global__", "hipLaunchKernelGGL", "TileBallot(", "TileRank(", "LaunchTileScan(", "TileCompaction(", "hipGetLastError", "hipMemcpy"):
+        assert copy not in src, copy
 
 
 # ---- GPU: the harness ----------------------------------------------------------------------------------------------------
@@ -566,6 +569,27 @@ def call_pass(torch, device, host, dev, n, part, which, cap, hits, spans):
                                         out.ptr("spans") if cap else None, cap, out.ptr("count"), stream_of(torch) if device else None)
     assert rc == 0, pb.lib().pire_hip_last_error()
     return out
+
+
+@gpu
+def test_no_strings_from_host_pointers_and_on_the_device(torch_cuda):
+    """n == 0: a count of 0, whatever the capacity; no list is touched, on either side"""
+    torch = torch_cuda
+    host = (np.array([BASE], dtype=np.uint64), np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64))   # (somewhere to point)
+    dev = [torch.as_tensor(i64(a), device="cuda") for a in host]
+    calls = 0
+    for which in ("both", "head", "tail"):
+        hl, tl = given(which, host[1][:0], host[2][:0])
+        for part in TRUTH[which][1]:
+            exp = model_affix_select(host[0], hl, tl, part)
+            assert exp["count"] == 0 and exp["spans"].shape == (0, 2)
+            for cap in (0, 7):
+                for hits, spans in ((True, False), (False, True), (True, True)) if cap else ((False, False),):
+                    for device in (True, False):
+                        what = (which, part, cap, hits, spans, "device" if device else "host")
+                        call_pass(torch, device, host, dev, 0, part, which, cap, hits, spans).check(exp, what)
+                        calls += 1
+    assert calls == 7 * 4 * 2
 
 
 @gpu

@@ -349,9 +349,14 @@ def test_the_pass_names_no_kernel_and_reads_no_environment():
         src = f.read()
     assert "NoteKernel" not in src and "getenv" not in src and "asm" not in src
     assert "atomic" not in src.lower().replace("no atomics", "").replace("no atomic", "")
-    for shared in ("TileCompaction(", "TileBallot(", "TileRank(", "LaunchTileScan("):
+    # its own classify kernel between the shared launcher's front and tail, the shared search and stage
+    for shared in ('#include "tile_pass.h"', "TilePass t(", "t.Front(", "TileBallot(", "t.Tail(", "WaveBound<false>(", "LoadU64(",
+                   "list.Count(", "list.List(", "list.Back()"):
         assert shared in src, shared
     assert "BlockExclusive" not in src                                             # (the scan is select.hip's, not a copy)
+    assert src.count("__global__") == 1 and src.count("hipLaunchKernelGGL") == 1   # (the classify kernel; the scatter is the shared one)
+    for copy in ("TileRank(", "TileCompaction(", "LaunchTileScan(", "__shfl", "__ballot", "UnalignedU64", "hipGetLastError", "hipMemcpyDeviceToHost"):
+        assert copy not in src, copy
 
 
 # ---- GPU: the harness ----------------------------------------------------------------------------------------------------
@@ -518,6 +523,25 @@ def test_the_pass_alone_from_host_pointers_and_on_the_device(torch_cuda, n):
     for hl in hls.values():
         hl.intact()
     assert calls == 7 * 4 * 2 + 5 * 3 * 2
+
+
+@gpu
+def test_no_lines_from_host_pointers_and_on_the_device(torch_cuda):
+    """n == 0: a count of 0 under any truth table, whatever the capacity; no list is touched, on either side.  On the device a
+    list may stand there all the same (nothing of it is read)."""
+    torch = torch_cuda
+    empty, some = Hits(torch, []), Hits(torch, [0, 5, 9])
+    for k in (1, 3, 6):
+        for truth in (1, 2, (1 << (1 << k)) - 1):
+            exp = model_combine([[]] * k, 0, truth)
+            assert exp["count"] == 0
+            for hit_cap in (0, 4):
+                for members in (True, False):
+                    for device in (True, False):
+                        run_pass(torch, device, [empty] * k, 0, truth, hit_cap, exp, (k, hex(truth), hit_cap, members, device), members=members)
+                    run_pass(torch, True, [some] + [empty] * (k - 1), 0, truth, hit_cap, exp, (k, hex(truth), hit_cap, members, "a list"), members=members)
+    empty.intact()
+    some.intact()
 
 
 @gpu

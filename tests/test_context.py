@@ -307,9 +307,14 @@ def test_the_pass_names_no_kernel_and_reads_no_environment():
         src = f.read()
     assert "NoteKernel" not in src and "getenv" not in src
     assert "atomic" not in src.lower().replace("no atomics", "").replace("no atomic", "")
-    for shared in ("TileCompaction(", "TileBallot(", "TileRank(", "LaunchTileScan("):
+    # its own classify kernel between the shared launcher's steps, the second scan for the runs, the shared search and stage
+    for shared in ('#include "tile_pass.h"', "TilePass t(", "t.Front(", "TileBallot(", "t.Scan(", "LaunchTileScan(", "t.Scatter(", "t.Done(",
+                   "WaveBound<false>(", "LoadU64(", "list.Count(", "list.List(", "list.Back()"):
         assert shared in src, shared
     assert "BlockExclusive" not in src                                             # (the scan is select.hip's, not a copy)
+    assert src.count("__global__") == 1 and src.count("hipLaunchKernelGGL") == 1   # (the classify kernel; the scatter is the shared one)
+    for copy in ("TileRank(", "TileCompaction(", "__shfl", "UnalignedU64", "hipGetLastError", "hipMemcpyDeviceToHost"):
+        assert copy not in src, copy
 
 
 # ---- GPU: the harness ----------------------------------------------------------------------------------------------------
@@ -443,6 +448,23 @@ def test_the_pass_alone_from_host_pointers_and_on_the_device(torch_cuda, n):
         assert got[hl.dev_lead:hl.dev_lead + 8 * hl.k].tobytes() == u64(hits).tobytes(), "the list was written to"
         assert (got[:hl.dev_lead] == POISON).all() and (got[hl.dev_lead + 8 * hl.k:] == POISON).all(), "the list's surroundings were written to"
     assert calls == 8 * 6 * 2
+
+
+@gpu
+def test_no_lines_from_host_pointers_and_on_the_device(torch_cuda):
+    """n == 0: a line count and a run count of 0, whatever the window and the capacity; no list is touched, on either side.  On
+    the device a list may stand there all the same (nothing of it is read)."""
+    torch = torch_cuda
+    exp = model_context([], 0, 0, 0)
+    assert (exp["count"], exp["groups"]) == (0, 0)
+    for hl in (Hits(torch, []), Hits(torch, [0, 5, 9])):
+        for before, after in ((0, 0), (2, 1), (MAX64, MAX64)):
+            for line_cap in (0, 4):
+                for groups in (True, False):
+                    for device in (True, False) if hl.k == 0 else (True,):
+                        run_pass(torch, device, hl, 0, before, after, line_cap, exp, (hl.k, before, after, line_cap, groups, device), groups=groups)
+        hl_now = hl.dev_room.cpu().numpy()
+        assert (np.delete(hl_now, np.arange(hl.dev_lead, hl.dev_lead + 8 * hl.k)) == POISON).all(), "the list's surroundings were written to"
 
 
 @gpu

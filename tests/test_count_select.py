@@ -464,6 +464,29 @@ def test_the_pass_alone_on_synthetic_results(torch_cuda, n, R):
 
 
 @gpu
+@pytest.mark.parametrize("R", (1, 3))
+def test_no_strings_from_host_pointers_and_on_the_device(torch_cuda, R):
+    """n == 0: a count of 0 and R totals of 0, whatever the capacity; no list is touched, on either side"""
+    torch = torch_cuda
+    res = np.zeros((0, R), dtype=np.uint32)
+    room = np.zeros(4, dtype=np.uint32)                       # (somewhere to point: nothing of it is read)
+    dev_room = torch.zeros(4, dtype=torch.int32, device="cuda")
+    m = np.full(R, 2, dtype=np.uint32)
+    dev_min = torch.as_tensor(m.astype(np.int32), device="cuda")
+    for mins in (None, m):
+        for all_ in (False, True):
+            exp = model_count_select(res, mins, all_)
+            assert exp["count"] == 0 and exp["totals"].tolist() == [0] * R
+            for cap in (0, 5):
+                for device in (True, False):
+                    ptr = dev_room.data_ptr() if device else room.ctypes.data
+                    what = (R, None if mins is None else mins.tolist(), all_, cap, "device" if device else "host")
+                    call_pass(torch, device, res, ptr, mins, all_, cap, dev_min=dev_min).check(exp, what)
+                    call_pass(torch, device, res, ptr, mins, all_, cap, totals=False, dev_min=dev_min).check(exp, what)
+    assert not dev_room.cpu().numpy().any()
+
+
+@gpu
 def test_totals_beyond_32_bits(torch_cuda):
     torch = torch_cuda
     n = 2049
@@ -487,11 +510,17 @@ def test_totals_beyond_32_bits(torch_cuda):
 
 @gpu
 def test_more_tiles_than_the_grid_has_blocks(torch_cuda):
-    """8 192 blocks at the most walk the tiles (count_select.hip kCntMaxBlocks, as the siblings): 8 194 tiles, and a tile scan of
-    nine steps"""
+    """8 192 blocks at the most walk the tiles (compact.h kTileMaxBlocks behind tile_pass.h TilePass::Grid(), the grid of the unit's
+    classify kernels and of the shared scatter, as the siblings'): 8 194 tiles, and a tile scan of nine steps"""
     torch = torch_cuda
-    with open(os.path.join(ROOT, "pire_amd", "csrc", "count_select.hip")) as f:
-        assert re.search(r"kCntMaxBlocks = 8192;", f.read())
+    csrc = os.path.join(ROOT, "pire_amd", "csrc")
+    with open(os.path.join(csrc, "compact.h")) as f:
+        assert re.search(r"kTileMaxBlocks = 8192;", f.read())
+    with open(os.path.join(csrc, "tile_pass.h")) as f:
+        assert "dim3 Grid() const { return dim3(std::min(s.tiles, kTileMaxBlocks)); }" in f.read()
+    with open(os.path.join(csrc, "count_select.hip")) as f:
+        src = f.read()
+    assert src.count("hipLaunchKernelGGL(CountClassifyKernel<") == src.count(">, t.Grid(), dim3(kBlockThreads)") == 2
     n = (1 << 23) + 1025
     assert (n + 1023) // 1024 > 8192
     res = (np.arange(n) % 7 == 0).astype(np.uint32).reshape(n, 1)

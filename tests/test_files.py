@@ -328,9 +328,15 @@ def test_the_pass_names_no_kernel_and_reads_no_environment():
         src = f.read()
     assert "NoteKernel" not in src and "getenv" not in src
     assert "atomic" not in src.lower().replace("no atomics", "").replace("no atomic", "")
-    for shared in ("TileCompaction(", "TileBallot(", "TileRank(", "LaunchTileScan("):
+    # the shared kernel pair between the bounds and the locate kernel, the shared search and stage; the lines kernel scans its own row
+    for shared in ('#include "tile_pass.h"', "TilePass t(", "t.Front(", "t.Classify(", "t.Scan(", "t.Scatter(", "t.Done(", "LaunchTileScan(",
+                   "WaveBound<true>(", "LoadU64(", "list.Count(", "list.List(", "list.Back()"):
         assert shared in src, shared
     assert "BlockExclusive" not in src and "asm" not in src                        # (the scan is select.hip's; plain HIP)
+    assert src.count("__global__") == 3 and src.count("hipLaunchKernelGGL") == 3   # (bounds, locate, lines)
+    assert src.count("hipGetLastError") == 1                                       # (the lines launcher's)
+    for copy in ("TileBallot(", "TileRank(", "TileCompaction(", "__shfl", "UnalignedU64", "hipMemcpyDeviceToHost"):
+        assert copy not in src, copy
     before = pb.lib().pire_hip_last_kernel()
     assert pb.files_host([], 0, [0])["count"] == 0 and pb.lib().pire_hip_last_kernel() == before
 
@@ -409,6 +415,21 @@ def test_the_pass_alone_from_host_pointers_and_on_the_device(torch_cuda, n):
         assert got[hl.dev_lead:hl.dev_lead + 8 * hl.k].tobytes() == u64(hits).tobytes(), "the list was written to"
         assert (got[:hl.dev_lead] == POISON).all() and (got[hl.dev_lead + 8 * hl.k:] == POISON).all(), "the list's surroundings were written to"
     assert calls == 7 * 4 * 2 * 2
+
+
+@gpu
+def test_no_files_from_host_pointers_and_on_the_device(torch_cuda):
+    """files == 0 (and so n == 0, and no hits): a file count of 0 and first[0] = 0, in either mode; no list is touched"""
+    torch = torch_cuda
+    hl, bd = TC.Hits(torch, []), Bounds(torch, [0])
+    assert bd.files == 0
+    for without in (False, True):
+        exp = model_files([], bd.np, without)
+        assert exp["count"] == 0 and exp["first"].tolist() == [0]
+        for null in ((), ("first",), ("first", "files")):
+            for device in (True, False):
+                run_pass(torch, device, hl, 0, bd, exp, (without, null, "device" if device else "host"), without=without, null=null)
+    assert bd.t.cpu().numpy().tolist() == [0]
 
 
 def hand_bounds():

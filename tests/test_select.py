@@ -409,7 +409,7 @@ def _state_pool(t, o, big):
 
 
 @gpu
-@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 1023, 1024, 1025, (1 << 20) + 37])
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 1023, 1024, 1025, 2049, (1 << 20) + 37])
 @pytest.mark.parametrize("table", ["set_a", "inline_glue3"])
 def test_edge_sizes(torch_cuda, table, n):
     """set_a (4 552 states: the masks are gathered from memory) and inline_glue3 (92 states: the large batch takes the
@@ -423,7 +423,7 @@ def test_edge_sizes(torch_cuda, table, n):
     for want in (None, [1], [0, 2]):
         exp = expected_select(t, idx, want)
         check(dev_select(torch, t, idx, want), exp)
-    if n in (65, 1025):
+    if n in (65, 1025, 2049):
         check(t.select(idx, want=[1]), expected_select(t, idx, [1]))   # host pointers
 
 

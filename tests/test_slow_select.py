@@ -359,9 +359,29 @@ def test_the_pass_names_no_kernel_and_reads_no_environment():
     with open(os.path.join(ROOT, "pire_amd", "csrc", "slow_hits.hip")) as f:
         src = f.read()
     assert "NoteKernel" not in src and "getenv" not in src and "atomic" not in src.lower().replace("no atomics", "")
-    for shared in ("TileCompaction(", "TileBallot(", "TileRank(", "LaunchTileScan("):
+    for shared in ('#include "tile_pass.h"', "TilePass t(", "t.Front(", "t.Classify(", "t.Tail(", "list.Count(", "list.List("):
         assert shared in src, shared
     assert "__shfl" not in src and "__ballot" not in src and "BlockExclusive" not in src   # (the scan is select.hip's, not a copy)
+    # both kernels, the launcher and the copies back are the shared ones: the unit has a predicate and a Write, nothing else of a pass
+    for copy in ("__global__", "hipLaunchKernelGGL", "TileBallot(", "TileRank(", "LaunchTileScan(", "TileCompaction(", "hipGetLastError", "hipMemcpy"):
+        assert copy not in src, copy
+
+
+def test_the_copy_back_of_a_hit_list_has_two_homes():
+    """"The lists come back only as far as they were written" is HitStage::Back (select.hip) and its row-pitch form HitsBack
+    (api.cpp): none of the eight hit passes copies from the device on its own, nor do the two scans that stage a capture pass."""
+    csrc = os.path.join(ROOT, "pire_amd", "csrc")
+    units = ("select.hip", "capture_select.hip", "count_select.hip", "slow_hits.hip", "affix.hip", "context.hip", "files.hip", "combine.hip")
+    for unit in units + ("slow_capture.hip",):
+        with open(os.path.join(csrc, unit)) as f:
+            src = f.read()
+        assert src.count("hipMemcpyDeviceToHost") == (1 if unit == "select.hip" else 0), unit
+    with open(os.path.join(csrc, "select.hip")) as f:
+        back = f.read().split("int HitStage::Back()")[1].split("\n}\n")[0]
+    assert "hipMemcpyDeviceToHost" in back and "std::min<uint64_t>(count, cap)" in back
+    with open(os.path.join(csrc, "api.cpp")) as f:
+        api = f.read()
+    assert api.count("const uint64_t written = std::min(") == 2   # HitsBack, and the gather's offsets in LinesFrame::Close
 
 
 # ---- GPU: the harness ----------------------------------------------------------------------------------------------------
@@ -420,7 +440,7 @@ def stream_of(torch):
 
 # ---- GPU: the pass alone -----------------------------------------------------------------------------------------------------
 
-SIZES = (1, 63, 64, 65, 1023, 1024, 1025, (1 << 20) + 1025)   # the last: 1 026 tiles, the tile scan carries between two steps
+SIZES = (1, 63, 64, 65, 1023, 1024, 1025, 2049, (1 << 20) + 1025)   # the last: 1 026 tiles, the tile scan carries between two steps
 PATTERNS = ("none", "all", "every third", "only the last", "lane 0 of every wave")
 
 
@@ -443,7 +463,7 @@ def test_the_pass_alone_on_flags_written_by_the_test(torch_cuda, n):
     """The classify kernel loads its flags byte by byte: no alignment cases.  The flags lie 3 bytes behind a 16-byte boundary
     all the same, on the host and on the device."""
     torch = torch_cuda
-    assert (n + 1023) // 1024 > 1024 or n <= 1025
+    assert (n + 1023) // 1024 > 1024 or n <= 2049
     room = np.zeros(n + 32, dtype=np.uint8)
     lead = 3 + (-room.ctypes.data % 16)
     fin = room[lead:lead + n]
@@ -483,6 +503,24 @@ def test_the_pass_alone_on_flags_written_by_the_test(torch_cuda, n):
     torch.cuda.synchronize()
     exp = model_final_select(fin)
     assert cnt.cpu().tolist() == [exp["count"]] * 2 and (lists.cpu().numpy()[:, :exp["count"]] == exp["hits"].astype(np.int64)).all()
+
+
+@gpu
+def test_no_strings_from_host_pointers_and_on_the_device(torch_cuda):
+    """n == 0: a count of 0 in either mode, whatever the capacity; the list is not touched, on either side"""
+    torch = torch_cuda
+    room = np.zeros(16, dtype=np.uint8)                       # (somewhere to point: nothing of it is read)
+    dev_room = torch.zeros(16, dtype=torch.uint8, device="cuda")
+    for mode in (0, ZERO):
+        exp = model_final_select(room[:0], mode == ZERO)
+        assert exp["count"] == 0
+        for cap in (0, 7):
+            for device in (True, False):
+                out = Outs(torch, device, cap)
+                rc = pb.lib().pire_hip_final_select(dev_room.data_ptr() if device else room.ctypes.data, 0, mode, pb.FLAG_ON_DEVICE if device else 0,
+                                                    out.ptr("hits") if cap else None, cap, out.ptr("count"), stream_of(torch) if device else None)
+                assert rc == 0, pb.lib().pire_hip_last_error()
+                out.check(exp, (mode, cap, "device" if device else "host"))
 
 
 @gpu
