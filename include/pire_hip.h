@@ -1308,6 +1308,72 @@ int pire_hip_affix_lines_gather(pire_hip_table* head, uint32_t head_opts, pire_h
                                 void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes,
                                 void* stream);
 
+/* ---- where the match lies: leftmost-longest spans, on the device ------------------------------------------------------ */
+
+#define PIRE_HIP_SEARCH_SHORTEST 1u        /* S: the forward leg is ShortestPrefix; without it LongestPrefix */
+#define PIRE_HIP_SEARCH_THROUGH_BEGIN 2u   /* B: the reference's throughBeginMark */
+#define PIRE_HIP_SEARCH_THROUGH_END 4u     /* E: the reference's throughEndMark */
+
+/*
+ * Where the leftmost-longest match of a regexp `re` lies inside every string of a batch: two searches of the reference's
+ * run.h, composed in ONE launch.  The caller holds two Pire::Scanners that are not Surround()ed, as tables:
+ *   fwd (F)  compiled from `re`
+ *   rev (R)  compiled from Fsm::Reverse() of `re` followed by `.*`
+ * For string i = text[offsets[i], offsets[i+1]) of length len_i (offsets[i+1] < offsets[i]: a string of length 0, as in
+ * pire_hip_affix_select), with the bits of opts B = THROUGH_BEGIN, E = THROUGH_END, S = SHORTEST:
+ *   t_i   = LongestSuffix(R, string i, throughEndMark = E, throughBeginMark = B)     length, or -1          run.h:313-341
+ *   b_i   = len_i - t_i                                                              the leftmost start
+ *   h_i   = S ? ShortestPrefix(F, string i from b_i, throughBeginMark = B && b_i == 0, throughEndMark = E)
+ *             : LongestPrefix (F, string i from b_i, ...the same...)                 length, or -1          run.h:277-311
+ *   found(i) = t_i >= 0 && h_i >= 0
+ *   begin[i] = found ? b_i : -1        end[i] = found ? b_i + h_i : -1              positions inside the string
+ * An empty match is a match: begin == end.  The semantics are POSIX's leftmost-longest, not the leftmost-first of
+ * backtracking engines: `abc|abcabc|b+` on `abcabc` gives [0, 6).  t_i >= 0 with h_i < 0 can only happen when the two tables
+ * do not belong together; the string is then not found, and nothing else is promised for such a pair.  rev and fwd may be
+ * the same table.
+ * out_begin[n], out_end[n] (required): written for all n strings.  n < 2^32.
+ * flags: PIRE_HIP_RUN_ON_DEVICE -> text, offsets and the outputs are device pointers and the call only enqueues on `stream`:
+ *        one kernel, one string per lane, 1 024-thread blocks that hold both tables' dense rows in LDS.  Otherwise host
+ *        pointers: the batch is staged once and the call synchronises.
+ * PIRE_HIP_EINVAL before any device is touched: null rev or fwd; unknown bits in opts; n > 0 with null text or offsets; null
+ * out_begin or out_end; n >= 2^32.  PIRE_HIP_EUNSUPPORTED before anything is launched where the two tables' dense rows do
+ * not fit the LDS of a block (two tables of 255 dense rows take 137 312 bytes; not on a device with 160 KiB).
+ * pire_hip_last_kernel() is not changed by the search.  No first-use self-test.
+ */
+int pire_hip_search(pire_hip_table* rev, pire_hip_table* fwd, uint32_t opts,
+                    const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
+                    int64_t* out_begin, int64_t* out_end, void* stream);
+
+/*
+ * pire_hip_search and, behind it on the same stream, pire_hip_capture_select without the BeginMark shift and without
+ * need_final: begin[i] and end[i] are exactly that pass's input -- found <=> both >= 0, spans clamped into the string.
+ * out_begin[n], out_end[n] (nullable): what the search wrote; what the caller has no array for lives in stream-ordered
+ * scratch of the library's own.  out_hits, out_spans, hit_cap, out_hit_count: as pire_hip_capture_select.  With host
+ * pointers the batch is staged once, and the search and the pass run on the staged copy before anything comes back.  It
+ * refuses what pire_hip_search refuses (the null result arrays excepted) and what pire_hip_capture_select refuses of its
+ * outputs.
+ */
+int pire_hip_search_run_select(pire_hip_table* rev, pire_hip_table* fwd, uint32_t opts,
+                    const void* text, const uint64_t* offsets, uint64_t n, uint32_t flags,
+                    int64_t* out_begin, int64_t* out_end,
+                    uint64_t* out_hits, uint64_t* out_spans, uint64_t hit_cap, uint64_t* out_hit_count, void* stream);
+
+/*
+ * Raw bytes in, the first (leftmost-longest) match of every line that has one out -- with tail_byte = delim, `grep -o` for
+ * the first match of each line.  The split into scratch, the search on the lines, the pass -- its spans counted in raw: line
+ * i of the split buffer lies i bytes further into raw --, the gather from raw through them.  rev, fwd, opts: as
+ * pire_hip_search.  Everything else as pire_hip_capture_lines_gather: out_line_count, delim, the one synchronisation of
+ * `stream`, the refusal of 2^32 lines (PIRE_HIP_EUNSUPPORTED); out_hits (nullable): the numbers of the lines with a match;
+ * out_spans (nullable): byte ranges of raw; tail_byte (the gather's `tail`), out_text, text_cap, out_offsets (hit_cap + 1
+ * entries), out_bytes: as pire_hip_gather_spans.  All four gather outputs null (text_cap == 0): spans only, the gather is
+ * skipped.  flags: PIRE_HIP_RUN_ON_DEVICE; the marks are opts', other bits are ignored.  Host pointers with size == 0: zeros (out_offsets[0] = 0 where it is not
+ * null), no device is touched.
+ */
+int pire_hip_search_lines_gather(pire_hip_table* rev, pire_hip_table* fwd, uint32_t opts,
+                    const void* raw, uint64_t size, uint32_t delim, uint32_t flags, uint32_t tail_byte,
+                    uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_spans, uint64_t hit_cap, uint64_t* out_hit_count,
+                    void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes, void* stream);
+
 /* ---- the strings that count, on the device ---------------------------------------------------------------------- */
 
 /*

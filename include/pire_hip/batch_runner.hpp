@@ -2531,6 +2531,162 @@ private:
 	std::string m_hitText;
 };
 
+/*
+ * Where the leftmost-longest match lies: Pire::LongestSuffix (run.h:313-341) through a scanner compiled from Fsm::Reverse() of
+ * `re` followed by anything, then Pire::LongestPrefix (run.h:277-311; ShortestPrefix with PIRE_HIP_SEARCH_SHORTEST) through the
+ * scanner of `re` from where the first search ended -- on the device, both in one launch (include/pire_hip.h, "where the match
+ * lies").  Neither scanner is Surround()ed; the options are PIRE_HIP_SEARCH_* bits.
+ *     Pire::Hip::SearchBatchRunner<Pire::Scanner> find(reversedTail, forward);
+ *     find.Run(text, offsets, n);      find.Run(strings);
+ *     find.Select();   (optional: Run() alone is enough)
+ *     find.Hits()      ascending indices of the strings with a match       find.HitCount()  how many
+ *     find.Spans()     [2 * k], [2 * k + 1]: the match of hit k is text[begin, end)
+ * A buffer as it was read, cut into lines on the device (pire_hip_search_lines_gather; getline's semantics, as
+ * BatchRunner::RunLines()): `grep -o` for the first match of each line:
+ *     find.RunLines(raw, size, '\n');
+ *     find.Spans()     byte ranges of raw                                  find.LineCount()  lines in the buffer
+ *     find.HitText()   the matches back to back, '\n' (or the byte given) behind each, gathered on the device
+ *     find.HitTextOffsets()   match k is HitText()[o[k], o[k + 1])
+ * The caller's arrays are read when an accessor first asks: they live until then.  HitText() is a call of its own, as in
+ * BatchRunner: after Hits() / Spans() it scans the buffer a second time.
+ */
+template <class Scanner>
+class SearchBatchRunner {
+public:
+	SearchBatchRunner(const Scanner& reversedTail, const Scanner& forward, uint32_t opts = 0)
+	    : m_rev(reversedTail), m_fwd(forward), m_opts(opts), m_form(kNone), m_text(nullptr), m_offsets(nullptr), m_n(0), m_len(0), m_delim('\n'),
+	      m_listed(false), m_haveText(false), m_textTail('\n'), m_hitCount(0), m_lineCount(0)
+	{
+	}
+
+	/* The batch: string i = text[offsets[i], offsets[i+1]).  Host pointers. */
+	SearchBatchRunner& Run(const char* text, const uint64_t* offsets, size_t n) { return SetBatch(kStrings, text, offsets, n, 0, '\n'); }
+	SearchBatchRunner& Run(const std::vector<ystring>& strings)
+	{
+		m_ownStrings.Assign(strings);
+		return Run(m_ownStrings.Text(), m_ownStrings.Offsets(), strings.size());
+	}
+	/* the strings with a match and where it lies: what Hits() / Spans() answer (there is one selection; the call is AffixBatchRunner's idiom) */
+	SearchBatchRunner& Select() { return *this; }
+	SearchBatchRunner& RunLines(const char* raw, size_t size, char delim = '\n') { return SetBatch(kLines, raw, nullptr, 0, size, delim); }
+	uint64_t HitCount() { FetchHits(); return m_hitCount; }
+	const std::vector<uint64_t>& Hits() { FetchHits(); return m_hits; }
+	const std::vector<uint64_t>& Spans() { FetchHits(); return m_spans; }
+	uint64_t LineCount() { NeedLines("LineCount()"); FetchHits(); return m_lineCount; }
+	const std::string& HitText(char tail = '\n') { FetchHitText(tail); return m_hitText; }
+	const std::vector<uint64_t>& HitTextOffsets()
+	{
+		if (!m_haveText)
+			FetchHitText('\n');
+		return m_hitTextOffsets;
+	}
+
+private:
+	SearchBatchRunner(const SearchBatchRunner&);
+	SearchBatchRunner& operator=(const SearchBatchRunner&);
+
+	enum Form { kNone, kStrings, kLines };
+	SearchBatchRunner& SetBatch(Form form, const char* text, const uint64_t* offsets, size_t n, size_t len, char delim)
+	{
+		m_form = form, m_text = text, m_offsets = offsets, m_n = n, m_len = len, m_delim = uint8_t(delim);
+		m_listed = m_haveText = false;
+		return *this;
+	}
+	void NeedLines(const char* what) const
+	{
+		if (m_form != kLines)
+			throw Pire::Error(std::string("pire_hip: ") + what + " follows RunLines()");
+	}
+
+	/* One call with room for every string -- RunLines(): for a hit on every line of 64 bytes or more, BatchRunner's first
+	 * capacity --, and a second one where there are more */
+	void FetchHits()
+	{
+		if (m_listed)
+			return;
+		if (m_form == kNone)
+			throw Pire::Error("pire_hip: Hits() follows Run() or RunLines()");
+		GrowAndRetry(m_form == kLines ? m_len / 64 + 1024 : m_n, [&](size_t cap) {
+			m_hits.resize(cap);
+			m_spans.resize(cap * 2);
+			Check(m_form == kLines
+			          ? pire_hip_search_lines_gather(m_rev.Handle(), m_fwd.Handle(), m_opts, m_text, m_len, m_delim, 0, PIRE_HIP_GATHER_NO_TAIL,
+			                                         &m_lineCount, m_hits.data(), m_spans.data(), cap, &m_hitCount, nullptr, 0, nullptr, nullptr,
+			                                         nullptr)
+			          : pire_hip_search_run_select(m_rev.Handle(), m_fwd.Handle(), m_opts, m_text, OwnedStrings::OffsetsOr(m_offsets, m_n), m_n, 0,
+			                                       nullptr, nullptr, m_hits.data(), m_spans.data(), cap, &m_hitCount, nullptr));
+			return size_t(m_hitCount);
+		});
+		m_hits.resize(m_hitCount);
+		m_spans.resize(m_hitCount * 2);
+		m_listed = true;
+	}
+
+	/* RunLines(): the matches as bytes; room for every byte they can have, and for the hits that are known, or else FetchHits()'s */
+	void FetchHitText(char tail)
+	{
+		NeedLines("HitText()");
+		if (m_haveText && m_textTail == tail)
+			return;
+		uint64_t count = 0, bytes = 0;
+		GrowAndRetry(m_listed ? size_t(m_hitCount) : m_len / 64 + 1024, [&](size_t cap) {
+			m_hitTextOffsets.resize(cap + 1);
+			m_hitText.resize(m_len + cap + 1);
+			Check(pire_hip_search_lines_gather(m_rev.Handle(), m_fwd.Handle(), m_opts, m_text, m_len, m_delim, 0, uint8_t(tail), &m_lineCount,
+			                                   nullptr, nullptr, cap, &count, &m_hitText[0], m_hitText.size(), m_hitTextOffsets.data(), &bytes,
+			                                   nullptr));
+			return size_t(count);   // (the text has room for the whole buffer and a tail per hit: where the hits fit, the bytes do)
+		});
+		m_hitText.resize(bytes);
+		m_hitTextOffsets.resize(count + 1);
+		m_textTail = tail;
+		m_haveText = true;
+	}
+
+	Table<Scanner> m_rev, m_fwd;
+	uint32_t m_opts;
+	Form m_form;
+	const char* m_text;           // Run(): the strings' text; RunLines(): the raw buffer of m_len bytes
+	const uint64_t* m_offsets;
+	size_t m_n, m_len;
+	uint8_t m_delim;
+	bool m_listed, m_haveText;    // m_hits, m_spans (and m_lineCount) / m_hitText are the batch's, with the tail m_textTail
+	char m_textTail;
+	OwnedStrings m_ownStrings;
+	uint64_t m_hitCount, m_lineCount;
+	std::vector<uint64_t> m_hits, m_spans, m_hitTextOffsets;
+	std::string m_hitText;
+};
+
+/*
+ * Both scanners of a search from ONE Pire::Fsm (not Surround()ed), and the runner over them:
+ *     Pire::Hip::MatchFinder find(Pire::Lexer("[0-9]+").Parse());
+ *     find.Runner().RunLines(raw, size).HitText();
+ *   Forward()        the Fsm, compiled                                                     (pattern `re`)
+ *   ReversedTail()   the Fsm + the lexer's `.*`, then Fsm::Reverse(), compiled             (pattern `(re).*`, reversed)
+ * The tail is the LEXER's `.*` and not Fsm::AppendAnything(): that one loops on every letter, BeginMark and EndMark included
+ * (fsm.cpp:1184-1196), and is another language wherever `re` takes a mark.
+ */
+class MatchFinder {
+public:
+	explicit MatchFinder(Pire::Fsm fsm, uint32_t opts = 0)
+	    : m_fwd(Pire::Fsm(fsm).Compile<Pire::Scanner>()), m_rev(Tail(fsm).Reverse().Compile<Pire::Scanner>()), m_runner(m_rev, m_fwd, opts)
+	{
+	}
+	const Pire::Scanner& Forward() const { return m_fwd; }
+	const Pire::Scanner& ReversedTail() const { return m_rev; }
+	SearchBatchRunner<Pire::Scanner>& Runner() { return m_runner; }
+
+private:
+	static Pire::Fsm Tail(const Pire::Fsm& fsm)
+	{
+		static const char kAny[] = ".*";
+		return fsm + Pire::Lexer(kAny, kAny + 2).Parse();
+	}
+	Pire::Scanner m_fwd, m_rev;   // (declared before the runner that reads them)
+	SearchBatchRunner<Pire::Scanner> m_runner;
+};
+
 }  // namespace Hip
 }  // namespace Pire
 

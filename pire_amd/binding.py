@@ -151,6 +151,7 @@ FILES_WITHOUT = 1   # include/pire_hip.h PIRE_HIP_FILES_WITHOUT (`file_mode`): l
 FIELDS_REST = 1   # include/pire_hip.h PIRE_HIP_FIELDS_REST (in `mode`): the span runs to the end of the string, `cut -f k-`
 AFFIX_HEAD, AFFIX_TAIL, AFFIX_REST = 0, 1, 2   # include/pire_hip.h PIRE_HIP_AFFIX_HEAD / _TAIL / _REST (`part`)
 AFFIX_LONGEST, AFFIX_THROUGH_BEGIN, AFFIX_THROUGH_END = 1, 2, 4   # include/pire_hip.h PIRE_HIP_AFFIX_* (`head_opts`, `tail_opts`)
+SEARCH_SHORTEST, SEARCH_THROUGH_BEGIN, SEARCH_THROUGH_END = 1, 2, 4   # include/pire_hip.h PIRE_HIP_SEARCH_* (`opts`)
 
 # every symbol include/pire_hip.h declares: (name, restype, argtypes)
 ABI = [
@@ -271,6 +272,9 @@ ABI = [
     ("pire_hip_affix_select", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_affix_run_select", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_affix_lines_gather", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_search", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_search_run_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_search_lines_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_context", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_run_lines_context_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_run_lines_context_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -930,6 +934,94 @@ def affix_lines_gather_device(head, tail, raw_ptr: int, size: int, out_line_coun
                                              FLAG_ON_DEVICE, _tail(delim if tail_byte == -1 else tail_byte), out_line_count_ptr or None,
                                              out_hits_ptr or None, out_spans_ptr or None, hit_cap, out_hit_count_ptr or None,
                                              out_text_ptr or None, text_cap, out_offsets_ptr or None, out_bytes_ptr or None, stream or None))
+
+
+# --- where the match lies: leftmost-longest spans (pire_hip_search and the forms on top of it).  rev: the Table of the
+# reversed `(re).*`, fwd: the Table of `re`.
+def search_opts(shortest=False, through_begin=False, through_end=False) -> int:
+    """the PIRE_HIP_SEARCH_* bits"""
+    return (SEARCH_SHORTEST if shortest else 0) | (SEARCH_THROUGH_BEGIN if through_begin else 0) | (SEARCH_THROUGH_END if through_end else 0)
+
+
+def search(rev, fwd, text, offsets, opts=0):
+    """pire_hip_search on host strings: (begin i64[n], end i64[n])."""
+    text = _raw_bytes(text)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    begin, end = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64)
+    _check(lib().pire_hip_search(_table_ptr(rev), _table_ptr(fwd), opts, text.ctypes.data if text.size else None, offsets.ctypes.data, n, 0,
+                                 begin.ctypes.data, end.ctypes.data, None))
+    return begin, end
+
+
+def search_device(rev, fwd, text_ptr: int, offsets_ptr: int, n: int, out_begin_ptr: int, out_end_ptr: int, opts=0, stream: int = 0):
+    """pire_hip_search on device pointers: only enqueues on `stream`."""
+    _check(lib().pire_hip_search(_table_ptr(rev), _table_ptr(fwd), opts, text_ptr or None, offsets_ptr or None, n, FLAG_ON_DEVICE,
+                                 out_begin_ptr or None, out_end_ptr or None, stream or None))
+
+
+def search_run_select(rev, fwd, text, offsets, opts=0, hit_cap: Optional[int] = None, positions=True):
+    """pire_hip_search_run_select on host strings: {"hits", "spans", "count"} and, with positions, {"begin", "end"}; without,
+    the library keeps those arrays to itself."""
+    text = _raw_bytes(text)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    cap = n if hit_cap is None else int(hit_cap)
+    begin = np.empty(n, dtype=np.int64) if positions else None
+    end = np.empty(n, dtype=np.int64) if positions else None
+    hits = np.zeros(cap, dtype=np.uint64)
+    spans = np.zeros((cap, 2), dtype=np.uint64)
+    cnt = C.c_uint64(0)
+    _check(lib().pire_hip_search_run_select(_table_ptr(rev), _table_ptr(fwd), opts, text.ctypes.data if text.size else None, offsets.ctypes.data,
+                                            n, 0, _np_ptr(begin), _np_ptr(end), hits.ctypes.data if cap else None,
+                                            spans.ctypes.data if cap else None, cap, C.byref(cnt), None))
+    k = min(int(cnt.value), cap)
+    out = {"hits": hits[:k], "spans": spans[:k], "count": int(cnt.value)}
+    if positions:
+        out.update(begin=begin, end=end)
+    return out
+
+
+def search_run_select_device(rev, fwd, text_ptr: int, offsets_ptr: int, n: int, out_hit_count_ptr: int, opts=0, out_begin_ptr=0,
+                             out_end_ptr=0, out_hits_ptr=0, out_spans_ptr=0, hit_cap=0, stream: int = 0):
+    """pire_hip_search_run_select on device pointers: only enqueues on `stream`."""
+    _check(lib().pire_hip_search_run_select(_table_ptr(rev), _table_ptr(fwd), opts, text_ptr or None, offsets_ptr or None, n, FLAG_ON_DEVICE,
+                                            out_begin_ptr or None, out_end_ptr or None, out_hits_ptr or None, out_spans_ptr or None, hit_cap,
+                                            out_hit_count_ptr or None, stream or None))
+
+
+def search_lines_gather_host(rev, fwd, raw, opts=0, delim: int = 10, tail_byte=-1, hit_cap=None, text_cap=None, gather=True):
+    """pire_hip_search_lines_gather on a host buffer: {"lines", "hits", "spans", "count"} and, with gather, {"text", "offsets",
+    "bytes"}.  tail_byte -1 = the delimiter, None = none; hit_cap None = room for a hit on every line, text_cap None = for all
+    of them."""
+    raw = _raw_bytes(raw)
+    cap = raw.size if hit_cap is None else int(hit_cap)
+    room = (raw.size + cap if text_cap is None else int(text_cap)) if gather else 0
+    hits = np.zeros(cap, dtype=np.uint64)
+    spans = np.zeros((cap, 2), dtype=np.uint64)
+    text = np.zeros(max(room, 1), dtype=np.uint8)
+    offsets = np.zeros(cap + 1, dtype=np.uint64)
+    lines, cnt, total = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    _check(lib().pire_hip_search_lines_gather(_table_ptr(rev), _table_ptr(fwd), opts, raw.ctypes.data if raw.size else None, raw.size, delim, 0,
+                                              _tail(delim if tail_byte == -1 else tail_byte), C.byref(lines),
+                                              hits.ctypes.data if cap else None, spans.ctypes.data if cap else None, cap, C.byref(cnt),
+                                              text.ctypes.data if room else None, room, offsets.ctypes.data if gather else None,
+                                              C.byref(total) if gather else None, None))
+    k = min(int(cnt.value), cap)
+    out = {"lines": int(lines.value), "hits": hits[:k], "spans": spans[:k], "count": int(cnt.value)}
+    if gather:
+        out.update(text=text[:min(int(total.value), room)], offsets=offsets[:k + 1], bytes=int(total.value))
+    return out
+
+
+def search_lines_gather_device(rev, fwd, raw_ptr: int, size: int, out_line_count_ptr: int, out_hit_count_ptr: int, opts=0, out_bytes_ptr=0,
+                               delim: int = 10, tail_byte=-1, out_hits_ptr=0, out_spans_ptr=0, hit_cap=0, out_text_ptr=0, text_cap=0,
+                               out_offsets_ptr=0, stream: int = 0):
+    """pire_hip_search_lines_gather on device pointers (synchronises `stream` once, as run_lines_select_device does)."""
+    _check(lib().pire_hip_search_lines_gather(_table_ptr(rev), _table_ptr(fwd), opts, raw_ptr or None, size, delim, FLAG_ON_DEVICE,
+                                              _tail(delim if tail_byte == -1 else tail_byte), out_line_count_ptr or None,
+                                              out_hits_ptr or None, out_spans_ptr or None, hit_cap, out_hit_count_ptr or None,
+                                              out_text_ptr or None, text_cap, out_offsets_ptr or None, out_bytes_ptr or None, stream or None))
 
 
 def capture_select_host(offsets, begin, end, final=None, flags=FLAG_BEGIN, need_final=False, hit_cap: Optional[int] = None,

@@ -4021,6 +4021,232 @@ try {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
 
+// ---- where the match lies: the leftmost-longest match of every string (search.hip) and of the lines of a buffer --------------
+namespace {
+
+int SearchArgsInvalid(const char* who, pire_hip_table* rev, pire_hip_table* fwd, uint32_t opts)
+{
+	const uint32_t known = PIRE_HIP_SEARCH_SHORTEST | PIRE_HIP_SEARCH_THROUGH_BEGIN | PIRE_HIP_SEARCH_THROUGH_END;
+	const char* what = !rev           ? "null rev"
+	                   : !fwd         ? "null fwd"
+	                   : opts & ~known ? "unknown bits in opts"
+	                                   : nullptr;
+	if (!what)
+		return PIRE_HIP_OK;
+	SetError(std::string(who) + ": " + what);
+	return PIRE_HIP_EINVAL;
+}
+
+int SearchBatchInvalid(const char* who, const void* text, const uint64_t* offsets, uint64_t n)
+{
+	const char* what = n && (!text || !offsets) ? "n > 0 with null text or offsets"
+	                   : n >= (1ull << 32)      ? "2^32 strings or more in one call"
+	                                            : nullptr;
+	if (!what)
+		return PIRE_HIP_OK;
+	SetError(std::string(who) + ": " + what);
+	return PIRE_HIP_EINVAL;
+}
+
+// Both tables held still for one entry point (in address order, as AffixTables), and their scan parameters: R's start state is
+// LongestSuffix's, F's the two candidates of the forward leg.
+struct SearchTables {
+	TableUse use1, use2;
+	ScanParams pr, pf;
+	uint32_t fwdStartBegin = 0;
+	int Prepare(pire_hip_table* rev, pire_hip_table* fwd, uint32_t opts, bool enqueueOnly)
+	{
+		use1.Acquire(std::min(rev, fwd), enqueueOnly);
+		if (rev != fwd)
+			use2.Acquire(std::max(rev, fwd), enqueueOnly);
+		if (int rc = SuffixParams(rev, &pr, (opts & PIRE_HIP_SEARCH_THROUGH_END) != 0))
+			return rc;
+		if (int rc = FillParams(fwd, &pf, 0))   // startPerm = Initialize()
+			return rc;
+		const HostTable& h = fwd->host;
+		fwdStartBegin = pf.hostPermOfOrig[h.next[size_t(h.initial) * h.letters + h.cls[kBeginMark]]];   // + Step(BeginMark), run.h:282-283
+		return PIRE_HIP_OK;
+	}
+	// the search enqueued on `stream`, device pointers only (n > 0)
+	int Enqueue(uint32_t opts, const void* dText, const uint64_t* dOffsets, uint64_t n, int64_t* dBegin, int64_t* dEnd, hipStream_t stream)
+	{
+		pr.n = n;
+		pr.text = static_cast<const uint8_t*>(dText);
+		pr.offsets = dOffsets;
+		return LaunchSearch(pr, pf, fwdStartBegin, opts, reinterpret_cast<long long*>(dBegin), reinterpret_cast<long long*>(dEnd), stream);
+	}
+};
+
+// The search and the capture pass behind it on `stream`, device pointers only (n > 0).  dBegin / dEnd: nullable -- what the caller
+// has no array for lives in stream-ordered scratch.  shift: as LaunchCaptureSelect's.
+int SearchEnqueue(SearchTables& tabs, uint32_t opts, const void* dText, const uint64_t* dOffsets, uint64_t n, int64_t* dBegin, int64_t* dEnd,
+                  uint64_t shift, uint64_t* dHits, uint64_t* dSpans, uint64_t cap, uint64_t* dCount, hipStream_t stream)
+{
+	StreamScratch own(stream);
+	if (!dBegin || !dEnd) {
+		if (int rc = own.Alloc(size_t(n) * 16, "hipMallocAsync(search positions)"))
+			return rc;
+		if (!dBegin)
+			dBegin = own.as<int64_t>();
+		if (!dEnd)
+			dEnd = own.as<int64_t>() + n;
+	}
+	if (int rc = tabs.Enqueue(opts, dText, dOffsets, n, dBegin, dEnd, stream))
+		return rc;
+	return LaunchCaptureSelect(dOffsets, n, false, reinterpret_cast<const long long*>(dBegin), reinterpret_cast<const long long*>(dEnd), nullptr,
+	                           shift, dHits, dSpans, cap, dCount, stream);
+}
+
+}  // namespace
+
+int pire_hip_search(pire_hip_table* rev, pire_hip_table* fwd, uint32_t opts, const void* text, const uint64_t* offsets, uint64_t n,
+                    uint32_t flags, int64_t* out_begin, int64_t* out_end, void* streamPtr)
+try {
+	const char* who = "pire_hip_search";
+	if (int rc = SearchArgsInvalid(who, rev, fwd, opts))
+		return rc;
+	if (int rc = SearchBatchInvalid(who, text, offsets, n))
+		return rc;
+	if (!out_begin || !out_end) {
+		SetError(std::string(who) + ": null out_begin or out_end");
+		return PIRE_HIP_EINVAL;
+	}
+	if (n == 0)
+		return PIRE_HIP_OK;
+	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
+	if (!onDevice) {   // what the scans refuse of a host batch, before a device is touched
+		uint64_t textBytes = 0;
+		if (int rc = CheckHostBatch(text, offsets, n, 0, 0, &textBytes))
+			return rc;
+	}
+	SearchTables tabs;
+	if (int rc = tabs.Prepare(rev, fwd, opts, onDevice))
+		return rc;
+	BatchIO io(stream, onDevice);
+	const uint8_t* dText = nullptr;
+	const uint64_t* dOffsets = nullptr;
+	int64_t *dBegin = nullptr, *dEnd = nullptr;
+	if (int rc = io.Text(text, offsets, n, 0, 0, &dText, &dOffsets))
+		return rc;
+	if (int rc = io.Result(out_begin, size_t(n), size_t(n), &dBegin))
+		return rc;
+	if (int rc = io.Result(out_end, size_t(n), size_t(n), &dEnd))
+		return rc;
+	if (int rc = io.Ready())
+		return rc;
+	if (int rc = tabs.Enqueue(opts, dText, dOffsets, n, dBegin, dEnd, stream))
+		return rc;
+	return io.Finish();
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+int pire_hip_search_run_select(pire_hip_table* rev, pire_hip_table* fwd, uint32_t opts, const void* text, const uint64_t* offsets, uint64_t n,
+                               uint32_t flags, int64_t* out_begin, int64_t* out_end, uint64_t* out_hits, uint64_t* out_spans, uint64_t hit_cap,
+                               uint64_t* out_hit_count, void* streamPtr)
+try {
+	const char* who = "pire_hip_search_run_select";
+	if (int rc = SearchArgsInvalid(who, rev, fwd, opts))
+		return rc;
+	if (int rc = SearchBatchInvalid(who, text, offsets, n))
+		return rc;
+	if (int rc = CaptureSelectOutputsInvalid(who, n, 0, true, out_hits || out_spans, hit_cap, out_hit_count))
+		return rc;
+	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
+	if (n == 0) {   // the pass itself zeroes the count on the stream; host pointers: no device is touched
+		if (onDevice)
+			return LaunchCaptureSelect(nullptr, 0, false, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, out_hit_count, stream);
+		*out_hit_count = 0;
+		return PIRE_HIP_OK;
+	}
+	if (!onDevice) {
+		uint64_t textBytes = 0;
+		if (int rc = CheckHostBatch(text, offsets, n, 0, 0, &textBytes))
+			return rc;
+	}
+	SearchTables tabs;
+	if (int rc = tabs.Prepare(rev, fwd, opts, onDevice))
+		return rc;
+	// host pointers: the text staged once, the search and the pass on the staged copy, then everything back
+	BatchIO io(stream, onDevice);
+	const uint8_t* dText = nullptr;
+	const uint64_t* dOffsets = nullptr;
+	int64_t *dBegin = nullptr, *dEnd = nullptr;
+	if (int rc = io.Text(text, offsets, n, 0, 0, &dText, &dOffsets))
+		return rc;
+	if (out_begin)
+		if (int rc = io.Result(out_begin, size_t(n), size_t(n), &dBegin))
+			return rc;
+	if (out_end)
+		if (int rc = io.Result(out_end, size_t(n), size_t(n), &dEnd))
+			return rc;
+	HitStage list(onDevice, out_hit_count, "hipMemcpy(hits)");
+	uint64_t *dHits = nullptr, *dSpans = nullptr;
+	int rc;
+	if ((rc = list.Count(io, hit_cap, n)) || (rc = list.List(io, out_hits, 1, &dHits)) || (rc = list.List(io, out_spans, 2, &dSpans)) ||
+	    (rc = io.Ready()))
+		return rc;
+	if ((rc = SearchEnqueue(tabs, opts, dText, dOffsets, n, dBegin, dEnd, 0, dHits, dSpans, list.cap, list.dCount, stream)))
+		return rc;
+	if ((rc = io.Finish()))
+		return rc;
+	return list.Back();
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+// The frame around the search: the search on the lines, the pass with shift = 1 (string i of the split buffer lies i bytes
+// further into raw), the gather from raw through its spans.
+int pire_hip_search_lines_gather(pire_hip_table* rev, pire_hip_table* fwd, uint32_t opts, const void* raw, uint64_t size, uint32_t delim,
+                                 uint32_t flags, uint32_t tail_byte, uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_spans,
+                                 uint64_t hit_cap, uint64_t* out_hit_count, void* out_text, uint64_t text_cap, uint64_t* out_offsets,
+                                 uint64_t* out_bytes, void* streamPtr)
+try {
+	const char* who = "pire_hip_search_lines_gather";
+	if (int rc = SearchArgsInvalid(who, rev, fwd, opts))
+		return rc;
+	flags &= PIRE_HIP_RUN_ON_DEVICE;   // (the marks are the search's own: opts)
+	if (int rc = SplitArgsInvalid(who, raw, size, delim, out_line_count, "out_line_count"))
+		return rc;
+	// no gather output at all: spans only.  (The gather form keeps the span list to itself where the caller has no array for it.)
+	const bool gathers = out_text || text_cap || out_offsets || out_bytes;
+	if (int rc = CaptureSelectOutputsInvalid(who, 0, 0, true, out_hits || out_spans || gathers, hit_cap, out_hit_count))
+		return rc;
+	if (gathers) {
+		if (int rc = GatherOutputsInvalid(who, "hit_cap", hit_cap, tail_byte, out_text, text_cap, out_offsets, out_bytes))
+			return rc;
+		if (int rc = GatherOverlaps(who, raw, size, out_text, text_cap))
+			return rc;
+	}
+	const LinesGather gather = {tail_byte, out_text, text_cap, out_offsets, out_bytes, false, "hipMallocAsync(search spans)"};
+	LinesFrame f(who, raw, size, delim, flags, gathers ? &gather : nullptr, streamPtr);
+	if (f.HostEdge(out_line_count)) {
+		*out_hit_count = 0;
+		return PIRE_HIP_OK;
+	}
+	if (int rc = f.Open())
+		return rc;
+	if (int rc = f.Split(out_line_count, out_hit_count, 1, hit_cap, true))
+		return rc;
+	if (int rc = f.Lists(out_hits, out_spans))
+		return rc;
+	if (f.n == 0) {
+		if (int rc = f.ZeroCounts("hipMemsetAsync(hit count)"))
+			return rc;
+	} else {
+		SearchTables tabs;
+		if (int rc = tabs.Prepare(rev, fwd, opts, f.onDevice))
+			return rc;
+		if (int rc = SearchEnqueue(tabs, opts, f.Text(), f.Offsets(), f.n, nullptr, nullptr, 1, f.dHits, f.dSpans, f.cap, f.dCounts, f.stream))
+			return rc;
+	}
+	return f.Close("hipMemcpy(search spans)");
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
 int pire_hip_step(pire_hip_table* t, uint32_t* state_idx, uint64_t n, uint32_t ch, void* stream)
 try {
 	if (!t || (n && !state_idx) || ch >= kMaxCharUnaligned || ch == kEpsilon) {

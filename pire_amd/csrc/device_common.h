@@ -225,6 +225,147 @@ __device__ __forceinline__ uint32_t StartState(const ScanParams& p, uint64_t s)
 	return StartStateFrom(p, p.initIdx[s]);
 }
 
+// The walk of Pire::LongestPrefix / ShortestPrefix (run.h:277-311) over text[0, len) for one lane, from the start state `st`
+// (a perm id: Initialize(), + Step(BeginMark) where the caller takes the mark): the length of the prefix, -1 where the
+// reference returns null.  `text` may have any alignment.  The prefix kernel's (exact.hip) and the forward leg of the search's
+// (search.hip).
+__device__ __forceinline__ long long PrefixWalk(const ScanParams& p, const uint8_t* lds, const LdsLayout& L, const uint8_t* text,
+                                                uint64_t len, uint32_t st, uint32_t longest, uint32_t throughEnd)
+{
+	long long pos = -1;
+	bool stop = false;
+	uint32_t f = StateFlags(p, lds, L, st);
+	if (f & kFinal) {
+		pos = 0;                                     // run.h:284 / 301-302
+		stop = !longest;
+	}
+	const bool foundAtStart = stop;
+	if (!stop) {
+		uint64_t i = 0;
+		auto step = [&](uint32_t byte) {
+			st = SlowStep(p, lds, L, st, byte);
+			f = StateFlags(p, lds, L, st);
+			++i;
+			if (f & kFinal) {
+				pos = (long long)i;
+				if (!longest)
+					stop = true;                     // ShortestPrefixPred: Stop on the first Final
+			}
+			if (f & kDead)
+				stop = true;                         // both predicates stop on a dead state
+			return !stop;
+		};
+		// line-aligned vector loads instead of byte loads (walk.h); whole blocks first through the dense rows alone:
+		// neither a Dead nor a Final state among the 16 (the rows are ordered plain, Dead, Final) -> nothing to record,
+		// take the state; otherwise the block again, step by step (round 3: 0.25 us per byte before, one wave alone)
+		WalkBlocks(text, text + len, [&](walk_u32x4 v, uint32_t skip, uint32_t count) {
+			if (st < p.hot) {
+				uint32_t h = st;
+				const uint32_t mx = count == 16 ? DenseChunk(lds, L, v, h) : DenseBytes(lds, L, v, skip, count, h);
+				if (mx < p.hotDeadLo) {
+					st = h;
+					i += count;
+					return true;
+				}
+			}
+			return BlockBytes(v, skip, count, step);
+		});
+	}
+	if (throughEnd && !foundAtStart) {
+		st = p.nextPerm[size_t(st) * p.letters + p.endCls];
+		if (StateFlags(p, lds, L, st) & kFinal) {
+			if (longest || pos < 0)
+				pos = (long long)len;                // run.h:286-290 / 305-309
+		}
+	}
+	return pos;
+}
+
+// The walk of Pire::LongestSuffix / ShortestSuffix (run.h:313-362) for one lane: the bytes at addresses [lo, top) BACKWARDS
+// from top - 1, in 16-byte blocks from the top down, only blocks that hold at least one byte of the string.  Start state:
+// p.startPerm.  The length of the suffix, -1 where the reference returns null.  The suffix kernel's (exact.hip) and the
+// backward leg of the search's (search.hip).
+__device__ __forceinline__ long long SuffixWalk(const ScanParams& p, const uint8_t* lds, const LdsLayout& L, uint64_t lo, uint64_t top,
+                                                uint32_t longest, uint32_t throughBegin)
+{
+	uint64_t cur = top;        // one past the next byte to take
+	uint32_t st = p.startPerm;
+	uint32_t f = StateFlags(p, lds, L, st);
+	long long pos = -1;
+	// LongestSuffix: while (bytes left && !Dead) { if Final: pos = here; step }   run.h:326-333
+	// ShortestSuffix: while (bytes left && !Final && !Dead) step                  run.h:354-357
+	bool go = cur > lo && !(f & kDead) && (longest || !(f & kFinal));
+	while (go) {
+		const uint64_t block = (cur - 1) & ~uint64_t(15);
+		u32x4 v = *reinterpret_cast<const u32x4*>(block);
+		uint32_t k = uint32_t(cur - 1 - block);                          // index of the next byte inside the block
+		const uint32_t kLow = block >= lo ? 0u : uint32_t(lo - block);   // first index that belongs to the string
+		// A whole block of the string from a state with a dense row: its sixteen bytes top down through the dense rows alone
+		// (round 6; the prefix kernel's DenseChunk, backwards).  Neither a Dead nor a Final state among the sixteen reached
+		// (the rows are ordered plain, Dead, Final) -> nothing to record but what the state in front of them says, take the
+		// state; otherwise the block byte by byte below.  The suffix searches were never measured before round 6: 0.52 TB/s of
+		// log lines with the byte-wise walk alone (a SlowStep, a flag lookup and three funnel shifts per byte).
+		if (k == 15 && kLow == 0 && st < p.hot) {
+			uint32_t h = st, mx = 0;
+#pragma unroll
+			for (int w = 3; w >= 0; --w) {
+				const uint32_t x = v[w];
+#pragma unroll
+				for (int b2 = 3; b2 >= 0; --b2) {
+					h = lds[h * L.pitch + ((x >> (8 * b2)) & 0xFFu)];
+					mx = mx > h ? mx : h;
+				}
+			}
+			if (mx < p.hotDeadLo) {
+				if (longest && (f & kFinal))
+					pos = (long long)(top - cur);
+				st = h;
+				f = 0;   // a plain dense state: neither Final nor Dead
+				cur -= 16;
+				go = cur > lo;
+				continue;
+			}
+		}
+		// bring byte k to the top of the 128-bit value, then peel bytes off the top
+		for (uint32_t sh = 15 - k; sh; --sh) {
+			v.w = __builtin_amdgcn_alignbit(v.w, v.z, 24);
+			v.z = __builtin_amdgcn_alignbit(v.z, v.y, 24);
+			v.y = __builtin_amdgcn_alignbit(v.y, v.x, 24);
+			v.x <<= 8;
+		}
+		for (;;) {
+			if (longest && (f & kFinal))
+				pos = (long long)(top - cur);
+			st = SlowStep(p, lds, L, st, v.w >> 24);
+			f = StateFlags(p, lds, L, st);
+			--cur;
+			go = cur > lo && !(f & kDead) && (longest || !(f & kFinal));
+			if (!go || k == kLow)
+				break;
+			--k;
+			v.w = __builtin_amdgcn_alignbit(v.w, v.z, 24);
+			v.z = __builtin_amdgcn_alignbit(v.z, v.y, 24);
+			v.y = __builtin_amdgcn_alignbit(v.y, v.x, 24);
+			v.x <<= 8;
+		}
+	}
+	const long long here = (long long)(top - cur);
+	if (longest) {
+		if (f & kFinal)
+			pos = here;                                              // run.h:334-335
+		if (throughBegin) {
+			st = p.nextPerm[size_t(st) * p.letters + p.beginCls];
+			if (StateFlags(p, lds, L, st) & kFinal)
+				pos = here;                                          // run.h:336-340
+		}
+	} else {
+		if (throughBegin)
+			st = p.nextPerm[size_t(st) * p.letters + p.beginCls];    // run.h:358-359
+		pos = (StateFlags(p, lds, L, st) & kFinal) ? here : -1;      // run.h:360
+	}
+	return pos;
+}
+
 // End(), outputs and block-local match counters for one finished string.  One 16-byte record load replaces the
 // chain  nextPerm[EndMark] -> flags -> origOfPerm -> acceptMask  of dependent lookups.
 __device__ __forceinline__ void Finish(const ScanParams& p, uint8_t* lds, const LdsLayout& L, uint64_t s,

@@ -201,56 +201,8 @@ __global__ __launch_bounds__(1024) void PrefixKernel(PrefixParams q)
 			b = s * p.stride;
 			e = b + p.len;
 		}
-		const uint8_t* text = p.text + b;
-		const uint64_t len = e - b;
-		uint32_t st = p.startPerm;                       // Initialize (+ BeginMark if throughBeginMark), run.h:280-283
-		long long pos = -1;
-		bool stop = false;
-		uint32_t f = StateFlags(p, lds, L, st);
-		if (f & kFinal) {
-			pos = 0;                                     // run.h:284 / 301-302
-			stop = !q.longest;
-		}
-		const bool foundAtStart = stop;
-		if (!stop) {
-			uint64_t i = 0;
-			auto step = [&](uint32_t byte) {
-				st = SlowStep(p, lds, L, st, byte);
-				f = StateFlags(p, lds, L, st);
-				++i;
-				if (f & kFinal) {
-					pos = (long long)i;
-					if (!q.longest)
-						stop = true;                     // ShortestPrefixPred: Stop on the first Final
-				}
-				if (f & kDead)
-					stop = true;                         // both predicates stop on a dead state
-				return !stop;
-			};
-			// line-aligned vector loads instead of byte loads (walk.h); whole blocks first through the dense rows alone:
-			// neither a Dead nor a Final state among the 16 (the rows are ordered plain, Dead, Final) -> nothing to record,
-			// take the state; otherwise the block again, step by step (round 3: 0.25 us per byte before, one wave alone)
-			WalkBlocks(text, text + len, [&](walk_u32x4 v, uint32_t skip, uint32_t count) {
-				if (st < p.hot) {
-					uint32_t h = st;
-					const uint32_t mx = count == 16 ? DenseChunk(lds, L, v, h) : DenseBytes(lds, L, v, skip, count, h);
-					if (mx < p.hotDeadLo) {
-						st = h;
-						i += count;
-						return true;
-					}
-				}
-				return BlockBytes(v, skip, count, step);
-			});
-		}
-		if (q.throughEnd && !foundAtStart) {
-			st = p.nextPerm[size_t(st) * p.letters + p.endCls];
-			if (StateFlags(p, lds, L, st) & kFinal) {
-				if (q.longest || pos < 0)
-					pos = (long long)len;                // run.h:286-290 / 305-309
-			}
-		}
-		q.outLen[s] = pos;
+		// startPerm: Initialize (+ BeginMark if throughBeginMark), run.h:280-283
+		q.outLen[s] = PrefixWalk(p, lds, L, p.text + b, e - b, p.startPerm, q.longest, q.throughEnd);
 	}
 }
 
@@ -280,84 +232,7 @@ __global__ __launch_bounds__(1024) void SuffixKernel(SuffixParams q)
 			b = s * p.stride;
 			e = b + p.len;
 		}
-		const uint64_t lo = reinterpret_cast<uint64_t>(p.text) + b;   // address of the first byte
-		uint64_t cur = reinterpret_cast<uint64_t>(p.text) + e;        // one past the next byte to take
-		const uint64_t top = cur;
-		uint32_t st = p.startPerm;
-		uint32_t f = StateFlags(p, lds, L, st);
-		long long pos = -1;
-		// LongestSuffix: while (bytes left && !Dead) { if Final: pos = here; step }   run.h:326-333
-		// ShortestSuffix: while (bytes left && !Final && !Dead) step                  run.h:354-357
-		bool go = cur > lo && !(f & kDead) && (q.longest || !(f & kFinal));
-		while (go) {
-			const uint64_t block = (cur - 1) & ~uint64_t(15);
-			u32x4 v = *reinterpret_cast<const u32x4*>(block);
-			uint32_t k = uint32_t(cur - 1 - block);                          // index of the next byte inside the block
-			const uint32_t kLow = block >= lo ? 0u : uint32_t(lo - block);   // first index that belongs to the string
-			// A whole block of the string from a state with a dense row: its sixteen bytes top down through the dense rows alone
-			// (round 6; the prefix kernel's DenseChunk, backwards).  Neither a Dead nor a Final state among the sixteen reached
-			// (the rows are ordered plain, Dead, Final) -> nothing to record but what the state in front of them says, take the
-			// state; otherwise the block byte by byte below.  The suffix searches were never measured before round 6: 0.52 TB/s of
-			// log lines with the byte-wise walk alone (a SlowStep, a flag lookup and three funnel shifts per byte).
-			if (k == 15 && kLow == 0 && st < p.hot) {
-				uint32_t h = st, mx = 0;
-#pragma unroll
-				for (int w = 3; w >= 0; --w) {
-					const uint32_t x = v[w];
-#pragma unroll
-					for (int b2 = 3; b2 >= 0; --b2) {
-						h = lds[h * L.pitch + ((x >> (8 * b2)) & 0xFFu)];
-						mx = mx > h ? mx : h;
-					}
-				}
-				if (mx < p.hotDeadLo) {
-					if (q.longest && (f & kFinal))
-						pos = (long long)(top - cur);
-					st = h;
-					f = 0;   // a plain dense state: neither Final nor Dead
-					cur -= 16;
-					go = cur > lo;
-					continue;
-				}
-			}
-			// bring byte k to the top of the 128-bit value, then peel bytes off the top
-			for (uint32_t sh = 15 - k; sh; --sh) {
-				v.w = __builtin_amdgcn_alignbit(v.w, v.z, 24);
-				v.z = __builtin_amdgcn_alignbit(v.z, v.y, 24);
-				v.y = __builtin_amdgcn_alignbit(v.y, v.x, 24);
-				v.x <<= 8;
-			}
-			for (;;) {
-				if (q.longest && (f & kFinal))
-					pos = (long long)(top - cur);
-				st = SlowStep(p, lds, L, st, v.w >> 24);
-				f = StateFlags(p, lds, L, st);
-				--cur;
-				go = cur > lo && !(f & kDead) && (q.longest || !(f & kFinal));
-				if (!go || k == kLow)
-					break;
-				--k;
-				v.w = __builtin_amdgcn_alignbit(v.w, v.z, 24);
-				v.z = __builtin_amdgcn_alignbit(v.z, v.y, 24);
-				v.y = __builtin_amdgcn_alignbit(v.y, v.x, 24);
-				v.x <<= 8;
-			}
-		}
-		const long long here = (long long)(top - cur);
-		if (q.longest) {
-			if (f & kFinal)
-				pos = here;                                              // run.h:334-335
-			if (q.throughBegin) {
-				st = p.nextPerm[size_t(st) * p.letters + p.beginCls];
-				if (StateFlags(p, lds, L, st) & kFinal)
-					pos = here;                                          // run.h:336-340
-			}
-		} else {
-			if (q.throughBegin)
-				st = p.nextPerm[size_t(st) * p.letters + p.beginCls];    // run.h:358-359
-			pos = (StateFlags(p, lds, L, st) & kFinal) ? here : -1;      // run.h:360
-		}
-		q.outLen[s] = pos;
+		q.outLen[s] = SuffixWalk(p, lds, L, reinterpret_cast<uint64_t>(p.text) + b, reinterpret_cast<uint64_t>(p.text) + e, q.longest, q.throughBegin);
 	}
 }
 

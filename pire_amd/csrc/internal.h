@@ -1446,6 +1446,12 @@ int LaunchPairTiled(const ScanParams& a, const ScanParams& b, uint32_t* outIdxB,
                     const uint32_t* segJ = nullptr, uint32_t* guessA = nullptr, uint32_t* guessB = nullptr);
 int LaunchOrFinal(uint8_t* fin, const uint8_t* other, uint64_t n, hipStream_t stream);
 int LaunchSuffix(const ScanParams& p, bool longest, bool throughBegin, long long* outLen, hipStream_t stream);
+// search.hip: the leftmost-longest match of every string (pire_hip_search), one launch: LongestSuffix through `rev`, then
+// Longest- / ShortestPrefix through `fwd` from where it ended.  rev carries the batch (n, text, offsets: device pointers) and
+// its start state (Initialize [+ EndMark]); fwd.startPerm is Initialize(), fwdStartBegin Initialize() + Step(BeginMark).
+// opts: PIRE_HIP_SEARCH_*.  PIRE_HIP_EUNSUPPORTED before the launch where the two dense images do not fit a block's LDS.
+int LaunchSearch(const ScanParams& rev, const ScanParams& fwd, uint32_t fwdStartBegin, uint32_t opts, long long* outBegin,
+                 long long* outEnd, hipStream_t stream);
 int LaunchCorpusFill(uint8_t* out, uint64_t seed, uint64_t first, uint64_t count, uint64_t len, uint64_t stride,
                      const void* plantsHost, hipStream_t stream);
 
