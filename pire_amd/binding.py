@@ -1093,6 +1093,9 @@ class Table:
     @classmethod
     def glue(cls, lhs: "Table", rhs: "Table", max_size: int = 0, gpu: bool = False):
         """Scanner::Glue(lhs, rhs, maxSize) on two ingested tables (reference numbering); gpu=True: BFS on the device."""
+        for t in (lhs, rhs):
+            if not isinstance(t, Table):   # a CountingTable's or SlowTable's handle is another C type: never hand it over
+                raise PireHipError(-1, "Glue is defined for Pire::Scanner tables, not for a %s" % type(t).__name__)
         h = C.c_void_p()
         fn = lib().pire_hip_table_glue_gpu if gpu else lib().pire_hip_table_glue
         _check(fn(lhs._h, rhs._h, max_size, C.byref(h)))
