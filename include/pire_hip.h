@@ -1374,6 +1374,67 @@ int pire_hip_search_lines_gather(pire_hip_table* rev, pire_hip_table* fwd, uint3
                     uint64_t* out_line_count, uint64_t* out_hits, uint64_t* out_spans, uint64_t hit_cap, uint64_t* out_hit_count,
                     void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes, void* stream);
 
+/*
+ * EVERY leftmost-longest match of every string, not the first alone: the two searches of pire_hip_search, iterated.  rev (R),
+ * fwd (F) and opts (S, B, E) are exactly as for pire_hip_search.  For string s of length len:
+ *   p = 0, k = 0
+ *   while p < len:
+ *       t = LongestSuffix(R, s[p, len), throughEndMark = E, throughBeginMark = B && p == 0)      run.h:313-341
+ *       if t <= 0: stop                      (t == 0: only the empty match at len is left)
+ *       b = len - t
+ *       h = S ? ShortestPrefix(F, s[b, len), throughBeginMark = B && b == 0, throughEndMark = E)
+ *             : LongestPrefix (F, ...the same...)                                                 run.h:277-311
+ *       if h < 0: stop                       (two tables that do not belong together)
+ *       if h > 0: match k of the string = [b, b + h);  k += 1
+ *       p = b + max(h, 1)
+ * The matches of a string do not overlap and they ascend.  An empty match is never reported (`grep -o` drops it too); the
+ * walk steps one byte past it.  `^` matches at byte 0 only: B is handed to a leg only at byte 0.  The first reported match
+ * is pire_hip_search's wherever that one is not empty.
+ * The device does not run one backward search per match: R's state after the bytes len-1 .. j does not depend on p, so
+ *   LongestSuffix(R, s[p, len)) = len - min{ j >= p : mark(j) }
+ *   mark(j) = Final(state after byte j) || (j == 0 && B && Final(Step(that state, BeginMark)))
+ * with no marks below the position where the walk reached a Dead state: one backward pass writes the marks, one bit per byte
+ * of text in stream-ordered scratch of 2 * (text_bytes / 16 + n + 2) bytes.  The forward leg walks until F is Dead
+ * (LongestPrefix's rule): a pattern such as `a.*b|a` on a line of `a`s without a `b` costs len steps per match, len^2 for
+ * the line.  That is the definition's cost, not the kernel's.
+ * text_bytes: the size of the buffer behind `text`; the caller promises that every offset is <= text_bytes.  The kernels clamp
+ * whatever is larger, so nothing outside the scratch or the text is touched.  Offsets must not decrease; where
+ * offsets[i+1] < offsets[i], string i is empty (as in pire_hip_search).  Strings that OVERLAP in text (which takes such a
+ * decrease) get unspecified matches -- their marks share words --, but nothing is accessed out of bounds.
+ * out_rows[n + 1] (nullable): CSR row starts, the matches of string i are entries [rows[i], rows[i+1]) of the lists.  Never
+ *        capped: rows[n] = the match count.
+ * out_owners[match_cap] (nullable): the string of match k; ascending, with repeats.
+ * out_spans[2 * match_cap] (nullable): match k as a byte range of text, (offsets[i] + b, offsets[i] + b + h): the convention of
+ *        pire_hip_capture_select, the input form of pire_hip_gather_spans.
+ * out_match_count (required): the number of matches, also where it exceeds match_cap; then the first match_cap entries of
+ *        the lists are written and nothing beyond them.
+ * flags: PIRE_HIP_RUN_ON_DEVICE -> everything is a device pointer, the call only enqueues on `stream` (four launches) and
+ *        does not wait.  Otherwise host pointers: the batch is staged once and the call synchronises.
+ * PIRE_HIP_EINVAL before any device is touched: null rev or fwd; unknown bits in opts; n > 0 with null text or offsets;
+ * n >= 2^32; null out_match_count; match_cap > 0 with null out_owners and null out_spans; host pointers: offsets that
+ * decrease, or an offset beyond text_bytes.  PIRE_HIP_EUNSUPPORTED as pire_hip_search (the dense rows and the LDS).
+ * n == 0: the count is 0 (and rows[0]); device pointers: zeroed on the stream; host pointers: no device is touched.
+ * pire_hip_last_kernel() is not changed.  No first-use self-test.
+ */
+int pire_hip_search_all(pire_hip_table* rev, pire_hip_table* fwd, uint32_t opts,
+                    const void* text, uint64_t text_bytes, const uint64_t* offsets, uint64_t n, uint32_t flags,
+                    uint64_t* out_rows, uint64_t* out_owners, uint64_t* out_spans, uint64_t match_cap,
+                    uint64_t* out_match_count, void* stream);
+
+/*
+ * Raw bytes in, every match of every line out -- with tail_byte = delim, `grep -o`'s output byte for byte.  As
+ * pire_hip_search_lines_gather, with the list form of the search: a line can have many matches, so the lists are match_cap
+ * long (not min(match_cap, lines)).  out_owners (nullable): the line number of match k; out_spans (nullable): byte ranges of
+ * raw (line i of the split buffer lies i bytes further into raw); out_match_count: the matches, also beyond match_cap.  The
+ * gather runs straight from raw through the spans, tail_byte behind each match; all four gather outputs null: spans only.
+ * The matches do not overlap, so size + match_cap bytes of out_text always suffice.  One synchronisation of `stream`; 2^32
+ * lines are refused (PIRE_HIP_EUNSUPPORTED).  Host pointers with size == 0: zeros, no device is touched.
+ */
+int pire_hip_search_all_lines_gather(pire_hip_table* rev, pire_hip_table* fwd, uint32_t opts,
+                    const void* raw, uint64_t size, uint32_t delim, uint32_t flags, uint32_t tail_byte,
+                    uint64_t* out_line_count, uint64_t* out_owners, uint64_t* out_spans, uint64_t match_cap, uint64_t* out_match_count,
+                    void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes, void* stream);
+
 /* ---- the strings that count, on the device ---------------------------------------------------------------------- */
 
 /*

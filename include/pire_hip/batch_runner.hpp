@@ -2547,6 +2547,14 @@ private:
  *     find.Spans()     byte ranges of raw                                  find.LineCount()  lines in the buffer
  *     find.HitText()   the matches back to back, '\n' (or the byte given) behind each, gathered on the device
  *     find.HitTextOffsets()   match k is HitText()[o[k], o[k + 1])
+ * EVERY match of every string (line), not the first alone (pire_hip_search_all / pire_hip_search_all_lines_gather; an empty
+ * match is never reported): All() behind Run() or RunLines() -- with RunLines() and '\n', `grep -o`'s output:
+ *     find.Run(strings).All();
+ *     find.Hits()      the string of match k: ascending, with repeats       find.HitCount()  matches
+ *     find.Spans()     as above, one pair per match                         find.Rows()      [n + 1]: the matches of string i are
+ *                                                                                            entries [rows[i], rows[i+1]); Run() only
+ *     find.RunLines(raw, size).All().HitText();
+ * Select() switches back to the first match, which is what a new batch starts with.
  * The caller's arrays are read when an accessor first asks: they live until then.  HitText() is a call of its own, as in
  * BatchRunner: after Hits() / Spans() it scans the buffer a second time.
  */
@@ -2555,7 +2563,7 @@ class SearchBatchRunner {
 public:
 	SearchBatchRunner(const Scanner& reversedTail, const Scanner& forward, uint32_t opts = 0)
 	    : m_rev(reversedTail), m_fwd(forward), m_opts(opts), m_form(kNone), m_text(nullptr), m_offsets(nullptr), m_n(0), m_len(0), m_delim('\n'),
-	      m_listed(false), m_haveText(false), m_textTail('\n'), m_hitCount(0), m_lineCount(0)
+	      m_fetchAll(nullptr), m_linesCall(pire_hip_search_lines_gather), m_listed(false), m_haveText(false), m_textTail('\n'), m_hitCount(0), m_lineCount(0)
 	{
 	}
 
@@ -2567,7 +2575,9 @@ public:
 		return Run(m_ownStrings.Text(), m_ownStrings.Offsets(), strings.size());
 	}
 	/* the strings with a match and where it lies: what Hits() / Spans() answer (there is one selection; the call is AffixBatchRunner's idiom) */
-	SearchBatchRunner& Select() { return *this; }
+	SearchBatchRunner& Select() { return SetAll(nullptr, pire_hip_search_lines_gather); }
+	/* every match of every string (line): Hits() answers the owners, one entry per match */
+	SearchBatchRunner& All() { return SetAll(&SearchBatchRunner::FetchAll, pire_hip_search_all_lines_gather); }
 	SearchBatchRunner& RunLines(const char* raw, size_t size, char delim = '\n') { return SetBatch(kLines, raw, nullptr, 0, size, delim); }
 	uint64_t HitCount() { FetchHits(); return m_hitCount; }
 	const std::vector<uint64_t>& Hits() { FetchHits(); return m_hits; }
@@ -2580,6 +2590,14 @@ public:
 			FetchHitText('\n');
 		return m_hitTextOffsets;
 	}
+	/* All() behind Run(): n + 1 row starts into Hits() / Spans() */
+	const std::vector<uint64_t>& Rows()
+	{
+		if (m_form != kStrings || !m_fetchAll)
+			throw Pire::Error("pire_hip: Rows() follows Run() and All()");
+		FetchHits();
+		return m_rows;
+	}
 
 private:
 	SearchBatchRunner(const SearchBatchRunner&);
@@ -2590,12 +2608,41 @@ private:
 	{
 		m_form = form, m_text = text, m_offsets = offsets, m_n = n, m_len = len, m_delim = uint8_t(delim);
 		m_listed = m_haveText = false;
+		return Select();
+	}
+	/* (the list form's entry points are named by All() alone: a program that never asks for it does not link them) */
+	typedef void (SearchBatchRunner::*Fetch)();
+	typedef int (*LinesCall)(pire_hip_table*, pire_hip_table*, uint32_t, const void*, uint64_t, uint32_t, uint32_t, uint32_t, uint64_t*, uint64_t*,
+	                         uint64_t*, uint64_t, uint64_t*, void*, uint64_t, uint64_t*, uint64_t*, void*);
+	SearchBatchRunner& SetAll(Fetch fetchAll, LinesCall linesCall)
+	{
+		if (m_fetchAll != fetchAll)
+			m_listed = m_haveText = false;
+		m_fetchAll = fetchAll, m_linesCall = linesCall;
 		return *this;
 	}
 	void NeedLines(const char* what) const
 	{
 		if (m_form != kLines)
 			throw Pire::Error(std::string("pire_hip: ") + what + " follows RunLines()");
+	}
+
+	/* All(): one call with room for a match per string -- RunLines(): per 64 bytes --, and a second one where there are more */
+	void FetchAll()
+	{
+		const uint64_t* offsets = OwnedStrings::OffsetsOr(m_offsets, m_n);
+		GrowAndRetry(m_form == kLines ? m_len / 64 + 1024 : m_n, [&](size_t cap) {
+			m_hits.resize(cap);
+			m_spans.resize(cap * 2);
+			if (m_form == kStrings)
+				m_rows.resize(m_n + 1);
+			Check(m_form == kLines
+			          ? m_linesCall(m_rev.Handle(), m_fwd.Handle(), m_opts, m_text, m_len, m_delim, 0, PIRE_HIP_GATHER_NO_TAIL, &m_lineCount,
+			                        m_hits.data(), m_spans.data(), cap, &m_hitCount, nullptr, 0, nullptr, nullptr, nullptr)
+			          : pire_hip_search_all(m_rev.Handle(), m_fwd.Handle(), m_opts, m_text, m_n ? offsets[m_n] : 0, offsets, m_n, 0, m_rows.data(),
+			                                m_hits.data(), m_spans.data(), cap, &m_hitCount, nullptr));
+			return size_t(m_hitCount);
+		});
 	}
 
 	/* One call with room for every string -- RunLines(): for a hit on every line of 64 bytes or more, BatchRunner's first
@@ -2606,6 +2653,13 @@ private:
 			return;
 		if (m_form == kNone)
 			throw Pire::Error("pire_hip: Hits() follows Run() or RunLines()");
+		if (m_fetchAll) {
+			(this->*m_fetchAll)();
+			m_hits.resize(m_hitCount);
+			m_spans.resize(m_hitCount * 2);
+			m_listed = true;
+			return;
+		}
 		GrowAndRetry(m_form == kLines ? m_len / 64 + 1024 : m_n, [&](size_t cap) {
 			m_hits.resize(cap);
 			m_spans.resize(cap * 2);
@@ -2632,9 +2686,8 @@ private:
 		GrowAndRetry(m_listed ? size_t(m_hitCount) : m_len / 64 + 1024, [&](size_t cap) {
 			m_hitTextOffsets.resize(cap + 1);
 			m_hitText.resize(m_len + cap + 1);
-			Check(pire_hip_search_lines_gather(m_rev.Handle(), m_fwd.Handle(), m_opts, m_text, m_len, m_delim, 0, uint8_t(tail), &m_lineCount,
-			                                   nullptr, nullptr, cap, &count, &m_hitText[0], m_hitText.size(), m_hitTextOffsets.data(), &bytes,
-			                                   nullptr));
+			Check(m_linesCall(m_rev.Handle(), m_fwd.Handle(), m_opts, m_text, m_len, m_delim, 0, uint8_t(tail), &m_lineCount, nullptr, nullptr, cap,
+			                  &count, &m_hitText[0], m_hitText.size(), m_hitTextOffsets.data(), &bytes, nullptr));
 			return size_t(count);   // (the text has room for the whole buffer and a tail per hit: where the hits fit, the bytes do)
 		});
 		m_hitText.resize(bytes);
@@ -2650,11 +2703,13 @@ private:
 	const uint64_t* m_offsets;
 	size_t m_n, m_len;
 	uint8_t m_delim;
+	Fetch m_fetchAll;             // All(): every match, not the first of each string; null: the first
+	LinesCall m_linesCall;        // the lines entry point of the selection
 	bool m_listed, m_haveText;    // m_hits, m_spans (and m_lineCount) / m_hitText are the batch's, with the tail m_textTail
 	char m_textTail;
 	OwnedStrings m_ownStrings;
 	uint64_t m_hitCount, m_lineCount;
-	std::vector<uint64_t> m_hits, m_spans, m_hitTextOffsets;
+	std::vector<uint64_t> m_hits, m_spans, m_rows, m_hitTextOffsets;
 	std::string m_hitText;
 };
 

@@ -275,6 +275,8 @@ ABI = [
     ("pire_hip_search", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_search_run_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_search_lines_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_search_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("pire_hip_search_all_lines_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_context", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_run_lines_context_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_run_lines_context_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1022,6 +1024,70 @@ def search_lines_gather_device(rev, fwd, raw_ptr: int, size: int, out_line_count
                                               _tail(delim if tail_byte == -1 else tail_byte), out_line_count_ptr or None,
                                               out_hits_ptr or None, out_spans_ptr or None, hit_cap, out_hit_count_ptr or None,
                                               out_text_ptr or None, text_cap, out_offsets_ptr or None, out_bytes_ptr or None, stream or None))
+
+
+def search_all(rev, fwd, text, offsets, opts=0, match_cap: Optional[int] = None, text_bytes: Optional[int] = None, want_rows=True,
+               want_owners=True, want_spans=True):
+    """pire_hip_search_all on host strings: {"rows" u64[n + 1], "owners" u64[k], "spans" u64[k, 2], "count"}, k = min(count,
+    match_cap); an output that is not wanted is None.  match_cap None = room for a match at every byte; text_bytes None = the
+    size of `text`."""
+    text = _raw_bytes(text)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    cap = text.size if match_cap is None else int(match_cap)
+    rows = np.zeros(n + 1, dtype=np.uint64) if want_rows else None
+    owners = np.zeros(cap, dtype=np.uint64) if want_owners and cap else None
+    spans = np.zeros((cap, 2), dtype=np.uint64) if want_spans and cap else None
+    cnt = C.c_uint64(0)
+    _check(lib().pire_hip_search_all(_table_ptr(rev), _table_ptr(fwd), opts, text.ctypes.data if text.size else None,
+                                     text.size if text_bytes is None else int(text_bytes), offsets.ctypes.data, n, 0, _np_ptr(rows),
+                                     _np_ptr(owners), _np_ptr(spans), cap, C.byref(cnt), None))
+    k = min(int(cnt.value), cap)
+    return {"rows": rows, "owners": None if owners is None else owners[:k], "spans": None if spans is None else spans[:k],
+            "count": int(cnt.value)}
+
+
+def search_all_device(rev, fwd, text_ptr: int, text_bytes: int, offsets_ptr: int, n: int, out_match_count_ptr: int, opts=0, out_rows_ptr=0,
+                      out_owners_ptr=0, out_spans_ptr=0, match_cap=0, stream: int = 0):
+    """pire_hip_search_all on device pointers: only enqueues on `stream`."""
+    _check(lib().pire_hip_search_all(_table_ptr(rev), _table_ptr(fwd), opts, text_ptr or None, text_bytes, offsets_ptr or None, n,
+                                     FLAG_ON_DEVICE, out_rows_ptr or None, out_owners_ptr or None, out_spans_ptr or None, match_cap,
+                                     out_match_count_ptr or None, stream or None))
+
+
+def search_all_lines_gather_host(rev, fwd, raw, opts=0, delim: int = 10, tail_byte=-1, match_cap=None, text_cap=None, gather=True):
+    """pire_hip_search_all_lines_gather on a host buffer: {"lines", "owners", "spans", "count"} and, with gather, {"text",
+    "offsets", "bytes"}.  tail_byte -1 = the delimiter, None = none; match_cap None = room for a match at every byte, text_cap
+    None = for all of them."""
+    raw = _raw_bytes(raw)
+    cap = raw.size if match_cap is None else int(match_cap)
+    room = (raw.size + cap if text_cap is None else int(text_cap)) if gather else 0
+    owners = np.zeros(cap, dtype=np.uint64)
+    spans = np.zeros((cap, 2), dtype=np.uint64)
+    text = np.zeros(max(room, 1), dtype=np.uint8)
+    offsets = np.zeros(cap + 1, dtype=np.uint64)
+    lines, cnt, total = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    _check(lib().pire_hip_search_all_lines_gather(_table_ptr(rev), _table_ptr(fwd), opts, raw.ctypes.data if raw.size else None, raw.size, delim,
+                                                  0, _tail(delim if tail_byte == -1 else tail_byte), C.byref(lines),
+                                                  owners.ctypes.data if cap else None, spans.ctypes.data if cap else None, cap,
+                                                  C.byref(cnt), text.ctypes.data if room else None, room,
+                                                  offsets.ctypes.data if gather else None, C.byref(total) if gather else None, None))
+    k = min(int(cnt.value), cap)
+    out = {"lines": int(lines.value), "owners": owners[:k], "spans": spans[:k], "count": int(cnt.value)}
+    if gather:
+        out.update(text=text[:min(int(total.value), room)], offsets=offsets[:k + 1], bytes=int(total.value))
+    return out
+
+
+def search_all_lines_gather_device(rev, fwd, raw_ptr: int, size: int, out_line_count_ptr: int, out_match_count_ptr: int, opts=0,
+                                   out_bytes_ptr=0, delim: int = 10, tail_byte=-1, out_owners_ptr=0, out_spans_ptr=0, match_cap=0,
+                                   out_text_ptr=0, text_cap=0, out_offsets_ptr=0, stream: int = 0):
+    """pire_hip_search_all_lines_gather on device pointers (synchronises `stream` once, as search_lines_gather_device does)."""
+    _check(lib().pire_hip_search_all_lines_gather(_table_ptr(rev), _table_ptr(fwd), opts, raw_ptr or None, size, delim, FLAG_ON_DEVICE,
+                                                  _tail(delim if tail_byte == -1 else tail_byte), out_line_count_ptr or None,
+                                                  out_owners_ptr or None, out_spans_ptr or None, match_cap, out_match_count_ptr or None,
+                                                  out_text_ptr or None, text_cap, out_offsets_ptr or None, out_bytes_ptr or None,
+                                                  stream or None))
 
 
 def capture_select_host(offsets, begin, end, final=None, flags=FLAG_BEGIN, need_final=False, hit_cap: Optional[int] = None,

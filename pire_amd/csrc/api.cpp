@@ -4247,6 +4247,148 @@ try {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
 
+// ---- every match of every string (search_all.hip) and of the lines of a buffer -------------------------------------------------
+namespace {
+
+// What the list forms of the search refuse of their outputs before any device is touched (haveList: the matches have somewhere to go)
+int SearchAllOutputsInvalid(const char* who, bool haveList, uint64_t matchCap, const void* outMatchCount)
+{
+	const char* what = !outMatchCount          ? "null out_match_count"
+	                   : matchCap && !haveList ? "match_cap > 0 with null out_owners and null out_spans"
+	                                           : nullptr;
+	if (!what)
+		return PIRE_HIP_OK;
+	SetError(std::string(who) + ": " + what);
+	return PIRE_HIP_EINVAL;
+}
+
+// The list form of the search enqueued on `stream`, device pointers only
+int SearchAllEnqueue(SearchTables& tabs, uint32_t opts, const void* dText, uint64_t textBytes, const uint64_t* dOffsets, uint64_t n, uint64_t shift,
+                     uint64_t* dRows, uint64_t* dOwners, uint64_t* dSpans, uint64_t cap, uint64_t* dCount, hipStream_t stream)
+{
+	tabs.pr.n = n;
+	tabs.pr.text = static_cast<const uint8_t*>(dText);
+	tabs.pr.offsets = dOffsets;
+	return LaunchSearchAll(tabs.pr, tabs.pf, tabs.fwdStartBegin, opts, textBytes, shift, dRows, dOwners, dSpans, cap, dCount, stream);
+}
+
+}  // namespace
+
+int pire_hip_search_all(pire_hip_table* rev, pire_hip_table* fwd, uint32_t opts, const void* text, uint64_t text_bytes, const uint64_t* offsets,
+                        uint64_t n, uint32_t flags, uint64_t* out_rows, uint64_t* out_owners, uint64_t* out_spans, uint64_t match_cap,
+                        uint64_t* out_match_count, void* streamPtr)
+try {
+	const char* who = "pire_hip_search_all";
+	if (int rc = SearchArgsInvalid(who, rev, fwd, opts))
+		return rc;
+	if (int rc = SearchBatchInvalid(who, text, offsets, n))
+		return rc;
+	if (int rc = SearchAllOutputsInvalid(who, out_owners || out_spans, match_cap, out_match_count))
+		return rc;
+	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
+	if (n == 0) {   // device pointers: the count (and rows[0]) zeroed on the stream; host pointers: no device is touched
+		if (onDevice) {
+			ScanParams none{};
+			return LaunchSearchAll(none, none, 0, opts, 0, 0, out_rows, nullptr, nullptr, 0, out_match_count, stream);
+		}
+		*out_match_count = 0;
+		if (out_rows)
+			out_rows[0] = 0;
+		return PIRE_HIP_OK;
+	}
+	uint64_t textBytes = text_bytes;
+	if (!onDevice) {   // what the scans refuse of a host batch, before a device is touched
+		if (int rc = CheckHostBatch(text, offsets, n, 0, 0, &textBytes))
+			return rc;
+		if (textBytes > text_bytes) {
+			SetError(std::string(who) + ": an offset exceeds text_bytes");
+			return PIRE_HIP_EINVAL;
+		}
+	}
+	SearchTables tabs;
+	if (int rc = tabs.Prepare(rev, fwd, opts, onDevice))
+		return rc;
+	// host pointers: the text staged once (offsets[n] bytes of it), the passes on the staged copy, then everything back
+	BatchIO io(stream, onDevice);
+	const uint8_t* dText = nullptr;
+	const uint64_t* dOffsets = nullptr;
+	uint64_t* dRows = nullptr;
+	if (int rc = io.Text(text, offsets, n, 0, 0, &dText, &dOffsets))
+		return rc;
+	if (out_rows)
+		if (int rc = io.Result(out_rows, size_t(n) + 1, size_t(n) + 1, &dRows))
+			return rc;
+	HitStage list(onDevice, out_match_count, "hipMemcpy(matches)");
+	// (HitStage::Count's part, with this pass's bound: matches are not empty and do not overlap, so a host call stages no more
+	// entries than the text has bytes)
+	list.cap = onDevice ? match_cap : std::min<uint64_t>(match_cap, textBytes);
+	uint64_t *dOwners = nullptr, *dSpans = nullptr;
+	int rc;
+	if ((rc = io.Result(onDevice ? out_match_count : &list.count, 1, 1, &list.dCount)) || (rc = list.List(io, out_owners, 1, &dOwners)) ||
+	    (rc = list.List(io, out_spans, 2, &dSpans)) || (rc = io.Ready()))
+		return rc;
+	if ((rc = SearchAllEnqueue(tabs, opts, dText, textBytes, dOffsets, n, 0, dRows, dOwners, dSpans, list.cap, list.dCount, stream)))
+		return rc;
+	if ((rc = io.Finish()))
+		return rc;
+	return list.Back();
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+// The frame around the list form of the search: the search on the lines with shift = 1 (string i of the split buffer lies i bytes
+// further into raw), the gather from raw through its spans.  A line can have many matches: the lists are match_cap long.
+int pire_hip_search_all_lines_gather(pire_hip_table* rev, pire_hip_table* fwd, uint32_t opts, const void* raw, uint64_t size, uint32_t delim,
+                                     uint32_t flags, uint32_t tail_byte, uint64_t* out_line_count, uint64_t* out_owners, uint64_t* out_spans,
+                                     uint64_t match_cap, uint64_t* out_match_count, void* out_text, uint64_t text_cap, uint64_t* out_offsets,
+                                     uint64_t* out_bytes, void* streamPtr)
+try {
+	const char* who = "pire_hip_search_all_lines_gather";
+	if (int rc = SearchArgsInvalid(who, rev, fwd, opts))
+		return rc;
+	flags &= PIRE_HIP_RUN_ON_DEVICE;   // (the marks are the search's own: opts)
+	if (int rc = SplitArgsInvalid(who, raw, size, delim, out_line_count, "out_line_count"))
+		return rc;
+	// no gather output at all: spans only.  (The gather form keeps the span list to itself where the caller has no array for it.)
+	const bool gathers = out_text || text_cap || out_offsets || out_bytes;
+	if (int rc = SearchAllOutputsInvalid(who, out_owners || out_spans || gathers, match_cap, out_match_count))
+		return rc;
+	if (gathers) {
+		if (int rc = GatherOutputsInvalid(who, "match_cap", match_cap, tail_byte, out_text, text_cap, out_offsets, out_bytes))
+			return rc;
+		if (int rc = GatherOverlaps(who, raw, size, out_text, text_cap))
+			return rc;
+	}
+	const LinesGather gather = {tail_byte, out_text, text_cap, out_offsets, out_bytes, false, "hipMallocAsync(search spans)"};
+	LinesFrame f(who, raw, size, delim, flags, gathers ? &gather : nullptr, streamPtr);
+	if (f.HostEdge(out_line_count)) {
+		*out_match_count = 0;
+		return PIRE_HIP_OK;
+	}
+	if (int rc = f.Open())
+		return rc;
+	if (int rc = f.Split(out_line_count, out_match_count, 1, match_cap, false))
+		return rc;
+	if (!f.onDevice)
+		f.cap = std::min<uint64_t>(f.cap, size);   // matches are not empty and do not overlap: a host call stages no more
+	if (int rc = f.Lists(out_owners, out_spans))
+		return rc;
+	if (f.n == 0) {
+		if (int rc = f.ZeroCounts("hipMemsetAsync(match count)"))
+			return rc;
+	} else {
+		SearchTables tabs;
+		if (int rc = tabs.Prepare(rev, fwd, opts, f.onDevice))
+			return rc;
+		if (int rc = SearchAllEnqueue(tabs, opts, f.Text(), size, f.Offsets(), f.n, 1, nullptr, f.dHits, f.dSpans, f.cap, f.dCounts, f.stream))
+			return rc;
+	}
+	return f.Close("hipMemcpy(search spans)");
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
 int pire_hip_step(pire_hip_table* t, uint32_t* state_idx, uint64_t n, uint32_t ch, void* stream)
 try {
 	if (!t || (n && !state_idx) || ch >= kMaxCharUnaligned || ch == kEpsilon) {

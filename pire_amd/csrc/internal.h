@@ -1452,6 +1452,13 @@ int LaunchSuffix(const ScanParams& p, bool longest, bool throughBegin, long long
 // opts: PIRE_HIP_SEARCH_*.  PIRE_HIP_EUNSUPPORTED before the launch where the two dense images do not fit a block's LDS.
 int LaunchSearch(const ScanParams& rev, const ScanParams& fwd, uint32_t fwdStartBegin, uint32_t opts, long long* outBegin,
                  long long* outEnd, hipStream_t stream);
+// search_all.hip: every leftmost-longest match of every string (pire_hip_search_all), four launches: the marks of one backward
+// walk through `rev` and the matches per string, the scan of those into rows, the lists.  rev, fwd, fwdStartBegin, opts: as
+// LaunchSearch.  textBytes: the buffer behind rev.text (offsets beyond it are clamped); shift: as LaunchCaptureSelect's.
+// outRows[n + 1], outOwners[cap], outSpans[2 * cap]: nullable; *outCount: the matches, capped nowhere.  n == 0: the count
+// (and outRows[0]) zeroed on the stream.
+int LaunchSearchAll(const ScanParams& rev, const ScanParams& fwd, uint32_t fwdStartBegin, uint32_t opts, uint64_t textBytes, uint64_t shift,
+                    uint64_t* outRows, uint64_t* outOwners, uint64_t* outSpans, uint64_t cap, uint64_t* outCount, hipStream_t stream);
 int LaunchCorpusFill(uint8_t* out, uint64_t seed, uint64_t first, uint64_t count, uint64_t len, uint64_t stride,
                      const void* plantsHost, hipStream_t stream);
 
