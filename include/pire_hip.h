@@ -1435,6 +1435,79 @@ int pire_hip_search_all_lines_gather(pire_hip_table* rev, pire_hip_table* fwd, u
                     uint64_t* out_line_count, uint64_t* out_owners, uint64_t* out_spans, uint64_t match_cap, uint64_t* out_match_count,
                     void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes, void* stream);
 
+/* ---- the matches replaced, on the device ------------------------------------------------------------------------- */
+
+#define PIRE_HIP_SPLICE_KEEP 1u        /* the match itself stays, between head and tail */
+#define PIRE_HIP_SPLICE_FIRST 2u       /* the lines form: the first match of every line (pire_hip_search), not every match */
+#define PIRE_HIP_SPLICE_PIECE_MAX 256u /* head and tail: at most this many bytes each */
+
+/*
+ * The mirror image of pire_hip_gather_spans: the gather keeps the spans and drops the rest, this keeps the rest and puts a
+ * piece where every span was -- `sed 's/re/repl/g'` (head = repl), deletion (no head, no tail), redaction, and with KEEP
+ * `grep --color` or `sed 's/re/<b>&<\/b>/g'`.  It takes no table and no scan: it reads what pire_hip_search_all,
+ * pire_hip_search_run_select, pire_hip_capture_select, pire_hip_affix_select or the slow capture pass wrote.
+ *   k = min(span_count ? *span_count : span_cap, span_cap)
+ *   [b_j, e_j) = [spans[2j], spans[2j+1])                      span j of raw, 0 <= j < k
+ *   b_j <= e_j <= size,  e_{j-1} <= b_j                        ascending and disjoint; b_j == e_j: an insertion point
+ *   piece_j = head ++ (KEEP ? raw[b_j, e_j) : "") ++ tail      P_j = |piece_j|
+ *   out = raw[0, b_0) ++ piece_0 ++ raw[e_0, b_1) ++ piece_1 ++ ... ++ piece_{k-1} ++ raw[e_{k-1}, size)
+ *   D(j) = sum over i < j of (P_i - (e_i - b_i))               64-bit, wrap-around
+ *   *out_bytes = size + D(k)
+ *   out_pos[j] = b_j + D(j)                                    where piece j begins in out
+ *   out_offsets[i] = offsets[i] + D(first j with b_j >= offsets[i])        (that j is k where there is none)
+ * Several empty spans at one position insert in list order.  k == 0: out is a copy of raw; size == 0: the pieces alone.
+ * out_bytes (required): the whole need, also beyond text_cap; only the bytes of out_text at positions < text_cap are written.
+ * out_pos[span_cap] (nullable): entries [0, k) are written and nothing behind them.  Where it is null the pass keeps them in
+ *        stream-ordered scratch of 8 * span_cap bytes; where it is not, the pass allocates nothing.
+ * offsets[n + 1], out_offsets[n + 1] (nullable together): string boundaries in raw, not decreasing, <= size, and where they
+ *        lie in out.  A span belongs to the string it begins in, an empty span on a boundary to the string that BEGINS there
+ *        -- so an empty match at the very end of string i-1 moves to string i (the one odd case; it does not arise in the
+ *        lines forms, where a delimiter lies between two lines).  The caller promises that no span straddles a boundary.
+ * head, tail: HOST memory in every mode, head_len and tail_len <= PIRE_HIP_SPLICE_PIECE_MAX, read before the call returns.
+ *        They travel as kernel arguments: the device form allocates nothing for them and stays legal inside a stream capture.
+ * flags: PIRE_HIP_RUN_ON_DEVICE -> every other pointer is a device pointer, the call only enqueues on `stream` (four
+ *        launches) and does not wait.  Otherwise host pointers: staged once, and the call synchronises.  Not in place.
+ * PIRE_HIP_EINVAL before any device is touched: null out_bytes; head_len or tail_len > 256; a length > 0 with a null pointer;
+ * unknown bits in mode (FIRST is the lines form's); span_cap > 0 with null spans; text_cap > 0 with null out_text; exactly one
+ * of offsets / out_offsets null; size > 0 with null raw; span_cap >= 2^32 or n >= 2^32; out_text[0, text_cap) overlapping
+ * raw[0, size); host pointers: a list that is not ascending and disjoint or leaves [0, size], offsets that decrease or
+ * exceed size.
+ * Device pointers and a list that breaks the promise: the output bytes and *out_bytes are unspecified, but nothing is read
+ * outside raw[0, size) or the lists and nothing is written outside out_text[0, text_cap), out_pos[0, k), out_offsets[0, n]
+ * and out_bytes: every source position is clamped (the rule pire_hip_search_all has for strings that overlap).
+ * pire_hip_last_kernel() is not changed.  No first-use self-test.
+ */
+int pire_hip_splice(const void* raw, uint64_t size,
+                    const uint64_t* spans, const uint64_t* span_count, uint64_t span_cap,
+                    const void* head, uint32_t head_len, const void* tail, uint32_t tail_len, uint32_t mode,
+                    const uint64_t* offsets, uint64_t n, uint32_t flags,
+                    void* out_text, uint64_t text_cap, uint64_t* out_pos, uint64_t* out_offsets,
+                    uint64_t* out_bytes, void* stream);
+
+/*
+ * Raw bytes in, rewritten bytes out -- `sed 's/re/repl/g'` on a resident buffer: the split, the search on the lines, the
+ * splice straight over raw.  The delimiters are kept text, so out_text is the buffer as sed would print it and can be split
+ * again.  rev, fwd, opts as pire_hip_search; head, tail, mode as pire_hip_splice.
+ * Without PIRE_HIP_SPLICE_FIRST: the list form of the search (pire_hip_search_all), lists match_cap long.  An empty match is
+ *        never replaced -- the list form never reports one --, so `sed 's|x*|-|g'`, which also inserts at every empty
+ *        match, differs here: only the runs of x are replaced.
+ * With FIRST: pire_hip_search's first match of every line; an empty first match is an insertion, as in sed (`s/^/> /`).  The
+ *        lists are min(match_cap, lines) long.
+ * out_line_count, out_match_count (required): the lines, and the matches found -- also beyond match_cap; then only the first
+ *        match_cap matches are replaced and the rest of the text is copied as it is: the caller sees the need and retries.
+ * out_spans[2 * match_cap], out_pos[match_cap] (nullable): the replaced ranges of raw and where their pieces begin in
+ *        out_text; where null the library keeps them in scratch.
+ * out_bytes (required), out_text[text_cap]: as pire_hip_splice.  size + match_cap * (head_len + tail_len) bytes always suffice.
+ * It refuses what pire_hip_search_all_lines_gather refuses of its inputs and what pire_hip_splice refuses of its outputs.  One
+ * synchronisation of `stream`; 2^32 lines are refused (PIRE_HIP_EUNSUPPORTED).  Host pointers with size == 0: zeros, no
+ * device is touched.
+ */
+int pire_hip_search_lines_splice(pire_hip_table* rev, pire_hip_table* fwd, uint32_t opts,
+                    const void* raw, uint64_t size, uint32_t delim, uint32_t flags,
+                    const void* head, uint32_t head_len, const void* tail, uint32_t tail_len, uint32_t mode,
+                    uint64_t* out_line_count, uint64_t* out_spans, uint64_t* out_pos, uint64_t match_cap,
+                    uint64_t* out_match_count, void* out_text, uint64_t text_cap, uint64_t* out_bytes, void* stream);
+
 /* ---- the strings that count, on the device ---------------------------------------------------------------------- */
 
 /*

@@ -31,6 +31,7 @@
  *     LineContext       a Context(before, after) and what was fetched for it                      BatchRunner, SlowBatchRunner
  *     LineFiles         a Files(fileBytes) and what was fetched for it                            BatchRunner, SlowBatchRunner
  *     LineQuery, Truth  several scanners over the lines of one buffer and a boolean function of what they match; tables of its own
+ *     Substitution      the matches of a MatchFinder replaced in a buffer of lines, the rest kept; tables of its own
  * Which C calls these make, in which order and with which arguments, is recorded: tests/cpp/shim_calls_test.cpp,
  * tests/cpp/shim_calls.expected.txt.
  */
@@ -2725,11 +2726,12 @@ private:
 class MatchFinder {
 public:
 	explicit MatchFinder(Pire::Fsm fsm, uint32_t opts = 0)
-	    : m_fwd(Pire::Fsm(fsm).Compile<Pire::Scanner>()), m_rev(Tail(fsm).Reverse().Compile<Pire::Scanner>()), m_runner(m_rev, m_fwd, opts)
+	    : m_fwd(Pire::Fsm(fsm).Compile<Pire::Scanner>()), m_rev(Tail(fsm).Reverse().Compile<Pire::Scanner>()), m_opts(opts), m_runner(m_rev, m_fwd, opts)
 	{
 	}
 	const Pire::Scanner& Forward() const { return m_fwd; }
 	const Pire::Scanner& ReversedTail() const { return m_rev; }
+	uint32_t Opts() const { return m_opts; }
 	SearchBatchRunner<Pire::Scanner>& Runner() { return m_runner; }
 
 private:
@@ -2739,7 +2741,95 @@ private:
 		return fsm + Pire::Lexer(kAny, kAny + 2).Parse();
 	}
 	Pire::Scanner m_fwd, m_rev;   // (declared before the runner that reads them)
+	uint32_t m_opts;
 	SearchBatchRunner<Pire::Scanner> m_runner;
+};
+
+/*
+ * The matches of a buffer REPLACED, the rest kept -- `sed 's/re/repl/g'` on the device (pire_hip_search_lines_splice; the
+ * delimiters are kept text, so Text() is the buffer as sed would print it and can go into the next RunLines()):
+ *     Pire::Hip::MatchFinder find(Pire::Lexer("[0-9]+").Parse());
+ *     Pire::Hip::Substitution sub(find);                    tables of its own over find's two scanners, find's opts
+ *     sub.With("#").RunLines(raw, size, '\n');             every match becomes "#"
+ *     sub.Text()  the rewritten buffer      sub.Bytes()  its size      sub.MatchCount()  matches replaced      sub.LineCount()
+ *   With(repl)          the match is replaced by repl                              s/re/repl/g
+ *   Wrap(head, tail)    the match stays, between head and tail                     s/re/head&tail/g, grep --color
+ *   Delete()            the match goes                                             s/re//g            (what a new object does)
+ *   FirstOnly(bool)     the first match of every line and not every match          s/re/repl/ ; an empty first match is an insertion
+ * An empty match is never replaced without FirstOnly() (the list form of the search reports none).  head, tail and repl: at
+ * most PIRE_HIP_SPLICE_PIECE_MAX bytes each.  The buffer is read when an accessor first asks: it lives until then.  One call at
+ * a first capacity of matches and of bytes, and one more for each of the two that did not suffice (GrowAndRetry).
+ */
+class Substitution {
+public:
+	explicit Substitution(const MatchFinder& find)
+	    : m_rev(find.ReversedTail()), m_fwd(find.Forward()), m_opts(find.Opts()), m_mode(0), m_raw(nullptr), m_len(0), m_delim('\n'), m_have(false),
+	      m_done(false), m_matchCount(0), m_lineCount(0), m_bytes(0)
+	{
+	}
+	Substitution& With(const std::string& repl) { return Piece(repl, std::string(), 0); }
+	Substitution& Wrap(const std::string& head, const std::string& tail) { return Piece(head, tail, PIRE_HIP_SPLICE_KEEP); }
+	Substitution& Delete() { return Piece(std::string(), std::string(), 0); }
+	Substitution& FirstOnly(bool first = true)
+	{
+		m_mode = first ? m_mode | PIRE_HIP_SPLICE_FIRST : m_mode & ~uint32_t(PIRE_HIP_SPLICE_FIRST);
+		m_done = false;
+		return *this;
+	}
+	Substitution& RunLines(const char* raw, size_t size, char delim = '\n')
+	{
+		m_raw = raw, m_len = size, m_delim = uint8_t(delim);
+		m_have = true, m_done = false;
+		return *this;
+	}
+	const std::string& Text() { Fetch(); return m_text; }
+	uint64_t Bytes() { Fetch(); return m_bytes; }
+	uint64_t MatchCount() { Fetch(); return m_matchCount; }
+	uint64_t LineCount() { Fetch(); return m_lineCount; }
+
+private:
+	Substitution(const Substitution&);
+	Substitution& operator=(const Substitution&);
+
+	Substitution& Piece(const std::string& head, const std::string& tail, uint32_t keep)
+	{
+		m_head = head, m_tail = tail;
+		m_mode = (m_mode & PIRE_HIP_SPLICE_FIRST) | keep;
+		m_done = false;
+		return *this;
+	}
+
+	/* Room for a match per 64 bytes and for a result an eighth longer than the buffer; where the matches did not fit, that is
+	 * settled first (the text of such a call is only partly rewritten), then the bytes. */
+	void Fetch()
+	{
+		if (m_done)
+			return;
+		if (!m_have)
+			throw Pire::Error("pire_hip: Text() follows RunLines()");
+		size_t room = m_len + m_len / 8 + 64;
+		GrowAndRetry(m_len / 64 + 1024, [&](size_t cap) {
+			room = GrowAndRetry(room, [&](size_t textCap) {
+				m_text.resize(textCap);
+				Check(pire_hip_search_lines_splice(m_rev.Handle(), m_fwd.Handle(), m_opts, m_raw, m_len, m_delim, 0, m_head.data(), uint32_t(m_head.size()),
+				                                   m_tail.data(), uint32_t(m_tail.size()), m_mode, &m_lineCount, nullptr, nullptr, cap, &m_matchCount,
+				                                   &m_text[0], textCap, &m_bytes, nullptr));
+				return m_matchCount <= cap ? size_t(m_bytes) : size_t(0);
+			});
+			return size_t(m_matchCount);
+		});
+		m_text.resize(m_bytes);
+		m_done = true;
+	}
+
+	Table<Pire::Scanner> m_rev, m_fwd;
+	uint32_t m_opts, m_mode;
+	const char* m_raw;            // RunLines(): the raw buffer of m_len bytes
+	size_t m_len;
+	uint8_t m_delim;
+	bool m_have, m_done;          // a buffer was given / m_text and the counts are its result under the present pieces
+	std::string m_head, m_tail, m_text;
+	uint64_t m_matchCount, m_lineCount, m_bytes;
 };
 
 }  // namespace Hip

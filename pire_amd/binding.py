@@ -152,6 +152,7 @@ FIELDS_REST = 1   # include/pire_hip.h PIRE_HIP_FIELDS_REST (in `mode`): the spa
 AFFIX_HEAD, AFFIX_TAIL, AFFIX_REST = 0, 1, 2   # include/pire_hip.h PIRE_HIP_AFFIX_HEAD / _TAIL / _REST (`part`)
 AFFIX_LONGEST, AFFIX_THROUGH_BEGIN, AFFIX_THROUGH_END = 1, 2, 4   # include/pire_hip.h PIRE_HIP_AFFIX_* (`head_opts`, `tail_opts`)
 SEARCH_SHORTEST, SEARCH_THROUGH_BEGIN, SEARCH_THROUGH_END = 1, 2, 4   # include/pire_hip.h PIRE_HIP_SEARCH_* (`opts`)
+SPLICE_KEEP, SPLICE_FIRST, SPLICE_PIECE_MAX = 1, 2, 256                 # include/pire_hip.h PIRE_HIP_SPLICE_* (`mode`)
 
 # every symbol include/pire_hip.h declares: (name, restype, argtypes)
 ABI = [
@@ -277,6 +278,8 @@ ABI = [
     ("pire_hip_search_lines_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_search_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_search_all_lines_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_splice", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_search_lines_splice", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_context", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_run_lines_context_select", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_run_lines_context_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1088,6 +1091,68 @@ def search_all_lines_gather_device(rev, fwd, raw_ptr: int, size: int, out_line_c
                                                   out_owners_ptr or None, out_spans_ptr or None, match_cap, out_match_count_ptr or None,
                                                   out_text_ptr or None, text_cap, out_offsets_ptr or None, out_bytes_ptr or None,
                                                   stream or None))
+
+
+def splice(raw, spans, head=b"", tail=b"", mode=0, offsets=None, text_cap: Optional[int] = None, want_pos=True):
+    """pire_hip_splice on host arrays: {"text" u8[min(bytes, text_cap)], "bytes", "pos" u64[k] or None, "offsets" u64[n + 1] or
+    None}.  spans: u64[k, 2], ascending and disjoint; head, tail: bytes, at most SPLICE_PIECE_MAX each; text_cap None = room
+    for the whole result."""
+    raw = _raw_bytes(raw)
+    spans = np.ascontiguousarray(spans, dtype=np.uint64).reshape(-1, 2)
+    head, tail = bytes(head), bytes(tail)
+    k = spans.shape[0]
+    grown = k * (len(head) + len(tail)) - (0 if mode & SPLICE_KEEP else int((spans[:, 1] - spans[:, 0]).sum()))
+    room = max(raw.size + grown, 0) if text_cap is None else int(text_cap)
+    offs = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
+    out_offs = None if offs is None else np.zeros(offs.size, dtype=np.uint64)
+    pos = np.zeros(k, dtype=np.uint64) if want_pos and k else None
+    text = np.zeros(max(room, 1), dtype=np.uint8)
+    total = C.c_uint64(0)
+    _check(lib().pire_hip_splice(raw.ctypes.data if raw.size else None, raw.size, spans.ctypes.data if k else None, None, k,
+                                 head or None, len(head), tail or None, len(tail), mode, _np_ptr(offs), 0 if offs is None else offs.size - 1, 0,
+                                 text.ctypes.data if room else None, room, _np_ptr(pos), _np_ptr(out_offs), C.byref(total), None))
+    return {"text": text[:min(int(total.value), room)], "bytes": int(total.value), "pos": pos, "offsets": out_offs}
+
+
+def splice_device(raw_ptr: int, size: int, spans_ptr: int, span_cap: int, out_bytes_ptr: int, head=b"", tail=b"", mode=0, span_count_ptr=0,
+                  offsets_ptr=0, n=0, out_text_ptr=0, text_cap=0, out_pos_ptr=0, out_offsets_ptr=0, stream: int = 0):
+    """pire_hip_splice on device pointers (head and tail are host bytes in every mode): only enqueues on `stream`."""
+    head, tail = bytes(head), bytes(tail)
+    _check(lib().pire_hip_splice(raw_ptr or None, size, spans_ptr or None, span_count_ptr or None, span_cap, head or None, len(head),
+                                 tail or None, len(tail), mode, offsets_ptr or None, n, FLAG_ON_DEVICE, out_text_ptr or None, text_cap,
+                                 out_pos_ptr or None, out_offsets_ptr or None, out_bytes_ptr or None, stream or None))
+
+
+def search_lines_splice_host(rev, fwd, raw, head=b"", tail=b"", mode=0, opts=0, delim: int = 10, match_cap=None, text_cap=None):
+    """pire_hip_search_lines_splice on a host buffer: {"lines", "count", "spans" u64[k, 2], "pos" u64[k], "text", "bytes"}, k =
+    min(count, match_cap).  match_cap None = room for a match at every byte (and one more: an insertion at the end); text_cap
+    None = for all of them."""
+    raw = _raw_bytes(raw)
+    head, tail = bytes(head), bytes(tail)
+    cap = raw.size + 1 if match_cap is None else int(match_cap)
+    room = raw.size + cap * (len(head) + len(tail)) if text_cap is None else int(text_cap)
+    spans = np.zeros((cap, 2), dtype=np.uint64)
+    pos = np.zeros(cap, dtype=np.uint64)
+    text = np.zeros(max(room, 1), dtype=np.uint8)
+    lines, cnt, total = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    _check(lib().pire_hip_search_lines_splice(_table_ptr(rev), _table_ptr(fwd), opts, raw.ctypes.data if raw.size else None, raw.size, delim, 0,
+                                              head or None, len(head), tail or None, len(tail), mode, C.byref(lines),
+                                              spans.ctypes.data if cap else None, pos.ctypes.data if cap else None, cap, C.byref(cnt),
+                                              text.ctypes.data if room else None, room, C.byref(total), None))
+    k = min(int(cnt.value), cap)
+    return {"lines": int(lines.value), "count": int(cnt.value), "spans": spans[:k], "pos": pos[:k],
+            "text": text[:min(int(total.value), room)], "bytes": int(total.value)}
+
+
+def search_lines_splice_device(rev, fwd, raw_ptr: int, size: int, out_line_count_ptr: int, out_match_count_ptr: int, out_bytes_ptr: int,
+                               head=b"", tail=b"", mode=0, opts=0, delim: int = 10, out_spans_ptr=0, out_pos_ptr=0, match_cap=0,
+                               out_text_ptr=0, text_cap=0, stream: int = 0):
+    """pire_hip_search_lines_splice on device pointers (synchronises `stream` once, as search_lines_gather_device does)."""
+    head, tail = bytes(head), bytes(tail)
+    _check(lib().pire_hip_search_lines_splice(_table_ptr(rev), _table_ptr(fwd), opts, raw_ptr or None, size, delim, FLAG_ON_DEVICE,
+                                              head or None, len(head), tail or None, len(tail), mode, out_line_count_ptr or None,
+                                              out_spans_ptr or None, out_pos_ptr or None, match_cap, out_match_count_ptr or None,
+                                              out_text_ptr or None, text_cap, out_bytes_ptr or None, stream or None))
 
 
 def capture_select_host(offsets, begin, end, final=None, flags=FLAG_BEGIN, need_final=False, hit_cap: Optional[int] = None,

@@ -4389,6 +4389,199 @@ try {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
 
+// ---- the matches replaced, the rest kept (splice.hip) ------------------------------------------------------------------------
+namespace {
+
+// What both splice entry points refuse of the pieces and of their outputs before any device is touched
+int SpliceArgsInvalid(const char* who, const void* head, uint32_t headLen, const void* tail, uint32_t tailLen, uint32_t mode, uint32_t known,
+                      const void* outText, uint64_t textCap, const void* outBytes)
+{
+	const char* what = !outBytes                                                        ? "null out_bytes"
+	                   : headLen > PIRE_HIP_SPLICE_PIECE_MAX                            ? "head_len > 256"
+	                   : tailLen > PIRE_HIP_SPLICE_PIECE_MAX                            ? "tail_len > 256"
+	                   : headLen && !head                                               ? "head_len > 0 with null head"
+	                   : tailLen && !tail                                               ? "tail_len > 0 with null tail"
+	                   : mode & ~known                                                  ? "unknown bits in mode"
+	                   : textCap && !outText                                            ? "text_cap > 0 with null out_text"
+	                                                                                    : nullptr;
+	return what ? GatherRefuse(who, what) : PIRE_HIP_OK;
+}
+
+}  // namespace
+
+int pire_hip_splice(const void* raw, uint64_t size, const uint64_t* spans, const uint64_t* span_count, uint64_t span_cap, const void* head,
+                    uint32_t head_len, const void* tail, uint32_t tail_len, uint32_t mode, const uint64_t* offsets, uint64_t n, uint32_t flags,
+                    void* out_text, uint64_t text_cap, uint64_t* out_pos, uint64_t* out_offsets, uint64_t* out_bytes, void* streamPtr)
+try {
+	const char* who = "pire_hip_splice";
+	if (int rc = SpliceArgsInvalid(who, head, head_len, tail, tail_len, mode, PIRE_HIP_SPLICE_KEEP, out_text, text_cap, out_bytes))
+		return rc;
+	if (span_cap && !spans)
+		return GatherRefuse(who, "span_cap > 0 with null spans");
+	if (!offsets != !out_offsets)
+		return GatherRefuse(who, "offsets and out_offsets: one without the other");
+	if (size && !raw)
+		return GatherRefuse(who, "size > 0 with null raw");
+	if (span_cap >= (1ull << 32) || n >= (1ull << 32))
+		return GatherRefuse(who, "2^32 spans or strings or more in one call");
+	if (int rc = GatherOverlaps(who, raw, size, out_text, text_cap))
+		return rc;
+	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
+	// host pointers: the host's own look at the list -- k spans, ascending and disjoint inside raw -- and at the offsets; it
+	// knows the need before the device does
+	uint64_t k = span_cap, total = kSpliceTotalUnknown;
+	if (!onDevice) {
+		k = std::min(span_count ? *span_count : span_cap, span_cap);
+		uint64_t grown = 0, behind = 0;
+		for (uint64_t j = 0; j < k; ++j) {
+			const uint64_t b = spans[2 * j], e = spans[2 * j + 1];
+			if (b < behind || e < b || e > size)
+				return GatherRefuse(who, "spans must ascend, must not overlap and must lie inside raw");
+			grown += uint64_t(head_len) + tail_len - ((mode & PIRE_HIP_SPLICE_KEEP) ? 0 : e - b);
+			behind = e;
+		}
+		total = size + grown;
+		if (offsets) {
+			if (int rc = CheckOffsets(offsets, n))
+				return rc;
+			if (offsets[n] > size)
+				return GatherRefuse(who, "an offset exceeds size");
+		}
+	}
+	BatchIO io(stream, onDevice);
+	const uint8_t* dRaw = nullptr;
+	const uint64_t *dSpans = nullptr, *dOffsets = nullptr;
+	if (int rc = io.In(static_cast<const uint8_t*>(raw), size_t(size), &dRaw))
+		return rc;
+	if (int rc = io.In(spans, size_t(k) * 2, &dSpans))
+		return rc;
+	if (offsets)
+		if (int rc = io.In(offsets, size_t(n) + 1, &dOffsets))
+			return rc;
+	uint64_t *dBytes = nullptr, *dPos = nullptr, *dOutOffsets = nullptr;
+	uint8_t* dOutText = nullptr;
+	const uint64_t room = std::min(total, text_cap);
+	if (int rc = io.Result(out_bytes, 1, 1, &dBytes))
+		return rc;
+	if (out_pos && k)
+		if (int rc = io.Result(out_pos, size_t(k), size_t(k), &dPos))
+			return rc;
+	if (out_offsets)
+		if (int rc = io.Result(out_offsets, size_t(n) + 1, size_t(n) + 1, &dOutOffsets))
+			return rc;
+	if (room)
+		if (int rc = io.Result(static_cast<uint8_t*>(out_text), size_t(room), size_t(room), &dOutText))
+			return rc;
+	if (int rc = io.Ready())
+		return rc;
+	StreamScratch own(stream);   // where the pieces begin, where the caller has no array for that
+	if (!dPos && k) {
+		if (int rc = own.Alloc(size_t(k) * 8, "hipMallocAsync(splice positions)"))
+			return rc;
+		dPos = own.as<uint64_t>();
+	}
+	if (int rc = LaunchSplice(dRaw, size, dSpans, onDevice ? span_count : nullptr, k, head, head_len, tail, tail_len, mode, dOffsets, n, dOutText, room,
+	                          dPos, dOutOffsets, dBytes, total, stream))
+		return rc;
+	return io.Finish();
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+// The frame around the search and the splice: the search on the lines with shift = 1 (its spans are ranges of raw), then the
+// splice straight over raw through those spans -- the delimiters are kept text.
+int pire_hip_search_lines_splice(pire_hip_table* rev, pire_hip_table* fwd, uint32_t opts, const void* raw, uint64_t size, uint32_t delim,
+                                 uint32_t flags, const void* head, uint32_t head_len, const void* tail, uint32_t tail_len, uint32_t mode,
+                                 uint64_t* out_line_count, uint64_t* out_spans, uint64_t* out_pos, uint64_t match_cap, uint64_t* out_match_count,
+                                 void* out_text, uint64_t text_cap, uint64_t* out_bytes, void* streamPtr)
+try {
+	const char* who = "pire_hip_search_lines_splice";
+	if (int rc = SearchArgsInvalid(who, rev, fwd, opts))
+		return rc;
+	flags &= PIRE_HIP_RUN_ON_DEVICE;   // (the marks are the search's own: opts)
+	if (int rc = SplitArgsInvalid(who, raw, size, delim, out_line_count, "out_line_count"))
+		return rc;
+	if (!out_match_count)
+		return GatherRefuse(who, "null out_match_count");
+	if (int rc = SpliceArgsInvalid(who, head, head_len, tail, tail_len, mode, PIRE_HIP_SPLICE_KEEP | PIRE_HIP_SPLICE_FIRST, out_text, text_cap,
+	                               out_bytes))
+		return rc;
+	if (match_cap >= (1ull << 32))
+		return GatherRefuse(who, "2^32 spans or strings or more in one call");
+	if (int rc = GatherOverlaps(who, raw, size, out_text, text_cap))
+		return rc;
+	const bool first = (mode & PIRE_HIP_SPLICE_FIRST) != 0;
+	LinesFrame f(who, raw, size, delim, flags, nullptr, streamPtr);
+	if (f.HostEdge(out_line_count)) {
+		*out_match_count = 0;
+		*out_bytes = 0;
+		return PIRE_HIP_OK;
+	}
+	if (int rc = f.Open())
+		return rc;
+	if (int rc = f.Split(out_line_count, out_match_count, 1, match_cap, first))   // (FIRST: n lines have at most n first matches)
+		return rc;
+	if (!first && !f.onDevice)
+		f.cap = std::min<uint64_t>(f.cap, size);   // matches are not empty and do not overlap: a host call stages no more
+	if (int rc = f.Lists(nullptr, out_spans))
+		return rc;
+	// the spans and the positions in scratch of the library's own where the caller has no array for them
+	StreamScratch ownSpans(f.stream), ownPos(f.stream);
+	uint64_t *dSpans = f.dSpans, *dPos = nullptr, *dBytes = nullptr;
+	uint8_t* dOutText = nullptr;
+	const uint64_t room = f.onDevice ? text_cap : std::min(text_cap, size + f.cap * (uint64_t(head_len) + tail_len));
+	if (int rc = f.io.Result(out_bytes, 1, 1, &dBytes))
+		return rc;
+	if (out_pos && f.cap)
+		if (int rc = f.io.Result(out_pos, size_t(f.cap), 0, &dPos))
+			return rc;
+	if (room)
+		if (int rc = f.io.Result(static_cast<uint8_t*>(out_text), size_t(room), 0, &dOutText))
+			return rc;
+	if (!dSpans && f.cap) {
+		if (int rc = ownSpans.Alloc(size_t(f.cap) * 16, "hipMallocAsync(search spans)"))
+			return rc;
+		dSpans = ownSpans.as<uint64_t>();
+	}
+	if (!dPos && f.cap) {
+		if (int rc = ownPos.Alloc(size_t(f.cap) * 8, "hipMallocAsync(splice positions)"))
+			return rc;
+		dPos = ownPos.as<uint64_t>();
+	}
+	if (f.n == 0) {
+		if (int rc = f.ZeroCounts("hipMemsetAsync(match count)"))
+			return rc;
+	} else {
+		SearchTables tabs;
+		if (int rc = tabs.Prepare(rev, fwd, opts, f.onDevice))
+			return rc;
+		if (first) {
+			if (int rc = SearchEnqueue(tabs, opts, f.Text(), f.Offsets(), f.n, nullptr, nullptr, 1, nullptr, dSpans, f.cap, f.dCounts, f.stream))
+				return rc;
+		} else if (int rc = SearchAllEnqueue(tabs, opts, f.Text(), size, f.Offsets(), f.n, 1, nullptr, nullptr, dSpans, f.cap, f.dCounts, f.stream))
+			return rc;
+	}
+	// (the pass reads min(*count, cap) spans: what lies beyond match_cap stays as it is)
+	if (int rc = LaunchSplice(f.dRaw, size, dSpans, f.dCounts, f.cap, head, head_len, tail, tail_len, mode & PIRE_HIP_SPLICE_KEEP, nullptr, 0, dOutText,
+	                          room, dPos, nullptr, dBytes, kSpliceTotalUnknown, f.stream))
+		return rc;
+	if (int rc = f.Close("hipMemcpy(splice)"))
+		return rc;
+	if (f.onDevice)
+		return PIRE_HIP_OK;
+	if (int rc = HitsBack(1, out_match_count, f.cap, f.cap, out_pos ? dPos : nullptr, out_pos, 8, "hipMemcpy(splice)"))
+		return rc;
+	if (const uint64_t bytes = std::min(*out_bytes, room)) {
+		const hipError_t e = hipMemcpy(out_text, dOutText, size_t(bytes), hipMemcpyDeviceToHost);
+		if (e != hipSuccess)
+			return HipFail(e, "hipMemcpy(splice)");
+	}
+	return PIRE_HIP_OK;
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
 int pire_hip_step(pire_hip_table* t, uint32_t* state_idx, uint64_t n, uint32_t ch, void* stream)
 try {
 	if (!t || (n && !state_idx) || ch >= kMaxCharUnaligned || ch == kEpsilon) {

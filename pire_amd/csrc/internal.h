@@ -1459,6 +1459,15 @@ int LaunchSearch(const ScanParams& rev, const ScanParams& fwd, uint32_t fwdStart
 // (and outRows[0]) zeroed on the stream.
 int LaunchSearchAll(const ScanParams& rev, const ScanParams& fwd, uint32_t fwdStartBegin, uint32_t opts, uint64_t textBytes, uint64_t shift,
                     uint64_t* outRows, uint64_t* outOwners, uint64_t* outSpans, uint64_t cap, uint64_t* outCount, hipStream_t stream);
+// splice.hip: the spans of a buffer replaced by head ++ (the match, under PIRE_HIP_SPLICE_KEEP) ++ tail, the rest kept
+// (pire_hip_splice).  Device pointers only -- but head and tail, which are the host's and travel as kernel arguments --, four
+// kernels enqueued on `stream`, no allocation: outPos[cap] is required where cap > 0 (the caller's array or its scratch).
+// offsets / outOffsets: nullable together.  hostTotal: *outBytes where the host knows it (it sizes the copy pass's grid
+// exactly), kSpliceTotalUnknown where it does not (the grid then comes from textCap and the largest possible output).
+constexpr uint64_t kSpliceTotalUnknown = ~0ull;
+int LaunchSplice(const void* raw, uint64_t size, const uint64_t* spans, const uint64_t* count, uint64_t cap, const void* head, uint32_t headLen,
+                 const void* tail, uint32_t tailLen, uint32_t mode, const uint64_t* offsets, uint64_t n, void* outText, uint64_t textCap,
+                 uint64_t* outPos, uint64_t* outOffsets, uint64_t* outBytes, uint64_t hostTotal, hipStream_t stream);
 int LaunchCorpusFill(uint8_t* out, uint64_t seed, uint64_t first, uint64_t count, uint64_t len, uint64_t stride,
                      const void* plantsHost, hipStream_t stream);
 
