@@ -1435,6 +1435,69 @@ int pire_hip_search_all_lines_gather(pire_hip_table* rev, pire_hip_table* fwd, u
                     uint64_t* out_line_count, uint64_t* out_owners, uint64_t* out_spans, uint64_t match_cap, uint64_t* out_match_count,
                     void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes, void* stream);
 
+/* ---- labelled matches and tokens, on the device ------------------------------------------------------------------ */
+
+#define PIRE_HIP_LEX_SHORTEST 1u       /* = PIRE_HIP_SEARCH_SHORTEST */
+#define PIRE_HIP_LEX_THROUGH_BEGIN 2u  /* = PIRE_HIP_SEARCH_THROUGH_BEGIN */
+#define PIRE_HIP_LEX_THROUGH_END 4u    /* = PIRE_HIP_SEARCH_THROUGH_END */
+#define PIRE_HIP_LEX_TOKENS 8u         /* maximal-munch tokens and the gaps between them, through fwd alone */
+
+/*
+ * Which regexp each match belongs to: Scanner::Glue followed by AcceptedRegexps, per MATCH instead of per string.
+ * fwd (F): a glued Scanner of R regexps re_0 .. re_{R-1}, 1 <= R <= 64, not Surround()ed.  rev (R~): the Scanner of
+ * `((re_0)|(re_1)|...)` followed by the lexer's `.*`, compiled from Fsm::Reverse() -- MatchFinder's construction over the
+ * union.  opts: S, B, E with the values and the meaning of PIRE_HIP_SEARCH_*, and PIRE_HIP_LEX_TOKENS.
+ *
+ * SEARCH MODE (no TOKENS) is exactly pire_hip_search_all's loop over rev and fwd: spans, owners and rows are bit for bit what
+ * that call writes for the same tables.  Every reported match k also gets mask[k]:
+ *   q = F's state after the h bytes of the match, from Initialize() (+ Step(BeginMark) where the leg took the mark)
+ *   mask = AcceptedRegexps(q) as bits                                  if Final(q)
+ *   mask |= AcceptedRegexps(Step(q, EndMark)) as bits                  if E, the match ends at len and Final(Step(q, EndMark))
+ * The mask of a reported match is never 0.
+ *
+ * TOKEN MODE (TOKENS) does not use rev, which may be null; no mark pass, no mark scratch.  For string s of length len:
+ *   p = 0
+ *   while p < len:
+ *       h = S ? ShortestPrefix(F, s[p, len), throughBeginMark = B && p == 0, throughEndMark = E)
+ *             : LongestPrefix (F, ...the same...)                                                 run.h:277-311
+ *       if h > 0: an entry [p, p + h) with its mask as above;  p += h
+ *       else:     byte p is a gap byte;  p += 1
+ *   a maximal run of gap bytes is ONE entry with mask 0
+ * The entries of a string tile [0, len) exactly, in ascending order; an empty string has none.  Without E, dropping the gaps
+ * leaves search mode's list.  With E, search mode only sees matches that accept through the EndMark (as pire_hip_search);
+ * token mode is how to get a per-token `$`.  The walk restarts at every gap byte: a pattern whose forward leg runs far before
+ * it fails (`a.*b`) costs that run per gap byte -- the definition's cost.
+ *
+ * text, text_bytes, offsets, n, flags, out_rows, out_owners, out_spans, match_cap, out_match_count: as pire_hip_search_all
+ * (entries instead of matches), clamping, decreasing offsets and n == 0 included.
+ * out_masks[match_cap] (nullable): the mask of entry k.
+ * out_label_counts[R + 1] (nullable): entry r = the number of entries whose LOWEST set bit is r (lex's first-rule-wins), entry
+ *        R = the number of gaps.  Counted over all entries, also beyond match_cap; exact 64-bit integers, the same for the
+ *        same input.
+ * PIRE_HIP_EINVAL before any device is touched: unknown bits in opts; null fwd; null rev without TOKENS; match_cap > 0 with
+ * null out_owners, out_spans and out_masks; a SimpleScanner table; and what pire_hip_search_all refuses of its batch.
+ * PIRE_HIP_EUNSUPPORTED before any device is touched: a fwd of more than 64 regexps (it has no accept masks).
+ * PIRE_HIP_EUNSUPPORTED: the dense rows do not fit the LDS (token mode: F's alone count).
+ * pire_hip_last_kernel() is not changed.  No first-use self-test.  Four launches on `stream`.
+ */
+int pire_hip_lex(pire_hip_table* rev, pire_hip_table* fwd, uint32_t opts,
+                    const void* text, uint64_t text_bytes, const uint64_t* offsets, uint64_t n, uint32_t flags,
+                    uint64_t* out_rows, uint64_t* out_owners, uint64_t* out_spans, uint64_t* out_masks, uint64_t match_cap,
+                    uint64_t* out_match_count, uint64_t* out_label_counts, void* stream);
+
+/*
+ * Raw bytes in, every labelled match (or token) of every line out: split, pire_hip_lex on the lines, then the gather from raw
+ * through the spans with tail_byte behind each entry.  As pire_hip_search_all_lines_gather, plus out_masks[match_cap] and
+ * out_label_counts[R + 1] (both nullable).  Spans are byte ranges of raw.  In token mode the gathered entries of a line are
+ * the line itself, cut.  size + match_cap bytes of out_text always suffice.  One synchronisation of `stream`; 2^32 lines are
+ * refused (PIRE_HIP_EUNSUPPORTED).  Host pointers with size == 0: zeros (the label counts too), no device is touched.
+ */
+int pire_hip_lex_lines_gather(pire_hip_table* rev, pire_hip_table* fwd, uint32_t opts,
+                    const void* raw, uint64_t size, uint32_t delim, uint32_t flags, uint32_t tail_byte,
+                    uint64_t* out_line_count, uint64_t* out_owners, uint64_t* out_spans, uint64_t* out_masks, uint64_t match_cap,
+                    uint64_t* out_match_count, uint64_t* out_label_counts,
+                    void* out_text, uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes, void* stream);
+
 /* ---- the matches replaced, on the device ------------------------------------------------------------------------- */
 
 #define PIRE_HIP_SPLICE_KEEP 1u        /* the match itself stays, between head and tail */

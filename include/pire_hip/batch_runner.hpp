@@ -2746,6 +2746,212 @@ private:
 };
 
 /*
+ * Which regexp each match belongs to, and tokens: pire_hip_lex / pire_hip_lex_lines_gather over a glued scanner (include/pire_hip.h,
+ * "labelled matches and tokens").  The runner takes the two scanners of a TokenFinder (below) or the caller's own:
+ *     Pire::Hip::LexBatchRunner lex(reversedTail, gluedForward);
+ *     lex.Run(strings);                every leftmost-longest match of every string (SearchBatchRunner::All()'s) ...
+ *     lex.Hits()  lex.Spans()  lex.Rows()  lex.HitCount()    ... as there, and per match:
+ *     lex.Masks()        bit r: regexp r accepts the match                 lex.Labels()   its lowest regexp (lex's first-rule-wins)
+ *     lex.LabelCounts()  [R + 1]: matches per label, gaps last -- counted on the device
+ *     lex.Run(strings).Tokens();       maximal-munch tokens instead; what no regexp takes comes as gap entries, mask 0 and label
+ *                                      kGap: the entries of a string tile it
+ *     lex.RunLines(raw, size, '\n').Tokens().HitText('\n');   every token and gap of every line, a '\n' behind each
+ * A new batch starts in search mode.  The caller's arrays are read when an accessor first asks: they live until then.
+ */
+class LexBatchRunner {
+public:
+	static const uint32_t kGap = 0xFFFFFFFFu;   // Labels(): the entry is a gap
+
+	LexBatchRunner(const Pire::Scanner& reversedTail, const Pire::Scanner& forward, uint32_t opts = 0)
+	    : m_rev(reversedTail), m_fwd(forward), m_regexps(forward.RegexpsCount()), m_opts(opts & ~uint32_t(PIRE_HIP_LEX_TOKENS)), m_mode(0),
+	      m_form(kNone), m_text(nullptr), m_offsets(nullptr), m_n(0), m_len(0), m_delim('\n'), m_listed(false), m_haveText(false), m_textTail('\n'),
+	      m_hitCount(0), m_lineCount(0)
+	{
+	}
+
+	/* The batch: string i = text[offsets[i], offsets[i+1]).  Host pointers. */
+	LexBatchRunner& Run(const char* text, const uint64_t* offsets, size_t n) { return SetBatch(kStrings, text, offsets, n, 0, '\n'); }
+	LexBatchRunner& Run(const std::vector<ystring>& strings)
+	{
+		m_ownStrings.Assign(strings);
+		return Run(m_ownStrings.Text(), m_ownStrings.Offsets(), strings.size());
+	}
+	LexBatchRunner& RunLines(const char* raw, size_t size, char delim = '\n') { return SetBatch(kLines, raw, nullptr, 0, size, delim); }
+	/* tokens and gaps instead of matches (PIRE_HIP_LEX_TOKENS) */
+	LexBatchRunner& Tokens(bool tokens = true)
+	{
+		const uint32_t mode = tokens ? PIRE_HIP_LEX_TOKENS : 0;
+		if (mode != m_mode)
+			m_listed = m_haveText = false;
+		m_mode = mode;
+		return *this;
+	}
+	uint64_t HitCount() { FetchHits("HitCount()"); return m_hitCount; }
+	const std::vector<uint64_t>& Hits() { FetchHits("Hits()"); return m_hits; }
+	const std::vector<uint64_t>& Spans() { FetchHits("Spans()"); return m_spans; }
+	const std::vector<uint64_t>& Masks() { FetchHits("Masks()"); return m_masks; }
+	const std::vector<uint32_t>& Labels() { FetchHits("Labels()"); return m_labels; }
+	const std::vector<uint64_t>& LabelCounts() { FetchHits("LabelCounts()"); return m_labelCounts; }
+	uint64_t LineCount() { NeedLines("LineCount()"); FetchHits("LineCount()"); return m_lineCount; }
+	const std::string& HitText(char tail = '\n') { FetchHitText(tail); return m_hitText; }
+	const std::vector<uint64_t>& HitTextOffsets()
+	{
+		if (!m_haveText)
+			FetchHitText('\n');
+		return m_hitTextOffsets;
+	}
+	/* behind Run(): n + 1 row starts into the lists */
+	const std::vector<uint64_t>& Rows()
+	{
+		if (m_form != kStrings)
+			throw Pire::Error("pire_hip: Rows() follows Run()");
+		FetchHits("Rows()");
+		return m_rows;
+	}
+
+private:
+	LexBatchRunner(const LexBatchRunner&);
+	LexBatchRunner& operator=(const LexBatchRunner&);
+
+	enum Form { kNone, kStrings, kLines };
+	LexBatchRunner& SetBatch(Form form, const char* text, const uint64_t* offsets, size_t n, size_t len, char delim)
+	{
+		m_form = form, m_text = text, m_offsets = offsets, m_n = n, m_len = len, m_delim = uint8_t(delim);
+		m_listed = m_haveText = false;
+		m_mode = 0;
+		return *this;
+	}
+	void NeedLines(const char* what) const
+	{
+		if (m_form != kLines)
+			throw Pire::Error(std::string("pire_hip: ") + what + " follows RunLines()");
+	}
+
+	/* One call with room for an entry per string -- RunLines(): per 64 bytes --, and a second one where there are more
+	 * (SearchBatchRunner::FetchAll's capacities) */
+	void FetchHits(const char* what)
+	{
+		if (m_listed)
+			return;
+		if (m_form == kNone)
+			throw Pire::Error(std::string("pire_hip: ") + what + " follows Run() or RunLines()");
+		const uint64_t* offsets = OwnedStrings::OffsetsOr(m_offsets, m_n);
+		m_labelCounts.assign(size_t(m_regexps) + 1, 0);
+		GrowAndRetry(m_form == kLines ? m_len / 64 + 1024 : m_n, [&](size_t cap) {
+			m_hits.resize(cap);
+			m_spans.resize(cap * 2);
+			m_masks.resize(cap);
+			if (m_form == kStrings)
+				m_rows.resize(m_n + 1);
+			Check(m_form == kLines
+			          ? pire_hip_lex_lines_gather(m_rev.Handle(), m_fwd.Handle(), m_opts | m_mode, m_text, m_len, m_delim, 0, PIRE_HIP_GATHER_NO_TAIL,
+			                                      &m_lineCount, m_hits.data(), m_spans.data(), m_masks.data(), cap, &m_hitCount, m_labelCounts.data(),
+			                                      nullptr, 0, nullptr, nullptr, nullptr)
+			          : pire_hip_lex(m_rev.Handle(), m_fwd.Handle(), m_opts | m_mode, m_text, m_n ? offsets[m_n] : 0, offsets, m_n, 0, m_rows.data(),
+			                         m_hits.data(), m_spans.data(), m_masks.data(), cap, &m_hitCount, m_labelCounts.data(), nullptr));
+			return size_t(m_hitCount);
+		});
+		m_hits.resize(m_hitCount);
+		m_spans.resize(m_hitCount * 2);
+		m_masks.resize(m_hitCount);
+		m_labels.resize(m_hitCount);
+		for (size_t k = 0; k < m_masks.size(); ++k) {
+			uint32_t low = 0;
+			while (low < 64 && !((m_masks[k] >> low) & 1))
+				++low;
+			m_labels[k] = low < 64 ? low : kGap;
+		}
+		m_listed = true;
+	}
+
+	/* RunLines(): the entries as bytes; room for every byte they can have, and for the entries that are known, or else FetchHits()'s */
+	void FetchHitText(char tail)
+	{
+		NeedLines("HitText()");
+		if (m_haveText && m_textTail == tail)
+			return;
+		uint64_t count = 0, bytes = 0;
+		GrowAndRetry(m_listed ? size_t(m_hitCount) : m_len / 64 + 1024, [&](size_t cap) {
+			m_hitTextOffsets.resize(cap + 1);
+			m_hitText.resize(m_len + cap + 1);
+			Check(pire_hip_lex_lines_gather(m_rev.Handle(), m_fwd.Handle(), m_opts | m_mode, m_text, m_len, m_delim, 0, uint8_t(tail), &m_lineCount,
+			                                nullptr, nullptr, nullptr, cap, &count, nullptr, &m_hitText[0], m_hitText.size(), m_hitTextOffsets.data(),
+			                                &bytes, nullptr));
+			return size_t(count);   // (the text has room for the whole buffer and a tail per entry: where the entries fit, the bytes do)
+		});
+		m_hitText.resize(bytes);
+		m_hitTextOffsets.resize(count + 1);
+		m_textTail = tail;
+		m_haveText = true;
+	}
+
+	Table<Pire::Scanner> m_rev, m_fwd;
+	uint32_t m_regexps, m_opts, m_mode;   // m_mode: PIRE_HIP_LEX_TOKENS or 0
+	Form m_form;
+	const char* m_text;           // Run(): the strings' text; RunLines(): the raw buffer of m_len bytes
+	const uint64_t* m_offsets;
+	size_t m_n, m_len;
+	uint8_t m_delim;
+	bool m_listed, m_haveText;    // the lists (and m_lineCount) / m_hitText are the batch's in the present mode, with the tail m_textTail
+	char m_textTail;
+	OwnedStrings m_ownStrings;
+	uint64_t m_hitCount, m_lineCount;
+	std::vector<uint64_t> m_hits, m_spans, m_masks, m_labelCounts, m_rows, m_hitTextOffsets;
+	std::vector<uint32_t> m_labels;
+	std::string m_hitText;
+};
+
+/*
+ * Both scanners of pire_hip_lex from the Fsms of the regexps (none Surround()ed), and the runner over them:
+ *     std::vector<Pire::Fsm> rules;   rules.push_back(Pire::Lexer("[a-z]+").Parse());   rules.push_back(Pire::Lexer("[0-9]+").Parse());
+ *     Pire::Hip::TokenFinder lexer(rules);
+ *     lexer.Runner().RunLines(raw, size).Tokens().Labels();
+ *   Forward()        Scanner::Glue of the compiled Fsms, in order: regexp r of the glued scanner is rules[r]
+ *   ReversedTail()   the union of the Fsms + the lexer's `.*`, then Fsm::Reverse(), compiled   (MatchFinder's construction)
+ * It throws Pire::Error for no Fsm, for more than 64, and where Glue answers the empty scanner (the product is too large).
+ */
+class TokenFinder {
+public:
+	explicit TokenFinder(const std::vector<Pire::Fsm>& fsms, uint32_t opts = 0)
+	    : m_fwd(Glued(fsms)), m_rev(Tail(Union(fsms)).Reverse().Compile<Pire::Scanner>()), m_opts(opts), m_runner(m_rev, m_fwd, opts)
+	{
+	}
+	const Pire::Scanner& Forward() const { return m_fwd; }
+	const Pire::Scanner& ReversedTail() const { return m_rev; }
+	uint32_t Opts() const { return m_opts; }
+	LexBatchRunner& Runner() { return m_runner; }
+
+private:
+	static Pire::Scanner Glued(const std::vector<Pire::Fsm>& fsms)
+	{
+		if (fsms.empty() || fsms.size() > 64)
+			throw Pire::Error("pire_hip: TokenFinder takes 1 to 64 regexps");
+		Pire::Scanner glued = Pire::Fsm(fsms[0]).Compile<Pire::Scanner>();
+		for (size_t i = 1; i < fsms.size(); ++i) {
+			glued = Pire::Scanner::Glue(glued, Pire::Fsm(fsms[i]).Compile<Pire::Scanner>());
+			if (glued.Empty())
+				throw Pire::Error("pire_hip: TokenFinder: Scanner::Glue answered the empty scanner (the glued table is too large)");
+		}
+		return glued;
+	}
+	static Pire::Fsm Union(const std::vector<Pire::Fsm>& fsms)
+	{
+		Pire::Fsm all = fsms[0];
+		for (size_t i = 1; i < fsms.size(); ++i)
+			all |= fsms[i];
+		return all;
+	}
+	static Pire::Fsm Tail(const Pire::Fsm& fsm)
+	{
+		static const char kAny[] = ".*";
+		return fsm + Pire::Lexer(kAny, kAny + 2).Parse();
+	}
+	Pire::Scanner m_fwd, m_rev;   // (declared before the runner that reads them)
+	uint32_t m_opts;
+	LexBatchRunner m_runner;
+};
+
+/*
  * The matches of a buffer REPLACED, the rest kept -- `sed 's/re/repl/g'` on the device (pire_hip_search_lines_splice; the
  * delimiters are kept text, so Text() is the buffer as sed would print it and can go into the next RunLines()):
  *     Pire::Hip::MatchFinder find(Pire::Lexer("[0-9]+").Parse());

@@ -152,6 +152,8 @@ FIELDS_REST = 1   # include/pire_hip.h PIRE_HIP_FIELDS_REST (in `mode`): the spa
 AFFIX_HEAD, AFFIX_TAIL, AFFIX_REST = 0, 1, 2   # include/pire_hip.h PIRE_HIP_AFFIX_HEAD / _TAIL / _REST (`part`)
 AFFIX_LONGEST, AFFIX_THROUGH_BEGIN, AFFIX_THROUGH_END = 1, 2, 4   # include/pire_hip.h PIRE_HIP_AFFIX_* (`head_opts`, `tail_opts`)
 SEARCH_SHORTEST, SEARCH_THROUGH_BEGIN, SEARCH_THROUGH_END = 1, 2, 4   # include/pire_hip.h PIRE_HIP_SEARCH_* (`opts`)
+LEX_SHORTEST, LEX_THROUGH_BEGIN, LEX_THROUGH_END, LEX_TOKENS = 1, 2, 4, 8   # include/pire_hip.h PIRE_HIP_LEX_* (`opts`)
+LEX_GAP = 0xFFFFFFFF   # the label of a gap (lex_labels)
 SPLICE_KEEP, SPLICE_FIRST, SPLICE_PIECE_MAX = 1, 2, 256                 # include/pire_hip.h PIRE_HIP_SPLICE_* (`mode`)
 
 # every symbol include/pire_hip.h declares: (name, restype, argtypes)
@@ -278,6 +280,8 @@ ABI = [
     ("pire_hip_search_lines_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_search_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_search_all_lines_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_lex", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("pire_hip_lex_lines_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_splice", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("pire_hip_search_lines_splice", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("pire_hip_context", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1091,6 +1095,86 @@ def search_all_lines_gather_device(rev, fwd, raw_ptr: int, size: int, out_line_c
                                                   out_owners_ptr or None, out_spans_ptr or None, match_cap, out_match_count_ptr or None,
                                                   out_text_ptr or None, text_cap, out_offsets_ptr or None, out_bytes_ptr or None,
                                                   stream or None))
+
+
+def lex_labels(masks) -> np.ndarray:
+    """u32 per entry: the lowest regexp of its mask (lex's first-rule-wins), LEX_GAP for a gap"""
+    m = np.ascontiguousarray(masks, dtype=np.uint64)
+    low = m & (~m + np.uint64(1))
+    out = np.full(m.shape, LEX_GAP, dtype=np.uint32)
+    nz = low != 0
+    out[nz] = np.log2(low[nz].astype(np.float64)).astype(np.uint32)   # (a power of two: exact)
+    return out
+
+
+def lex(rev, fwd, text, offsets, opts=0, match_cap: Optional[int] = None, text_bytes: Optional[int] = None, want_rows=True,
+        want_owners=True, want_spans=True, want_masks=True, want_label_counts=True):
+    """pire_hip_lex on host strings: {"rows" u64[n + 1], "owners" u64[k], "spans" u64[k, 2], "masks" u64[k], "label_counts"
+    u64[R + 1], "count"}, k = min(count, match_cap); an output that is not wanted is None.  rev may be None with LEX_TOKENS.
+    match_cap None = room for an entry at every byte; text_bytes None = the size of `text`."""
+    text = _raw_bytes(text)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    cap = text.size if match_cap is None else int(match_cap)
+    rows = np.zeros(n + 1, dtype=np.uint64) if want_rows else None
+    owners = np.zeros(cap, dtype=np.uint64) if want_owners and cap else None
+    spans = np.zeros((cap, 2), dtype=np.uint64) if want_spans and cap else None
+    masks = np.zeros(cap, dtype=np.uint64) if want_masks and cap else None
+    labels = np.zeros(fwd.info.regexps + 1, dtype=np.uint64) if want_label_counts and fwd is not None else None
+    cnt = C.c_uint64(0)
+    _check(lib().pire_hip_lex(_table_ptr(rev), _table_ptr(fwd), opts, text.ctypes.data if text.size else None,
+                              text.size if text_bytes is None else int(text_bytes), offsets.ctypes.data, n, 0, _np_ptr(rows), _np_ptr(owners),
+                              _np_ptr(spans), _np_ptr(masks), cap, C.byref(cnt), _np_ptr(labels), None))
+    k = min(int(cnt.value), cap)
+    return {"rows": rows, "owners": None if owners is None else owners[:k], "spans": None if spans is None else spans[:k],
+            "masks": None if masks is None else masks[:k], "label_counts": labels, "count": int(cnt.value)}
+
+
+def lex_device(rev, fwd, text_ptr: int, text_bytes: int, offsets_ptr: int, n: int, out_match_count_ptr: int, opts=0, out_rows_ptr=0,
+               out_owners_ptr=0, out_spans_ptr=0, out_masks_ptr=0, match_cap=0, out_label_counts_ptr=0, stream: int = 0):
+    """pire_hip_lex on device pointers: only enqueues on `stream`."""
+    _check(lib().pire_hip_lex(_table_ptr(rev), _table_ptr(fwd), opts, text_ptr or None, text_bytes, offsets_ptr or None, n, FLAG_ON_DEVICE,
+                              out_rows_ptr or None, out_owners_ptr or None, out_spans_ptr or None, out_masks_ptr or None, match_cap,
+                              out_match_count_ptr or None, out_label_counts_ptr or None, stream or None))
+
+
+def lex_lines_gather_host(rev, fwd, raw, opts=0, delim: int = 10, tail_byte=-1, match_cap=None, text_cap=None, gather=True):
+    """pire_hip_lex_lines_gather on a host buffer: {"lines", "owners", "spans", "masks", "label_counts", "count"} and, with
+    gather, {"text", "offsets", "bytes"}.  tail_byte -1 = the delimiter, None = none; match_cap None = room for an entry at every
+    byte, text_cap None = for all of them."""
+    raw = _raw_bytes(raw)
+    cap = raw.size if match_cap is None else int(match_cap)
+    room = (raw.size + cap if text_cap is None else int(text_cap)) if gather else 0
+    owners = np.zeros(cap, dtype=np.uint64)
+    spans = np.zeros((cap, 2), dtype=np.uint64)
+    masks = np.zeros(cap, dtype=np.uint64)
+    labels = np.zeros(fwd.info.regexps + 1, dtype=np.uint64)
+    text = np.zeros(max(room, 1), dtype=np.uint8)
+    offsets = np.zeros(cap + 1, dtype=np.uint64)
+    lines, cnt, total = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    _check(lib().pire_hip_lex_lines_gather(_table_ptr(rev), _table_ptr(fwd), opts, raw.ctypes.data if raw.size else None, raw.size, delim, 0,
+                                           _tail(delim if tail_byte == -1 else tail_byte), C.byref(lines),
+                                           owners.ctypes.data if cap else None, spans.ctypes.data if cap else None,
+                                           masks.ctypes.data if cap else None, cap, C.byref(cnt), labels.ctypes.data,
+                                           text.ctypes.data if room else None, room, offsets.ctypes.data if gather else None,
+                                           C.byref(total) if gather else None, None))
+    k = min(int(cnt.value), cap)
+    out = {"lines": int(lines.value), "owners": owners[:k], "spans": spans[:k], "masks": masks[:k], "label_counts": labels,
+           "count": int(cnt.value)}
+    if gather:
+        out.update(text=text[:min(int(total.value), room)], offsets=offsets[:k + 1], bytes=int(total.value))
+    return out
+
+
+def lex_lines_gather_device(rev, fwd, raw_ptr: int, size: int, out_line_count_ptr: int, out_match_count_ptr: int, opts=0, out_bytes_ptr=0,
+                            delim: int = 10, tail_byte=-1, out_owners_ptr=0, out_spans_ptr=0, out_masks_ptr=0, match_cap=0,
+                            out_label_counts_ptr=0, out_text_ptr=0, text_cap=0, out_offsets_ptr=0, stream: int = 0):
+    """pire_hip_lex_lines_gather on device pointers (synchronises `stream` once, as search_all_lines_gather_device does)."""
+    _check(lib().pire_hip_lex_lines_gather(_table_ptr(rev), _table_ptr(fwd), opts, raw_ptr or None, size, delim, FLAG_ON_DEVICE,
+                                           _tail(delim if tail_byte == -1 else tail_byte), out_line_count_ptr or None, out_owners_ptr or None,
+                                           out_spans_ptr or None, out_masks_ptr or None, match_cap, out_match_count_ptr or None,
+                                           out_label_counts_ptr or None, out_text_ptr or None, text_cap, out_offsets_ptr or None,
+                                           out_bytes_ptr or None, stream or None))
 
 
 def splice(raw, spans, head=b"", tail=b"", mode=0, offsets=None, text_cap: Optional[int] = None, want_pos=True):

@@ -4389,6 +4389,214 @@ try {
 	return pirehip::HandleException();   // an exception must not unwind through the C ABI
 }
 
+// ---- labelled matches and tokens (lex.hip) and those of the lines of a buffer -------------------------------------------------------
+namespace {
+
+// What both lex entry points refuse of their tables and opts before any device is touched
+int LexArgsInvalid(const char* who, pire_hip_table* rev, pire_hip_table* fwd, uint32_t opts)
+{
+	const uint32_t known = PIRE_HIP_LEX_SHORTEST | PIRE_HIP_LEX_THROUGH_BEGIN | PIRE_HIP_LEX_THROUGH_END | PIRE_HIP_LEX_TOKENS;
+	const bool tokens = (opts & PIRE_HIP_LEX_TOKENS) != 0;
+	const char* what = opts & ~known                                                                        ? "unknown bits in opts"
+	                   : !fwd                                                                               ? "null fwd"
+	                   : !rev && !tokens                                                                    ? "null rev without PIRE_HIP_LEX_TOKENS"
+	                   : fwd->host.scannerType != 1 || (!tokens && rev->host.scannerType != 1)              ? "a SimpleScanner table"
+	                                                                                                        : nullptr;
+	if (what) {
+		SetError(std::string(who) + ": " + what);
+		return PIRE_HIP_EINVAL;
+	}
+	if (fwd->host.regexps > 64) {
+		SetError(std::string(who) + ": fwd has " + std::to_string(fwd->host.regexps) + " regexps; more than 64 have no accept masks");
+		return PIRE_HIP_EUNSUPPORTED;
+	}
+	return PIRE_HIP_OK;
+}
+
+int LexOutputsInvalid(const char* who, bool haveList, uint64_t matchCap, const void* outMatchCount)
+{
+	const char* what = !outMatchCount          ? "null out_match_count"
+	                   : matchCap && !haveList ? "match_cap > 0 with null out_owners, out_spans and out_masks"
+	                                           : nullptr;
+	if (!what)
+		return PIRE_HIP_OK;
+	SetError(std::string(who) + ": " + what);
+	return PIRE_HIP_EINVAL;
+}
+
+// The tables of one lex entry point held still, and their scan parameters (SearchTables'; token mode: fwd alone, rev is ignored)
+struct LexTables {
+	TableUse use1, use2;
+	ScanParams pr{}, pf;
+	uint32_t fwdStartBegin = 0;
+	bool tokens = false;
+	int Prepare(pire_hip_table* rev, pire_hip_table* fwd, uint32_t opts, bool enqueueOnly)
+	{
+		tokens = (opts & PIRE_HIP_LEX_TOKENS) != 0;
+		if (tokens) {
+			use1.Acquire(fwd, enqueueOnly);
+		} else {
+			use1.Acquire(std::min(rev, fwd), enqueueOnly);
+			if (rev != fwd)
+				use2.Acquire(std::max(rev, fwd), enqueueOnly);
+			if (int rc = SuffixParams(rev, &pr, (opts & PIRE_HIP_LEX_THROUGH_END) != 0))
+				return rc;
+		}
+		if (int rc = FillParams(fwd, &pf, 0))   // startPerm = Initialize()
+			return rc;
+		const HostTable& h = fwd->host;
+		fwdStartBegin = pf.hostPermOfOrig[h.next[size_t(h.initial) * h.letters + h.cls[kBeginMark]]];   // + Step(BeginMark), run.h:282-283
+		return PIRE_HIP_OK;
+	}
+	// the pass enqueued on `stream`, device pointers only
+	int Enqueue(uint32_t opts, const void* dText, uint64_t textBytes, const uint64_t* dOffsets, uint64_t n, uint64_t shift, uint64_t* dRows,
+	            uint64_t* dOwners, uint64_t* dSpans, uint64_t* dMasks, uint64_t cap, uint64_t* dCount, uint64_t* dLabels, hipStream_t stream)
+	{
+		ScanParams& batch = tokens ? pf : pr;
+		batch.n = n;
+		batch.text = static_cast<const uint8_t*>(dText);
+		batch.offsets = dOffsets;
+		return LaunchLex(pr, pf, fwdStartBegin, opts, textBytes, shift, dRows, dOwners, dSpans, dMasks, cap, dCount, dLabels, stream);
+	}
+};
+
+}  // namespace
+
+int pire_hip_lex(pire_hip_table* rev, pire_hip_table* fwd, uint32_t opts, const void* text, uint64_t text_bytes, const uint64_t* offsets,
+                 uint64_t n, uint32_t flags, uint64_t* out_rows, uint64_t* out_owners, uint64_t* out_spans, uint64_t* out_masks,
+                 uint64_t match_cap, uint64_t* out_match_count, uint64_t* out_label_counts, void* streamPtr)
+try {
+	const char* who = "pire_hip_lex";
+	if (int rc = LexArgsInvalid(who, rev, fwd, opts))
+		return rc;
+	if (int rc = SearchBatchInvalid(who, text, offsets, n))
+		return rc;
+	if (int rc = LexOutputsInvalid(who, out_owners || out_spans || out_masks, match_cap, out_match_count))
+		return rc;
+	hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+	const bool onDevice = (flags & PIRE_HIP_RUN_ON_DEVICE) != 0;
+	const size_t labels = size_t(fwd->host.regexps) + 1;
+	if (n == 0) {   // device pointers: the counts (and rows[0]) zeroed on the stream; host pointers: no device is touched
+		if (onDevice) {
+			ScanParams none{};
+			none.regexps = fwd->host.regexps;
+			return LaunchLex(none, none, 0, opts, 0, 0, out_rows, nullptr, nullptr, nullptr, 0, out_match_count, out_label_counts, stream);
+		}
+		*out_match_count = 0;
+		if (out_rows)
+			out_rows[0] = 0;
+		if (out_label_counts)
+			std::fill(out_label_counts, out_label_counts + labels, uint64_t(0));
+		return PIRE_HIP_OK;
+	}
+	uint64_t textBytes = text_bytes;
+	if (!onDevice) {   // what the scans refuse of a host batch, before a device is touched
+		if (int rc = CheckHostBatch(text, offsets, n, 0, 0, &textBytes))
+			return rc;
+		if (textBytes > text_bytes) {
+			SetError(std::string(who) + ": an offset exceeds text_bytes");
+			return PIRE_HIP_EINVAL;
+		}
+	}
+	LexTables tabs;
+	if (int rc = tabs.Prepare(rev, fwd, opts, onDevice))
+		return rc;
+	// host pointers: the text staged once (offsets[n] bytes of it), the passes on the staged copy, then everything back
+	BatchIO io(stream, onDevice);
+	const uint8_t* dText = nullptr;
+	const uint64_t* dOffsets = nullptr;
+	uint64_t *dRows = nullptr, *dLabels = nullptr;
+	if (int rc = io.Text(text, offsets, n, 0, 0, &dText, &dOffsets))
+		return rc;
+	if (out_rows)
+		if (int rc = io.Result(out_rows, size_t(n) + 1, size_t(n) + 1, &dRows))
+			return rc;
+	if (out_label_counts)
+		if (int rc = io.Result(out_label_counts, labels, labels, &dLabels))
+			return rc;
+	HitStage list(onDevice, out_match_count, "hipMemcpy(lex entries)");
+	// (entries are not empty and do not overlap, so a host call stages no more of them than the text has bytes)
+	list.cap = onDevice ? match_cap : std::min<uint64_t>(match_cap, textBytes);
+	uint64_t *dOwners = nullptr, *dSpans = nullptr, *dMasks = nullptr;
+	int rc;
+	if ((rc = io.Result(onDevice ? out_match_count : &list.count, 1, 1, &list.dCount)) || (rc = list.List(io, out_owners, 1, &dOwners)) ||
+	    (rc = list.List(io, out_spans, 2, &dSpans)) || (rc = list.List(io, out_masks, 1, &dMasks)) || (rc = io.Ready()))
+		return rc;
+	if ((rc = tabs.Enqueue(opts, dText, textBytes, dOffsets, n, 0, dRows, dOwners, dSpans, dMasks, list.cap, list.dCount, dLabels, stream)))
+		return rc;
+	if ((rc = io.Finish()))
+		return rc;
+	return list.Back();
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
+// The frame around pire_hip_lex: the pass on the lines with shift = 1 (string i of the split buffer lies i bytes further into
+// raw), the gather from raw through its spans.
+int pire_hip_lex_lines_gather(pire_hip_table* rev, pire_hip_table* fwd, uint32_t opts, const void* raw, uint64_t size, uint32_t delim,
+                              uint32_t flags, uint32_t tail_byte, uint64_t* out_line_count, uint64_t* out_owners, uint64_t* out_spans,
+                              uint64_t* out_masks, uint64_t match_cap, uint64_t* out_match_count, uint64_t* out_label_counts, void* out_text,
+                              uint64_t text_cap, uint64_t* out_offsets, uint64_t* out_bytes, void* streamPtr)
+try {
+	const char* who = "pire_hip_lex_lines_gather";
+	if (int rc = LexArgsInvalid(who, rev, fwd, opts))
+		return rc;
+	flags &= PIRE_HIP_RUN_ON_DEVICE;   // (the marks are the pass's own: opts)
+	if (int rc = SplitArgsInvalid(who, raw, size, delim, out_line_count, "out_line_count"))
+		return rc;
+	// no gather output at all: spans only.  (The gather form keeps the span list to itself where the caller has no array for it.)
+	const bool gathers = out_text || text_cap || out_offsets || out_bytes;
+	if (int rc = LexOutputsInvalid(who, out_owners || out_spans || out_masks || gathers, match_cap, out_match_count))
+		return rc;
+	if (gathers) {
+		if (int rc = GatherOutputsInvalid(who, "match_cap", match_cap, tail_byte, out_text, text_cap, out_offsets, out_bytes))
+			return rc;
+		if (int rc = GatherOverlaps(who, raw, size, out_text, text_cap))
+			return rc;
+	}
+	const size_t labels = size_t(fwd->host.regexps) + 1;
+	const LinesGather gather = {tail_byte, out_text, text_cap, out_offsets, out_bytes, false, "hipMallocAsync(lex spans)"};
+	LinesFrame f(who, raw, size, delim, flags, gathers ? &gather : nullptr, streamPtr);
+	if (f.HostEdge(out_line_count)) {
+		*out_match_count = 0;
+		if (out_label_counts)
+			std::fill(out_label_counts, out_label_counts + labels, uint64_t(0));
+		return PIRE_HIP_OK;
+	}
+	if (int rc = f.Open())
+		return rc;
+	if (int rc = f.Split(out_line_count, out_match_count, 1, match_cap, false))
+		return rc;
+	if (!f.onDevice)
+		f.cap = std::min<uint64_t>(f.cap, size);   // entries are not empty and do not overlap: a host call stages no more
+	if (int rc = f.Lists(out_owners, out_spans))
+		return rc;
+	uint64_t *dMasks = nullptr, *dLabels = nullptr;
+	if (out_masks && f.cap)
+		if (int rc = f.io.Result(out_masks, size_t(f.cap), 0, &dMasks))
+			return rc;
+	if (out_label_counts)
+		if (int rc = f.io.Result(out_label_counts, labels, labels, &dLabels))
+			return rc;
+	if (f.n == 0) {
+		if (int rc = f.ZeroCounts("hipMemsetAsync(entry count)"))
+			return rc;
+		if (dLabels && hipMemsetAsync(dLabels, 0, labels * 8, f.stream) != hipSuccess)
+			return HipFail(hipGetLastError(), "hipMemsetAsync(label counts)");
+	} else {
+		LexTables tabs;
+		if (int rc = tabs.Prepare(rev, fwd, opts, f.onDevice))
+			return rc;
+		if (int rc = tabs.Enqueue(opts, f.Text(), size, f.Offsets(), f.n, 1, nullptr, f.dHits, f.dSpans, dMasks, f.cap, f.dCounts, dLabels, f.stream))
+			return rc;
+	}
+	if (int rc = f.Close("hipMemcpy(lex spans)"))
+		return rc;
+	return f.onDevice ? PIRE_HIP_OK : HitsBack(1, out_match_count, f.cap, f.cap, dMasks, out_masks, 8, "hipMemcpy(lex masks)");
+} catch (...) {
+	return pirehip::HandleException();   // an exception must not unwind through the C ABI
+}
+
 // ---- the matches replaced, the rest kept (splice.hip) ------------------------------------------------------------------------
 namespace {
 

@@ -1459,6 +1459,14 @@ int LaunchSearch(const ScanParams& rev, const ScanParams& fwd, uint32_t fwdStart
 // (and outRows[0]) zeroed on the stream.
 int LaunchSearchAll(const ScanParams& rev, const ScanParams& fwd, uint32_t fwdStartBegin, uint32_t opts, uint64_t textBytes, uint64_t shift,
                     uint64_t* outRows, uint64_t* outOwners, uint64_t* outSpans, uint64_t cap, uint64_t* outCount, hipStream_t stream);
+// lex.hip: the matches of LaunchSearchAll with the regexps that accept each (pire_hip_lex), or -- PIRE_HIP_LEX_TOKENS -- the
+// maximal-munch tokens of every string and the gaps between them, through `fwd` alone (`rev` is then not read).  Four launches
+// either way: marks + counts (tokens: counts), the row scan of search_all.hip, the lists.  fwd carries the batch in token mode,
+// rev otherwise, as LaunchSearchAll; fwd.acceptMaskPerm must be there.  outMasks[cap], outLabelCounts[fwd.regexps + 1]:
+// nullable.  n == 0: the count, outRows[0] and the label counts zeroed on the stream.
+int LaunchLex(const ScanParams& rev, const ScanParams& fwd, uint32_t fwdStartBegin, uint32_t opts, uint64_t textBytes, uint64_t shift,
+              uint64_t* outRows, uint64_t* outOwners, uint64_t* outSpans, uint64_t* outMasks, uint64_t cap, uint64_t* outCount,
+              uint64_t* outLabelCounts, hipStream_t stream);
 // splice.hip: the spans of a buffer replaced by head ++ (the match, under PIRE_HIP_SPLICE_KEEP) ++ tail, the rest kept
 // (pire_hip_splice).  Device pointers only -- but head and tail, which are the host's and travel as kernel arguments --, four
 // kernels enqueued on `stream`, no allocation: outPos[cap] is required where cap > 0 (the caller's array or its scratch).

@@ -23,157 +23,24 @@
 //   rows          exclusive 64-bit scan of the counts (compact.h's BlockExclusive per tile of 1 024, tile sums, a scan of the
 //                 tile sums by one block); the total is the match count.
 //   fill          the forward loop again, F only: owners and spans into [rows[i], rows[i+1]) below the capacity.
+// The parameters, the marks and the forward loop are in match_loop.h: lex.hip walks the same loop and labels what it finds.
 // Plain HIP with compiler-placed waits: nothing here keeps data on its way in registers.
 
 #include "device_common.h"
 #include "walk.h"
 #include "compact.h"
+#include "match_loop.h"
 
 namespace pirehip {
 
 namespace {
 
-struct SearchAllParams {
-	ScanParams rev, fwd;       // as SearchParams': rev.startPerm Initialize() (+ Step(EndMark)), fwd.startPerm Initialize()
-	uint32_t fwdStartBegin;    // F's Initialize() + Step(BeginMark)
-	uint32_t longest, throughBegin, throughEnd;
-	uint64_t textBytes;        // offsets beyond it are clamped to it
-	uint64_t shift;            // string i lies shift * i bytes further into the buffer the spans are counted in
-	uint16_t* marks;           // [textBytes / 16 + n + 2]
-	uint64_t* counts;          // [n] matches per string
-	uint64_t* tileSums;        // [tiles]; after the scan: matches in front of the tile
-	uint64_t* rows;            // [n + 1]; between the scans: matches in front of the string inside its tile
-	uint64_t* outOwners;       // nullable
-	uint64_t* outSpans;        // nullable
-	uint64_t cap;
-	uint64_t* outCount;
-};
-
-// String s of the batch: where it starts in the text and how long it is, both clamped to the text
-__device__ __forceinline__ void StringOf(const SearchAllParams& q, uint64_t s, uint64_t* begin, uint64_t* len)
+// The forward leg of MatchLoop (match_loop.h): LongestPrefix / ShortestPrefix through F, its dense rows at ldsF
+__device__ __forceinline__ auto ForwardLeg(const SearchAllParams& q, const uint8_t* ldsF, const LdsLayout& LF)
 {
-	const uint64_t o0 = q.rev.offsets[s], o1 = q.rev.offsets[s + 1];
-	const uint64_t b = o0 < q.textBytes ? o0 : q.textBytes;
-	const uint64_t e = o1 < q.textBytes ? o1 : q.textBytes;
-	*begin = b;
-	*len = e >= b ? e - b : 0;   // offsets that decrease: an empty string
-}
-
-// The word of the block at address `block` (a multiple of 16) of string s
-__device__ __forceinline__ uint64_t MarkIndex(const SearchAllParams& q, uint64_t block, uint64_t s)
-{
-	return (block >> 4) - (reinterpret_cast<uint64_t>(q.rev.text) >> 4) + s;
-}
-
-// The backward walk of string s at addresses [lo, top) through R: LongestSuffix's loop (run.h:326-340), which writes the
-// marks of every position instead of remembering the lowest one.
-__device__ __forceinline__ void MarkWalk(const SearchAllParams& q, const uint8_t* lds, const LdsLayout& L, uint64_t s, uint64_t lo, uint64_t top)
-{
-	const ScanParams& p = q.rev;
-	uint64_t cur = top;   // one past the next byte to take
-	uint32_t st = p.startPerm;
-	bool dead = (StateFlags(p, lds, L, st) & kDead) != 0;
-	while (cur > lo) {
-		const uint64_t block = (cur - 1) & ~uint64_t(15);
-		uint32_t k = uint32_t(cur - 1 - block);                          // index of the next byte inside the block
-		const uint32_t kLow = block >= lo ? 0u : uint32_t(lo - block);   // first index that belongs to the string
-		uint32_t word = 0;
-		if (dead) {
-			cur = block + kLow;   // below a Dead state: no marks, the text is not read
-		} else {
-			u32x4 v = *reinterpret_cast<const u32x4*>(block);
-			bool taken = false;
-			// a whole block from a state with a dense row: neither a Dead nor a Final state among the sixteen reached (the
-			// rows are ordered plain, Dead, Final) -> no marks in it, take the state
-			if (k == 15 && kLow == 0 && st < p.hot) {
-				uint32_t h = st, mx = 0;
-#pragma unroll
-				for (int w = 3; w >= 0; --w) {
-					const uint32_t x = v[w];
-#pragma unroll
-					for (int b2 = 3; b2 >= 0; --b2) {
-						h = lds[h * L.pitch + ((x >> (8 * b2)) & 0xFFu)];
-						mx = mx > h ? mx : h;
-					}
-				}
-				if (mx < p.hotDeadLo) {
-					st = h;
-					cur -= 16;
-					taken = true;
-				}
-			}
-			if (!taken) {
-				// bring byte k to the top of the 128-bit value, then peel bytes off the top
-				for (uint32_t sh = 15 - k; sh; --sh) {
-					v.w = __builtin_amdgcn_alignbit(v.w, v.z, 24);
-					v.z = __builtin_amdgcn_alignbit(v.z, v.y, 24);
-					v.y = __builtin_amdgcn_alignbit(v.y, v.x, 24);
-					v.x <<= 8;
-				}
-				for (;;) {
-					st = SlowStep(p, lds, L, st, v.w >> 24);
-					const uint32_t f = StateFlags(p, lds, L, st);
-					--cur;
-					if (f & kFinal)
-						word |= 1u << k;   // the suffix from byte k of the block matches
-					dead = (f & kDead) != 0;
-					if (dead || k == kLow)
-						break;
-					--k;
-					v.w = __builtin_amdgcn_alignbit(v.w, v.z, 24);
-					v.z = __builtin_amdgcn_alignbit(v.z, v.y, 24);
-					v.y = __builtin_amdgcn_alignbit(v.y, v.x, 24);
-					v.x <<= 8;
-				}
-				if (dead)
-					cur = block + kLow;   // the rest of the block has no marks either
-			}
-			if (cur == lo && !dead && q.throughBegin) {   // run.h:336-340, byte 0 only
-				const uint32_t sb = p.nextPerm[size_t(st) * p.letters + p.beginCls];
-				if (StateFlags(p, lds, L, sb) & kFinal)
-					word |= 1u << kLow;
-			}
-		}
-		q.marks[MarkIndex(q, block, s)] = uint16_t(word);
-	}
-}
-
-// The forward loop of string s (text + b, len bytes) over its marks: emit(k, begin, end) for match k; returns their number.
-// `limit`: no more than that many (the fill pass: what the count pass counted).
-template <class Emit>
-__device__ __forceinline__ uint64_t MatchLoop(const SearchAllParams& q, const uint8_t* ldsF, const LdsLayout& LF, uint64_t s, uint64_t b,
-                                              uint64_t len, uint64_t limit, Emit&& emit)
-{
-	const ScanParams& pf = q.fwd;
-	const uint8_t* str = q.rev.text + b;
-	const uint64_t lo = reinterpret_cast<uint64_t>(str);
-	const uint64_t lastBlock = (lo + len - 1) & ~uint64_t(15);   // (len > 0 where it is used)
-	uint64_t p = 0, k = 0;
-	while (p < len && k < limit) {
-		// the next mark at or behind p
-		uint64_t block = (lo + p) & ~uint64_t(15);
-		uint32_t word = q.marks[MarkIndex(q, block, s)] & (0xFFFFu << uint32_t((lo + p) & 15));
-		while (!word && block < lastBlock) {
-			block += 16;
-			word = q.marks[MarkIndex(q, block, s)];
-		}
-		if (!word)
-			break;
-		const uint64_t at = block + uint32_t(__builtin_ctz(word));
-		if (at < lo || at - lo >= len)   // (strings that overlap in the text: another lane's bits)
-			break;
-		const uint64_t from = at - lo;
-		const uint32_t st = q.throughBegin && from == 0 ? q.fwdStartBegin : pf.startPerm;
-		const long long h = PrefixWalk(pf, ldsF, LF, str + from, len - from, st, q.longest, q.throughEnd);
-		if (h < 0)
-			break;   // two tables that do not belong together
-		if (h > 0) {
-			emit(k, from, from + uint64_t(h));
-			++k;
-		}
-		p = from + (h > 0 ? uint64_t(h) : 1u);   // one byte past an empty match
-	}
-	return k;
+	return [&q, ldsF, &LF](const uint8_t* text, uint64_t len, uint32_t st) {
+		return PrefixWalk(q.fwd, ldsF, LF, text, len, st, q.longest, q.throughEnd);
+	};
 }
 
 __global__ __launch_bounds__(1024) void SearchAllMarkKernel(SearchAllParams q)
@@ -194,7 +61,7 @@ __global__ __launch_bounds__(1024) void SearchAllMarkKernel(SearchAllParams q)
 		if (len) {
 			const uint64_t lo = reinterpret_cast<uint64_t>(pr.text) + b;
 			MarkWalk(q, lds, LR, s, lo, lo + len);
-			count = MatchLoop(q, ldsF, LF, s, b, len, ~uint64_t(0), [](uint64_t, uint64_t, uint64_t) {});
+			count = MatchLoop(q, s, b, len, ~uint64_t(0), ForwardLeg(q, ldsF, LF), [](uint64_t, uint64_t, uint64_t) {});
 		}
 		q.counts[s] = count;
 	}
@@ -258,7 +125,7 @@ __global__ __launch_bounds__(1024) void SearchAllFillKernel(SearchAllParams q, u
 		uint64_t b, len;
 		StringOf(q, s, &b, &len);
 		const uint64_t base = b + q.shift * s;
-		MatchLoop(q, lds, LF, s, b, len, count < room ? count : room, [&](uint64_t k, uint64_t begin, uint64_t end) {
+		MatchLoop(q, s, b, len, count < room ? count : room, ForwardLeg(q, lds, LF), [&](uint64_t k, uint64_t begin, uint64_t end) {
 			if (q.outOwners)
 				q.outOwners[row + k] = s;
 			if (q.outSpans) {
@@ -270,6 +137,14 @@ __global__ __launch_bounds__(1024) void SearchAllFillKernel(SearchAllParams q, u
 }
 
 }  // namespace
+
+int LaunchSearchAllRows(const SearchAllParams& q, uint32_t tiles, hipStream_t stream)
+{
+	hipLaunchKernelGGL(SearchAllTileKernel, dim3(std::min(tiles, kTileMaxBlocks)), dim3(kBlockThreads), 0, stream, q, tiles);
+	hipLaunchKernelGGL(SearchAllSumKernel, dim3(1), dim3(kBlockThreads), 0, stream, q, tiles);
+	const hipError_t e = hipGetLastError();
+	return e == hipSuccess ? PIRE_HIP_OK : HipFail(e, "search rows launch");
+}
 
 int LaunchSearchAll(const ScanParams& rev, const ScanParams& fwd, uint32_t fwdStartBegin, uint32_t opts, uint64_t textBytes, uint64_t shift,
                     uint64_t* outRows, uint64_t* outOwners, uint64_t* outSpans, uint64_t cap, uint64_t* outCount, hipStream_t stream)
@@ -327,11 +202,8 @@ int LaunchSearchAll(const ScanParams& rev, const ScanParams& fwd, uint32_t fwdSt
 	const unsigned blocks = unsigned(std::max<uint64_t>(1, std::min<uint64_t>(tiles, uint64_t(cus) * 2)));
 	if (int rc = Launch(SearchAllMarkKernel, blocks, threads, ldsBytes, stream, "search marks launch", q))
 		return rc;
-	hipLaunchKernelGGL(SearchAllTileKernel, dim3(std::min(tiles, kTileMaxBlocks)), dim3(threads), 0, stream, q, tiles);
-	hipLaunchKernelGGL(SearchAllSumKernel, dim3(1), dim3(threads), 0, stream, q, tiles);
-	e = hipGetLastError();
-	if (e != hipSuccess)
-		return HipFail(e, "search rows launch");
+	if (int rc = LaunchSearchAllRows(q, tiles, stream))
+		return rc;
 	const uint32_t lists = q.outOwners || q.outSpans ? 1 : 0;
 	if (!lists && !outRows)
 		return PIRE_HIP_OK;   // the count alone

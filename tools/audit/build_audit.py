@@ -23,7 +23,7 @@ What is checked, per unit (the product's flags: -O3 --offload-arch=gfx950):
   counting                                the row kernels: a0..a31 named by the loads and v_accvgpr_read only, loads of the
                                           form `global_load_dwordx4 a[..], v[..], off`, no scratch inside the window loop,
                                           VGPRs + AGPRs <= 128; every other kernel of the unit: no scratch
-  exact / slow / segmented / order / select / capture_select / count_select / slow_hits / affix / search / search_all / splice / context / files / combine / slow_capture / split / gather / route / fields   no scratch (per-lane counter arrays stay in registers)
+  exact / slow / segmented / order / select / capture_select / count_select / slow_hits / affix / search / search_all / lex / splice / context / files / combine / slow_capture / split / gather / route / fields   no scratch (per-lane counter arrays stay in registers)
 """
 import argparse
 import importlib.util
@@ -52,7 +52,7 @@ WALKED = {"tiled.hip": ["ScanTiledKernel"], "wide.hip": ["ScanWideKernel", "Scan
 # ... whose INNER tile loop's exits are followed as well (the kernel that chains tasks through its ring of two tiles and leaves
 # the tile loop early when a wave's strings are all absorbed: where round 5's wrong-result bug was)
 INNER_EXITS = {"wide.hip": ["ScanWideKernel"]}
-NO_SCRATCH = ["exact.hip", "slow.hip", "segmented.hip", "order.hip", "select.hip", "capture_select.hip", "count_select.hip", "slow_hits.hip", "affix.hip", "search.hip", "search_all.hip", "splice.hip", "context.hip", "files.hip", "combine.hip", "slow_capture.hip", "split.hip", "gather.hip", "route.hip", "fields.hip", "counting.hip"]
+NO_SCRATCH = ["exact.hip", "slow.hip", "segmented.hip", "order.hip", "select.hip", "capture_select.hip", "count_select.hip", "slow_hits.hip", "affix.hip", "search.hip", "search_all.hip", "lex.hip", "splice.hip", "context.hip", "files.hip", "combine.hip", "slow_capture.hip", "split.hip", "gather.hip", "route.hip", "fields.hip", "counting.hip"]
 UNITS = sorted(set(WINDOW) | set(NO_SCRATCH))
 
 
